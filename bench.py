@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config, on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs when --dump-outputs is given and prints the line.
+Everything else the script measures runs only with --full (off by default): the live PMC passes, the HIP-event loop and
+the copy ceiling of `roofline`, the objects `strong_config5`, `configs`, `rfft_reference_bench`, `cpu_baseline` and
+`vendor_rocfft`, and under --scaling strong the end-to-end and per-slab-kernel legs and the model.  The --no-* switches
+narrow a --full run.
+
+--dump-outputs DIR writes what the last timed step computed -- the `out` tensor a caller of the timed path receives, in
+the run's precision -- as DIR/out.npy; above DUMP_BYTES it is a fixed, seeded sample (dump_sample).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one pass of the hot path (one plan_fft'd `fft(out, x)` call) over one batch of synthetic complex64 input
 that is already resident in HBM.  At N=1 the workload is BASELINE.json configs[1]: 100k x 1024 1-D C2C fp32 with the
@@ -16,18 +26,19 @@ the ranks.  Either way WORLD_SIZE must equal --gpus, and `ranks_seen` (an all-re
   --scaling strong BASELINE configs[4]: ONE 10 x 128^3 batch split over the ranks (2,2,1,..,1 volumes at N=8: the ideal
                    speed-up is 5x, 3.33x at N=4, 2x at N=2); "compute, shards resident" and "end-to-end incl. the
                    scatter/gather of ShardedFFT.fft_from_root over RCCL" are reported separately
-The default run also carries the strong-scaling leg as the object `strong_config5`.
+A --full run of the headline also carries the strong-scaling leg as the object `strong_config5`.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0): `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, and
   roofline       HBM roofline of the dominant kernel; `achieved` / `frac` = algorithmic bytes per launch (16 B per complex
-                 element: one 8-B read + one 8-B write) / ms_per_step of the K TIMED STEPS; the same
-                 figure from HIP events on the launch stream inside libmifft (mifft_time_exec, a separate loop right
-                 after the timed steps) is `frac_hip_events`; `traffic` = HBM bytes per step from `rocprofv3 --pmc
-                 FETCH_SIZE` / `--pmc WRITE_SIZE` child passes of this command, run by this process BEFORE it touches
-                 the GPU (N=1 default run; else the committed profile of the same command); `copy` = COPY kernels with
-                 the tile shapes and cache policy of the FFT passes moving the same bytes in this run on this box
-                 (tools/libmifft_probe.so: what the chip gives a kernel that only moves the pass's bytes)
+                 element: one 8-B read + one 8-B write) / ms_per_step of the K TIMED STEPS; `traffic` =
+                 HBM bytes per step from the committed profile of the same command.  With --full: the same figure from
+                 HIP events on the launch stream inside libmifft (mifft_time_exec, a separate loop right after the timed
+                 steps) is `frac_hip_events`; `traffic` comes from `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`
+                 child passes of this command, run by this process BEFORE it touches the GPU (N=1 headline run); `copy`
+                 = COPY kernels with the tile shapes and cache policy of the FFT passes moving the same bytes in this
+                 run on this box (tools/libmifft_probe.so: what the chip gives a kernel that only moves the pass's bytes)
   ramp           the untimed clock / cache ramp that precedes the W warm-up steps (ms, execs)
+Extra objects (--full):
   configs        (N=1) the other four BASELINE.json configs, each timed the same way in this run
   rfft_reference_bench  (N=1) the shapes of the reference's own GPU benchmark in ITS mode: real input, full complex
                  spectrum out (fft/bench.mojo:57-97,108-124); fraction of the roofline on 4 B read + 8 B written per point
@@ -86,6 +97,7 @@ OTHER_BASELINE_CONFIGS = ["1d_500kx128", "1d_500kx93_radix31x3", "2d_100x640x480
 RFFT_REFERENCE_SHAPES = [(250000, 93), (250000, 128), (100000, 1024), (100, 640, 480), (100, 64, 64, 64),
                          (10, 128, 128, 128), (1, 256, 256, 256)]
 RAMP_S = float(os.environ.get("MIFFT_BENCH_RAMP_S", "0.05"))  # (the env override is for tools/ramp_probe.sh only)
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of samples (64 MB in all with room to spare)
 
 
 def flops_5nlogn(shape):
@@ -128,6 +140,43 @@ def measured_traffic(workload, kernels):
         if ks and len(ks) == len(set(kernels)) and (d.get("bench_kernels") in (None, sorted(set(kernels)))):
             best = (sum(k["hbm_traffic_bytes"] for k in ks), os.path.basename(f), names)
     return best
+
+
+def dump_sample(shape, elem_bytes):
+    """Which part of an output of `shape` (complex dim last) --dump-outputs writes: (lead, idx).  The output is viewed
+    as slices along its `lead` leading dimensions -- whole transforms (lead = 1) when one fits DUMP_BYTES, else the
+    slices of the next dimension, and so on -- and idx is a fixed seeded choice of as many slices as fit, ascending (all
+    of them when the whole output fits).  It depends on the shape and element size only, so every run with the same
+    arguments writes the same elements."""
+    import numpy as np
+    total = elem_bytes
+    for d in shape:
+        total *= d
+    units = 1
+    for lead in range(1, len(shape)):
+        units *= shape[lead - 1]
+        if total // units <= DUMP_BYTES:
+            break
+    k = min(units, DUMP_BYTES // (total // units))
+    if k == units:
+        return lead, np.arange(units)
+    return lead, np.sort(np.random.default_rng(0).choice(units, size=k, replace=False))
+
+
+def dump_outputs(dump_dir, out):
+    """DIR/out.npy: the tensor the last timed step wrote (float32 or float64, like the run), or its dump_sample: an
+    array (slices, *slice shape)."""
+    import numpy as np
+    import torch
+    shape = tuple(out.shape)
+    lead, idx = dump_sample(shape, out.element_size())
+    view = out.reshape((-1,) + shape[lead:])
+    sample = view if len(idx) == view.shape[0] else view[torch.as_tensor(idx, device=out.device)]
+    arr = sample.cpu().numpy()
+    os.makedirs(dump_dir, exist_ok=True)
+    path = os.path.join(dump_dir, "out.npy")
+    np.save(path, arr)
+    sys.stderr.write(f"bench.py: {path}: {len(idx)} of {view.shape[0]} slices of out{list(shape)}, {arr.nbytes} bytes\n")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -372,11 +421,16 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/out.npy (a seeded sample above 48 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well (module docstring); the --no-* switches below "
+                         "narrow it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the array of the other BASELINE configs (N=1)")
     ap.add_argument("--no-strong-leg", action="store_true", help="skip the config-5 strong-scaling object")
     ap.add_argument("--compare-vendor", dest="vendor", action="store_true", default=None,
-                    help="rocFFT comparator column (default: on at N=1 when tools/vendor_fft_bench exists)")
+                    help="rocFFT comparator column in a --full run (default: on at N=1 for the headline workload)")
     ap.add_argument("--no-compare-vendor", dest="vendor", action="store_false")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not collect roofline.traffic with rocprofv3 child runs (N=1, headline workload only); the "
@@ -388,7 +442,10 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N ranks share the visible GPU(s) and talk over gloo: exercises the N-rank launch, split and "
                          "timing code on a 1-GPU box (RCCL refuses two ranks on one device); not a scaling measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -510,9 +567,11 @@ class Bench:
         x = torch.randn(tuple(shape) + (comps,), generator=gen, device=self.dev, dtype=self.tdt)
         return x, torch.empty(tuple(shape) + (2,), device=self.dev, dtype=self.tdt)
 
-    def run_workload(self, name, steps, warmup, plan=None, x=None, out=None):
-        """time one workload on this rank's GPU (every rank its own copy of the shape)"""
+    def run_workload(self, name, steps, warmup, plan=None, x=None, out=None, dump_dir=None):
+        """time one workload on this rank's GPU (every rank its own copy of the shape); rank 0 writes `out` as the last
+        timed step left it to dump_dir when one is given"""
         mf = self.mf
+        full = self.args.full
         shape, bases, cfg_idx = WORKLOADS[name]
         comps = 1 if name.endswith("_real") else 2
         if x is None:
@@ -521,8 +580,10 @@ class Bench:
             plan = mf.plan_fft(self.tdt, self.tdt, x.shape, out.shape, bases=bases, ctx=self.ctx,
                                faithful_stages=self.args.faithful)
         elapsed, n_ramp, ramp_s = self.timed(lambda: mf.fft(out, x, self.ctx, plan=plan), steps, warmup)
+        if dump_dir and self.rank == 0:
+            dump_outputs(dump_dir, out)
         # kernel-level time: HIP events on the launch stream, inside the library
-        launch_ms = mf.time_fft(out, x, plan=plan, iters=max(10, min(steps, 200)), ctx=self.ctx)
+        launch_ms = mf.time_fft(out, x, plan=plan, iters=max(10, min(steps, 200)), ctx=self.ctx) if full else None
         ms_per_step = elapsed * 1e3 / steps
         elems = 1
         for d in shape:
@@ -530,10 +591,9 @@ class Bench:
         # one complex (or real) read + one complex write per element, per exec on ONE gpu
         algo_bytes = (2.0 + comps) * self.esz * elems
         achieved = algo_bytes / (ms_per_step * 1e-3) / 1e9          # the K timed steps
-        achieved_ev = algo_bytes / (launch_ms * 1e-3) / 1e9         # the separate HIP-event loop
         kernels = [plan.kernel_name(d) for d in range(len(shape) - 1)]
         copy = None
-        if comps == 2 and self.args.dtype == "f32" and not self.args.no_copy_ceiling:
+        if full and comps == 2 and self.args.dtype == "f32" and not self.args.no_copy_ceiling:
             passes = copy_ceiling(name, kernels, x, out)
             if passes:
                 # two-pass shapes: the alternating pair is the ceiling (what pass 2 finds in the caches depends on pass 1)
@@ -564,13 +624,14 @@ class Bench:
                 "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "frac_source": "algorithmic bytes / ms_per_step of the timed steps",
-                "frac_hip_events": round(achieved_ev / HBM_PEAK_GBS, 4),
+                # the separate HIP-event loop (--full)
+                "frac_hip_events": round(algo_bytes / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if full else None,
                 "copy": copy,
                 "traffic": traffic[0] if traffic else None,
                 "traffic_source": (traffic[1] if traffic[1].startswith("live") else
                                    traffic[1] + " (committed rocprofv3 --pmc passes of this command)") if traffic else None,
                 "kernel": "+".join(kernels), "algorithmic_bytes_per_launch": algo_bytes,
-                "launch_ms_hip_events": round(launch_ms, 5),
+                "launch_ms_hip_events": round(launch_ms, 5) if full else None,
             },
         }
 
@@ -594,7 +655,7 @@ class Bench:
                 "roofline_frac": round(algo_bytes / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
 
     # ---- strong scaling: ONE config-5 batch over all ranks ----------------------------
-    def strong_leg(self, steps, warmup):
+    def strong_leg(self, steps, warmup, dump_dir=None):
         torch, mf = self.torch, self.mf
         from hackathon_fft_amd.dist import ShardedFFT, all_shard_bounds
         shape, bases, _ = WORKLOADS[STRONG_WORKLOAD]
@@ -605,6 +666,20 @@ class Bench:
         x_slab = torch.randn(sharded.slab_in_shape, generator=gen, device=self.dev, dtype=self.tdt)
         out_slab = torch.empty_like(x_slab)
         t_res, _, _ = self.timed(lambda: sharded.fft(out_slab, x_slab), steps, warmup)
+        if dump_dir and self.rank == 0:
+            dump_outputs(dump_dir, out_slab)
+        ms_res = t_res * 1e3 / steps
+        flops = flops_5nlogn(shape)
+        leg = {
+            "workload": STRONG_WORKLOAD, "baseline_config_index": 4, "scaling": "strong", "n_gpus": self.world,
+            "volumes_per_rank": counts, "ideal_speedup_vs_1gpu": round(shape[0] / max(counts), 3),
+            "compute_shards_resident": {"ms_per_step": round(ms_res, 5), "gflops": round(flops / (ms_res * 1e-3) / 1e9, 2),
+                                        "steps": steps, "kernel_choice": "for the whole batch (bit-identical to 1 GPU)"},
+            "compute_shards_resident_own_size": None, "end_to_end_from_root": None, "model": None,  # --full
+            "kernels": [sharded._backend.plan.kernel_name(d) for d in range(len(shape) - 1)] if sharded.count else [],
+        }
+        if not self.args.full:
+            return leg
         # end to end from a root-held tensor: scatter (grouped P2P over RCCL / xGMI), transform, gather
         x_full = out_full = None
         if self.rank == 0:
@@ -619,8 +694,7 @@ class Bench:
             sharded.fft_from_root(out_full, x_full, root=0, device=self.dev)
         self.barrier()
         t_e2e = self.allmax(time.perf_counter() - t0)
-        ms_res, ms_e2e = t_res * 1e3 / steps, t_e2e * 1e3 / e2e_steps
-        flops = flops_5nlogn(shape)
+        ms_e2e = t_e2e * 1e3 / e2e_steps
         # the same resident-shard leg with every rank choosing its kernels for ITS OWN slab size (match_single_gpu=False:
         # results agree with the single-GPU plan to rounding, not bit for bit; the default pays 6-9 % on cache-resident
         # slabs for bit-identity, hackathon_fft_amd/dist.py)
@@ -652,11 +726,7 @@ class Bench:
                     "compute, so end to end this leg is transfer-bound by construction; compute_shards_resident is the "
                     "strong-scaling figure of the transform itself",
         }
-        return {
-            "workload": STRONG_WORKLOAD, "baseline_config_index": 4, "scaling": "strong", "n_gpus": self.world,
-            "volumes_per_rank": counts, "ideal_speedup_vs_1gpu": round(shape[0] / max(counts), 3),
-            "compute_shards_resident": {"ms_per_step": round(ms_res, 5), "gflops": round(flops / (ms_res * 1e-3) / 1e9, 2),
-                                        "steps": steps, "kernel_choice": "for the whole batch (bit-identical to 1 GPU)"},
+        leg.update({
             "compute_shards_resident_own_size": own,
             "end_to_end_from_root": {"ms_per_step": round(ms_e2e, 5), "gflops": round(flops / (ms_e2e * 1e-3) / 1e9, 2),
                                      "steps": e2e_steps,
@@ -665,8 +735,8 @@ class Bench:
                                                    "second communicator" if self.world > 1 else
                                                    "none (one rank owns the whole batch)")},
             "model": model,
-            "kernels": [sharded._backend.plan.kernel_name(d) for d in range(len(shape) - 1)] if sharded.count else [],
-        }
+        })
+        return leg
 
 
 def worker(args, json_out, live_traffic=None):
@@ -678,7 +748,7 @@ def worker(args, json_out, live_traffic=None):
     shape, bases, cfg_idx = WORKLOADS[name]
     result = {"metric": METRIC}
     if strong:
-        leg = b.strong_leg(args.steps, args.warmup)
+        leg = b.strong_leg(args.steps, args.warmup, dump_dir=args.dump_outputs)
         r = leg["compute_shards_resident"]
         result.update({
             "value": r["gflops"], "unit": "GFLOP/s", "n_gpus": b.world, "ranks_seen": b.ranks_seen,
@@ -697,9 +767,10 @@ def worker(args, json_out, live_traffic=None):
             sharded = ShardedFFT(b.tdt, b.tdt, gshape, gshape, bases=bases, device=b.dev_index)
             x, out = b.make_input(shape)
             assert sharded.slab_in_shape == tuple(x.shape)
-            main = b.run_workload(name, args.steps, args.warmup, plan=sharded._backend.plan, x=x, out=out)
+            main = b.run_workload(name, args.steps, args.warmup, plan=sharded._backend.plan, x=x, out=out,
+                                  dump_dir=args.dump_outputs)
         else:
-            main = b.run_workload(name, args.steps, args.warmup)
+            main = b.run_workload(name, args.steps, args.warmup, dump_dir=args.dump_outputs)
         n_gpus = b.world
         value = flops_5nlogn(shape) * n_gpus / (main["ms_per_step"] * 1e-3) / 1e9
         result.update({
@@ -719,7 +790,8 @@ def worker(args, json_out, live_traffic=None):
         })
         del main
         b.torch.cuda.empty_cache()
-        if not args.no_strong_leg and name == DEFAULT_WORKLOAD and args.dtype == "f32" and not args.faithful:
+        if (args.full and not args.no_strong_leg and name == DEFAULT_WORKLOAD and args.dtype == "f32" and
+                not args.faithful):
             # The headline above is complete; the strong-scaling leg is an extra object and must never cost the line.
             # It is the only part of the run with point-to-point traffic between GPUs, so a watchdog bounds it: if it
             # has not finished in time, every rank leaves (rank 0 prints the line without the leg first).
@@ -741,7 +813,8 @@ def worker(args, json_out, live_traffic=None):
                 result["strong_config5"] = {"error": repr(e)[:300]}
             finally:
                 watchdog.cancel()
-        if b.world == 1 and not args.no_configs and name == DEFAULT_WORKLOAD and args.dtype == "f32" and not args.faithful:
+        if (args.full and b.world == 1 and not args.no_configs and name == DEFAULT_WORKLOAD and args.dtype == "f32" and
+                not args.faithful):
             cfgs = []
             for w in OTHER_BASELINE_CONFIGS:
                 c = b.run_workload(w, args.steps, args.warmup)
@@ -755,11 +828,11 @@ def worker(args, json_out, live_traffic=None):
                 b.torch.cuda.empty_cache()
             result["rfft_reference_bench"] = rf
     if b.rank == 0:
-        if b.world == 1 and not args.no_cpu_baseline and args.dtype == "f32":
+        if args.full and b.world == 1 and not args.no_cpu_baseline and args.dtype == "f32":
             result["cpu_baseline"] = cpu_baseline(shape, bases)
         want_vendor = args.vendor if args.vendor is not None else (
             b.world == 1 and name == DEFAULT_WORKLOAD and not strong and args.dtype == "f32" and not args.faithful)
-        if want_vendor and b.world == 1:
+        if args.full and want_vendor and b.world == 1:
             b.torch.cuda.synchronize()
             result["vendor_rocfft"] = vendor_compare()
         json_out.write(json.dumps(result) + "\n")
@@ -784,8 +857,8 @@ def main():
     # the child rocprofv3 would exec python3 out of an initialised process (the GPU pool refuses that exec)
     under_profiler = ("rocprofiler" in os.environ.get("LD_PRELOAD", "") or
                       any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ))
-    if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and headline and not args.no_live_pmc and
-            args.dtype == "f32" and not args.faithful and not under_profiler):
+    if (args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and headline and
+            not args.no_live_pmc and args.dtype == "f32" and not args.faithful and not under_profiler):
         # child processes under rocprofv3; this process has not touched the GPU yet.  Bounded: one failed or slow pass
         # ends the collection (the committed profiles are the fallback), and the whole of it gets at most 2 minutes
         t_live = time.perf_counter()

@@ -122,11 +122,12 @@ def test_bench_launcher_starts_one_process_per_rank():
     touched).  There is no GPU here, so each rank stops at the device check -- which is enough to see that two ranks
     with WORLD_SIZE=2 were started and that the launcher reports their failure."""
     import subprocess
+    if torch.cuda.is_available():
+        # before the launch: with a GPU, rank 0 would wait for a rank 1 that has no device of its own
+        pytest.skip("GPU present: covered by the -m gpu rehearsal test")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, env=env, timeout=300)
-    if torch.cuda.is_available():
-        pytest.skip("GPU present: covered by the -m gpu rehearsal test")
     assert r.returncode != 0
     assert r.stderr.count("bench.py needs a HIP device") == 2, r.stderr[-2000:]
     assert "rank exit codes" in r.stderr and r.stdout.strip() == ""

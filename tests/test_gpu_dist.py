@@ -72,7 +72,7 @@ def test_fft_from_root_runs_over_rccl_on_one_gpu():
 def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu",
-                        "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+                        "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -87,7 +87,7 @@ def test_bench_starts_its_own_ranks():
 
 def test_bench_single_gpu_line_carries_every_baseline_config():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3",
-                        "--no-cpu-baseline", "--no-compare-vendor"], capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--no-compare-vendor", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["roofline"]["bound"] == "hbm" and d["ramp"]["execs"] > 0

@@ -4,7 +4,7 @@ for w in 1d_100kx1024_radix2 1d_500kx128 1d_500kx93_radix31x3 2d_100x640x480 3d_
   for tag in "$@"; do
     lib=build_alt/$tag/libmifft.so
     [ "$tag" = default ] && lib=hackathon_fft_amd/csrc/libmifft.so
-    MIFFT_LIBRARY=$PWD/$lib timeout -k 10 120 python bench.py --workload $w --no-cpu-baseline --no-live-pmc --no-copy-ceiling --steps 200 --warmup 20 2>/dev/null | python -c "
+    MIFFT_LIBRARY=$PWD/$lib timeout -k 10 120 python bench.py --full --workload $w --no-cpu-baseline --no-live-pmc --no-copy-ceiling --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('%-14s %-24s %8.4f ms  ev %8.4f  %s' % ('$tag', d['config']['workload'], d['ms_per_step'], d['roofline']['launch_ms_hip_events'], d['config']['kernels']))"

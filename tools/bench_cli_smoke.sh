@@ -1,5 +1,5 @@
 set -o pipefail
-run() { python bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline --no-compare-vendor --no-live-pmc 2>/tmp/err.txt | python -c "
+run() { python bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline --no-compare-vendor --no-live-pmc 2>/tmp/err.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('OK', d['config']['workload'], d['scaling'], d['dtype'], d['ms_per_step'], d['roofline']['frac'] if 'roofline' in d else '-')" || { echo "FAIL $@"; tail -3 /tmp/err.txt; }; }

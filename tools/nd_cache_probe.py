@@ -54,8 +54,8 @@ def main():
             if m == 0:
                 ref = chk.split()[0] if chk else None
             same = bool(chk) and chk.split()[0] == ref
-            line = run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps", "300", "--warmup",
-                        "20", "--no-cpu-baseline"], env)
+            line = run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", wl, "--steps", "300",
+                        "--warmup", "20", "--no-cpu-baseline"], env)
             if not line:
                 continue
             d = json.loads(line)

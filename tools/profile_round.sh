@@ -13,7 +13,7 @@ out=$root/gpurun_out/prof_${tag}_$wl
 rm -rf $out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-FLAGS="--workload $wl --steps 100 --warmup 20 --no-cpu-baseline --no-configs --no-strong-leg --no-compare-vendor --no-live-pmc --no-copy-ceiling"
+FLAGS="--full --workload $wl --steps 100 --warmup 20 --no-cpu-baseline --no-configs --no-strong-leg --no-compare-vendor --no-live-pmc --no-copy-ceiling"
 # 0. the same command un-profiled on THIS box: the ms_per_step the profiled kernel durations must stay below
 python3 $root/bench.py $FLAGS > $out/bench_unprofiled.json 2> $out/bench_unprofiled.err || { echo "bench failed"; tail -5 $out/bench_unprofiled.err; exit 1; }
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $root/bench.py $FLAGS > $out/trace.log 2>&1 || { echo "trace failed"; tail -5 $out/trace.log; exit 1; }

@@ -8,7 +8,7 @@ mkdir -p $out
 cd $root
 for g in 17 18; do timeout -k 10 300 tools/tune/tune_tile_g$g > $out/tune_g$g.txt 2>&1 || echo "tune $g failed"; done
 timeout -k 10 900 python -m pytest tests/test_gpu_dist.py -x -q > $out/pytest_dist.log 2>&1; echo "pytest dist rc=$?"
-timeout -k 10 600 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 for wl in 2d_100x640x480 3d_10x128x128x128; do
   for m in 0 1 3; do

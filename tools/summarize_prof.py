@@ -119,7 +119,7 @@ algo = line["roofline"]["algorithmic_bytes_per_launch"]
 step_us = sum(k["avg_us"] * k["launches_per_step"] for k in kernels) if kernels else None
 res = {
     "tag": tag, "workload": wl,
-    "command": f"python3 bench.py --workload {wl} --steps {line['steps']} --warmup {line['warmup']} --no-cpu-baseline "
+    "command": f"python3 bench.py --full --workload {wl} --steps {line['steps']} --warmup {line['warmup']} --no-cpu-baseline "
                "--no-configs --no-strong-leg --no-compare-vendor",
     "bench_kernels": sorted(set(line["config"]["kernels"])),
     "launches_in_trace": n_all, "ramp_execs": line["ramp"]["execs"], "warmup": line["warmup"], "steps": line["steps"],
