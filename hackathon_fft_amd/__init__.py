@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     fft,
     fftn,
     ifftn,
+    irfftn,
     ordered_bases,
     plan_fft,
     rfftn,
@@ -20,5 +21,5 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "DeviceContext", "GPUTest", "Plan", "clear_plan_cache", "MifftError", "estimate_best_bases", "estimate_best_bases_nd",
-    "fft", "fftn", "ifftn", "ordered_bases", "plan_fft", "rfftn", "time_fft",
+    "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "rfftn", "time_fft",
 ]

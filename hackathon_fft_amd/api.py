@@ -33,6 +33,8 @@ if hasattr(torch, "uint16"):
 _OUT_DTYPES = (torch.float32, torch.float64)
 
 FLAG_FAITHFUL_STAGES = 1
+FLAG_HALF_SPECTRUM = 2  # MIFFT_FLAG_HALF_SPECTRUM: numpy's one-sided rfftn / irfftn layouts (include/mifft.h)
+ERR_UNSUPPORTED = -15   # MIFFT_ERR_UNSUPPORTED
 
 
 class GPUTest(enum.Enum):
@@ -112,22 +114,53 @@ def _check_layout_conditions_nd(in_shape: tuple, out_shape: tuple) -> None:
             raise MifftError(-2, "no inner dimension should be of size 1")
 
 
+def _check_half_layout(in_shape: tuple, out_shape: tuple, inverse: bool) -> tuple:
+    """Layouts of a half-spectrum plan (MIFFT_FLAG_HALF_SPECTRUM); returns the logical real dims d0..d{k-1}.
+    forward: x (batch, d0.., n, 1) -> out (batch, d0.., n // 2 + 1, 2); inverse: the other way round."""
+    rank = len(out_shape)
+    if rank <= 2 or len(in_shape) != rank:
+        raise MifftError(-1, "half-spectrum layouts are (batch, d0[, d1..], C) with equal ranks")
+    real, cplx = (out_shape, in_shape) if inverse else (in_shape, out_shape)
+    if real[-1] != 1:
+        raise MifftError(-3, f"the real side of a half-spectrum plan has 1 component, got {real[-1]}")
+    if cplx[-1] != 2:
+        raise MifftError(-3, f"the half-spectrum side of a plan has 2 components, got {cplx[-1]}")
+    dims = real[1:-1]
+    if any(d == 1 for d in dims):
+        raise MifftError(-2, "no inner dimension should be of size 1")
+    n = dims[-1]
+    if n % 2:
+        raise MifftError(ERR_UNSUPPORTED, f"half spectrum of an odd last dimension ({n}) is not supported")
+    if tuple(cplx[:-2]) != tuple(real[:-2]) or cplx[-2] != n // 2 + 1:
+        raise MifftError(-2, f"half-spectrum side {cplx} does not match the real side {real}: the last dimension "
+                             f"holds n // 2 + 1 = {n // 2 + 1} bins")
+    return dims
+
+
 class Plan:
-    """_GPUPlan (fft/fft/_ndim_fft_gpu.mojo:153-207): owns the device twiddle tables."""
+    """_GPUPlan (fft/fft/_ndim_fft_gpu.mojo:153-207): owns the device twiddle tables.
+
+    ``half_spectrum=True`` (no reference counterpart): numpy's one-sided layouts, see _check_half_layout."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
-                 device: int = 0, flags: int = 0, whole_batch: int = 0):
+                 device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
-        _check_layout_conditions_nd(in_shape, out_shape)
+        half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
+        if half_spectrum:
+            dims = _check_half_layout(in_shape, out_shape, bool(inverse))
+            flags = int(flags) | FLAG_HALF_SPECTRUM
+        else:
+            _check_layout_conditions_nd(in_shape, out_shape)
+            dims = out_shape[1:-1]
         if in_dtype not in _DTYPE_CODE or out_dtype not in _OUT_DTYPES:
             raise MifftError(-4, f"unsupported dtype {in_dtype} -> {out_dtype} (out_dtype must be floating point)")
-        dims = out_shape[1:-1]
         if bases is not None and len(bases) != len(dims):
             raise MifftError(-7, "The bases list should have the same outer size as the amount of internal "
                                  "dimensions. e.g. (batches, dim_0, dim_1, dim_2, 2) -> len(bases) == 3")
         self.in_dtype, self.out_dtype = in_dtype, out_dtype
         self.in_shape, self.out_shape = in_shape, out_shape
         self.inverse, self.device, self.flags = bool(inverse), int(device), int(flags)
+        self.half_spectrum = bool(half_spectrum)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if bases is not None:
             flat = [int(b) for bs in bases for b in bs]
@@ -198,7 +231,7 @@ class Plan:
 def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence[int], *, bases=None,
              inverse: bool = False, runtime_twfs: bool = True, max_cluster_size: int = 8,
              _test: Optional[GPUTest] = None, faithful_stages: bool = False,
-             ctx: Optional[DeviceContext] = None, whole_batch: int = 0) -> Plan:
+             ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False) -> Plan:
     """GPU overload of plan_fft (fft/fft/fft.mojo:161-210).
 
     ``runtime_twfs`` and ``max_cluster_size`` are accepted for call-site compatibility
@@ -207,13 +240,17 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     ``whole_batch`` (no reference counterpart): this plan covers one slab of a batch of that many transforms split over
     several plans / GPUs; size-dependent kernel choices follow the whole batch, so the slab's results equal the same
     rows of one plan over the whole batch bit for bit.
+    ``half_spectrum`` (no reference counterpart): numpy's one-sided layouts, forward (batch, d0.., n, 1) ->
+    (batch, d0.., n // 2 + 1, 2), inverse the other way round (include/mifft.h, MIFFT_FLAG_HALF_SPECTRUM).
     """
     del runtime_twfs, max_cluster_size
+    if half_spectrum:  # (layout errors before any device work)
+        _check_half_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout), bool(inverse))
     if ctx is None:
         ctx = DeviceContext()
     flags = FLAG_FAITHFUL_STAGES if (faithful_stages or _test is not None) else 0
     return Plan(in_dtype, out_dtype, in_layout, out_layout, bases=bases, inverse=inverse,
-                device=ctx.device, flags=flags, whole_batch=whole_batch)
+                device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum)
 
 
 def _check_tensor(t: "torch.Tensor", shape: tuple, dtype, device: int, what: str) -> None:
@@ -274,7 +311,8 @@ _PLAN_CACHE_SCRATCH_BYTES = 8 << 30  # ... and at most this much plan-owned scra
 _PLAN_CACHE_LOCK = threading.RLock()
 
 
-def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device) -> Plan:
+def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
+                 half_spectrum: bool = False) -> Plan:
     """Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
     costs a hipMalloc + copy per dimension, and its tables must outlive the kernels enqueued with it.
 
@@ -283,26 +321,31 @@ def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, fai
     (include/mifft.h).  Execs are ordered on a stream; the cache therefore keeps one plan PER STREAM -- two streams (or
     two threads on their own streams) transforming the same shape never share a plan -- and is guarded by a lock."""
     with _PLAN_CACHE_LOCK:
-        return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device)
+        return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
+                                   half_spectrum)
 
 
-def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device) -> Plan:
+def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
+                        half_spectrum: bool = False) -> Plan:
     key = (in_dtype, out_dtype, in_shape, out_shape,
            None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
-           bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream))
+           bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
+           bool(half_spectrum))
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         try:
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
-                            faithful_stages=faithful_stages, ctx=DeviceContext(device))
+                            faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
             # primes <= 97 otherwise, fft/fft/fft.mojo:49-104) rejects lengths with a larger prime factor.  The
             # numpy-style wrappers are this repository's own surface, so they retry with the full prime factorisation.
             if radices is not None or e.status not in (-5, -7):
                 raise
-            plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=[_prime_factors(int(n)) for n in in_shape[1:-1]],
-                            inverse=inverse, faithful_stages=faithful_stages, ctx=DeviceContext(device))
+            dims = _check_half_layout(in_shape, out_shape, inverse) if half_spectrum else in_shape[1:-1]
+            plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=[_prime_factors(int(n)) for n in dims],
+                            inverse=inverse, faithful_stages=faithful_stages, ctx=DeviceContext(device),
+                            half_spectrum=half_spectrum)
         _PLAN_CACHE[key] = plan
         while len(_PLAN_CACHE) > 1 and (len(_PLAN_CACHE) > _PLAN_CACHE_SIZE or
                                         sum(q.scratch_bytes for q in _PLAN_CACHE.values()) > _PLAN_CACHE_SCRATCH_BYTES):
@@ -364,10 +407,56 @@ def ifftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: b
     return _run(x, radices=radices, inverse=True, out_dtype=out_dtype, faithful_stages=faithful_stages)
 
 
-def rfftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False) -> "torch.Tensor":
+def rfftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False,
+          onesided: bool = False) -> "torch.Tensor":
     """Real-input transform: ``x`` is real ``(batch, d0..)``; returns the FULL spectrum as
-    interleaved ``(batch, d0.., 2)`` like the reference (fft/fft/_fft.mojo:254-257), not numpy's half spectrum."""
+    interleaved ``(batch, d0.., 2)`` like the reference (fft/fft/_fft.mojo:254-257), not numpy's half spectrum.
+    ``onesided=True``: numpy's / torch's rfftn instead, complex ``(batch, d0.., n // 2 + 1)`` (an even last dim)."""
     if x.is_complex():
         raise MifftError(-3, "rfftn expects a real tensor")
-    return _run(x.unsqueeze(-1), radices=radices, inverse=False, out_dtype=out_dtype,
-                faithful_stages=faithful_stages)
+    if not onesided:
+        return _run(x.unsqueeze(-1), radices=radices, inverse=False, out_dtype=out_dtype,
+                    faithful_stages=faithful_stages)
+    xr = x.unsqueeze(-1).contiguous()
+    in_shape = tuple(xr.shape)
+    out_shape = in_shape[:-2] + (in_shape[-2] // 2 + 1, 2)
+    _check_half_layout(in_shape, out_shape, False)
+    if out_dtype is None:
+        out_dtype = xr.dtype if xr.dtype in (torch.float32, torch.float64) else torch.float64
+    out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
+    with _PLAN_CACHE_LOCK:
+        plan = _cached_plan_locked(xr.dtype, out_dtype, in_shape, out_shape, radices, False, faithful_stages,
+                                   xr.device.index, half_spectrum=True)
+        fft(out, xr, DeviceContext(xr.device.index), plan=plan)
+    return torch.view_as_complex(out)
+
+
+def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtype=None) -> "torch.Tensor":
+    """Inverse of the one-sided rfftn (numpy.fft.irfftn(X, s=dims) over every dim but the first): ``X`` is complex
+    ``(batch, d0.., h)`` or interleaved ``(batch, d0.., h, 2)``; ``n`` is the length of the last real dimension (default
+    2 (h - 1); even, with n // 2 + 1 == h).  Returns real ``(batch, d0.., n)``, 1/N per dimension.  As numpy does, the
+    imaginary parts of bins 0 and n / 2 of the last dimension are ignored (after the other dimensions are transformed)."""
+    Xr = torch.view_as_real(X) if X.is_complex() else X
+    if Xr.dim() < 3 or Xr.shape[-1] != 2:
+        raise MifftError(-3, f"irfftn expects complex (batch, d0.., h) or interleaved (batch, d0.., h, 2), got "
+                             f"{tuple(X.shape)} {X.dtype}")
+    h = int(Xr.shape[-2])
+    n = 2 * (h - 1) if n is None else int(n)
+    if n % 2:
+        raise MifftError(ERR_UNSUPPORTED, f"irfftn of an odd length ({n}) is not supported")
+    if n // 2 + 1 != h:
+        raise MifftError(-2, f"irfftn: n = {n} needs n // 2 + 1 = {n // 2 + 1} bins, X has {h}")
+    if out_dtype is None:
+        out_dtype = Xr.dtype if Xr.dtype in (torch.float32, torch.float64) else torch.float64
+    if out_dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"irfftn: out_dtype must be float32 or float64, got {out_dtype}")
+    Xr = Xr.to(out_dtype).contiguous()  # (the inverse reads the plan's own float type)
+    in_shape = tuple(Xr.shape)
+    out_shape = in_shape[:-2] + (n, 1)
+    _check_half_layout(in_shape, out_shape, True)
+    out = torch.empty(out_shape, dtype=out_dtype, device=Xr.device)
+    with _PLAN_CACHE_LOCK:
+        plan = _cached_plan_locked(out_dtype, out_dtype, in_shape, out_shape, radices, True, False, Xr.device.index,
+                                   half_spectrum=True)
+        fft(out, Xr, DeviceContext(Xr.device.index), plan=plan)
+    return out.squeeze(-1)

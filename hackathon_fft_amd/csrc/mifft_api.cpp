@@ -28,6 +28,14 @@ int hip_error(hipError_t e, const char* what) {
 
 size_t Plan::in_elem_bytes() const { return dtype_size(in_dtype) * (size_t)in_components; }
 size_t Plan::out_elem_bytes() const { return dtype_size(out_dtype) * 2; }
+size_t Plan::in_row_bytes() const {
+    return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
+}
+size_t Plan::out_row_bytes() const {
+    if (!half_spectrum()) return (size_t)prod * out_elem_bytes();
+    return inverse ? (size_t)prod * dtype_size(out_dtype) : (size_t)prod_half * out_elem_bytes();
+}
+size_t Plan::scratch_row_bytes() const { return (size_t)(half_spectrum() ? prod_half : prod) * out_elem_bytes(); }
 
 // W_N^n = exp(-+ 2*pi*i*n/N), evaluated in long double and rounded once to the
 // output dtype (reference formula: fft/fft/_utils.mojo:63-104, which rounds theta
@@ -141,6 +149,7 @@ const char* mifft_status_string(int s) {
         case MIFFT_ERR_NULL: return "null argument";
         case MIFFT_ERR_ALIAS: return "x and out overlap";
         case MIFFT_ERR_BUFFER_TOO_SMALL: return "buffer too small";
+        case MIFFT_ERR_UNSUPPORTED: return "unsupported request";
     }
     return "unknown";
 }
@@ -215,6 +224,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         p.dims[i] = dims[i];
         p.prod *= dims[i];
     }
+    p.prod_half = p.prod / dims[ndim - 1] * (dims[ndim - 1] / 2 + 1);
 
     // ---- radix planning per dimension (host only; errors before any device use) ----
     std::vector<std::vector<uint32_t>> ordered(ndim), processed(ndim);
@@ -254,6 +264,16 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         }
     }
 
+    // ---- half-spectrum plans: what can be refused without a device is refused here ----
+    if (p.half_spectrum()) {
+        std::string why;
+        const int rc = half_spectrum_check(p, why);
+        if (rc) {
+            delete h;
+            return set_error(rc, why);
+        }
+    }
+
     // ---- device ----
     const int ndev = device_count_quiet();
     if (device < 0 || device >= ndev) {
@@ -289,6 +309,17 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
 
     // ---- passes in execution order: last dimension first ----
     p.stage_radices = ordered;
+    if (p.half_spectrum()) {  // its own route (half_spectrum.cpp); none of the selections below are involved
+        std::string why;
+        const int rc = build_half_spectrum(p, ordered, processed, why);
+        if (rc) {
+            free_plan_device(p);
+            delete h;
+            return rc == MIFFT_ERR_HIP ? rc : set_error(rc, why);
+        }
+        *out_plan = h;
+        return MIFFT_OK;
+    }
     auto upload_twiddles = [&](DimPass& ps) -> hipError_t {
         // (four-step rows inside LDS: the table of the row side, M / N1 points; the column side's goes to d_aux when it
         //  differs, the M-entry table to d_aux3)
@@ -640,7 +671,7 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
         return set_error(MIFFT_ERR_BAD_BATCH, "batch range out of bounds");
     if (count == 0) return MIFFT_OK;
     if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
-    const size_t in_row = (size_t)p.prod * p.in_elem_bytes(), out_row = (size_t)p.prod * p.out_elem_bytes();
+    const size_t in_row = p.in_row_bytes(), out_row = p.out_row_bytes();
     const char* xb = (const char*)x + (size_t)first * in_row;
     char* ob = (char*)out + (size_t)first * out_row;
     // out-of-place contract (reference: first stage reads x, all writes go elsewhere)
@@ -649,7 +680,7 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     DeviceGuard guard(p.device);
     MIFFT_HIP_TRY(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    char* sb = p.d_scratch ? (char*)p.d_scratch + (size_t)first * out_row : nullptr;
+    char* sb = p.d_scratch ? (char*)p.d_scratch + (size_t)first * p.scratch_row_bytes() : nullptr;
     auto buf = [&](int which) -> char* { return which == 0 ? (char*)xb : which == 2 ? sb : ob; };
     for (const DimPass& ps : p.passes) {
         const void* src = ps.src_buf >= 0 ? buf(ps.src_buf) : (ps.first ? (const char*)xb : ob);
@@ -695,11 +726,11 @@ int mifft_plan_num_launches(const mifft_plan* plan) {
 }
 
 size_t mifft_plan_in_bytes(const mifft_plan* plan) {
-    return plan ? (size_t)plan->p.batch * plan->p.prod * plan->p.in_elem_bytes() : 0;
+    return plan ? (size_t)plan->p.batch * plan->p.in_row_bytes() : 0;
 }
 
 size_t mifft_plan_out_bytes(const mifft_plan* plan) {
-    return plan ? (size_t)plan->p.batch * plan->p.prod * plan->p.out_elem_bytes() : 0;
+    return plan ? (size_t)plan->p.batch * plan->p.out_row_bytes() : 0;
 }
 
 size_t mifft_plan_scratch_bytes(const mifft_plan* plan) { return plan && plan->p.d_scratch ? plan->p.scratch_bytes : 0; }

@@ -91,6 +91,8 @@ struct DimPass {
     // kernel ONLY, `hs` says the selected kernel is one
     bool want_half = false, hs = false;
     bool r2c = false;  // packed real rows (TileCfg::R2C): the kernel runs N / 2 points; d_twiddle is that table, d_aux W_N^k
+    bool c2r = false;  // half spectrum -> packed real rows (TileCfg::C2R): the same tables as r2c
+    int64_t half_pitch = 0;  // R2C / C2R: row pitch (complex elements) of the half-spectrum side; 0 = N (full-spectrum rows)
     int store_lim = 0;
     bool regime_twin = false;  // select_fast took an entry tuned for a size regime (non-temporal twin): not to be traded for
                                // a runtime-specialised half-store kernel
@@ -131,6 +133,15 @@ struct Plan {
     int herm_axis = 1;
     size_t in_elem_bytes() const;
     size_t out_elem_bytes() const;  // bytes of one complex output element
+    // MIFFT_FLAG_HALF_SPECTRUM: the last dimension is stored as its n / 2 + 1 non-negative bins on the complex side
+    // (out of a forward plan, x of an inverse one); prod_half = prod / n * (n / 2 + 1)
+    bool half_spectrum() const { return (flags & MIFFT_FLAG_HALF_SPECTRUM) != 0; }
+    int64_t prod_half = 0;
+    // bytes of ONE transform (one batch entry) of x, out and the plan scratch: the slab offsets and the alias check of
+    // mifft_exec_batch and the size queries.  Without the flag: prod * in_elem_bytes(), prod * out_elem_bytes() twice.
+    size_t in_row_bytes() const;
+    size_t out_row_bytes() const;
+    size_t scratch_row_bytes() const;
 };
 
 // Hermitian twins: the trailing dimensions of the column space of the last pass (dims[1..ndim-1], at most three; absent
@@ -197,6 +208,22 @@ bool select_fast(const Plan& plan, DimPass& pass);
 bool select_dpp_rows(const Plan& plan, DimPass& pass);
 // the tile kernel specialised at plan time with hipRTC for a length without a table entry (kernels_jit.cpp)
 bool select_jit(const Plan& plan, DimPass& pass, std::string& why_not);
+// packed real rows of a half-spectrum plan (kernels_jit.cpp): R2C (forward) or C2R (inverse) for the last dimension, length
+// pass.N; half_rows_supported is the same check without a device (false + the reason: MIFFT_ERR_UNSUPPORTED)
+bool half_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_half_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+// the precompiled packed-row kernels (kernels_half_rows.hip): the configuration's TileCfg type text, the kernel, its LDS bytes
+struct HalfRowsKernel {
+    const char* cfg;
+    const void* fn;
+    size_t lds_bytes;
+};
+const HalfRowsKernel* half_rows_kernels(int* count);
+// plans with MIFFT_FLAG_HALF_SPECTRUM (half_spectrum.cpp): the checks that need no device, then the passes (a status;
+// plan.passes / d_scratch filled on success)
+int half_spectrum_check(const Plan& plan, std::string& why);
+int build_half_spectrum(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
+                        const std::vector<std::vector<uint32_t>>& processed, std::string& why);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

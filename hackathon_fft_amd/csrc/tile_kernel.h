@@ -34,7 +34,9 @@
 // columns that are not beyond their mirror image and store every result twice (TileCfg::HERM: contiguous runs of tiles, a
 // carried column so that mirrored lines leave whole); the pass in front of it stores only the half it reads (TileCfg::HS),
 // or -- three-pass plans -- the first pass does and the middle pass transforms a column prefix (TileParams::col_lim).
-// TileCfg::R2C (packed real rows) is a measured tie kept for the lab build.  Selection and policy: mifft_api.cpp, herm_pays().
+// TileCfg::R2C (packed real rows) is the first pass of a half-spectrum forward plan (and a measured tie as the half-store
+// first pass of the full-spectrum schedules, kept for the lab build); TileCfg::C2R, its mirror, is the last pass of a
+// half-spectrum inverse plan (half_spectrum.cpp).  Selection and policy: mifft_api.cpp, herm_pays().
 #pragma once
 
 #include "fft_radix.h"
@@ -140,9 +142,10 @@ struct TileParams {
     // HS configurations (the pass BEFORE a HERM last pass; a plane: its column side): results with an output index above
     // store_lim are not stored -- the last pass reads only the half of that dimension up to its middle and writes the rest
     int store_lim;
-    // R2C configurations: W_(2N)^k, k = 0 .. N (forward, whatever the plan's direction), and the row pitch of `out` (2 N)
+    // R2C / C2R configurations: W_(2N)^k, k = 0 .. N (forward, whatever the plan's direction), and the row pitch (complex
+    // elements) of the half-spectrum side: `out` of R2C (2 N in a full-spectrum plan, N + 1 in a half-spectrum one), `in` of C2R
     const void* r2c_tw;
-    long long out_pitch;
+    long long half_pitch;
     // column tiles of a pass that transforms only a PREFIX of its column space (the middle pass of a half-spectrum schedule):
     // columns from col_lim on are neither loaded nor stored (0 = all `inner` columns)
     long long col_lim;
@@ -232,7 +235,7 @@ constexpr int rader_lds_elems(int R, int inst, int esz) {
 template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int TILE_, int THREADS_, bool COLS_,
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
-          bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false>
+          bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -341,9 +344,18 @@ struct TileCfg {
     static constexpr bool R2C = R2C_;
     static_assert(!R2C_ || (!COLS_ && !LAST_DIRECT_ && !IN_REAL_ && !TSTORE_ && !FS1_ && !HERM_ && !HS_ && !DMA_),
                   "R2C: a row tile that leaves its last pass in LDS");
+    // C2R: the mirror of R2C, the last pass of a half-spectrum inverse.  A row of N + 1 bins X[0 .. N] of a 2 N-point REAL
+    // signal is folded into the N-point spectrum Z[k] = E[k] + i O[k] of the packed row z_n = x_2n + i x_2n+1 as it is loaded
+    // (E[k] = X[k] + conj X[N-k], O[k] = (X[k] - conj X[N-k]) W^-k, W = e^(-2 pi i / 2N); the imaginary parts of X[0] and X[N]
+    // are ignored, as numpy's irfft does), transformed back by the ordinary passes and stored as a plain row of N complex =
+    // 2 N reals with the scale 1 / 2N of the plan's pass.  Half the butterflies of a complex row.
+    static constexpr bool C2R = C2R_;
+    static_assert(!C2R_ || (!COLS_ && !FIRST_DIRECT_ && !IN_REAL_ && !TSTORE_ && !FS1_ && !HERM_ && !HS_ && !DMA_ && !R2C_ &&
+                            same_t<IT_, T_>::value && R0_ <= 32),
+                  "C2R: a row tile whose pass 0 reads the folded row from LDS");
     // inverse plans run conj(F(conj x)): complex input is conjugated as it is loaded (a real input is its own conjugate; the
-    // packed rows of R2C are unpacked first and conjugated as they are stored)
-    static constexpr bool CONJ_IN = !IN_REAL_ && !R2C_;
+    // packed rows of R2C are unpacked first and conjugated as they are stored; C2R conjugates the folded row it writes)
+    static constexpr bool CONJ_IN = !IN_REAL_ && !R2C_ && !C2R_;
     static_assert(!FS1_ || (COLS_ && FIRST_DIRECT_ && LAST_DIRECT_ && !TSTORE_ && !WSUB_), "FS1: a direct column tile");
     static constexpr int CPITCH = TSTORE_ ? TILE_ + 1 : TILE_;
     static_assert(!TSTORE_ || (COLS_ && !LAST_DIRECT_ && FIRST_DIRECT_), "TSTORE: column tile, last pass left in LDS");
@@ -1306,6 +1318,54 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 lds[lds_index<C, -1>(c, n)] = x;
             }
             __syncthreads();
+        } else if constexpr (C::C2R) {
+            // One thread per pair (k, N - k), k = 0 .. N / 2: X[k] and X[N - k] of the pitch-h row (two contiguous runs over the
+            // lanes), folded into Z[k] and Z[N - k].  A fixed number of pairs per thread, in groups of G whose loads are all
+            // issued before the first fold (G bounds the registers they hold); the pair index advances by a constant step (no
+            // division per element).
+            const V* gin = (const V*)p.in;
+            const V* w = (const V*)p.r2c_tw;
+            constexpr int PAIRS = C::N / 2 + 1, DC = C::THREADS / PAIRS, DK = C::THREADS - DC * PAIRS;
+            constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS, G = IT < 4 ? IT : 4;
+            const long long row0 = base / C::N;
+            const T s = p.inverse ? (T)-1 : (T)1;
+            int c = tid / PAIRS, k = tid - c * PAIRS;
+#pragma unroll 1
+            for (int i0 = 0; i0 < IT; i0 += G) {
+                int cs[G], ks[G];
+                V xk[G], xm[G];
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    cs[j] = (IT % G == 0 || i0 + j < IT) ? c : nv;  // (past the last pair: nothing to do)
+                    ks[j] = k;
+                    if (cs[j] < nv) {
+                        const V* row = gin + (row0 + c) * p.half_pitch;
+                        xk[j] = gload<(C::NT & 1) != 0>(row + k);
+                        xm[j] = gload<(C::NT & 1) != 0>(row + (C::N - k));  // (k = 0: X[N], the last bin of the row)
+                    }
+                    c += DC;
+                    k += DK;
+                    if (k >= PAIRS) {
+                        k -= PAIRS;
+                        ++c;
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    if (cs[j] < nv) {
+                        const int kk = ks[j];
+                        V a = xk[j], b = xm[j];
+                        if (kk == 0) a.y = b.y = (T)0;
+                        const V wk = w[kk];
+                        const T ex = a.x + b.x, ey = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
+                        const T ox = dx * wk.x + dy * wk.y, oy = dy * wk.x - dx * wk.y;  // O = D * conj(W^k)
+                        // Z[k] = E + i O, Z[N - k] = conj(E) + i conj(O); stored conjugated for the inverse (conj(F(conj Z)))
+                        lds[lds_index<C, -1>(cs[j], kk)] = {ex - oy, s * (ey + ox)};
+                        if (kk != 0 && 2 * kk != C::N) lds[lds_index<C, -1>(cs[j], C::N - kk)] = {ex + oy, s * (ox - ey)};
+                    }
+                }
+            }
+            __syncthreads();
         } else if constexpr (!C::FIRST_DIRECT) {
             // flat, fully coalesced HBM -> LDS copy of the tile (rows need not be 16-B aligned: N = 93)
             const V* gin = (const V*)p.in;
@@ -1451,7 +1511,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     b.x *= (T)p.scale;
                     b.y *= -(T)p.scale;
                 }
-                V* row = gout + (row0 + c) * p.out_pitch;
+                V* row = gout + (row0 + c) * p.half_pitch;
                 gstore<(C::NT & 2) != 0>(row + k, a);
                 if (2 * k != C::N) gstore<(C::NT & 2) != 0>(row + C::N - k, b);
             }

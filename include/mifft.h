@@ -23,7 +23,8 @@
  * (fft/fft/_fft.mojo:254-257), not numpy's half spectrum.  (For real input with 2..4
  * transformed dimensions the last pass may compute only half of the spectrum and store the
  * other half as its conjugate mirror image -- the same values to rounding, exactly Hermitian;
- * never with MIFFT_FLAG_FAITHFUL_STAGES.)
+ * never with MIFFT_FLAG_FAITHFUL_STAGES.)  MIFFT_FLAG_HALF_SPECTRUM plans take or give numpy's half spectrum
+ * instead (rfftn / irfftn; see the flag below).
  *
  * Environment (read ONCE per process, at the first plan; hackathon_fft_amd/csrc/mifft_config.h):
  *     MIFFT_JIT=0           no runtime specialisation (hipRTC): lengths without a precompiled kernel run
@@ -90,7 +91,9 @@ typedef enum {
     MIFFT_ERR_HIP = -11,           /* HIP runtime error; text via mifft_last_error()          */
     MIFFT_ERR_NULL = -12,          /* NULL plan / buffer                                      */
     MIFFT_ERR_ALIAS = -13,         /* x and out overlap (reference is out-of-place)           */
-    MIFFT_ERR_BUFFER_TOO_SMALL = -14
+    MIFFT_ERR_BUFFER_TOO_SMALL = -14,
+    MIFFT_ERR_UNSUPPORTED = -15    /* a valid request this library does not route (MIFFT_FLAG_HALF_SPECTRUM cases below);
+                                      the reason via mifft_last_error(); never silently worked around */
 } mifft_status;
 
 /* plan flags */
@@ -102,6 +105,28 @@ typedef enum {
  * specialised kernel exists for the dimension.  Mirrors the reference's
  * `_test=` code-path forcing (fft/fft/_ndim_fft_gpu.mojo:453-459). */
 #define MIFFT_FLAG_FAITHFUL_STAGES 1u
+/* Half-spectrum real transforms (numpy.fft.rfftn / irfftn over axes 1..ndim; no reference counterpart: the reference
+ * always produces the full spectrum, fft/fft/_fft.mojo:254-257).  `dims` are the LOGICAL REAL dims d0..d{k-1}; let
+ * h = d{k-1} / 2 + 1 and H = d0 * .. * d{k-2} * h.
+ *   forward (inverse = 0, in_components = 1, any in_dtype):
+ *       x   (batch, d0.., d{k-1}, 1)  ->  out (batch, d0.., h, 2)      = numpy rfftn
+ *   inverse (inverse = 1, in_components = 2, in_dtype == out_dtype in {F32, F64}):
+ *       x   (batch, d0.., h, 2)       ->  out (batch, d0.., d{k-1}, 1) = numpy irfftn(X, s = dims), 1/N per dimension;
+ *       after the other dimensions are inverse-transformed, the imaginary parts of bins 0 and d{k-1} / 2 are ignored
+ *       (numpy's handling of an input that is not Hermitian).  x is never written.
+ * mifft_plan_in_bytes / out_bytes are those sizes; an inverse plan with ndim >= 2 owns a scratch of H complex per batch
+ * entry (mifft_plan_scratch_bytes).  One launch per dimension: the packed real-row kernel of the last dimension (first
+ * in a forward plan, last in an inverse one) and an ordinary column pass per other dimension.
+ * A wrong in_components for the direction is MIFFT_ERR_BAD_COMPONENTS, a foreign in_dtype of an inverse plan
+ * MIFFT_ERR_BAD_DTYPE.  MIFFT_ERR_UNSUPPORTED (with the reason) for:
+ *   - an odd last dim, or one below 8;
+ *   - MIFFT_FLAG_FAITHFUL_STAGES together with this flag (the reference has no half spectrum to be faithful to);
+ *   - a last dim whose half d{k-1} / 2 has no packed configuration: a prime factor above 32, a last dim above 16384
+ *     (F64: above 8192), a row tile beyond 96 KiB of LDS;
+ *   - an outer dim above 4096 points (it would need the four-step routes), or one without a column kernel;
+ *   - MIFFT_JIT=0 and a last dim without a precompiled packed-row kernel: precompiled for 128, 480, 1024, 1080 and 1920
+ *     points (F32 and F64, input of the plan's own float type); every other length is specialised at run time. */
+#define MIFFT_FLAG_HALF_SPECTRUM 2u
 
 typedef struct mifft_plan mifft_plan;
 
