@@ -15,11 +15,12 @@ from .api import (  # noqa: F401
     irfftn,
     ordered_bases,
     plan_fft,
+    reduce_dims,
     rfftn,
     time_fft,
 )
 
 __all__ = [
     "DeviceContext", "GPUTest", "Plan", "clear_plan_cache", "MifftError", "estimate_best_bases", "estimate_best_bases_nd",
-    "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "rfftn", "time_fft",
+    "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "reduce_dims", "rfftn", "time_fft",
 ]

@@ -34,6 +34,15 @@ _OUT_DTYPES = (torch.float32, torch.float64)
 
 FLAG_FAITHFUL_STAGES = 1
 FLAG_HALF_SPECTRUM = 2  # MIFFT_FLAG_HALF_SPECTRUM: numpy's one-sided rfftn / irfftn layouts (include/mifft.h)
+MAX_DIMS = 6            # MIFFT_MAX_DIMS
+
+
+def FLAG_KEEP_DIM(d: int) -> int:
+    """MIFFT_FLAG_KEEP_DIM(d): dim d (0 = the first after the batch) is carried through untransformed"""
+    return 1 << (8 + int(d))
+
+
+FLAG_KEEP_MASK = 0x3F00
 ERR_UNSUPPORTED = -15   # MIFFT_ERR_UNSUPPORTED
 
 
@@ -137,13 +146,28 @@ def _check_half_layout(in_shape: tuple, out_shape: tuple, inverse: bool) -> tupl
     return dims
 
 
+def _keep_flags(rank: int, axes) -> int:
+    """keep bits (MIFFT_FLAG_KEEP_DIM) of the layout positions 1 .. rank - 2 NOT in ``axes`` (None: every one transformed)"""
+    if axes is None:
+        return 0
+    ax = [int(a) for a in axes]
+    for a in ax:
+        if not 1 <= a <= rank - 2:
+            raise MifftError(-2, f"axes are layout positions 1 .. {rank - 2} (the dims between batch and C), got {a}")
+    if len(set(ax)) != len(ax):
+        raise MifftError(-2, f"repeated axis in {tuple(ax)}")
+    return sum(FLAG_KEEP_DIM(p - 1) for p in range(1, rank - 1) if p not in ax)
+
+
 class Plan:
     """_GPUPlan (fft/fft/_ndim_fft_gpu.mojo:153-207): owns the device twiddle tables.
 
-    ``half_spectrum=True`` (no reference counterpart): numpy's one-sided layouts, see _check_half_layout."""
+    ``half_spectrum=True`` (no reference counterpart): numpy's one-sided layouts, see _check_half_layout.
+    ``axes`` (no reference counterpart): the layout positions (1 .. rank - 2) to transform; the others are carried through
+    untransformed (MIFFT_FLAG_KEEP_DIM).  None: all of them.  With ``bases``, a kept dim's list is empty."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
-                 device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False):
+                 device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         if half_spectrum:
@@ -157,9 +181,11 @@ class Plan:
         if bases is not None and len(bases) != len(dims):
             raise MifftError(-7, "The bases list should have the same outer size as the amount of internal "
                                  "dimensions. e.g. (batches, dim_0, dim_1, dim_2, 2) -> len(bases) == 3")
+        flags = int(flags) | _keep_flags(len(out_shape), axes)
         self.in_dtype, self.out_dtype = in_dtype, out_dtype
         self.in_shape, self.out_shape = in_shape, out_shape
         self.inverse, self.device, self.flags = bool(inverse), int(device), int(flags)
+        self.axes = None if axes is None else tuple(int(a) for a in axes)
         self.half_spectrum = bool(half_spectrum)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if bases is not None:
@@ -231,7 +257,8 @@ class Plan:
 def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence[int], *, bases=None,
              inverse: bool = False, runtime_twfs: bool = True, max_cluster_size: int = 8,
              _test: Optional[GPUTest] = None, faithful_stages: bool = False,
-             ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False) -> Plan:
+             ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False,
+             axes: Optional[Sequence[int]] = None) -> Plan:
     """GPU overload of plan_fft (fft/fft/fft.mojo:161-210).
 
     ``runtime_twfs`` and ``max_cluster_size`` are accepted for call-site compatibility
@@ -242,15 +269,18 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     rows of one plan over the whole batch bit for bit.
     ``half_spectrum`` (no reference counterpart): numpy's one-sided layouts, forward (batch, d0.., n, 1) ->
     (batch, d0.., n // 2 + 1, 2), inverse the other way round (include/mifft.h, MIFFT_FLAG_HALF_SPECTRUM).
+    ``axes`` (no reference counterpart): the layout positions 1 .. rank - 2 to transform, None = all of them; the others
+    are carried through untransformed (include/mifft.h, MIFFT_FLAG_KEEP_DIM).
     """
     del runtime_twfs, max_cluster_size
     if half_spectrum:  # (layout errors before any device work)
         _check_half_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout), bool(inverse))
+    _keep_flags(len(out_layout), axes)
     if ctx is None:
         ctx = DeviceContext()
     flags = FLAG_FAITHFUL_STAGES if (faithful_stages or _test is not None) else 0
     return Plan(in_dtype, out_dtype, in_layout, out_layout, bases=bases, inverse=inverse,
-                device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum)
+                device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum, axes=axes)
 
 
 def _check_tensor(t: "torch.Tensor", shape: tuple, dtype, device: int, what: str) -> None:
@@ -312,7 +342,7 @@ _PLAN_CACHE_LOCK = threading.RLock()
 
 
 def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                 half_spectrum: bool = False) -> Plan:
+                 half_spectrum: bool = False, axes=None) -> Plan:
     """Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
     costs a hipMalloc + copy per dimension, and its tables must outlive the kernels enqueued with it.
 
@@ -322,20 +352,21 @@ def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, fai
     two threads on their own streams) transforming the same shape never share a plan -- and is guarded by a lock."""
     with _PLAN_CACHE_LOCK:
         return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                                   half_spectrum)
+                                   half_spectrum, axes)
 
 
 def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                        half_spectrum: bool = False) -> Plan:
+                        half_spectrum: bool = False, axes=None) -> Plan:
     key = (in_dtype, out_dtype, in_shape, out_shape,
            None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
            bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
-           bool(half_spectrum))
+           bool(half_spectrum), _keep_flags(len(out_shape), axes))
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         try:
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
-                            faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum)
+                            faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
+                            axes=axes)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
             # primes <= 97 otherwise, fft/fft/fft.mojo:49-104) rejects lengths with a larger prime factor.  The
@@ -343,9 +374,10 @@ def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inver
             if radices is not None or e.status not in (-5, -7):
                 raise
             dims = _check_half_layout(in_shape, out_shape, inverse) if half_spectrum else in_shape[1:-1]
-            plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=[_prime_factors(int(n)) for n in dims],
+            bases = [_prime_factors(int(n)) if axes is None or p + 1 in axes else [] for p, n in enumerate(dims)]
+            plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=bases,
                             inverse=inverse, faithful_stages=faithful_stages, ctx=DeviceContext(device),
-                            half_spectrum=half_spectrum)
+                            half_spectrum=half_spectrum, axes=axes)
         _PLAN_CACHE[key] = plan
         while len(_PLAN_CACHE) > 1 and (len(_PLAN_CACHE) > _PLAN_CACHE_SIZE or
                                         sum(q.scratch_bytes for q in _PLAN_CACHE.values()) > _PLAN_CACHE_SCRATCH_BYTES):
@@ -379,63 +411,154 @@ def clear_plan_cache() -> None:
         _PLAN_CACHE.clear()
 
 
-def _run(x: "torch.Tensor", *, radices, inverse: bool, out_dtype, faithful_stages: bool) -> "torch.Tensor":
+def reduce_dims(shape: Sequence[int], dim) -> Optional[tuple]:
+    """torch ``dim=`` on a logical shape -> the plan that computes it without moving data: ``(layout_dims, axes)`` with
+    layout_dims = (batch, e0, .., ek) a reshape of ``shape`` and axes the layout positions (1 .. k + 1) to transform.
+    None when nothing is transformed (an empty ``dim``, or only size-1 dims: the identity).  Rules, in order:
+      1. size-1 dims are dropped (a length-1 transform is the identity);
+      2. the dims before the first transformed one fold into the batch (a batch of 1 when dim 0 is transformed);
+      3. runs of adjacent kept dims merge into one;
+    and at most MAX_DIMS dims may remain between batch and C (MifftError -1 otherwise).  Negative dims count from the end;
+    an out-of-range or repeated dim is MifftError -2.  Pure host logic: no tensor is touched."""
+    shape = tuple(int(v) for v in shape)
+    rank = len(shape)
+    dims = (dim,) if isinstance(dim, int) else tuple(dim)
+    norm = []
+    for d in dims:
+        d = int(d)
+        if not -rank <= d < rank:
+            raise MifftError(-2, f"dim {d} is out of range for a tensor of rank {rank}")
+        norm.append(d % rank)
+    if len(set(norm)) != len(norm):
+        raise MifftError(-2, f"repeated dim in {tuple(dims)}")
+    want = set(norm)
+    kept_run = []  # (size, transformed) of the dims that remain, size-1 dims dropped
+    for i, n in enumerate(shape):
+        if n != 1:
+            kept_run.append((n, i in want))
+    first = next((k for k, (_, t) in enumerate(kept_run) if t), None)
+    if first is None:
+        return None
+    batch = 1
+    for n, _ in kept_run[:first]:
+        batch *= n
+    out, axes = [], []
+    for n, t in kept_run[first:]:
+        if t:
+            out.append(n)
+            axes.append(len(out))
+        elif out and (len(out) not in axes):  # the previous dim is kept too: one merged dim
+            out[-1] *= n
+        else:
+            out.append(n)
+    if len(out) > MAX_DIMS:
+        raise MifftError(-1, f"dim={tuple(dims)} on {shape} leaves {len(out)} dims after merging the kept ones; at most "
+                             f"{MAX_DIMS} are supported")
+    return (batch,) + tuple(out), tuple(axes)
+
+
+def _dim_plan(logical: tuple, dim):
+    """(layout dims, axes) of a wrapper call; dim=None: every dim but the first, as without ``dim`` (axes None)"""
+    if dim is None:
+        return logical, None
+    r = reduce_dims(logical, dim)
+    if r is None:
+        return None, None
+    dims, axes = r
+    return dims, (None if len(axes) == len(dims) - 1 else axes)
+
+
+def _run(x: "torch.Tensor", *, radices, inverse: bool, out_dtype, faithful_stages: bool, dim=None) -> "torch.Tensor":
     xr, was_complex = _as_interleaved(x)
     if out_dtype is None:
         out_dtype = xr.dtype if xr.dtype in (torch.float32, torch.float64) else torch.float64
-    out_shape = tuple(xr.shape[:-1]) + (2,)
+    logical = tuple(xr.shape[:-1])
+    comps = int(xr.shape[-1])
+    layout, axes = _dim_plan(logical, dim)
+    if layout is None:  # nothing to transform: a converted copy, as torch returns
+        out = torch.zeros(logical + (2,), dtype=out_dtype, device=xr.device)
+        out[..., :comps] = xr.to(out_dtype)
+        return torch.view_as_complex(out) if was_complex else out
+    xr = xr.reshape(layout + (comps,))
+    out_shape = layout + (2,)
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
     # lookup AND enqueue under the cache lock: another thread that inserts a plan may evict (synchronise + close) only
     # plans that have nothing left to enqueue
     with _PLAN_CACHE_LOCK:
         plan = _cached_plan_locked(xr.dtype, out_dtype, tuple(xr.shape), out_shape, radices, inverse, faithful_stages,
-                                   xr.device.index)
+                                   xr.device.index, axes=axes)
         fft(out, xr, DeviceContext(xr.device.index), plan=plan)  # asynchronous on the current stream, like torch ops
+    out = out.reshape(logical + (2,))
     return torch.view_as_complex(out) if was_complex else out
 
 
-def fftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False) -> "torch.Tensor":
+def fftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False, dim=None) -> "torch.Tensor":
     """Forward C2C transform over every dim but the first (batch).  ``x``: complex
     ``(batch, d0..)`` or real-typed interleaved ``(batch, d0.., 2)``; ``radices``: one list per dim.
-    Asynchronous on the current torch stream; plans are cached per (shape, dtype, radices, device, stream), so
+    ``dim``: torch's ``dim=`` on the logical shape (without the trailing 2 of interleaved input); dim 0 and negative dims
+    allowed; the other dims are carried through untransformed (reduce_dims).  None: every dim but the first.  With
+    ``dim``, ``radices`` has one list per dim of the reduced layout (an empty one for a kept dim).
+    Asynchronous on the current torch stream; plans are cached per (shape, dtype, radices, dims, device, stream), so
     concurrent streams never share a plan's scratch (one exec in flight per plan, include/mifft.h)."""
-    return _run(x, radices=radices, inverse=False, out_dtype=out_dtype, faithful_stages=faithful_stages)
+    return _run(x, radices=radices, inverse=False, out_dtype=out_dtype, faithful_stages=faithful_stages, dim=dim)
 
 
-def ifftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False) -> "torch.Tensor":
-    """Inverse C2C transform (1/N per dimension), same layout rules as fftn."""
-    return _run(x, radices=radices, inverse=True, out_dtype=out_dtype, faithful_stages=faithful_stages)
+def ifftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False, dim=None) -> "torch.Tensor":
+    """Inverse C2C transform (1/N per transformed dimension), same layout and ``dim`` rules as fftn."""
+    return _run(x, radices=radices, inverse=True, out_dtype=out_dtype, faithful_stages=faithful_stages, dim=dim)
+
+
+def _halved_dim(logical: tuple, dim) -> int:
+    """the dim a one-sided transform halves: the last entry of ``dim`` (torch), which must be the innermost dim of size
+    above 1 -- the library halves the last dimension of its layout"""
+    rank = len(logical)
+    last = (int(dim) if isinstance(dim, int) else int(tuple(dim)[-1])) % rank
+    inner = max(i for i, n in enumerate(logical) if n != 1 or i == last)
+    if last != inner:
+        raise MifftError(ERR_UNSUPPORTED, f"a one-sided transform halves the last dim of `dim` ({last}); only the innermost "
+                                          f"dim of size above 1 ({inner}) is supported")
+    return last
 
 
 def rfftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: bool = False,
-          onesided: bool = False) -> "torch.Tensor":
+          onesided: bool = False, dim=None) -> "torch.Tensor":
     """Real-input transform: ``x`` is real ``(batch, d0..)``; returns the FULL spectrum as
     interleaved ``(batch, d0.., 2)`` like the reference (fft/fft/_fft.mojo:254-257), not numpy's half spectrum.
-    ``onesided=True``: numpy's / torch's rfftn instead, complex ``(batch, d0.., n // 2 + 1)`` (an even last dim)."""
+    ``onesided=True``: numpy's / torch's rfftn instead, complex ``(batch, d0.., n // 2 + 1)`` (an even last dim).
+    ``dim``: as fftn; one-sided, the last entry of ``dim`` is the halved dim and must be the innermost one."""
     if x.is_complex():
         raise MifftError(-3, "rfftn expects a real tensor")
     if not onesided:
         return _run(x.unsqueeze(-1), radices=radices, inverse=False, out_dtype=out_dtype,
-                    faithful_stages=faithful_stages)
+                    faithful_stages=faithful_stages, dim=dim)
     xr = x.unsqueeze(-1).contiguous()
+    logical = tuple(x.shape)
+    if out_dtype is None:
+        out_dtype = xr.dtype if xr.dtype in (torch.float32, torch.float64) else torch.float64
+    if dim is not None and len((dim,) if isinstance(dim, int) else tuple(dim)) > 0:
+        _halved_dim(logical, dim)
+    layout, axes = _dim_plan(logical, dim)
+    if layout is None:
+        return xr.squeeze(-1).to(out_dtype).to(torch.complex64 if out_dtype == torch.float32 else torch.complex128)
+    xr = xr.reshape(layout + (1,))
     in_shape = tuple(xr.shape)
     out_shape = in_shape[:-2] + (in_shape[-2] // 2 + 1, 2)
     _check_half_layout(in_shape, out_shape, False)
-    if out_dtype is None:
-        out_dtype = xr.dtype if xr.dtype in (torch.float32, torch.float64) else torch.float64
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
         plan = _cached_plan_locked(xr.dtype, out_dtype, in_shape, out_shape, radices, False, faithful_stages,
-                                   xr.device.index, half_spectrum=True)
+                                   xr.device.index, half_spectrum=True, axes=axes)
         fft(out, xr, DeviceContext(xr.device.index), plan=plan)
-    return torch.view_as_complex(out)
+    return torch.view_as_complex(out.reshape(logical[:-1] + (logical[-1] // 2 + 1, 2)))
 
 
-def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtype=None) -> "torch.Tensor":
+def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtype=None, dim=None) -> "torch.Tensor":
     """Inverse of the one-sided rfftn (numpy.fft.irfftn(X, s=dims) over every dim but the first): ``X`` is complex
     ``(batch, d0.., h)`` or interleaved ``(batch, d0.., h, 2)``; ``n`` is the length of the last real dimension (default
     2 (h - 1); even, with n // 2 + 1 == h).  Returns real ``(batch, d0.., n)``, 1/N per dimension.  As numpy does, the
-    imaginary parts of bins 0 and n / 2 of the last dimension are ignored (after the other dimensions are transformed)."""
+    imaginary parts of bins 0 and n / 2 of the last dimension are ignored (after the other dimensions are transformed).
+    ``dim``: as fftn, on the complex logical shape; ``n`` applies to the last entry of ``dim``, which must be the
+    innermost dim."""
     Xr = torch.view_as_real(X) if X.is_complex() else X
     if Xr.dim() < 3 or Xr.shape[-1] != 2:
         raise MifftError(-3, f"irfftn expects complex (batch, d0.., h) or interleaved (batch, d0.., h, 2), got "
@@ -451,12 +574,20 @@ def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtyp
     if out_dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"irfftn: out_dtype must be float32 or float64, got {out_dtype}")
     Xr = Xr.to(out_dtype).contiguous()  # (the inverse reads the plan's own float type)
+    logical = tuple(Xr.shape[:-1])
+    axes = None
+    if dim is not None:
+        if len((dim,) if isinstance(dim, int) else tuple(dim)) == 0:
+            raise MifftError(-2, "irfftn: an empty dim has no last dim to take n from")
+        _halved_dim(logical, dim)
+        layout, axes = _dim_plan(logical, dim)
+        Xr = Xr.reshape(layout + (2,))
     in_shape = tuple(Xr.shape)
     out_shape = in_shape[:-2] + (n, 1)
     _check_half_layout(in_shape, out_shape, True)
     out = torch.empty(out_shape, dtype=out_dtype, device=Xr.device)
     with _PLAN_CACHE_LOCK:
         plan = _cached_plan_locked(out_dtype, out_dtype, in_shape, out_shape, radices, True, False, Xr.device.index,
-                                   half_spectrum=True)
+                                   half_spectrum=True, axes=axes)
         fft(out, Xr, DeviceContext(Xr.device.index), plan=plan)
-    return out.squeeze(-1)
+    return out.reshape(logical[:-1] + (n,))

@@ -64,7 +64,7 @@ int half_spectrum_check(const Plan& p, std::string& why) {
         return MIFFT_ERR_UNSUPPORTED;
     }
     for (int i = 0; i + 1 < p.ndim; ++i)
-        if (p.dims[i] > kMaxColumn) {
+        if (!p.kept(i) && p.dims[i] > kMaxColumn) {
             why = "half spectrum: dimension " + std::to_string(i) + " (" + std::to_string(p.dims[i]) +
                   " points) is longer than one column tile (" + std::to_string(kMaxColumn) + ")";
             return MIFFT_ERR_UNSUPPORTED;
@@ -139,11 +139,14 @@ int build_half_spectrum(Plan& p, const std::vector<std::vector<uint32_t>>& order
         r.first = true;
         rc = rows(r);
         for (int j = nd - 2; j >= 0 && rc == MIFFT_OK; --j) {
+            if (p.kept(j)) continue;  // (MIFFT_FLAG_KEEP_DIM: carried through, counted in the inner / outer of the others)
             DimPass c;  // in place on out
             rc = column(j, c);
         }
     } else {
-        if (nd >= 2) {
+        int ncols = 0;  // column passes (the dimensions before the last one that are not kept)
+        for (int j = 0; j + 1 < nd; ++j) ncols += p.kept(j) ? 0 : 1;
+        if (ncols > 0) {
             p.scratch_bytes = (size_t)p.batch * p.scratch_row_bytes();
             if (p.scratch_bytes > 0) {
                 const hipError_t e = hipMalloc(&p.d_scratch, p.scratch_bytes);
@@ -154,16 +157,19 @@ int build_half_spectrum(Plan& p, const std::vector<std::vector<uint32_t>>& order
                 }
             }
         }
+        bool from_x = true;
         for (int j = nd - 2; j >= 0 && rc == MIFFT_OK; --j) {
+            if (p.kept(j)) continue;
             DimPass c;
-            c.src_buf = j == nd - 2 ? 0 : 2;  // x -> scratch, then in place on the scratch
+            c.src_buf = from_x ? 0 : 2;  // x -> scratch, then in place on the scratch
             c.dst_buf = 2;
+            from_x = false;
             rc = column(j, c);
         }
         if (rc == MIFFT_OK) {
             DimPass r;
-            r.first = nd == 1;
-            r.src_buf = nd == 1 ? 0 : 2;
+            r.first = ncols == 0;
+            r.src_buf = ncols == 0 ? 0 : 2;
             r.dst_buf = 1;
             rc = rows(r);
         }

@@ -195,38 +195,40 @@ static hipError_t launch_one(const GenericParams& gp, int grid, int threads, siz
     return hipGetLastError();
 }
 
-template <typename T>
+// the first pass reads x: any element type, real or complex; ROWS = false is a strided first pass (a plan with kept
+// dimensions after the first transformed one, MIFFT_FLAG_KEEP_DIM)
+template <typename T, bool ROWS>
 static hipError_t launch_first(const Plan& plan, const GenericParams& gp, int grid, int threads, size_t lds,
                                hipStream_t s, bool prep = false) {
     const int c = plan.in_components;
     switch (plan.in_dtype) {
         case MIFFT_F32:
-            return c == 1 ? launch_one<T, float, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, float, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, float, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, float, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_F64:
-            return c == 1 ? launch_one<T, double, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, double, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, double, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, double, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_U8:
-            return c == 1 ? launch_one<T, unsigned char, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, unsigned char, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, unsigned char, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, unsigned char, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_I32:
-            return c == 1 ? launch_one<T, int, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, int, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, int, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, int, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_I8:
-            return c == 1 ? launch_one<T, signed char, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, signed char, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, signed char, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, signed char, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_I16:
-            return c == 1 ? launch_one<T, short, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, short, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, short, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, short, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_U16:
-            return c == 1 ? launch_one<T, unsigned short, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, unsigned short, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, unsigned short, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, unsigned short, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_F16:
-            return c == 1 ? launch_one<T, _Float16, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, _Float16, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, _Float16, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, _Float16, 2, ROWS>(gp, grid, threads, lds, s, prep);
         case MIFFT_BF16:
-            return c == 1 ? launch_one<T, bf16_t, 1, true>(gp, grid, threads, lds, s, prep)
-                          : launch_one<T, bf16_t, 2, true>(gp, grid, threads, lds, s, prep);
+            return c == 1 ? launch_one<T, bf16_t, 1, ROWS>(gp, grid, threads, lds, s, prep)
+                          : launch_one<T, bf16_t, 2, ROWS>(gp, grid, threads, lds, s, prep);
     }
     return hipErrorInvalidValue;
 }
@@ -236,9 +238,12 @@ static hipError_t dispatch_generic(const Plan& plan, const DimPass& pass, const 
                                    hipStream_t stream, bool prep) {
     const bool rows = pass.inner == 1;
     const bool f32 = plan.out_dtype == MIFFT_F32;
+    if (pass.first && rows)
+        return f32 ? launch_first<float, true>(plan, gp, grid, pass.threads, pass.lds_bytes, stream, prep)
+                   : launch_first<double, true>(plan, gp, grid, pass.threads, pass.lds_bytes, stream, prep);
     if (pass.first)
-        return f32 ? launch_first<float>(plan, gp, grid, pass.threads, pass.lds_bytes, stream, prep)
-                   : launch_first<double>(plan, gp, grid, pass.threads, pass.lds_bytes, stream, prep);
+        return f32 ? launch_first<float, false>(plan, gp, grid, pass.threads, pass.lds_bytes, stream, prep)
+                   : launch_first<double, false>(plan, gp, grid, pass.threads, pass.lds_bytes, stream, prep);
     if (rows)
         return f32 ? launch_one<float, float, 2, true>(gp, grid, pass.threads, pass.lds_bytes, stream, prep)
                    : launch_one<double, double, 2, true>(gp, grid, pass.threads, pass.lds_bytes, stream, prep);
@@ -286,10 +291,6 @@ bool select_generic(const Plan& plan, DimPass& pass, std::string& why_not) {
     const size_t max_lds = 160 * 1024;
     const bool rows = pass.inner == 1;
     const int64_t N = pass.N;
-    if (pass.first && !rows) {
-        why_not = "internal: first pass must be the contiguous dimension";
-        return false;
-    }
     // LDS row pitch: odd for column tiles so that the transposing HBM->LDS
     // writes of adjacent columns land on distinct banks.
     int64_t ld = rows ? N : (N | 1);

@@ -207,6 +207,20 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         if (dims[i] < 2) return set_error(MIFFT_ERR_BAD_DIM, "no inner dimension should be of size 1");
     if ((bases_flat == nullptr) != (bases_len == nullptr))
         return set_error(MIFFT_ERR_NULL, "bases_flat and bases_len must both be given or both be NULL");
+    // ---- kept dimensions (MIFFT_FLAG_KEEP_DIM; axes.cpp) ----
+    const uint32_t keep = (flags & MIFFT_FLAG_KEEP_MASK) >> 8;
+    if (keep) {
+        if (keep >> ndim)
+            return set_error(MIFFT_ERR_BAD_DIM, "MIFFT_FLAG_KEEP_DIM names a dimension at or beyond ndim (" + std::to_string(ndim) + ")");
+        if (keep == (1u << ndim) - 1u) return set_error(MIFFT_ERR_BAD_DIM, "every dimension is kept: no dimension to transform");
+        if (flags & MIFFT_FLAG_FAITHFUL_STAGES)
+            return set_error(MIFFT_ERR_UNSUPPORTED,
+                             "MIFFT_FLAG_KEEP_DIM with MIFFT_FLAG_FAITHFUL_STAGES: the reference has no axes to be faithful to");
+        if (bases_len)
+            for (int i = 0; i < ndim; ++i)
+                if (((keep >> i) & 1u) && bases_len[i] != 0)
+                    return set_error(MIFFT_ERR_BAD_BASES, "dimension " + std::to_string(i) + " is kept: its bases_len must be 0");
+    }
 
     mifft_plan* h = new mifft_plan();
     Plan& p = h->p;
@@ -230,6 +244,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
     std::vector<std::vector<uint32_t>> ordered(ndim), processed(ndim);
     const uint32_t* bp = bases_flat;
     for (int i = 0; i < ndim; ++i) {
+        if (p.kept(i)) continue;  // (no stages: mifft_plan_stages() reports 0)
         std::vector<uint64_t> user;
         if (bases_flat) {
             if (bases_len[i] < 0) {
@@ -253,7 +268,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
     {
         double inner = 1.0;
         for (int i = ndim - 1; i >= 0; --i) {
-            if (i < ndim - 1 && (double)dims[i] * inner + 64.0 >= 4294967296.0) {
+            if (i < ndim - 1 && !p.kept(i) && (double)dims[i] * inner + 64.0 >= 4294967296.0) {
                 delete h;
                 return set_error(MIFFT_ERR_TOO_LARGE,
                                  "dimension " + std::to_string(i) + " (" + std::to_string(dims[i]) + " points at stride " +
@@ -264,7 +279,15 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         }
     }
 
-    // ---- half-spectrum plans: what can be refused without a device is refused here ----
+    // ---- half-spectrum and masked plans: what can be refused without a device is refused here ----
+    if (p.keep_mask()) {
+        std::string why;
+        const int rc = axes_check(p, why);
+        if (rc) {
+            delete h;
+            return set_error(rc, why);
+        }
+    }
     if (p.half_spectrum()) {
         std::string why;
         const int rc = half_spectrum_check(p, why);
@@ -309,9 +332,9 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
 
     // ---- passes in execution order: last dimension first ----
     p.stage_radices = ordered;
-    if (p.half_spectrum()) {  // its own route (half_spectrum.cpp); none of the selections below are involved
+    if (p.keep_mask() || p.half_spectrum()) {  // their own routes (axes.cpp, half_spectrum.cpp); none of the selections below
         std::string why;
-        const int rc = build_half_spectrum(p, ordered, processed, why);
+        const int rc = p.keep_mask() ? build_axes(p, ordered, processed, why) : build_half_spectrum(p, ordered, processed, why);
         if (rc) {
             free_plan_device(p);
             delete h;
@@ -715,6 +738,7 @@ int mifft_plan_stages(const mifft_plan* plan, int dim, uint32_t* radices_out, in
 
 const char* mifft_plan_kernel_name(const mifft_plan* plan, int dim) {
     if (!plan) return "";
+    if (dim >= 0 && dim < plan->p.ndim && plan->p.kept(dim)) return "none";
     for (const DimPass& ps : plan->p.passes)
         if (ps.dim_index == dim || ps.dim_index2 == dim) return ps.kernel_name;
     return "";

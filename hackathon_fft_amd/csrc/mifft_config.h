@@ -79,6 +79,8 @@ struct Config {
                                      // MIFFT_HERM=0 never (A/B baseline), MIFFT_HERM=2 wherever a twin exists (small test shapes)
     int grid_per_cu = 0;             // forces the persistent grid of every table kernel (tools/grid_sweep.py)
     std::string jit_defines;         // extra -D options for the runtime compiler (A/B of kernel-header macros)
+    bool ilv = true;                 // interleaved block tiles for small kept strides of masked plans (MIFFT_ILV=0: the column
+                                     // tiles instead; same-call A/B of tools/axes_probe.py)
     bool test_fail_scratch_alloc = false;  // -DMIFFT_TESTING: the next scratch allocation reports out-of-memory
 };
 
@@ -114,6 +116,7 @@ inline Config load_config() {
     if (const char* v = env("MIFFT_HERM")) c.herm = v[0] == '0' ? 0 : v[0] == '2' ? 2 : 1;
     if (const char* v = env("MIFFT_GRID_PER_CU")) c.grid_per_cu = atoi(v);
     if (const char* v = env("MIFFT_JIT_DEFINES")) c.jit_defines = v;
+    if (const char* v = env("MIFFT_ILV")) c.ilv = v[0] != '0';
     if (const char* v = env("MIFFT_RADER_MIN")) c.rader_min = c.rader_min_pair = atoi(v);
     if (const char* v = env("MIFFT_RADER_PAD_MIN")) c.rader_pad_min = atoi(v);
 #endif

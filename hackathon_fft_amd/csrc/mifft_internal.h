@@ -94,6 +94,7 @@ struct DimPass {
     bool c2r = false;  // half spectrum -> packed real rows (TileCfg::C2R): the same tables as r2c
     int64_t half_pitch = 0;  // R2C / C2R: row pitch (complex elements) of the half-spectrum side; 0 = N (full-spectrum rows)
     int store_lim = 0;
+    bool ilv = false;  // interleaved block tile (TileCfg::ILV): `inner` (< 128 B of elements) transforms per block, launched as rows
     bool regime_twin = false;  // select_fast took an entry tuned for a size regime (non-temporal twin): not to be traded for
                                // a runtime-specialised half-store kernel
 };
@@ -136,6 +137,9 @@ struct Plan {
     // MIFFT_FLAG_HALF_SPECTRUM: the last dimension is stored as its n / 2 + 1 non-negative bins on the complex side
     // (out of a forward plan, x of an inverse one); prod_half = prod / n * (n / 2 + 1)
     bool half_spectrum() const { return (flags & MIFFT_FLAG_HALF_SPECTRUM) != 0; }
+    // MIFFT_FLAG_KEEP_DIM: dims left untransformed (bit d = dim d)
+    uint32_t keep_mask() const { return (flags & MIFFT_FLAG_KEEP_MASK) >> 8; }
+    bool kept(int d) const { return ((keep_mask() >> d) & 1u) != 0; }
     int64_t prod_half = 0;
     // bytes of ONE transform (one batch entry) of x, out and the plan scratch: the slab offsets and the alias check of
     // mifft_exec_batch and the size queries.  Without the flag: prod * in_elem_bytes(), prod * out_elem_bytes() twice.
@@ -208,6 +212,13 @@ bool select_fast(const Plan& plan, DimPass& pass);
 bool select_dpp_rows(const Plan& plan, DimPass& pass);
 // the tile kernel specialised at plan time with hipRTC for a length without a table entry (kernels_jit.cpp)
 bool select_jit(const Plan& plan, DimPass& pass, std::string& why_not);
+// interleaved block tile (TileCfg::ILV) of a masked plan's pass whose stride pass.inner holds fewer than 128 B of elements:
+// false (+ the reason) when the length or the block does not fit it
+bool select_jit_ilv(const Plan& plan, DimPass& pass, std::string& why_not);
+// plans with a keep bit (MIFFT_FLAG_KEEP_DIM, axes.cpp): the checks that need no device, then the passes
+int axes_check(const Plan& plan, std::string& why);
+int build_axes(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
+               const std::vector<std::vector<uint32_t>>& processed, std::string& why);
 // packed real rows of a half-spectrum plan (kernels_jit.cpp): R2C (forward) or C2R (inverse) for the last dimension, length
 // pass.N; half_rows_supported is the same check without a device (false + the reason: MIFFT_ERR_UNSUPPORTED)
 bool half_rows_supported(const Plan& plan, int64_t n, std::string& why_not);

@@ -235,7 +235,8 @@ constexpr int rader_lds_elems(int R, int inst, int esz) {
 template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int TILE_, int THREADS_, bool COLS_,
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
-          bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false>
+          bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
+          int ILV_ = 0>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -357,6 +358,16 @@ struct TileCfg {
     // packed rows of R2C are unpacked first and conjugated as they are stored; C2R conjugates the folded row it writes)
     static constexpr bool CONJ_IN = !IN_REAL_ && !R2C_ && !C2R_;
     static_assert(!FS1_ || (COLS_ && FIRST_DIRECT_ && LAST_DIRECT_ && !TSTORE_ && !WSUB_), "FS1: a direct column tile");
+    // ILV (interleaved blocks, I = ILV_ > 0): a row-shaped tile over TILE / I consecutive blocks of an (outer, N, I) tensor
+    // -- the pass over a dimension whose kept trailing dimensions hold I < 128 B of elements.  Transform t = g * I + c of the
+    // tile takes element n from flat index g * N * I + n * I + c of its block run: the tile's footprint is ONE flat run of
+    // TILE * N elements, copied HBM <-> LDS by the flat loops (every wave access contiguous), and the stride-I gather into
+    // the per-transform rows of LDS happens on the LDS side.  ROWPAD_ spreads the I transforms a 16-lane group of the copy
+    // touches over the banks (kernels_jit.cpp, ilv_rowpad).  The passes are the row tile's.
+    static constexpr int ILV = ILV_;
+    static_assert(!ILV_ || (!COLS_ && !FIRST_DIRECT_ && !LAST_DIRECT_ && TILE_ % ILV_ == 0 && !TSTORE_ && !FS1_ && !HERM_ &&
+                            !HS_ && !R2C_ && !C2R_ && !DMA_ && R0_ <= 32),
+                  "ILV: a row tile of whole blocks staged by the flat copies");
     static constexpr int CPITCH = TSTORE_ ? TILE_ + 1 : TILE_;
     static_assert(!TSTORE_ || (COLS_ && !LAST_DIRECT_ && FIRST_DIRECT_), "TSTORE: column tile, last pass left in LDS");
     static constexpr int DATA_ELEMS = COLS_ ? N_ * CPITCH : LD * TILE_;
@@ -496,6 +507,87 @@ MIFFT_DEV void vm_drain() {
 MIFFT_DEV void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+// flat offset f of a row tile's footprint -> (transform c of the tile, element n): rows f = c N + n; ILV blocks
+// f = g N I + n I + ci with c = g I + ci (constant divisors)
+template <class C>
+MIFFT_DEV void ilv_decode(int f, int& c, int& n) {
+    if constexpr (C::ILV > 0) {
+        constexpr int I = C::ILV;
+        const int g = f / (C::N * I), r = f - g * (C::N * I);
+        n = r / I;
+        c = g * I + (r - n * I);
+    } else {
+        c = f / C::N;
+        n = f - c * C::N;
+    }
+}
+
+// ILV: the flat copies of the tile's run of `total` elements, in chunks of up to 16 elements per thread whose HBM accesses
+// are all issued before the first LDS access (a load-then-write loop keeps one load in flight per wave: 12-25 % of HBM
+// bandwidth).  Loads past the end of a ragged last tile re-read its last element (branch-free; never stored).
+template <class C>
+MIFFT_DEV void ilv_load(const TileParams& p, cpx<typename C::T>* lds, long long base, int total, int tid) {
+    using T = typename C::T;
+    using V = cpx<T>;
+    constexpr int IT = (C::TILE * C::N + C::THREADS - 1) / C::THREADS, CH = IT < 16 ? IT : 16;
+#pragma unroll 1
+    for (int k0 = 0; k0 < IT; k0 += CH) {
+        V x[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            int f = tid + (k0 + j) * C::THREADS;
+            f = f < total ? f : total - 1;
+            if constexpr (!same_t<typename C::IT, T>::value)
+                x[j] = load_foreign<C>(p.in, base + f);
+            else if constexpr (C::IN_REAL)
+                x[j] = {gload_real<(C::NT & 1) != 0>((const T*)p.in + base + f), (T)0};
+            else
+                x[j] = gload<(C::NT & 1) != 0>((const V*)p.in + base + f);
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int f = tid + (k0 + j) * C::THREADS;
+            if ((IT % CH == 0 || k0 + j < IT) && f < total) {
+                int c, n;
+                ilv_decode<C>(f, c, n);
+                V v = x[j];
+                if (p.inverse && C::CONJ_IN) v.y = -v.y;
+                lds[lds_index<C, -1>(c, n)] = v;
+            }
+        }
+    }
+}
+template <class C>
+MIFFT_DEV void ilv_store(const TileParams& p, const cpx<typename C::T>* lds, long long base, int total, int tid) {
+    using T = typename C::T;
+    using V = cpx<T>;
+    constexpr int IT = (C::TILE * C::N + C::THREADS - 1) / C::THREADS, CH = IT < 16 ? IT : 16;
+    V* gout = (V*)p.out;
+#pragma unroll 1
+    for (int k0 = 0; k0 < IT; k0 += CH) {
+        V y[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            int f = tid + (k0 + j) * C::THREADS, c, n;
+            f = f < total ? f : total - 1;
+            ilv_decode<C>(f, c, n);
+            y[j] = lds[lds_index<C, C::NP - 1>(c, n)];
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int f = tid + (k0 + j) * C::THREADS;
+            if ((IT % CH == 0 || k0 + j < IT) && f < total) {
+                V v = y[j];
+                if (p.inverse) {
+                    v.x *= (T)p.scale;
+                    v.y *= -(T)p.scale;
+                }
+                gstore<(C::NT & 2) != 0>(gout + base + f, v);
+            }
+        }
+    }
 }
 
 // FS1: tile t = (outer o, n2, column tile): load base / store base / twiddle row n2
@@ -1366,6 +1458,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 }
             }
             __syncthreads();
+        } else if constexpr (C::ILV > 0) {
+            ilv_load<C>(p, lds, base, nv * C::N, tid);
+            __syncthreads();
         } else if constexpr (!C::FIRST_DIRECT) {
             // flat, fully coalesced HBM -> LDS copy of the tile (rows need not be 16-B aligned: N = 93)
             const V* gin = (const V*)p.in;
@@ -1515,6 +1610,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 gstore<(C::NT & 2) != 0>(row + k, a);
                 if (2 * k != C::N) gstore<(C::NT & 2) != 0>(row + C::N - k, b);
             }
+            __syncthreads();
+        } else if constexpr (C::ILV > 0) {
+            ilv_store<C>(p, lds, base, nv * C::N, tid);
             __syncthreads();
         } else if constexpr (!C::LAST_DIRECT) {
             V* gout = (V*)p.out;

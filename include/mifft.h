@@ -35,7 +35,7 @@
  * Nothing else is configurable in libmifft.so: every size threshold of the plan-time policy is a
  * constant derived from the 256-MiB Infinity Cache (kInfinityCacheBytes).  The measurement switches the
  * scripts under tools/ use (MIFFT_ND_CACHE, MIFFT_NTS_*, MIFFT_FOURSTEP_*, MIFFT_FS_*, MIFFT_ROW2D,
- * MIFFT_JIT_NT, MIFFT_JIT_IMAGE, MIFFT_DPP, MIFFT_HERM*, MIFFT_HS, MIFFT_GRID_PER_CU) and the fault injection of the tests
+ * MIFFT_JIT_NT, MIFFT_JIT_IMAGE, MIFFT_DPP, MIFFT_HERM*, MIFFT_HS, MIFFT_GRID_PER_CU, MIFFT_ILV) and the fault injection of the tests
  * (MIFFT_TEST_FAIL_SCRATCH_ALLOC) exist only in the LAB build, libmifft_lab.so
  * (-DMIFFT_EXPERIMENTAL -DMIFFT_TESTING, same ABI), together with the experimental kernels that stayed
  * negative results; the host package loads it only when MIFFT_LIBRARY points at it.
@@ -127,6 +127,24 @@ typedef enum {
  *   - MIFFT_JIT=0 and a last dim without a precompiled packed-row kernel: precompiled for 128, 480, 1024, 1080 and 1920
  *     points (F32 and F64, input of the plan's own float type); every other length is specialised at run time. */
 #define MIFFT_FLAG_HALF_SPECTRUM 2u
+/* Transform a subset of the dims (numpy `axes=`, torch `dim=`).  MIFFT_FLAG_KEEP_DIM(d), d in 0 .. MIFFT_MAX_DIMS-1, leaves
+ * dim d untransformed: it is carried through like an extra batch dimension.  Layouts, mifft_plan_in_bytes and
+ * mifft_plan_out_bytes do not change; an inverse scales by 1/N of the transformed dims only.  `bases_len` still has ndim
+ * entries, and a kept dim's entry must be 0.  One launch per transformed dim, innermost first: the first reads x and
+ * writes out, the others run in place on out; a pass over dim i runs at stride prod(dims after i) over prod(dims before
+ * i) * batch blocks, whether those dims are kept or not.  mifft_plan_stages() is 0 and mifft_plan_kernel_name() "none"
+ * for a kept dim; mifft_plan_num_launches() is the number of transformed dims.
+ * Refused before any device work:
+ *   - a keep bit at d >= ndim, or every dim kept ("no dimension to transform"): MIFFT_ERR_BAD_DIM;
+ *   - a nonzero bases_len[d] for a kept dim: MIFFT_ERR_BAD_BASES;
+ *   - MIFFT_FLAG_FAITHFUL_STAGES with any keep bit (the reference has no axes to be faithful to): MIFFT_ERR_UNSUPPORTED;
+ *   - with MIFFT_FLAG_HALF_SPECTRUM, a kept last dim (numpy halves the last TRANSFORMED axis): MIFFT_ERR_UNSUPPORTED.
+ * Routed: the innermost dim transformed up to the single-launch row limit (16384 points, F64 8192); any other transformed
+ * dim up to 4096 points.  Anything else is MIFFT_ERR_UNSUPPORTED with a reason: masked plans have no four-step, plane,
+ * Hermitian or half-store routes.  With MIFFT_FLAG_HALF_SPECTRUM the last dim is packed real rows as without a mask and
+ * the other transformed dims are column passes over the half-spectrum tensor. */
+#define MIFFT_FLAG_KEEP_DIM(d) ((uint32_t)1u << (8 + (d)))
+#define MIFFT_FLAG_KEEP_MASK 0x3F00u
 
 typedef struct mifft_plan mifft_plan;
 

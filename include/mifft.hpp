@@ -122,7 +122,8 @@ inline void check_layout_conditions_nd(const std::vector<int64_t>& in_layout, co
 // (_estimate_best_bases_nd[.., "gpu"]).  `runtime_twfs` / `max_cluster_size` have no MI355X meaning; `_test` maps to
 // flags = MIFFT_FLAG_FAITHFUL_STAGES (the user's stages run literally, one LDS pass each).  With MIFFT_FLAG_HALF_SPECTRUM the
 // layouts are those of include/mifft.h: the last dimension of the complex side holds h = n / 2 + 1 bins (checked by the
-// library: mifft_plan_create receives the logical real dims).
+// library: mifft_plan_create receives the logical real dims).  MIFFT_FLAG_KEEP_DIM(d) leaves dim d untransformed (its bases
+// list, when given, is empty).
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
