@@ -79,6 +79,7 @@ struct FastEntry {
                       // 0.25-0.55 GB / more than 0.05 GB per exec (non-temporal STORES), -1: any size
     int out_dtype;
     int N;
+    int np, r[4];  // passes and radices of the configuration (TileCfg NP, R0..R3)
     bool cols;
     const char* name;
     LaunchFn launch;
@@ -93,7 +94,7 @@ struct FastEntry {
     TileCfg<T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF, 0, REAL, false, NTM, TS>
 #define MIFFT_CFG_X(TS, REAL, NTM, STREAM, NAME, T, DT, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF) \
     {                                                                                                                      \
-        TS, REAL, STREAM, DT, N, COLS, NAME,                                                                               \
+        TS, REAL, STREAM, DT, N, NP, {R0, R1, R2, R3}, COLS, NAME,                                                         \
             launch_tile<MIFFT_TILECFG(TS, REAL, NTM, T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)>,  \
             prepare_tile<MIFFT_TILECFG(TS, REAL, NTM, T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)>, \
             TILE, THREADS,                                                                                                 \
@@ -104,7 +105,7 @@ struct FastEntry {
 // Hermitian twin of a strided configuration (TileCfg::HERM), optionally with wave-owned sub-problems
 #define MIFFT_CFG_HERM_X(WS, NAME, T, DT, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)                              \
     {                                                                                                                                      \
-        false, false, -1, DT, N, COLS, NAME "_h",                                                                                          \
+        false, false, -1, DT, N, NP, {R0, R1, R2, R3}, COLS, NAME "_h",                                                                    \
             launch_tile<TileCfg<T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF, 0, false, false, 0, false, T, WS, false, 0, true>>,  \
             prepare_tile<TileCfg<T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF, 0, false, false, 0, false, T, WS, false, 0, true>>, \
             TILE, THREADS,                                                                                                                 \
@@ -117,7 +118,7 @@ struct FastEntry {
     TileCfg<T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF, 0, REAL, false, NTM, false, T, WS, false, 0, false, true>
 #define MIFFT_CFG_HS_X(REAL, NTM, STREAM, WS, NAME, T, DT, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)                \
     {                                                                                                                                      \
-        false, REAL, STREAM, DT, N, COLS, NAME "_hs",                                                                                      \
+        false, REAL, STREAM, DT, N, NP, {R0, R1, R2, R3}, COLS, NAME "_hs",                                                                \
             launch_tile<MIFFT_HS_TILECFG(REAL, NTM, WS, T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)>,            \
             prepare_tile<MIFFT_HS_TILECFG(REAL, NTM, WS, T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)>,           \
             TILE, THREADS,                                                                                                                 \
@@ -129,7 +130,7 @@ struct FastEntry {
 // column tile whose passes 1..NP-1 run inside wave-owned sub-problems (TileCfg::WSUB): R0 a multiple of THREADS / 64
 #define MIFFT_CFG_WSUB(NAME, T, DT, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF)                        \
     {                                                                                                                          \
-        false, false, -1, DT, N, COLS, NAME,                                                                                   \
+        false, false, -1, DT, N, NP, {R0, R1, R2, R3}, COLS, NAME,                                                             \
             launch_tile<TileCfg<T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF, 0, false, false, 0, false, T, true>>,   \
             prepare_tile<TileCfg<T, N, NP, R0, R1, R2, R3, TILE, THREADS, COLS, FD, LD_, TWM, MINW, PF, 0, false, false, 0, false, T, true>>,  \
             TILE, THREADS,                                                                                                     \

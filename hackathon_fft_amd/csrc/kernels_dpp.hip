@@ -158,7 +158,7 @@ bool select_dpp_rows(const Plan& plan, DimPass& pass) {
     if (pass.inner != 1 || !pass.first || plan.out_dtype != MIFFT_F32 || plan.in_dtype != MIFFT_F32 ||
         plan.in_components != 2)
         return false;
-    const bool streaming = plan.size_batch() * (double)plan.prod * (double)plan.out_elem_bytes() * 2.0 > config().streaming_min_bytes;
+    const bool streaming = plan.exec_bytes() > config().streaming_min_bytes;
     // (16 rows per wave; the 20-row layout -- 15 of 16 lanes busy, blocks that are no whole number of lines -- measured
     //  0.20 ms against 0.163 and went with the MIFFT_DPP_VARIANT knob in round 3)
     const bool nt = streaming;

@@ -369,7 +369,7 @@ bool select_fast_plane(const Plan& plan, DimPass& pass) {
         if (e.ntl && e.N1 == 128 &&
             plan.size_batch() * (double)plan.prod * (double)plan.out_elem_bytes() < config().nd_plane128_min_bytes)
             continue;
-        if (e.nts && !(plan.ndim == 2 && nts_window_bytes(plan.size_batch() * (double)plan.prod * (double)plan.out_elem_bytes() * 2.0)))
+        if (e.nts && !(plan.ndim == 2 && nts_window_bytes(plan.exec_bytes())))
             continue;
         pass.kernel_name = e.name;
         pass.launch = e.launch;
@@ -483,7 +483,7 @@ bool select_fast(const Plan& plan, DimPass& pass) {
     if (pass.first && plan.in_dtype != plan.out_dtype) return false;
     const bool cols = pass.inner != 1;
     // read + write volume of one exec far beyond the 256-MB Infinity Cache -> non-temporal twins apply
-    const double total_bytes = plan.size_batch() * (double)plan.prod * (double)plan.out_elem_bytes() * 2.0;
+    const double total_bytes = plan.exec_bytes();
     const bool streaming = total_bytes > config().streaming_min_bytes;
     bool hand_table = true;  // the hand-tuned lengths keep their `_nts` twins up to the streaming threshold (0.6 GB), where
                              // the `_nt` twins take over: 50k x 1024 still gains 4-6 % with non-temporal stores
@@ -514,6 +514,8 @@ bool select_fast(const Plan& plan, DimPass& pass) {
         pass.wg_per_cu = grid_per_cu_of(e.name);
         pass.hs = e.hs;
         pass.regime_twin = e.stream_pref > 0;
+        pass.cfg_np = e.np;
+        std::copy(e.r, e.r + 4, pass.cfg_r);
         pass.prefix_ok = e.cols && !e.tstore && !e.herm;
         pass.herm_d0 = pass.herm_d1 = pass.herm_d2 = 0;
         if (e.herm) herm_set_dims(plan, pass);  // trailing dimensions of the column space

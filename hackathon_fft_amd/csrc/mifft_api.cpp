@@ -66,14 +66,19 @@ static void fill_twiddles(std::vector<T>& tab, int64_t N, bool inverse) {
     }
 }
 
+// Frees and nulls the four device tables of a pass.  A candidate pass that plan creation drops again has been through
+// selectors only: d_twiddle and d_aux3 are filled after selection (upload_twiddles; the four-step builders, which free their
+// own passes), so there this frees what a selector may upload -- the Rader tables in d_aux / d_aux2.
+static void free_pass_tables(DimPass& ps) {
+    if (ps.d_twiddle) (void)hipFree(ps.d_twiddle);
+    if (ps.d_aux) (void)hipFree(ps.d_aux);
+    if (ps.d_aux2) (void)hipFree(ps.d_aux2);
+    if (ps.d_aux3) (void)hipFree(ps.d_aux3);
+    ps.d_twiddle = ps.d_aux = ps.d_aux2 = ps.d_aux3 = nullptr;
+}
+
 static void free_plan_device(Plan& p) {
-    for (auto& ps : p.passes) {
-        if (ps.d_twiddle) (void)hipFree(ps.d_twiddle);
-        if (ps.d_aux) (void)hipFree(ps.d_aux);
-        if (ps.d_aux2) (void)hipFree(ps.d_aux2);
-        if (ps.d_aux3) (void)hipFree(ps.d_aux3);
-        ps.d_twiddle = ps.d_aux = ps.d_aux2 = ps.d_aux3 = nullptr;
-    }
+    for (auto& ps : p.passes) free_pass_tables(ps);
     if (p.d_scratch) (void)hipFree(p.d_scratch);
     p.d_scratch = nullptr;
 }
@@ -392,9 +397,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
             std::string why;
             ok = select_jit(p, t, why) && t.herm_d2 > 0;
         }
-        if (t.d_aux) (void)hipFree(t.d_aux);
-        if (t.d_aux2) (void)hipFree(t.d_aux2);
-        if (t.d_aux3) (void)hipFree(t.d_aux3);
+        free_pass_tables(t);
         herm_known = ok ? 1 : 0;
         return ok;
     };
@@ -413,10 +416,24 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         p.herm_axis = 1;
         p.hs_selected = false;
         herm_known = -1;  // (asked again, for the other schedule, when the pass over dimension 1 is selected)
-        if (t.d_aux) (void)hipFree(t.d_aux);
-        if (t.d_aux2) (void)hipFree(t.d_aux2);
-        t.d_aux = t.d_aux2 = nullptr;
+        free_pass_tables(t);
         return false;
+    };
+    // A half-store kernel (TileCfg::HS) for pass `t` (= `ps` with want_half and store_lim set): the lab's packed real rows (a
+    // measured tie with the tuned half-store kernels; row passes only), else a table twin, else a runtime-specialised one --
+    // unless the ordinary table entry is one tuned for a size regime (a non-temporal twin), which is not traded for it:
+    // 64 x 1024^2 0.372 -> 0.422 ms with `rows1024_16x8x8_hs_r_jit` in place of `rows1024_16x8x8_r_nt`
+    auto select_half_store = [&](const DimPass& ps, DimPass& t) -> bool {
+#ifdef MIFFT_EXPERIMENTAL
+        std::string whyr;
+        if (cfg.r2c_rows && ps.first && select_jit_r2c(p, t, whyr)) return true;
+#endif
+        if (select_fast(p, t)) return true;
+        if (ps.N > 4096) return false;
+        DimPass u = ps;
+        const bool tuned = select_fast(p, u) && u.regime_twin;
+        std::string whyh;
+        return !tuned && select_jit(p, t, whyh);
     };
 build_passes:
     for (int i = ndim - 1; i >= 0; --i) {
@@ -477,19 +494,7 @@ build_passes:
                 DimPass t = ps;
                 t.want_half = true;
                 t.store_lim = (int)(dims[2] / 2);
-                bool found = false;
-#ifdef MIFFT_EXPERIMENTAL  // packed real rows: a measured tie with the tuned half-store kernels, lab builds only
-                std::string whyr;
-                found = cfg.r2c_rows && select_jit_r2c(p, t, whyr);
-#endif
-                if (!found) found = select_fast(p, t);
-                if (!found && ps.N <= 4096) {
-                    DimPass u = ps;
-                    const bool tuned = select_fast(p, u) && u.regime_twin;
-                    std::string whyh;
-                    found = !tuned && select_jit(p, t, whyh);
-                }
-                if (try_first_axis(t, found)) {
+                if (try_first_axis(t, select_half_store(ps, t))) {
                     ps = t;
                     ok = first_axis = true;
                 }
@@ -500,33 +505,17 @@ build_passes:
             }
             // the pass over dimension 1 of a plan whose last pass will be a Hermitian twin: a half-store kernel, tuned or
             // runtime specialised, before anything else
-            // (a kernel tuned for a size regime -- a non-temporal twin -- is not traded for a runtime-specialised one: 64 x 1024^2
-            //  0.372 -> 0.422 ms with `rows1024_16x8x8_hs_r_jit` in place of `rows1024_16x8x8_r_nt`)
             if (!ok && i == 1 && !first_axis && herm_possible()) {
                 DimPass t = ps;
                 t.want_half = true;
                 t.store_lim = (int)(dims[1] / 2);
-                bool found = false;
-#ifdef MIFFT_EXPERIMENTAL  // (2-D plans: this is the row pass)
-                std::string whyr;
-                found = cfg.r2c_rows && ps.first && select_jit_r2c(p, t, whyr);
-#endif
-                if (!found) found = select_fast(p, t);
-                if (!found && ps.N <= 4096) {
-                    DimPass u = ps;
-                    const bool tuned = select_fast(p, u) && u.regime_twin;
-                    std::string whyh;
-                    found = !tuned && select_jit(p, t, whyh);
-                }
+                const bool found = select_half_store(ps, t);
                 p.hs_selected = found;
                 if (found && last_pass_will_be_hermitian()) {
                     ps = t;
                     ok = true;
                 } else {
-                    if (found) {  // (nothing but Rader tables could have been uploaded for t)
-                        if (t.d_aux) (void)hipFree(t.d_aux);
-                        if (t.d_aux2) (void)hipFree(t.d_aux2);
-                    }
+                    if (found) free_pass_tables(t);
                     p.hs_selected = false;
                 }
             }
@@ -548,13 +537,7 @@ build_passes:
                         return set_error(MIFFT_ERR_HIP, "four-step: " + why4);
                     }
                     // no two-pass split: drop whatever was appended and fall through to the single-kernel path
-                    for (size_t k = before; k < p.passes.size(); ++k) {
-                        DimPass& q = p.passes[k];
-                        if (q.d_twiddle) (void)hipFree(q.d_twiddle);
-                        if (q.d_aux) (void)hipFree(q.d_aux);
-                        if (q.d_aux2) (void)hipFree(q.d_aux2);
-                        if (q.d_aux3) (void)hipFree(q.d_aux3);
-                    }
+                    for (size_t k = before; k < p.passes.size(); ++k) free_pass_tables(p.passes[k]);
                     p.passes.resize(before);
                     if (p.d_scratch) {
                         (void)hipFree(p.d_scratch);

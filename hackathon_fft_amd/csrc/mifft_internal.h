@@ -52,6 +52,7 @@ struct DimPass {
     int64_t outer = 1;    // prod(dims before it)   (times batch at launch)
     std::vector<uint32_t> radices;    // descending stage radices (reference order)
     std::vector<uint32_t> processed;  // prefix products P_b
+    int cfg_np = 0, cfg_r[4] = {1, 1, 1, 1};  // select_fast: the selected table entry's passes and radices (TileCfg NP, R0..R3)
     void* d_twiddle = nullptr;        // device table W_N^n, n in [0,N), complex<out dtype>
     void* d_aux = nullptr;            // kernel-family specific device table (may be null)
     const char* kernel_name = "none";
@@ -111,6 +112,9 @@ struct Plan {
     int64_t sel_batch = 0;
     double size_batch() const { return (double)(sel_batch > 0 ? sel_batch : batch); }
     int64_t prod = 1;
+    // bytes one exec moves (the output-sized tensor read once and written once): what the size regimes of the kernel
+    // families (streaming twins, non-temporal store windows) are measured in
+    double exec_bytes() const { return size_batch() * (double)prod * (double)out_elem_bytes() * 2.0; }
     int in_components = 2;
     int inverse = 0;
     uint32_t flags = 0;

@@ -1,9 +1,12 @@
 """Randomised end-to-end check of the GPU path against fp64 pocketfft (GPU box):
-    python tools/fuzz_gpu.py [cases] [seed] [big]
+    python tools/fuzz_gpu.py [cases] [seed] [big|-] [plan-lines file]
 Random ranks 1-5, arbitrary lengths (so every kernel family is hit: tables, runtime-specialised rows / column tiles /
 planes, literal stages, four-step), fp32 / fp64, real / complex / uint8 / int32 input, forward / inverse, ragged batches.
-Prints every failure and a per-family count; exit status 1 on any failure."""
-import os, sys, time, collections
+Prints every failure and a per-family count; exit status 1 on any failure.
+With a plan-lines file the pocketfft comparison is skipped and one line per case is appended to the file instead -- the case,
+every kernel name, the launches, the scratch bytes and the SHA-1 of the output bytes -- so that two builds of the library
+(MIFFT_LIBRARY) can be compared plan for plan and bit for bit."""
+import os, sys, time, collections, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -14,6 +17,7 @@ seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 # "big": 2-D ... 4-D shapes of 2-30 M points, mostly real input -- large enough for the plan-time policy to take the Hermitian
 # last pass and the half-store pass in front of it (herm_pays, mifft_internal.h)
 BIG = len(sys.argv) > 3 and sys.argv[3] == "big"
+LINES = open(sys.argv[4], "a") if len(sys.argv) > 4 else None
 rng = np.random.default_rng(seed)
 fam = collections.Counter()
 fails = 0
@@ -79,6 +83,10 @@ for i in range(cases):
         fam[cat] += 1
         continue
     names = [plan.kernel_name(d) for d in range(nd)]
+    if LINES:
+        LINES.write(f"fuzz{'_big' if BIG else ''} {i} {shape} batch {batch} {kind} {x.dtype}->{out_dt.__name__} inv={inverse} {names} "
+                    f"launches={plan.num_launches} scratch={plan.scratch_bytes} sha1={hashlib.sha1(out.cpu().numpy().tobytes()).hexdigest()}\n")
+        continue
     if "generic" in names and os.environ.get("FUZZ_SHOW_GENERIC"):
         print(f"generic: {shape} batch {batch} {kind} {out_dt.__name__} {names}")
     for nm in set(names):
