@@ -3,14 +3,18 @@ martinvuyk/hackathon-fft).  See include/mifft.h for the C ABI, DESIGN.md for the
 """
 from ._lib import MifftError, LIB_PATH, EXPORTS  # noqa: F401
 from .api import (  # noqa: F401
+    FLAG_DCT,
+    FLAG_DCT_ORTHO,
     DeviceContext,
     GPUTest,
     Plan,
     clear_plan_cache,
+    dct,
     estimate_best_bases,
     estimate_best_bases_nd,
     fft,
     fftn,
+    idct,
     ifftn,
     irfftn,
     ordered_bases,
@@ -22,5 +26,6 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "DeviceContext", "GPUTest", "Plan", "clear_plan_cache", "MifftError", "estimate_best_bases", "estimate_best_bases_nd",
-    "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "reduce_dims", "rfftn", "time_fft",
+    "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "reduce_dims", "rfftn", "time_fft", "dct", "idct",
+    "FLAG_DCT", "FLAG_DCT_ORTHO",
 ]

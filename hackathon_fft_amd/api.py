@@ -34,6 +34,8 @@ _OUT_DTYPES = (torch.float32, torch.float64)
 
 FLAG_FAITHFUL_STAGES = 1
 FLAG_HALF_SPECTRUM = 2  # MIFFT_FLAG_HALF_SPECTRUM: numpy's one-sided rfftn / irfftn layouts (include/mifft.h)
+FLAG_DCT = 4            # MIFFT_FLAG_DCT: DCT-II (inverse: its inverse) of real rows, (batch, n, 1) on both sides
+FLAG_DCT_ORTHO = 8      # MIFFT_FLAG_DCT_ORTHO: scipy's norm="ortho" of such a plan
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -146,6 +148,29 @@ def _check_half_layout(in_shape: tuple, out_shape: tuple, inverse: bool) -> tupl
     return dims
 
 
+def _check_dct_layout(in_shape: tuple, out_shape: tuple) -> tuple:
+    """Layouts of a DCT plan (MIFFT_FLAG_DCT): both sides real rows (batch, n, 1) of one shape; returns the dims (n,)."""
+    if len(in_shape) != 3 or len(out_shape) != 3:
+        raise MifftError(-2, f"DCT layouts are (batch, n, 1) on both sides, got {in_shape} -> {out_shape}")
+    if in_shape[-1] != 1 or out_shape[-1] != 1:
+        raise MifftError(-3, f"both sides of a DCT plan have 1 component, got {in_shape[-1]} and {out_shape[-1]}")
+    if in_shape != out_shape:
+        raise MifftError(-2, f"a DCT writes as many reals as it reads: {in_shape} -> {out_shape}")
+    n = in_shape[1]
+    if n % 2 or n < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"DCT of an odd length or of fewer than 8 points ({n}) is not supported")
+    return (n,)
+
+
+def _dct_norm_flags(norm) -> int:
+    """scipy's ``norm`` of a DCT plan as flag bits: None / "backward" (the unnormalised forward) or "ortho" """
+    if norm is None or norm == "backward":
+        return 0
+    if norm == "ortho":
+        return FLAG_DCT_ORTHO
+    raise MifftError(ERR_UNSUPPORTED, f"norm must be None, \"backward\" or \"ortho\", got {norm!r}")
+
+
 def _keep_flags(rank: int, axes) -> int:
     """keep bits (MIFFT_FLAG_KEEP_DIM) of the layout positions 1 .. rank - 2 NOT in ``axes`` (None: every one transformed)"""
     if axes is None:
@@ -164,13 +189,22 @@ class Plan:
 
     ``half_spectrum=True`` (no reference counterpart): numpy's one-sided layouts, see _check_half_layout.
     ``axes`` (no reference counterpart): the layout positions (1 .. rank - 2) to transform; the others are carried through
-    untransformed (MIFFT_FLAG_KEEP_DIM).  None: all of them.  With ``bases``, a kept dim's list is empty."""
+    untransformed (MIFFT_FLAG_KEEP_DIM).  None: all of them.  With ``bases``, a kept dim's list is empty.
+    ``dct=True`` (no reference counterpart): DCT-II of real rows, ``inverse`` its inverse, both sides (batch, n, 1); ``norm``
+    is scipy's (None / "backward" / "ortho").  ``bases`` of such a plan holds one list whose radices multiply to n // 2, the
+    packed transform the plan runs and ``stages(0)`` reports -- not to n.  See _check_dct_layout and MIFFT_FLAG_DCT in
+    include/mifft.h."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
-                 device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None):
+                 device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
+                 dct: bool = False, norm=None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
-        if half_spectrum:
+        dct = bool(dct) or bool(int(flags) & FLAG_DCT)
+        if dct:  # (with half_spectrum as well: the library refuses the pair)
+            dims = _check_dct_layout(in_shape, out_shape)
+            flags = int(flags) | FLAG_DCT | _dct_norm_flags(norm) | (FLAG_HALF_SPECTRUM if half_spectrum else 0)
+        elif half_spectrum:
             dims = _check_half_layout(in_shape, out_shape, bool(inverse))
             flags = int(flags) | FLAG_HALF_SPECTRUM
         else:
@@ -187,6 +221,7 @@ class Plan:
         self.inverse, self.device, self.flags = bool(inverse), int(device), int(flags)
         self.axes = None if axes is None else tuple(int(a) for a in axes)
         self.half_spectrum = bool(half_spectrum)
+        self.dct = dct
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if bases is not None:
             flat = [int(b) for bs in bases for b in bs]
@@ -258,7 +293,7 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
              inverse: bool = False, runtime_twfs: bool = True, max_cluster_size: int = 8,
              _test: Optional[GPUTest] = None, faithful_stages: bool = False,
              ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False,
-             axes: Optional[Sequence[int]] = None) -> Plan:
+             axes: Optional[Sequence[int]] = None, dct: bool = False, norm=None) -> Plan:
     """GPU overload of plan_fft (fft/fft/fft.mojo:161-210).
 
     ``runtime_twfs`` and ``max_cluster_size`` are accepted for call-site compatibility
@@ -271,16 +306,23 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     (batch, d0.., n // 2 + 1, 2), inverse the other way round (include/mifft.h, MIFFT_FLAG_HALF_SPECTRUM).
     ``axes`` (no reference counterpart): the layout positions 1 .. rank - 2 to transform, None = all of them; the others
     are carried through untransformed (include/mifft.h, MIFFT_FLAG_KEEP_DIM).
+    ``dct`` (no reference counterpart): DCT-II (``inverse``: its inverse) of the real rows of a (batch, n, 1) tensor into
+    one of the same shape, ``norm`` None / "backward" / "ortho" as scipy.fft.dct (include/mifft.h, MIFFT_FLAG_DCT); ``bases``
+    then factor n // 2, the packed transform the plan runs.
     """
     del runtime_twfs, max_cluster_size
-    if half_spectrum:  # (layout errors before any device work)
+    if dct:  # (layout errors before any device work)
+        _check_dct_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout))
+        _dct_norm_flags(norm)
+    elif half_spectrum:
         _check_half_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout), bool(inverse))
     _keep_flags(len(out_layout), axes)
     if ctx is None:
         ctx = DeviceContext()
     flags = FLAG_FAITHFUL_STAGES if (faithful_stages or _test is not None) else 0
     return Plan(in_dtype, out_dtype, in_layout, out_layout, bases=bases, inverse=inverse,
-                device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum, axes=axes)
+                device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum, axes=axes,
+                dct=dct, norm=norm)
 
 
 def _check_tensor(t: "torch.Tensor", shape: tuple, dtype, device: int, what: str) -> None:
@@ -342,7 +384,7 @@ _PLAN_CACHE_LOCK = threading.RLock()
 
 
 def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                 half_spectrum: bool = False, axes=None) -> Plan:
+                 half_spectrum: bool = False, axes=None, dct_flags: int = 0) -> Plan:
     """Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
     costs a hipMalloc + copy per dimension, and its tables must outlive the kernels enqueued with it.
 
@@ -352,26 +394,29 @@ def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, fai
     two threads on their own streams) transforming the same shape never share a plan -- and is guarded by a lock."""
     with _PLAN_CACHE_LOCK:
         return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                                   half_spectrum, axes)
+                                   half_spectrum, axes, dct_flags)
 
 
 def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                        half_spectrum: bool = False, axes=None) -> Plan:
+                        half_spectrum: bool = False, axes=None, dct_flags: int = 0) -> Plan:
+    # dct_flags: FLAG_DCT (| FLAG_DCT_ORTHO) of the dct / idct wrappers' plans, 0 for every other
     key = (in_dtype, out_dtype, in_shape, out_shape,
            None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
            bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
-           bool(half_spectrum), _keep_flags(len(out_shape), axes))
+           bool(half_spectrum), _keep_flags(len(out_shape), axes), int(dct_flags))
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         try:
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
                             faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
-                            axes=axes)
+                            axes=axes, dct=bool(dct_flags & FLAG_DCT),
+                            norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
             # primes <= 97 otherwise, fft/fft/fft.mojo:49-104) rejects lengths with a larger prime factor.  The
             # numpy-style wrappers are this repository's own surface, so they retry with the full prime factorisation.
-            if radices is not None or e.status not in (-5, -7):
+            # (not for a DCT plan: a half length with a prime factor above 32 has been refused before the radix planning)
+            if radices is not None or dct_flags or e.status not in (-5, -7):
                 raise
             dims = _check_half_layout(in_shape, out_shape, inverse) if half_spectrum else in_shape[1:-1]
             bases = [_prime_factors(int(n)) if axes is None or p + 1 in axes else [] for p, n in enumerate(dims)]
@@ -591,3 +636,61 @@ def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtyp
                                    half_spectrum=True, axes=axes)
         fft(out, Xr, DeviceContext(Xr.device.index), plan=plan)
     return out.reshape(logical[:-1] + (n,))
+
+
+def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: bool) -> "torch.Tensor":
+    """dct / idct: validation on the host, then one plan over the (batch, n, 1) view of ``x``"""
+    name = "idct" if inverse else "dct"
+    if type != 2:
+        raise MifftError(ERR_UNSUPPORTED, f"{name}: only type 2 is supported, got type={type!r}")
+    dct_flags = FLAG_DCT | _dct_norm_flags(norm)
+    if x.is_complex():
+        raise MifftError(-3, f"{name} expects a real tensor")
+    if x.dim() < 1:
+        raise MifftError(-1, f"{name} expects a tensor of rank 1 or more")
+    logical = tuple(x.shape)
+    rank = len(logical)
+    if not -rank <= int(dim) < rank:
+        raise MifftError(-2, f"dim {dim} is out of range for a tensor of rank {rank}")
+    last = int(dim) % rank
+    inner = max(i for i, m in enumerate(logical) if m != 1 or i == last)
+    if last != inner:
+        raise MifftError(ERR_UNSUPPORTED, f"{name} along dim {last}: only the innermost dim of size above 1 ({inner}) is "
+                                          f"supported")
+    n = logical[last]
+    batch = 1
+    for i, m in enumerate(logical):
+        batch *= m if i != last else 1
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if out_dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"{name}: out_dtype must be float32 or float64, got {out_dtype}")
+    if not inverse and x.dtype not in _DTYPE_CODE:
+        raise MifftError(-4, f"{name}: unsupported input dtype {x.dtype}")
+    shape = (batch, n, 1)
+    _check_dct_layout(shape, shape)
+    if inverse:
+        x = x.to(out_dtype)  # (the inverse reads the plan's own float type)
+    xr = x.contiguous().reshape(shape)
+    device = DeviceContext(xr.device.index if xr.is_cuda else None).device
+    out = torch.empty(shape, dtype=out_dtype, device=xr.device)
+    with _PLAN_CACHE_LOCK:
+        plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device, dct_flags=dct_flags)
+        fft(out, xr, DeviceContext(device), plan=plan)
+    return out.reshape(logical)
+
+
+def dct(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: int = -1) -> "torch.Tensor":
+    """scipy.fft.dct(x, type=2, norm=norm) along the last dim of a real tensor of any rank >= 1 (an even length from 8 on):
+    ``X[k] = 2 sum_j x[j] cos(pi k (2j+1) / 2n)``; ``norm="ortho"`` scales X[0] by sqrt(1/4n) and the other bins by sqrt(1/2n).
+    The leading dims fold into the batch; the result has the shape of ``x`` and dtype ``out_dtype`` (default: that of a float32 /
+    float64 ``x``, else float64).  One kernel launch: n reals read once, n reals written once (MIFFT_FLAG_DCT).  Only
+    ``type=2``, and ``dim`` must be the innermost dim of size above 1 (MifftError -15 otherwise)."""
+    return _dct_rows(x, type, norm, out_dtype, dim, False)
+
+
+def idct(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: int = -1) -> "torch.Tensor":
+    """scipy.fft.idct(x, type=2, norm=norm), the inverse of dct under the same ``norm``:
+    ``x[j] = (X[0] + 2 sum_{k>=1} X[k] cos(pi k (2j+1) / 2n)) / 2n``.  Same layout, ``dim`` and dtype rules as dct; the input
+    is converted to ``out_dtype`` first."""
+    return _dct_rows(x, type, norm, out_dtype, dim, True)

@@ -1,0 +1,106 @@
+// dct.cpp -- the plans with MIFFT_FLAG_DCT (scipy.fft.dct / idct of type 2 over real rows; include/mifft.h).
+//
+// One launch, no scratch: the packed real-row kernel of the row length with TileCfg::DCT set.  The forward (DCT-II) is an R2C
+// tile whose load applies Makhoul's even / odd permutation on the LDS side and whose unpacking loop multiplies by the
+// quarter-sample twiddle W_4n^k and stores reals; the inverse is the mirror on a C2R tile (tile_kernel.h, TileCfg::DCT).  Both
+// sides of the plan are (batch, n, 1) real tensors, so every size-dependent choice sees batch * n real elements.
+#include <cmath>
+
+#include "mifft_config.h"
+#include "mifft_internal.h"
+
+namespace mifft {
+
+// checks that need no device: MIFFT_OK, or the status and its reason
+int dct_check(const Plan& p, std::string& why) {
+    if (p.flags & MIFFT_FLAG_HALF_SPECTRUM) {
+        why = "MIFFT_FLAG_DCT with MIFFT_FLAG_HALF_SPECTRUM: a DCT has no half spectrum";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.flags & MIFFT_FLAG_FAITHFUL_STAGES) {
+        why = "MIFFT_FLAG_DCT with MIFFT_FLAG_FAITHFUL_STAGES: the reference has no DCT to be faithful to";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.flags & MIFFT_FLAG_KEEP_MASK) {
+        why = "MIFFT_FLAG_DCT with MIFFT_FLAG_KEEP_DIM: a DCT plan transforms its one dimension";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 1) {
+        why = "a DCT reads and writes real rows (in_components = 1)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.ndim != 1) {
+        why = "MIFFT_FLAG_DCT transforms the rows of a (batch, n, 1) tensor: ndim must be 1, not " + std::to_string(p.ndim);
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.inverse && p.in_dtype != p.out_dtype) {
+        why = "an inverse DCT reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    const int64_t n = p.dims[0];
+    if (n % 2 != 0) {
+        why = "DCT of an odd length (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (n < 8) {
+        why = "DCT of fewer than 8 points (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!dct_rows_supported(p, n, w)) {
+        why = "DCT of " + std::to_string(n) + " points: " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    return MIFFT_OK;
+}
+
+// W_4n^k = e^(-2 pi i k / 4n), k = 0 .. n / 2, evaluated in long double and rounded once
+template <typename T>
+static hipError_t upload_quarter_table(int64_t n, void** d_table) {
+    const long double half_pi = 1.570796326794896619231321691639751442L;
+    std::vector<T> tab((size_t)(n / 2 + 1) * 2);
+    for (int64_t k = 0; k <= n / 2; ++k) {
+        const long double th = -half_pi * (long double)k / (long double)n;
+        tab[2 * k] = (T)cosl(th);
+        tab[2 * k + 1] = (T)sinl(th);
+    }
+    hipError_t e = hipMalloc(d_table, tab.size() * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(*d_table, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
+int build_dct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    const int64_t n = p.dims[0];
+    DimPass ps;
+    ps.dim_index = 0;
+    ps.N = n;
+    ps.inner = 1;
+    ps.outer = 1;
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    ps.half_pitch = n / 2 + 1;  // (unused by the DCT loads and stores: both sides are rows of n reals)
+    if (!select_jit_dct_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    // the scales of bin 0 and of the other bins.  Forward: X[k] = 2 Re(..), "ortho" times sqrt(1 / 4n) and sqrt(1 / 2n).
+    // Inverse: the bins are scaled as they are loaded -- the half of V[k] = conj(W) (X[k] - i X[n-k]) / 2, the 1 / n of the
+    // n-point real inverse, and "ortho" undone (times sqrt(4n) and sqrt(2n)).
+    const bool ortho = (p.flags & MIFFT_FLAG_DCT_ORTHO) != 0;
+    const long double dn = (long double)n;
+    if (!p.inverse) {
+        ps.dct_s0 = (double)(ortho ? 2.0L * sqrtl(1.0L / (4.0L * dn)) : 2.0L);
+        ps.dct_s1 = (double)(ortho ? 2.0L * sqrtl(1.0L / (2.0L * dn)) : 2.0L);
+    } else {
+        ps.dct_s0 = (double)(ortho ? sqrtl(4.0L * dn) / (2.0L * dn) : 1.0L / (2.0L * dn));
+        ps.dct_s1 = (double)(ortho ? sqrtl(2.0L * dn) / (2.0L * dn) : 1.0L / (2.0L * dn));
+    }
+    // the passes run n / 2 points; the fold / unpacking needs W_n^k, forward; the DCT twiddle W_4n^k
+    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, p.inverse != 0, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    if (e == hipSuccess)
+        e = p.out_dtype == MIFFT_F64 ? upload_quarter_table<double>(n, &ps.d_aux2) : upload_quarter_table<float>(n, &ps.d_aux2);
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "DCT table upload");
+    return MIFFT_OK;
+}
+
+}  // namespace mifft

@@ -93,6 +93,10 @@ struct DimPass {
     bool want_half = false, hs = false;
     bool r2c = false;  // packed real rows (TileCfg::R2C): the kernel runs N / 2 points; d_twiddle is that table, d_aux W_N^k
     bool c2r = false;  // half spectrum -> packed real rows (TileCfg::C2R): the same tables as r2c
+    // TileCfg::DCT of a packed-row pass (2: DCT-II on an r2c kernel, 3: its inverse on a c2r one): d_aux2 holds W_4N^k,
+    // k = 0 .. N / 2; the scales of bin 0 and of the other bins (TileParams::dct_s0 / dct_s1)
+    int dct = 0;
+    double dct_s0 = 1.0, dct_s1 = 1.0;
     int64_t half_pitch = 0;  // R2C / C2R: row pitch (complex elements) of the half-spectrum side; 0 = N (full-spectrum rows)
     int store_lim = 0;
     bool ilv = false;  // interleaved block tile (TileCfg::ILV): `inner` (< 128 B of elements) transforms per block, launched as rows
@@ -145,6 +149,9 @@ struct Plan {
     uint32_t keep_mask() const { return (flags & MIFFT_FLAG_KEEP_MASK) >> 8; }
     bool kept(int d) const { return ((keep_mask() >> d) & 1u) != 0; }
     int64_t prod_half = 0;
+    // MIFFT_FLAG_DCT: both sides are (batch, n, 1) real tensors; what one exec moves is batch * n reals read and written
+    bool dct() const { return (flags & MIFFT_FLAG_DCT) != 0; }
+    double dct_exec_bytes() const { return size_batch() * (double)prod * (double)(out_elem_bytes() / 2) * 2.0; }
     // bytes of ONE transform (one batch entry) of x, out and the plan scratch: the slab offsets and the alias check of
     // mifft_exec_batch and the size queries.  Without the flag: prod * in_elem_bytes(), prod * out_elem_bytes() twice.
     size_t in_row_bytes() const;
@@ -234,11 +241,18 @@ struct HalfRowsKernel {
     size_t lds_bytes;
 };
 const HalfRowsKernel* half_rows_kernels(int* count);
+const HalfRowsKernel* dct_rows_kernels(int* count);  // (kernels_dct_rows.hip: the TileCfg::DCT instances)
 // plans with MIFFT_FLAG_HALF_SPECTRUM (half_spectrum.cpp): the checks that need no device, then the passes (a status;
 // plan.passes / d_scratch filled on success)
 int half_spectrum_check(const Plan& plan, std::string& why);
 int build_half_spectrum(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                         const std::vector<std::vector<uint32_t>>& processed, std::string& why);
+// plans with MIFFT_FLAG_DCT (dct.cpp): the checks that need no device, then the single pass.  select_jit_dct_rows is the
+// packed-row kernel with TileCfg::DCT (kernels_jit.cpp), dct_rows_supported the same check without a device
+bool dct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_dct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+int dct_check(const Plan& plan, std::string& why);
+int build_dct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

@@ -59,6 +59,27 @@ template <typename T> struct native_vec2;
 template <> struct native_vec2<float> { typedef float type __attribute__((ext_vector_type(2))); };
 template <> struct native_vec2<double> { typedef double type __attribute__((ext_vector_type(2))); };
 
+// four adjacent reals (DCT tiles): one 16-byte access for float
+template <bool NT, typename T>
+MIFFT_DEV void gload4(const T* p, T (&v)[4]) {
+    typedef T vec4 __attribute__((ext_vector_type(4)));
+    vec4 q;
+    if constexpr (NT)
+        q = __builtin_nontemporal_load((const vec4*)p);
+    else
+        q = *(const vec4*)p;
+    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+}
+template <bool NT, typename T>
+MIFFT_DEV void gstore4(T* p, T a, T b, T c, T d) {
+    typedef T vec4 __attribute__((ext_vector_type(4)));
+    const vec4 q = {a, b, c, d};
+    if constexpr (NT)
+        __builtin_nontemporal_store(q, (vec4*)p);
+    else
+        *(vec4*)p = q;
+}
+
 template <bool NT, typename T>
 MIFFT_DEV cpx<T> gload(const cpx<T>* p) {
     if constexpr (NT) {
@@ -149,6 +170,11 @@ struct TileParams {
     // column tiles of a pass that transforms only a PREFIX of its column space (the middle pass of a half-spectrum schedule):
     // columns from col_lim on are neither loaded nor stored (0 = all `inner` columns)
     long long col_lim;
+    // DCT configurations: W_(4n)^k = e^(-2 pi i k / 4n), k = 0 .. N (n = 2 N real points per row), and the scales of bin 0 and
+    // of the other bins (the norm, the factor 2 of the forward, the 1 / 2n and the halves of the inverse): applied as the
+    // bins are stored (DCT = 2) or loaded (DCT = 3)
+    const void* dct_tw;
+    double dct_s0, dct_s1;
 };
 
 MIFFT_DEV long long tile_id(const TileParams& p, long long t) { return p.reverse ? p.n_tiles - 1 - t : t; }
@@ -236,7 +262,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
-          int ILV_ = 0>
+          int ILV_ = 0, int DCT_ = 0>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -368,6 +394,27 @@ struct TileCfg {
     static_assert(!ILV_ || (!COLS_ && !FIRST_DIRECT_ && !LAST_DIRECT_ && TILE_ % ILV_ == 0 && !TSTORE_ && !FS1_ && !HERM_ &&
                             !HS_ && !R2C_ && !C2R_ && !DMA_ && R0_ <= 32),
                   "ILV: a row tile of whole blocks staged by the flat copies");
+    // DCT (2 / 3; 0 = none): DCT-II of real rows of n = 2 N points on the packed-row kernels, by Makhoul's route.  The row
+    // v[j] = x[2j], v[n-1-j] = x[2j+1] is a real sequence whose transform V gives X[k] = 2 Re(W_4n^k V[k]) and
+    // X[n-k] = -2 Im(W_4n^k V[k]).  2: an R2C tile whose load scatters x into the real slots of v (slot q is component
+    // q & 1 of complex element q >> 1: the packed row of v lies in LDS with no staging) and whose unpacking loop, holding
+    // V[k] and V[N-k], multiplies by the quarter-sample twiddle and stores four runs of reals.  3, the inverse: a C2R
+    // tile whose load forms V[k] = conj(W_4n^k) (X[k] - i X[n-k]) / 2 from four runs of reals before the fold, and whose
+    // store reads x back from the slots of v.  n reals read once, n reals written once.
+    static constexpr int DCT = DCT_;
+    static_assert(DCT_ == 0 || DCT_ == 2 || DCT_ == 3, "DCT: 0, 2 (DCT-II) or 3 (its inverse)");
+    static_assert(DCT_ != 2 || (R2C_ && !FIRST_DIRECT_), "DCT-II: packed real rows staged in LDS by the permuting load");
+    static_assert(DCT_ != 3 || (C2R_ && !LAST_DIRECT_), "inverse DCT-II: folded rows whose last pass stays in LDS");
+    // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
+    // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
+    // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
+    // and so does every N under -DMIFFT_DCT_PAIRS (the A/B of profiles/r06_dct_ab.txt).  The accesses are as aligned as the
+    // caller's x and out: to one element at least, which the hardware's unaligned global accesses serve.
+#ifdef MIFFT_DCT_PAIRS
+    static constexpr bool DCT_QUADS = false;
+#else
+    static constexpr bool DCT_QUADS = DCT_ != 0 && N_ % 2 == 0;
+#endif
     static constexpr int CPITCH = TSTORE_ ? TILE_ + 1 : TILE_;
     static_assert(!TSTORE_ || (COLS_ && !LAST_DIRECT_ && FIRST_DIRECT_), "TSTORE: column tile, last pass left in LDS");
     static constexpr int DATA_ELEMS = COLS_ ? N_ * CPITCH : LD * TILE_;
@@ -1431,9 +1478,19 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     cs[j] = (IT % G == 0 || i0 + j < IT) ? c : nv;  // (past the last pair: nothing to do)
                     ks[j] = k;
                     if (cs[j] < nv) {
-                        const V* row = gin + (row0 + c) * p.half_pitch;
-                        xk[j] = gload<(C::NT & 1) != 0>(row + k);
-                        xm[j] = gload<(C::NT & 1) != 0>(row + (C::N - k));  // (k = 0: X[N], the last bin of the row)
+                        if constexpr (C::DCT == 3) {
+                            // four runs of reals over the lanes: X[k] and X[N + k] ascending, X[n - k] and X[N - k] descending
+                            // (k = 0: X[n] := 0, and X[N] twice)
+                            const T* row = (const T*)p.in + (row0 + c) * (2 * C::N);
+                            xk[j].x = gload_real<(C::NT & 1) != 0>(row + k);
+                            xk[j].y = k ? gload_real<(C::NT & 1) != 0>(row + (2 * C::N - k)) : (T)0;
+                            xm[j].x = gload_real<(C::NT & 1) != 0>(row + (C::N - k));
+                            xm[j].y = gload_real<(C::NT & 1) != 0>(row + (C::N + k));
+                        } else {
+                            const V* row = gin + (row0 + c) * p.half_pitch;
+                            xk[j] = gload<(C::NT & 1) != 0>(row + k);
+                            xm[j] = gload<(C::NT & 1) != 0>(row + (C::N - k));  // (k = 0: X[N], the last bin of the row)
+                        }
                     }
                     c += DC;
                     k += DK;
@@ -1447,6 +1504,14 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     if (cs[j] < nv) {
                         const int kk = ks[j];
                         V a = xk[j], b = xm[j];
+                        if constexpr (C::DCT == 3) {  // V[k] = conj(W_4n^k) (X[k] - i X[n-k]) / 2, V[N-k] likewise
+                            const V* w4 = (const V*)p.dct_tw;
+                            const V wa = w4[kk], wb = w4[C::N - kk];
+                            const T s1 = (T)p.dct_s1, s0 = kk == 0 ? (T)p.dct_s0 : s1;
+                            const T ar = s0 * a.x, ai = -s1 * a.y, br = s1 * b.x, bi = -s1 * b.y;
+                            a = {wa.x * ar + wa.y * ai, wa.x * ai - wa.y * ar};
+                            b = {wb.x * br + wb.y * bi, wb.x * bi - wb.y * br};
+                        }
                         if (kk == 0) a.y = b.y = (T)0;
                         const V wk = w[kk];
                         const T ex = a.x + b.x, ey = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
@@ -1460,6 +1525,38 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             __syncthreads();
         } else if constexpr (C::ILV > 0) {
             ilv_load<C>(p, lds, base, nv * C::N, tid);
+            __syncthreads();
+        } else if constexpr (C::DCT == 2) {
+            // the tile's nv * 2 N reals as one flat coalesced run; x[2j] goes to real slot j of its row, x[2j+1] to slot
+            // n - 1 - j (pairs: two runs of 4-byte LDS stores, one ascending and one descending)
+            constexpr bool NTL = (C::NT & 1) != 0;
+            if constexpr (C::DCT_QUADS) {  // quad e of a row: z_e and z_(N-1-e)
+                constexpr int H = C::N / 2;
+                for (int f = tid; f < nv * H; f += C::THREADS) {
+                    const int c = f / H, e = f - c * H;
+                    T x[4];
+                    if constexpr (!same_t<typename C::IT, T>::value) {
+                        const V lo = load_foreign<C>(p.in, base + 2 * f), hi = load_foreign<C>(p.in, base + 2 * f + 1);
+                        x[0] = lo.x, x[1] = lo.y, x[2] = hi.x, x[3] = hi.y;
+                    } else {
+                        gload4<NTL>((const T*)p.in + 2 * base + 4 * (long long)f, x);
+                    }
+                    lds[lds_index<C, -1>(c, e)] = {x[0], x[2]};
+                    lds[lds_index<C, -1>(c, C::N - 1 - e)] = {x[3], x[1]};
+                }
+            } else {
+                T* ldr = (T*)lds;
+                for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                    const int c = f / C::N, j = f - c * C::N, q = 2 * C::N - 1 - j;
+                    V x;
+                    if constexpr (!same_t<typename C::IT, T>::value)
+                        x = load_foreign<C>(p.in, base + f);
+                    else
+                        x = gload<NTL>((const V*)p.in + base + f);
+                    ldr[2 * lds_index<C, -1>(c, j >> 1) + (j & 1)] = x.x;
+                    ldr[2 * lds_index<C, -1>(c, q >> 1) + (q & 1)] = x.y;
+                }
+            }
             __syncthreads();
         } else if constexpr (!C::FIRST_DIRECT) {
             // flat, fully coalesced HBM -> LDS copy of the tile (rows need not be 16-B aligned: N = 93)
@@ -1600,6 +1697,22 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 const V wk = w[k];
                 const T tx = wk.x * ox - wk.y * oy, ty = wk.x * oy + wk.y * ox;
                 V a = {ex + tx, ey + ty}, b = {ex - tx, ty - ey};
+                if constexpr (C::DCT == 2) {
+                    // a = V[k], b = V[N-k]: t = W_4n^k a gives X[k] = 2 Re t and X[n-k] = -2 Im t, u = W_4n^(N-k) b gives
+                    // X[N-k] and X[N+k].  Four runs of reals over the lanes, two ascending and two descending.  k = 0: X[n]
+                    // does not exist and X[N] comes from Re u alone; 2 k = N: a and b are the same bin.
+                    const V* w4 = (const V*)p.dct_tw;
+                    const V wa = w4[k], wb = w4[C::N - k];
+                    const T s1 = (T)p.dct_s1, s0 = k == 0 ? (T)p.dct_s0 : s1;
+                    T* xrow = (T*)p.out + (row0 + c) * (2 * C::N);
+                    xrow[k] = s0 * (wa.x * a.x - wa.y * a.y);
+                    if (k) xrow[2 * C::N - k] = -s1 * (wa.x * a.y + wa.y * a.x);
+                    if (2 * k != C::N) {
+                        xrow[C::N - k] = s1 * (wb.x * b.x - wb.y * b.y);
+                        if (k) xrow[C::N + k] = -s1 * (wb.x * b.y + wb.y * b.x);
+                    }
+                    continue;
+                }
                 if (p.inverse) {  // the inverse of a real row: conj(X) / 2N
                     a.x *= (T)p.scale;
                     a.y *= -(T)p.scale;
@@ -1613,6 +1726,26 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             __syncthreads();
         } else if constexpr (C::ILV > 0) {
             ilv_store<C>(p, lds, base, nv * C::N, tid);
+            __syncthreads();
+        } else if constexpr (C::DCT == 3) {
+            // conj(z) of the packed row z_j = v[2j] + i v[2j+1] lies in LDS, already scaled: x[2j] is slot j of v, x[2j+1]
+            // slot n - 1 - j; stored as one flat run
+            if constexpr (C::DCT_QUADS) {  // quad e of a row from conj z_e and conj z_(N-1-e)
+                constexpr int H = C::N / 2;
+                for (int f = tid; f < nv * H; f += C::THREADS) {
+                    const int c = f / H, e = f - c * H;
+                    const V a = lds[lds_index<C, C::NP - 1>(c, e)], b = lds[lds_index<C, C::NP - 1>(c, C::N - 1 - e)];
+                    gstore4<(C::NT & 2) != 0>((T*)p.out + 2 * base + 4 * (long long)f, a.x, -b.y, -a.y, b.x);
+                }
+            } else {
+                const T* ldr = (const T*)lds;
+                for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                    const int c = f / C::N, j = f - c * C::N, q = 2 * C::N - 1 - j;
+                    const T x0 = ldr[2 * lds_index<C, C::NP - 1>(c, j >> 1) + (j & 1)];
+                    const T x1 = ldr[2 * lds_index<C, C::NP - 1>(c, q >> 1) + (q & 1)];
+                    gstore<(C::NT & 2) != 0>((V*)p.out + base + f, V{(j & 1) ? -x0 : x0, (q & 1) ? -x1 : x1});
+                }
+            }
             __syncthreads();
         } else if constexpr (!C::LAST_DIRECT) {
             V* gout = (V*)p.out;

@@ -146,6 +146,32 @@ typedef enum {
 #define MIFFT_FLAG_KEEP_DIM(d) ((uint32_t)1u << (8 + (d)))
 #define MIFFT_FLAG_KEEP_MASK 0x3F00u
 
+/* DCT-II / DCT-III of real rows (scipy.fft.dct / idct of type 2 along the last axis; no reference counterpart).  ndim = 1,
+ * dims = {n}, in_components = 1 in both directions; x and out are both REAL, (batch, n, 1):
+ *   forward (inverse = 0, any in_dtype):   X[k] = 2 sum_j x[j] cos(pi k (2j+1) / 2n)                = scipy dct(x, 2)
+ *   inverse (inverse = 1, in_dtype == out_dtype in {F32, F64}):
+ *       x[j] = (X[0] + 2 sum_{k>=1} X[k] cos(pi k (2j+1) / 2n)) / 2n                                = scipy idct(X, 2)
+ * With MIFFT_FLAG_DCT_ORTHO (scipy norm="ortho") the forward scales X[0] by sqrt(1/4n) and every other bin by sqrt(1/2n),
+ * and the inverse is the transpose of that orthonormal forward; forward then inverse is the identity in both norms.
+ * `bases_flat`, when given, lists the radices of the packed N = n / 2-point transform the plan runs and reports: they must
+ * multiply to n / 2, not to n (MIFFT_ERR_BAD_BASES otherwise); NULL selects the default estimate for n / 2.
+ * x and out need the alignment of one element only (the kernels' wider accesses tolerate any such pointer).
+ * mifft_plan_in_bytes / out_bytes are batch * n real elements.  One launch, no scratch: the packed real-row kernel of the
+ * N = n / 2-point transform (mifft_plan_stages(0) reports its stages), with the even / odd permutation in its load and the
+ * quarter-sample twiddle in its store; mifft_plan_kernel_name(0) is rows<n>[_f64]_dct2_<radices> or ..._dct3_<radices>.
+ * in_components != 1 is MIFFT_ERR_BAD_COMPONENTS, a foreign in_dtype of an inverse plan MIFFT_ERR_BAD_DTYPE.
+ * MIFFT_ERR_UNSUPPORTED (with the reason), before any device work, for:
+ *   - ndim != 1;
+ *   - an odd n, or one below 8;
+ *   - n / 2 without a packed configuration: a prime factor above 32, n above 16384 (F64: above 8192), a row tile beyond
+ *     96 KiB of LDS;
+ *   - MIFFT_FLAG_DCT together with MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_FAITHFUL_STAGES or any keep bit;
+ *   - MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT;
+ *   - MIFFT_JIT=0 and an n without a precompiled instance: precompiled for 1024 points (F32 and F64, input of the plan's
+ *     own float type); every other length is specialised at run time. */
+#define MIFFT_FLAG_DCT 4u
+#define MIFFT_FLAG_DCT_ORTHO 8u
+
 typedef struct mifft_plan mifft_plan;
 
 /*

@@ -123,7 +123,9 @@ inline void check_layout_conditions_nd(const std::vector<int64_t>& in_layout, co
 // flags = MIFFT_FLAG_FAITHFUL_STAGES (the user's stages run literally, one LDS pass each).  With MIFFT_FLAG_HALF_SPECTRUM the
 // layouts are those of include/mifft.h: the last dimension of the complex side holds h = n / 2 + 1 bins (checked by the
 // library: mifft_plan_create receives the logical real dims).  MIFFT_FLAG_KEEP_DIM(d) leaves dim d untransformed (its bases
-// list, when given, is empty).
+// list, when given, is empty).  MIFFT_FLAG_DCT (with MIFFT_FLAG_DCT_ORTHO for norm = "ortho") plans a DCT-II, or with
+// `inverse` its inverse, of real rows: its layouts are (batch, n, 1) on BOTH sides, which check_layout_conditions_nd refuses
+// (it wants a complex out_layout), so such a plan is created through mifft_plan_create itself.
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
