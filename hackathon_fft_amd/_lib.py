@@ -19,7 +19,7 @@ EXPORTS = (
     "mifft_plan_kernel_name", "mifft_plan_num_launches", "mifft_plan_in_bytes", "mifft_plan_out_bytes",
     "mifft_ordered_bases", "mifft_estimate_bases", "mifft_last_error", "mifft_status_string",
     "mifft_version", "mifft_device_count", "mifft_time_exec", "mifft_jit_precompile", "mifft_plan_scratch_bytes",
-    "mifft_plan_device_status", "mifft_plan_create_slab",
+    "mifft_plan_device_status", "mifft_plan_create_slab", "mifft_plan_pass_geometry",
 )
 
 
@@ -63,6 +63,7 @@ def lib() -> ctypes.CDLL:
     L.mifft_plan_kernel_name.argtypes = [vp, c.c_int]
     L.mifft_plan_kernel_name.restype = c.c_char_p
     L.mifft_plan_num_launches.argtypes = [vp]
+    L.mifft_plan_pass_geometry.argtypes = [vp, c.c_int, i64, c.POINTER(i64)]
     L.mifft_plan_in_bytes.argtypes = [vp]
     L.mifft_plan_in_bytes.restype = c.c_size_t
     L.mifft_plan_out_bytes.argtypes = [vp]

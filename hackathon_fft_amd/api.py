@@ -254,6 +254,16 @@ class Plan:
     def num_launches(self) -> int:
         return check(_lib.lib().mifft_plan_num_launches(self._h))
 
+    def pass_geometry(self, dim: int, count: Optional[int] = None) -> tuple:
+        """(tile, threads, n_tiles, grid) of the launch that an exec of ``count`` batch entries (default: the whole batch)
+        makes for dimension ``dim``: transforms per workgroup tile, threads per workgroup, tiles, persistent workgroups.
+        Workgroup w walks the tiles w, w + grid, ..; computed by the launch's own code (mifft_plan_pass_geometry).
+        MifftError -15 for a kept dim or a pass that is not one persistent tile-kernel launch."""
+        g = (ctypes.c_int64 * 4)()
+        count = self.out_shape[0] if count is None else int(count)
+        check(_lib.lib().mifft_plan_pass_geometry(self._h, int(dim), count, g))
+        return tuple(int(v) for v in g)
+
     @property
     def in_bytes(self) -> int:
         return int(_lib.lib().mifft_plan_in_bytes(self._h))

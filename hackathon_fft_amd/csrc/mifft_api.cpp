@@ -752,6 +752,23 @@ const char* mifft_plan_kernel_name(const mifft_plan* plan, int dim) {
     return "";
 }
 
+int mifft_plan_pass_geometry(const mifft_plan* plan, int dim, int64_t count, int64_t geometry_out[4]) {
+    if (!plan || !geometry_out) return set_error(MIFFT_ERR_NULL, "plan or geometry_out is NULL");
+    if (dim < 0 || dim >= plan->p.ndim) return set_error(MIFFT_ERR_BAD_RANK, "dim out of range");
+    if (count < 1) return set_error(MIFFT_ERR_BAD_BATCH, "count must be positive");
+    if (plan->p.kept(dim)) return set_error(MIFFT_ERR_UNSUPPORTED, "a kept dim has no pass");
+    const DimPass* found = nullptr;
+    for (const DimPass& ps : plan->p.passes)
+        if (ps.dim_index == dim || ps.dim_index2 == dim) {
+            if (found) return set_error(MIFFT_ERR_UNSUPPORTED, "the dimension takes more than one launch");
+            found = &ps;
+        }
+    if (!found || found->dim_index2 >= 0 || !tile_pass_geometry(plan->p, *found, count, geometry_out))
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("pass \"") + (found ? found->kernel_name : "none") +
+                                                    "\" is not one persistent tile_kernel launch");
+    return MIFFT_OK;
+}
+
 int mifft_plan_num_launches(const mifft_plan* plan) {
     if (!plan) return set_error(MIFFT_ERR_NULL, "plan is NULL");
     return (int)plan->p.passes.size();

@@ -223,6 +223,9 @@ bool select_fast(const Plan& plan, DimPass& pass);
 bool select_dpp_rows(const Plan& plan, DimPass& pass);
 // the tile kernel specialised at plan time with hipRTC for a length without a table entry (kernels_jit.cpp)
 bool select_jit(const Plan& plan, DimPass& pass, std::string& why_not);
+// {tile, threads, n_tiles, grid} of the launch such a pass (or a precompiled packed-row one) makes for `count` batch entries,
+// from the function the launch itself uses; false for a pass of another launcher (mifft_plan_pass_geometry)
+bool tile_pass_geometry(const Plan& plan, const DimPass& pass, int64_t count, int64_t geometry_out[4]);
 // interleaved block tile (TileCfg::ILV) of a masked plan's pass whose stride pass.inner holds fewer than 128 B of elements:
 // false (+ the reason) when the length or the block does not fit it
 bool select_jit_ilv(const Plan& plan, DimPass& pass, std::string& why_not);

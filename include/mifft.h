@@ -263,6 +263,12 @@ int mifft_plan_stages(const mifft_plan* plan, int dim, uint32_t* radices_out, in
 /* name of the kernel family chosen for dim `dim` ("generic", "wave1024", ...) */
 const char* mifft_plan_kernel_name(const mifft_plan* plan, int dim);
 
+/* tile (transforms per workgroup tile), threads, n_tiles and grid of the launch that an exec of
+ * `count` batch entries makes for dimension `dim`; MIFFT_ERR_UNSUPPORTED for a pass that is not one
+ * persistent tile_kernel launch, or for a kept dim.  The kernels are persistent: workgroup w walks the
+ * tiles w, w + grid, ... (n_tiles > grid: more than one round).  Computed by the launch's own code. */
+int mifft_plan_pass_geometry(const mifft_plan* plan, int dim, int64_t count, int64_t geometry_out[4]);
+
 /* number of kernel launches one exec enqueues (reference: d + 2(d-1),
  * fft/fft/_ndim_fft_gpu.mojo:634-642) */
 int mifft_plan_num_launches(const mifft_plan* plan);

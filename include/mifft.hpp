@@ -86,6 +86,12 @@ class Plan {
     }
     std::string kernel_name(int dim) const { return mifft_plan_kernel_name(h_, dim); }
     int num_launches() const { return mifft_plan_num_launches(h_); }
+    // {tile, threads, n_tiles, grid} of the launch for dimension `dim` over `count` batch entries
+    std::vector<int64_t> pass_geometry(int dim, int64_t count) const {
+        std::vector<int64_t> g(4);
+        check(mifft_plan_pass_geometry(h_, dim, count, g.data()));
+        return g;
+    }
     size_t in_bytes() const { return mifft_plan_in_bytes(h_); }
     size_t out_bytes() const { return mifft_plan_out_bytes(h_); }
     size_t scratch_bytes() const { return mifft_plan_scratch_bytes(h_); }

@@ -30,7 +30,7 @@ def test_flag_and_status_are_declared():
 
 
 def test_export_list_and_version_are_unchanged():
-    assert len(_lib.EXPORTS) == 20 and "mifft_plan_create_slab" in _lib.EXPORTS
+    assert len(_lib.EXPORTS) == 21 and "mifft_plan_create_slab" in _lib.EXPORTS  # (+ mifft_plan_pass_geometry)
     assert _lib.lib().mifft_version() == 1
 
 
