@@ -4,17 +4,20 @@ martinvuyk/hackathon-fft).  See include/mifft.h for the C ABI, DESIGN.md for the
 from ._lib import MifftError, LIB_PATH, EXPORTS  # noqa: F401
 from .api import (  # noqa: F401
     FLAG_DCT,
+    FLAG_DCT_ND,
     FLAG_DCT_ORTHO,
     DeviceContext,
     GPUTest,
     Plan,
     clear_plan_cache,
     dct,
+    dctn,
     estimate_best_bases,
     estimate_best_bases_nd,
     fft,
     fftn,
     idct,
+    idctn,
     ifftn,
     irfftn,
     ordered_bases,
@@ -27,5 +30,5 @@ from .api import (  # noqa: F401
 __all__ = [
     "DeviceContext", "GPUTest", "Plan", "clear_plan_cache", "MifftError", "estimate_best_bases", "estimate_best_bases_nd",
     "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "reduce_dims", "rfftn", "time_fft", "dct", "idct",
-    "FLAG_DCT", "FLAG_DCT_ORTHO",
+    "FLAG_DCT", "FLAG_DCT_ORTHO", "FLAG_DCT_ND", "dctn", "idctn",
 ]

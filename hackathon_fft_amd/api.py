@@ -36,6 +36,7 @@ FLAG_FAITHFUL_STAGES = 1
 FLAG_HALF_SPECTRUM = 2  # MIFFT_FLAG_HALF_SPECTRUM: numpy's one-sided rfftn / irfftn layouts (include/mifft.h)
 FLAG_DCT = 4            # MIFFT_FLAG_DCT: DCT-II (inverse: its inverse) of real rows, (batch, n, 1) on both sides
 FLAG_DCT_ORTHO = 8      # MIFFT_FLAG_DCT_ORTHO: scipy's norm="ortho" of such a plan
+FLAG_DCT_ND = 16        # MIFFT_FLAG_DCT_ND: N-D DCT-II (inverse: its inverse) of real tensors, (batch, d0.., 1) on both sides
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -162,6 +163,22 @@ def _check_dct_layout(in_shape: tuple, out_shape: tuple) -> tuple:
     return (n,)
 
 
+def _check_dctn_layout(in_shape: tuple, out_shape: tuple) -> tuple:
+    """Layouts of an N-D DCT plan (MIFFT_FLAG_DCT_ND): both sides real (batch, d0.., 1) of one shape; returns the dims d0.."""
+    if len(in_shape) < 3 or len(in_shape) != len(out_shape):
+        raise MifftError(-1, f"N-D DCT layouts are (batch, d0[, d1..], 1) with equal ranks, got {in_shape} -> {out_shape}")
+    if len(in_shape) - 2 > MAX_DIMS:
+        raise MifftError(-1, f"at most {MAX_DIMS} dims between batch and the trailing 1, got {len(in_shape) - 2}")
+    if in_shape[-1] != 1 or out_shape[-1] != 1:
+        raise MifftError(-3, f"both sides of a DCT plan have 1 component, got {in_shape[-1]} and {out_shape[-1]}")
+    if in_shape != out_shape:
+        raise MifftError(-2, f"a DCT writes as many reals as it reads: {in_shape} -> {out_shape}")
+    dims = in_shape[1:-1]
+    if any(d == 1 for d in dims):
+        raise MifftError(-2, "no inner dimension should be of size 1")
+    return dims
+
+
 def _dct_norm_flags(norm) -> int:
     """scipy's ``norm`` of a DCT plan as flag bits: None / "backward" (the unnormalised forward) or "ortho" """
     if norm is None or norm == "backward":
@@ -193,15 +210,23 @@ class Plan:
     ``dct=True`` (no reference counterpart): DCT-II of real rows, ``inverse`` its inverse, both sides (batch, n, 1); ``norm``
     is scipy's (None / "backward" / "ortho").  ``bases`` of such a plan holds one list whose radices multiply to n // 2, the
     packed transform the plan runs and ``stages(0)`` reports -- not to n.  See _check_dct_layout and MIFFT_FLAG_DCT in
-    include/mifft.h."""
+    include/mifft.h.
+    ``dctn=True`` (no reference counterpart): the N-D DCT-II (``inverse``: its inverse) over the dims of a real
+    (batch, d0.., 1) tensor, ``axes`` and ``norm`` as above (MIFFT_FLAG_DCT_ND in include/mifft.h, _check_dctn_layout);
+    ``bases`` factor n // 2 for a transformed last dim and n for the others."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
-                 dct: bool = False, norm=None):
+                 dct: bool = False, norm=None, dctn: bool = False):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
-        if dct:  # (with half_spectrum as well: the library refuses the pair)
+        dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
+        if dctn:  # (with dct or half_spectrum as well: the library refuses the pair)
+            dims = _check_dctn_layout(in_shape, out_shape)
+            flags = (int(flags) | FLAG_DCT_ND | _dct_norm_flags(norm) | (FLAG_DCT if dct else 0) |
+                     (FLAG_HALF_SPECTRUM if half_spectrum else 0))
+        elif dct:  # (with half_spectrum as well: the library refuses the pair)
             dims = _check_dct_layout(in_shape, out_shape)
             flags = int(flags) | FLAG_DCT | _dct_norm_flags(norm) | (FLAG_HALF_SPECTRUM if half_spectrum else 0)
         elif half_spectrum:
@@ -222,6 +247,7 @@ class Plan:
         self.axes = None if axes is None else tuple(int(a) for a in axes)
         self.half_spectrum = bool(half_spectrum)
         self.dct = dct
+        self.dctn = dctn
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if bases is not None:
             flat = [int(b) for bs in bases for b in bs]
@@ -303,7 +329,7 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
              inverse: bool = False, runtime_twfs: bool = True, max_cluster_size: int = 8,
              _test: Optional[GPUTest] = None, faithful_stages: bool = False,
              ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False,
-             axes: Optional[Sequence[int]] = None, dct: bool = False, norm=None) -> Plan:
+             axes: Optional[Sequence[int]] = None, dct: bool = False, norm=None, dctn: bool = False) -> Plan:
     """GPU overload of plan_fft (fft/fft/fft.mojo:161-210).
 
     ``runtime_twfs`` and ``max_cluster_size`` are accepted for call-site compatibility
@@ -319,9 +345,14 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     ``dct`` (no reference counterpart): DCT-II (``inverse``: its inverse) of the real rows of a (batch, n, 1) tensor into
     one of the same shape, ``norm`` None / "backward" / "ortho" as scipy.fft.dct (include/mifft.h, MIFFT_FLAG_DCT); ``bases``
     then factor n // 2, the packed transform the plan runs.
+    ``dctn`` (no reference counterpart): the N-D DCT-II (``inverse``: its inverse) of a real (batch, d0.., 1) tensor into one of
+    the same shape, over ``axes`` (None: every dim), ``norm`` as for ``dct`` (include/mifft.h, MIFFT_FLAG_DCT_ND).
     """
     del runtime_twfs, max_cluster_size
-    if dct:  # (layout errors before any device work)
+    if dctn:  # (layout errors before any device work)
+        _check_dctn_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout))
+        _dct_norm_flags(norm)
+    elif dct:
         _check_dct_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout))
         _dct_norm_flags(norm)
     elif half_spectrum:
@@ -332,7 +363,7 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     flags = FLAG_FAITHFUL_STAGES if (faithful_stages or _test is not None) else 0
     return Plan(in_dtype, out_dtype, in_layout, out_layout, bases=bases, inverse=inverse,
                 device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum, axes=axes,
-                dct=dct, norm=norm)
+                dct=dct, norm=norm, dctn=dctn)
 
 
 def _check_tensor(t: "torch.Tensor", shape: tuple, dtype, device: int, what: str) -> None:
@@ -409,7 +440,7 @@ def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, fai
 
 def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
                         half_spectrum: bool = False, axes=None, dct_flags: int = 0) -> Plan:
-    # dct_flags: FLAG_DCT (| FLAG_DCT_ORTHO) of the dct / idct wrappers' plans, 0 for every other
+    # dct_flags: FLAG_DCT or FLAG_DCT_ND (| FLAG_DCT_ORTHO) of the dct / idct / dctn / idctn wrappers' plans, 0 for every other
     key = (in_dtype, out_dtype, in_shape, out_shape,
            None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
            bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
@@ -419,7 +450,7 @@ def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inver
         try:
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
                             faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
-                            axes=axes, dct=bool(dct_flags & FLAG_DCT),
+                            axes=axes, dct=bool(dct_flags & FLAG_DCT), dctn=bool(dct_flags & FLAG_DCT_ND),
                             norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
@@ -704,3 +735,59 @@ def idct(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: in
     ``x[j] = (X[0] + 2 sum_{k>=1} X[k] cos(pi k (2j+1) / 2n)) / 2n``.  Same layout, ``dim`` and dtype rules as dct; the input
     is converted to ``out_dtype`` first."""
     return _dct_rows(x, type, norm, out_dtype, dim, True)
+
+
+def _dct_nd(x: "torch.Tensor", type: int, norm, dim, out_dtype, inverse: bool) -> "torch.Tensor":
+    """dctn / idctn: validation on the host, then one plan over the reduced (batch, e0.., 1) view of ``x``"""
+    name = "idctn" if inverse else "dctn"
+    if type != 2:
+        raise MifftError(ERR_UNSUPPORTED, f"{name}: only type 2 is supported, got type={type!r}")
+    dct_flags = FLAG_DCT_ND | _dct_norm_flags(norm)
+    if x.is_complex():
+        raise MifftError(-3, f"{name} expects a real tensor")
+    if x.dim() < 2:
+        raise MifftError(-1, f"{name} expects a tensor of rank 2 or more: (batch, d0..)")
+    logical = tuple(x.shape)
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if out_dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"{name}: out_dtype must be float32 or float64, got {out_dtype}")
+    if not inverse and x.dtype not in _DTYPE_CODE:
+        raise MifftError(-4, f"{name}: unsupported input dtype {x.dtype}")
+    r = reduce_dims(logical, tuple(range(1, len(logical))) if dim is None else dim)
+    if r is None:  # nothing to transform: a converted copy
+        return x.to(out_dtype, copy=True)
+    layout, axes = r
+    # a narrow input dtype goes to the plan only when the last dim is transformed (its row pass widens it); a plan whose
+    # first pass is a column pass, and every inverse, reads the plan's own float type
+    if inverse or (len(layout) - 1) not in axes:
+        x = x.to(out_dtype)
+    shape = layout + (1,)
+    _check_dctn_layout(shape, shape)
+    xr = x.contiguous().reshape(shape)
+    device = DeviceContext(xr.device.index if xr.is_cuda else None).device
+    out = torch.empty(shape, dtype=out_dtype, device=xr.device)
+    with _PLAN_CACHE_LOCK:
+        plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device,
+                                   axes=None if len(axes) == len(layout) - 1 else axes, dct_flags=dct_flags)
+        fft(out, xr, DeviceContext(device), plan=plan)
+    return out.reshape(logical)
+
+
+def dctn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=None) -> "torch.Tensor":
+    """scipy.fft.dctn(x, type=2, norm=norm) over the dims ``dim`` of a real tensor of rank >= 2: the DCT-II of ``dct`` along
+    each of them.  ``dim=None``: every dim but the first, as fftn; otherwise torch's ``dim=`` on the shape of ``x`` (dim 0 and
+    negative dims allowed), resolved through reduce_dims: the other dims are carried through in place.  One kernel launch per
+    transformed dim and no transposition (MIFFT_FLAG_DCT_ND): the innermost transformed dim, when it is the last dim of size
+    above 1, runs the row kernel of ``dct`` (an even length from 8 on); every other one is transformed in place as pairs of
+    adjacent real columns (any length from 2 to 4096 with prime factors up to 32, at an even stride of at least 4 elements).
+    The result has the shape of ``x`` and dtype ``out_dtype`` (default: that of a float32 / float64 ``x``, else float64); a
+    non-contiguous ``x`` is copied first; an empty ``dim`` or one of size-1 dims only returns a converted copy.  Only
+    ``type=2`` (MifftError -15 otherwise); ``norm`` as in ``dct``."""
+    return _dct_nd(x, type, norm, dim, out_dtype, False)
+
+
+def idctn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=None) -> "torch.Tensor":
+    """scipy.fft.idctn(x, type=2, norm=norm), the inverse of dctn under the same ``norm`` and ``dim``; the input is converted
+    to ``out_dtype`` first."""
+    return _dct_nd(x, type, norm, dim, out_dtype, True)

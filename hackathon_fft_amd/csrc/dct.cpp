@@ -56,7 +56,7 @@ int dct_check(const Plan& p, std::string& why) {
 
 // W_4n^k = e^(-2 pi i k / 4n), k = 0 .. n / 2, evaluated in long double and rounded once
 template <typename T>
-static hipError_t upload_quarter_table(int64_t n, void** d_table) {
+static hipError_t upload_quarter_table_t(int64_t n, void** d_table) {
     const long double half_pi = 1.570796326794896619231321691639751442L;
     std::vector<T> tab((size_t)(n / 2 + 1) * 2);
     for (int64_t k = 0; k <= n / 2; ++k) {
@@ -69,38 +69,51 @@ static hipError_t upload_quarter_table(int64_t n, void** d_table) {
     return e;
 }
 
-int build_dct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
-    const int64_t n = p.dims[0];
+hipError_t upload_quarter_table(int out_dtype, int64_t n, void** d_table) {
+    return out_dtype == MIFFT_F64 ? upload_quarter_table_t<double>(n, d_table) : upload_quarter_table_t<float>(n, d_table);
+}
+
+// the scales of bin 0 and of the other bins.  Forward: X[k] = 2 Re(..), "ortho" times sqrt(1 / 4n) and sqrt(1 / 2n).
+// Inverse: the bins are scaled as they are loaded -- the half of V[k] = conj(W) (X[k] - i X[n-k]) / 2, the 1 / n of the
+// n-point inverse, and "ortho" undone (times sqrt(4n) and sqrt(2n)).
+void dct_scales(int64_t n, bool inverse, bool ortho, double& s0, double& s1) {
+    const long double dn = (long double)n;
+    if (!inverse) {
+        s0 = (double)(ortho ? 2.0L * sqrtl(1.0L / (4.0L * dn)) : 2.0L);
+        s1 = (double)(ortho ? 2.0L * sqrtl(1.0L / (2.0L * dn)) : 2.0L);
+    } else {
+        s0 = (double)(ortho ? sqrtl(4.0L * dn) / (2.0L * dn) : 1.0L / (2.0L * dn));
+        s1 = (double)(ortho ? sqrtl(2.0L * dn) / (2.0L * dn) : 1.0L / (2.0L * dn));
+    }
+}
+
+// the packed-row pass of n points over `outer` rows per batch entry (the one pass of a MIFFT_FLAG_DCT plan, the first pass
+// of an N-D DCT plan whose last dimension is transformed): kernel, scales and tables; appended to plan.passes
+int build_dct_rows(Plan& p, int dim_index, int64_t outer, const std::vector<uint32_t>& ordered,
+                   const std::vector<uint32_t>& processed, std::string& why) {
+    const int64_t n = p.dims[dim_index];
     DimPass ps;
-    ps.dim_index = 0;
+    ps.dim_index = dim_index;
     ps.N = n;
     ps.inner = 1;
-    ps.outer = 1;
+    ps.outer = outer;
     ps.radices = ordered;
     ps.processed = processed;
     ps.first = true;
     ps.half_pitch = n / 2 + 1;  // (unused by the DCT loads and stores: both sides are rows of n reals)
     if (!select_jit_dct_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
-    // the scales of bin 0 and of the other bins.  Forward: X[k] = 2 Re(..), "ortho" times sqrt(1 / 4n) and sqrt(1 / 2n).
-    // Inverse: the bins are scaled as they are loaded -- the half of V[k] = conj(W) (X[k] - i X[n-k]) / 2, the 1 / n of the
-    // n-point real inverse, and "ortho" undone (times sqrt(4n) and sqrt(2n)).
-    const bool ortho = (p.flags & MIFFT_FLAG_DCT_ORTHO) != 0;
-    const long double dn = (long double)n;
-    if (!p.inverse) {
-        ps.dct_s0 = (double)(ortho ? 2.0L * sqrtl(1.0L / (4.0L * dn)) : 2.0L);
-        ps.dct_s1 = (double)(ortho ? 2.0L * sqrtl(1.0L / (2.0L * dn)) : 2.0L);
-    } else {
-        ps.dct_s0 = (double)(ortho ? sqrtl(4.0L * dn) / (2.0L * dn) : 1.0L / (2.0L * dn));
-        ps.dct_s1 = (double)(ortho ? sqrtl(2.0L * dn) / (2.0L * dn) : 1.0L / (2.0L * dn));
-    }
+    dct_scales(n, p.inverse != 0, (p.flags & MIFFT_FLAG_DCT_ORTHO) != 0, ps.dct_s0, ps.dct_s1);
     // the passes run n / 2 points; the fold / unpacking needs W_n^k, forward; the DCT twiddle W_4n^k
     hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, p.inverse != 0, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
-    if (e == hipSuccess)
-        e = p.out_dtype == MIFFT_F64 ? upload_quarter_table<double>(n, &ps.d_aux2) : upload_quarter_table<float>(n, &ps.d_aux2);
+    if (e == hipSuccess) e = upload_quarter_table(p.out_dtype, n, &ps.d_aux2);
     p.passes.push_back(ps);
     if (e != hipSuccess) return hip_error(e, "DCT table upload");
     return MIFFT_OK;
+}
+
+int build_dct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    return build_dct_rows(p, 0, 1, ordered, processed, why);
 }
 
 }  // namespace mifft

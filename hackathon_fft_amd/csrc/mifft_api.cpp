@@ -29,11 +29,11 @@ int hip_error(hipError_t e, const char* what) {
 size_t Plan::in_elem_bytes() const { return dtype_size(in_dtype) * (size_t)in_components; }
 size_t Plan::out_elem_bytes() const { return dtype_size(out_dtype) * 2; }
 size_t Plan::in_row_bytes() const {
-    if (dct()) return (size_t)prod * dtype_size(in_dtype);
+    if (dct_any()) return (size_t)prod * dtype_size(in_dtype);
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
-    if (dct()) return (size_t)prod * dtype_size(out_dtype);
+    if (dct_any()) return (size_t)prod * dtype_size(out_dtype);
     if (!half_spectrum()) return (size_t)prod * out_elem_bytes();
     return inverse ? (size_t)prod * dtype_size(out_dtype) : (size_t)prod_half * out_elem_bytes();
 }
@@ -215,22 +215,23 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
     if ((bases_flat == nullptr) != (bases_len == nullptr))
         return set_error(MIFFT_ERR_NULL, "bases_flat and bases_len must both be given or both be NULL");
     // ---- DCT plans (MIFFT_FLAG_DCT; dct.cpp): everything that can be refused without a device, before anything else ----
-    if ((flags & MIFFT_FLAG_DCT_ORTHO) && !(flags & MIFFT_FLAG_DCT))
-        return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT");
-    if (flags & MIFFT_FLAG_DCT) {
+    if ((flags & MIFFT_FLAG_DCT_ORTHO) && !(flags & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ND)))
+        return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND");
+    if (flags & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ND)) {  // (N-D plans, dctn.cpp: the same, and before the keep bits are looked at)
         Plan t;
         t.in_dtype = in_dtype;
         t.out_dtype = out_dtype;
         t.ndim = ndim;
         for (int i = 0; i < ndim; ++i) t.dims[i] = dims[i];
-        t.prod = dims[0];
+        t.prod = 1;
+        for (int i = 0; i < ndim; ++i) t.prod *= dims[i];
         t.batch = batch;
         t.sel_batch = whole_batch;
         t.in_components = in_components;
         t.inverse = inverse ? 1 : 0;
         t.flags = flags;
         std::string why;
-        const int rc = dct_check(t, why);
+        const int rc = (flags & MIFFT_FLAG_DCT_ND) ? dctn_check(t, why) : dct_check(t, why);
         if (rc) return set_error(rc, why);
     }
     // ---- kept dimensions (MIFFT_FLAG_KEEP_DIM; axes.cpp) ----
@@ -282,9 +283,10 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
             user = plan_estimate_bases((uint64_t)dims[i], /*gpu_target=*/true);
         }
         std::string err;
-        // (a DCT plan runs, and reports, the stages of its packed n / 2-point transform)
-        if (p.dct() && !bases_flat) user = plan_estimate_bases((uint64_t)dims[i] / 2, /*gpu_target=*/true);
-        int rc = plan_ordered_bases((uint64_t)dims[i] / (p.dct() ? 2 : 1), user, ordered[i], processed[i], err);
+        // (a DCT plan runs, and reports, the stages of its packed n / 2-point transform: for its rows, the last dimension)
+        const bool packed = p.dct() || (p.dct_nd() && i == ndim - 1);
+        if (packed && !bases_flat) user = plan_estimate_bases((uint64_t)dims[i] / 2, /*gpu_target=*/true);
+        int rc = plan_ordered_bases((uint64_t)dims[i] / (packed ? 2 : 1), user, ordered[i], processed[i], err);
         if (rc) {
             delete h;
             return set_error(rc, err);
@@ -308,7 +310,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
     }
 
     // ---- half-spectrum and masked plans: what can be refused without a device is refused here ----
-    if (p.keep_mask()) {
+    if (p.keep_mask() && !p.dct_nd()) {  // (an N-D DCT plan's own check has covered its lengths)
         std::string why;
         const int rc = axes_check(p, why);
         if (rc) {
@@ -360,9 +362,10 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
 
     // ---- passes in execution order: last dimension first ----
     p.stage_radices = ordered;
-    if (p.keep_mask() || p.half_spectrum() || p.dct()) {  // their own routes (axes.cpp, half_spectrum.cpp, dct.cpp); none of the selections below
+    if (p.keep_mask() || p.half_spectrum() || p.dct_any()) {  // their own routes (axes.cpp, half_spectrum.cpp, dct.cpp, dctn.cpp); none of the selections below
         std::string why;
         const int rc = p.dct()         ? build_dct(p, ordered[0], processed[0], why)
+                       : p.dct_nd()    ? build_dctn(p, ordered, processed, why)
                        : p.keep_mask() ? build_axes(p, ordered, processed, why)
                                        : build_half_spectrum(p, ordered, processed, why);
         if (rc) {

@@ -81,6 +81,8 @@ struct Config {
     std::string jit_defines;         // extra -D options for the runtime compiler (A/B of kernel-header macros)
     bool ilv = true;                 // interleaved block tiles for small kept strides of masked plans (MIFFT_ILV=0: the column
                                      // tiles instead; same-call A/B of tools/axes_probe.py)
+    bool dct_cols_direct = true;     // paired-column DCT-II tiles permute their rows in the direct pass-0 load (MIFFT_DCT_COLS_DIRECT=0:
+                                     // in a staging copy through LDS; same-call A/B of tools/dctn_probe.py)
     bool test_fail_scratch_alloc = false;  // -DMIFFT_TESTING: the next scratch allocation reports out-of-memory
 };
 
@@ -117,6 +119,7 @@ inline Config load_config() {
     if (const char* v = env("MIFFT_GRID_PER_CU")) c.grid_per_cu = atoi(v);
     if (const char* v = env("MIFFT_JIT_DEFINES")) c.jit_defines = v;
     if (const char* v = env("MIFFT_ILV")) c.ilv = v[0] != '0';
+    if (const char* v = env("MIFFT_DCT_COLS_DIRECT")) c.dct_cols_direct = v[0] != '0';
     if (const char* v = env("MIFFT_RADER_MIN")) c.rader_min = c.rader_min_pair = atoi(v);
     if (const char* v = env("MIFFT_RADER_PAD_MIN")) c.rader_pad_min = atoi(v);
 #endif

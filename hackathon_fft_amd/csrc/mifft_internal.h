@@ -93,8 +93,9 @@ struct DimPass {
     bool want_half = false, hs = false;
     bool r2c = false;  // packed real rows (TileCfg::R2C): the kernel runs N / 2 points; d_twiddle is that table, d_aux W_N^k
     bool c2r = false;  // half spectrum -> packed real rows (TileCfg::C2R): the same tables as r2c
-    // TileCfg::DCT of a packed-row pass (2: DCT-II on an r2c kernel, 3: its inverse on a c2r one): d_aux2 holds W_4N^k,
-    // k = 0 .. N / 2; the scales of bin 0 and of the other bins (TileParams::dct_s0 / dct_s1)
+    // TileCfg::DCT of a packed-row pass (2: DCT-II on an r2c kernel, 3: its inverse on a c2r one) or of a paired-column pass
+    // (neither r2c nor c2r; `inner` counts pairs of real columns): d_aux2 holds W_4N^k, k = 0 .. N / 2; the scales of bin 0
+    // and of the other bins (TileParams::dct_s0 / dct_s1)
     int dct = 0;
     double dct_s0 = 1.0, dct_s1 = 1.0;
     int64_t half_pitch = 0;  // R2C / C2R: row pitch (complex elements) of the half-spectrum side; 0 = N (full-spectrum rows)
@@ -151,6 +152,9 @@ struct Plan {
     int64_t prod_half = 0;
     // MIFFT_FLAG_DCT: both sides are (batch, n, 1) real tensors; what one exec moves is batch * n reals read and written
     bool dct() const { return (flags & MIFFT_FLAG_DCT) != 0; }
+    // MIFFT_FLAG_DCT_ND: both sides are (batch, d0.., 1) real tensors (dctn.cpp); dct_any: either DCT flag
+    bool dct_nd() const { return (flags & MIFFT_FLAG_DCT_ND) != 0; }
+    bool dct_any() const { return dct() || dct_nd(); }
     double dct_exec_bytes() const { return size_batch() * (double)prod * (double)(out_elem_bytes() / 2) * 2.0; }
     // bytes of ONE transform (one batch entry) of x, out and the plan scratch: the slab offsets and the alias check of
     // mifft_exec_batch and the size queries.  Without the flag: prod * in_elem_bytes(), prod * out_elem_bytes() twice.
@@ -256,6 +260,20 @@ bool dct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_dct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 int dct_check(const Plan& plan, std::string& why);
 int build_dct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
+// ... its pieces, shared with the N-D plans: the packed-row pass over dimension dim_index (`outer` rows per batch entry), the
+// scales of bin 0 and of the other bins, the table W_4n^k, k = 0 .. n / 2
+int build_dct_rows(Plan& plan, int dim_index, int64_t outer, const std::vector<uint32_t>& ordered,
+                   const std::vector<uint32_t>& processed, std::string& why);
+void dct_scales(int64_t n, bool inverse, bool ortho, double& s0, double& s1);
+hipError_t upload_quarter_table(int out_dtype, int64_t n, void** d_table);
+// plans with MIFFT_FLAG_DCT_ND (dctn.cpp): the checks that need no device, then one pass per transformed dimension.
+// select_jit_dct_cols is the column tile with TileCfg::DCT over pass.inner PAIRS of real columns (kernels_jit.cpp; compiled
+// at run time only), dct_cols_supported the same check without a device
+bool dct_cols_supported(const Plan& plan, int64_t n, int64_t inner, std::string& why_not);
+bool select_jit_dct_cols(const Plan& plan, DimPass& pass, std::string& why_not);
+int dctn_check(const Plan& plan, std::string& why);
+int build_dctn(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
+               const std::vector<std::vector<uint32_t>>& processed, std::string& why);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

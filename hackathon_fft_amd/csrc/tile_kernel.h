@@ -403,8 +403,23 @@ struct TileCfg {
     // store reads x back from the slots of v.  n reals read once, n reals written once.
     static constexpr int DCT = DCT_;
     static_assert(DCT_ == 0 || DCT_ == 2 || DCT_ == 3, "DCT: 0, 2 (DCT-II) or 3 (its inverse)");
-    static_assert(DCT_ != 2 || (R2C_ && !FIRST_DIRECT_), "DCT-II: packed real rows staged in LDS by the permuting load");
-    static_assert(DCT_ != 3 || (C2R_ && !LAST_DIRECT_), "inverse DCT-II: folded rows whose last pass stays in LDS");
+    //
+    // DCT on a COLUMN tile (N-D DCT plans, dctn.cpp): the dimension is n = N points at a stride of S reals, S even, and the
+    // tile's complex element at stride S / 2 is a PAIR of adjacent real columns, u = x_a + i x_b.  2: the rows of the tile are
+    // permuted as they are loaded (v[j] = u[2j], v[N-1-j] = u[2j+1]: in the direct pass-0 load, or by the staging copy when
+    // !FIRST_DIRECT), Z = F(v) stays in LDS, and the store loop -- one thread per pair of rows (k, N - k) and column --
+    // separates V_a = (Z[k] + conj Z[N-k]) / 2 and V_b = (Z[k] - conj Z[N-k]) / 2i, multiplies both by W_4n^k and stores
+    // row k as (s Re t_a, s Re t_b) and row N - k as (-s Im t_a, -s Im t_b).  3: the load combines rows k and N - k into
+    // Z[k] = conj(W_4n^k) (s_k U[k] - i s U[N-k]) and Z[N-k] in LDS (U[N] := 0), the passes run the inverse transform and
+    // the last pass stores element j straight to row 2j or 2 (N-1-j) + 1.  Every length N >= 2, odd ones included; every
+    // HBM access is a run of TILE adjacent elements.
+    static_assert(DCT_ != 2 || (COLS_ ? !LAST_DIRECT_ : (R2C_ && !FIRST_DIRECT_)),
+                  "DCT-II: packed real rows staged in LDS by the permuting load, or a paired-column tile whose last pass stays in LDS");
+    static_assert(DCT_ != 3 || (COLS_ ? (!FIRST_DIRECT_ && LAST_DIRECT_) : (C2R_ && !LAST_DIRECT_)),
+                  "inverse DCT-II: folded rows whose last pass stays in LDS, or a paired-column tile combined in LDS");
+    static_assert(!(DCT_ != 0 && COLS_) || (!R2C_ && !C2R_ && !IN_REAL_ && !TSTORE_ && !FS1_ && !HERM_ && !HS_ && !DMA_ && !WSUB_ &&
+                                            !ILV_ && same_t<IT_, T_>::value && R0_ <= 32 && R1_ <= 32),
+                  "DCT on a column tile: a plain in-place tile of register butterflies over pairs of real columns");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -413,7 +428,7 @@ struct TileCfg {
 #ifdef MIFFT_DCT_PAIRS
     static constexpr bool DCT_QUADS = false;
 #else
-    static constexpr bool DCT_QUADS = DCT_ != 0 && N_ % 2 == 0;
+    static constexpr bool DCT_QUADS = DCT_ != 0 && !COLS_ && N_ % 2 == 0;
 #endif
     static constexpr int CPITCH = TSTORE_ ? TILE_ + 1 : TILE_;
     static_assert(!TSTORE_ || (COLS_ && !LAST_DIRECT_ && FIRST_DIRECT_), "TSTORE: column tile, last pass left in LDS");
@@ -486,6 +501,17 @@ MIFFT_DEV int lds_index(int c, int n) {
         return n * C::CPITCH + c;
     else
         return c * C::LD + swz<C, E>(n);
+}
+
+// paired-column DCT tiles: element j of Makhoul's sequence v is row 2j of the column (j < ceil(N / 2)) or row 2 (N-1-j) + 1;
+// and its inverse, the element a row goes to
+template <class C>
+MIFFT_DEV int dct_row_of(int j) {
+    return j < (C::N + 1) / 2 ? 2 * j : 2 * (C::N - 1 - j) + 1;
+}
+template <class C>
+MIFFT_DEV int dct_elem_of(int row) {
+    return (row & 1) ? C::N - 1 - (row >> 1) : row >> 1;
 }
 
 template <class C>
@@ -773,6 +799,8 @@ MIFFT_DEV void load_pass0(const TileParams& p, cpx<typename C::T> (*v)[C::R(0)],
                 } else if constexpr (C::IN_REAL) {
                     v[k][j].x = gload_real<(C::NT & 1) != 0>((const T*)p.in + base + j * step + off);
                     v[k][j].y = (T)0;
+                } else if constexpr (C::DCT == 2 && C::COLS) {  // the permuted row: no longer affine in j
+                    v[k][j] = gload<(C::NT & 1) != 0>(gin + base + lane_off<C>(p, cc, dct_row_of<C>(b + j * NB)));
                 } else {
                     v[k][j] = gload<(C::NT & 1) != 0>(gin + base + j * step + off);
                 }
@@ -973,7 +1001,10 @@ MIFFT_DEV void pass_compute_scatter(const TileParams& p, cpx<typename C::T>* lds
                             y.x *= (T)p.scale;
                             y.y *= -(T)p.scale;
                         }
-                        if (!C::HS || o0 + s * P <= p.store_lim) gstore<(C::NT & 2) != 0>(gout + base + s * step + off, y);
+                        if constexpr (C::DCT == 3 && C::COLS)  // element o0 + s P of v: its row of the column
+                            gstore<(C::NT & 2) != 0>(gout + base + lane_off<C>(p, c, dct_row_of<C>(o0 + s * P)), y);
+                        else if (!C::HS || o0 + s * P <= p.store_lim)
+                            gstore<(C::NT & 2) != 0>(gout + base + s * step + off, y);
                     }
                 }
             } else {
@@ -1441,11 +1472,27 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             if constexpr (C::PREFETCH) vm_drain();
         };
         if constexpr (!C::FIRST_DIRECT && C::COLS) {
-            // column tile staged in LDS (only the big-prime pass 0 needs this): runs of TILE adjacent columns
-            static_assert(C::BIGP0, "column tiles load directly unless pass 0 works in LDS");
-            for (int f = tid; f < C::N * C::TILE; f += C::THREADS) {
+            // column tile staged in LDS (a big-prime pass 0 or a paired-column DCT needs this): runs of TILE adjacent columns
+            static_assert(C::BIGP0 || C::DCT != 0, "column tiles load directly unless pass 0 works in LDS");
+            // DCT = 3: one item per pair of rows (k, N - k), k = 0 .. N / 2, and column; else one per element
+            constexpr int LROWS = (C::DCT == 3) ? C::N / 2 + 1 : C::N;
+            for (int f = tid; f < LROWS * C::TILE; f += C::THREADS) {
                 const int n = f / C::TILE, c = f - n * C::TILE;
                 const int cc = c < nv ? c : nv - 1;  // ragged last tile: re-read a valid column, never stored
+                if constexpr (C::DCT == 3) {
+                    // U[k] and U[N-k] (U[N] := 0), both runs over the lanes: Z[k] = conj(W^k) (s_k U[k] - i s U[N-k]) and
+                    // Z[N-k] = i W^k (s U[N-k] - i s_k U[k]), W = W_4n^k; written conjugated (the passes run conj(F(conj Z)))
+                    const V* gin = (const V*)p.in;
+                    const V a = gload<(C::NT & 1) != 0>(gin + gaddr<C>(p, base, cc, n));
+                    const V b = n ? gload<(C::NT & 1) != 0>(gin + gaddr<C>(p, base, cc, C::N - n)) : V{(T)0, (T)0};
+                    const V w = ((const V*)p.dct_tw)[n];
+                    const T s1 = (T)p.dct_s1, sk = n == 0 ? (T)p.dct_s0 : s1;
+                    const T ar = sk * a.x, ai = sk * a.y, br = s1 * b.x, bi = s1 * b.y;
+                    const T qx = ar + bi, qy = ai - br, rx = br + ai, ry = bi - ar;
+                    lds[lds_index<C, -1>(c, n)] = {w.x * qx + w.y * qy, w.y * qx - w.x * qy};
+                    if (n != 0 && 2 * n != C::N) lds[lds_index<C, -1>(c, C::N - n)] = {-(w.x * ry + w.y * rx), w.y * ry - w.x * rx};
+                    continue;
+                }
                 V x;
                 if constexpr (!same_t<typename C::IT, T>::value)
                     x = load_foreign<C>(p.in, gaddr<C>(p, base, cc, n));
@@ -1454,7 +1501,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 else
                     x = gload<false>((const V*)p.in + gaddr<C>(p, base, cc, n));
                 if (p.inverse && C::CONJ_IN) x.y = -x.y;
-                lds[lds_index<C, -1>(c, n)] = x;
+                lds[lds_index<C, -1>(c, C::DCT == 2 ? dct_elem_of<C>(n) : n)] = x;
             }
             __syncthreads();
         } else if constexpr (C::C2R) {
@@ -1526,7 +1573,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
         } else if constexpr (C::ILV > 0) {
             ilv_load<C>(p, lds, base, nv * C::N, tid);
             __syncthreads();
-        } else if constexpr (C::DCT == 2) {
+        } else if constexpr (C::DCT == 2 && !C::COLS) {
             // the tile's nv * 2 N reals as one flat coalesced run; x[2j] goes to real slot j of its row, x[2j+1] to slot
             // n - 1 - j (pairs: two runs of 4-byte LDS stores, one ascending and one descending)
             constexpr bool NTL = (C::NT & 1) != 0;
@@ -1666,11 +1713,29 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             }
             __syncthreads();
         } else if constexpr (!C::LAST_DIRECT && C::COLS) {
-            // a strided PRIME length (one cooperative pass, result in LDS): runs of TILE adjacent columns
-            static_assert(C::BIGP(C::NP - 1), "column tiles store directly unless the last pass works in LDS");
+            // a strided PRIME length (one cooperative pass, result in LDS) or a paired-column DCT-II: runs of TILE adjacent columns
+            static_assert(C::BIGP(C::NP - 1) || C::DCT == 2, "column tiles store directly unless the last pass works in LDS");
             V* gout = (V*)p.out;
-            for (int f = tid; f < C::N * C::TILE; f += C::THREADS) {
+            // DCT = 2: one item per pair of rows (k, N - k), k = 0 .. N / 2, and column; else one per element
+            constexpr int SROWS = (C::DCT == 2) ? C::N / 2 + 1 : C::N;
+            for (int f = tid; f < SROWS * C::TILE; f += C::THREADS) {
                 const int n = f / C::TILE, c = f - n * C::TILE;
+                if constexpr (C::DCT == 2) {
+                    // V_a = (Z[k] + conj Z[N-k]) / 2 and V_b = (Z[k] - conj Z[N-k]) / 2i are the transforms of the two real
+                    // columns; t = W_4n^k V gives X[k] = s Re t and X[N-k] = -s Im t for each
+                    if (c < nv) {
+                        const V zk = lds[lds_index<C, C::NP - 1>(c, n)], zm = lds[lds_index<C, C::NP - 1>(c, n ? C::N - n : 0)];
+                        const T ax = (T)0.5 * (zk.x + zm.x), ay = (T)0.5 * (zk.y - zm.y);
+                        const T bx = (T)0.5 * (zk.y + zm.y), by = (T)-0.5 * (zk.x - zm.x);
+                        const V w = ((const V*)p.dct_tw)[n];
+                        const T s1 = (T)p.dct_s1, sk = n == 0 ? (T)p.dct_s0 : s1;
+                        gstore<(C::NT & 2) != 0>(gout + gaddr<C>(p, base, c, n), V{sk * (w.x * ax - w.y * ay), sk * (w.x * bx - w.y * by)});
+                        if (n != 0 && 2 * n != C::N)
+                            gstore<(C::NT & 2) != 0>(gout + gaddr<C>(p, base, c, C::N - n),
+                                                     V{-s1 * (w.x * ay + w.y * ax), -s1 * (w.x * by + w.y * bx)});
+                    }
+                    continue;
+                }
                 if (c < nv && (!C::HS || n <= p.store_lim)) {
                     V y = lds[lds_index<C, C::NP - 1>(c, n)];
                     if (p.inverse) {
@@ -1727,7 +1792,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
         } else if constexpr (C::ILV > 0) {
             ilv_store<C>(p, lds, base, nv * C::N, tid);
             __syncthreads();
-        } else if constexpr (C::DCT == 3) {
+        } else if constexpr (C::DCT == 3 && !C::COLS) {
             // conj(z) of the packed row z_j = v[2j] + i v[2j+1] lies in LDS, already scaled: x[2j] is slot j of v, x[2j+1]
             // slot n - 1 - j; stored as one flat run
             if constexpr (C::DCT_QUADS) {  // quad e of a row from conj z_e and conj z_(N-1-e)

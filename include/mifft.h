@@ -166,11 +166,48 @@ typedef enum {
  *   - n / 2 without a packed configuration: a prime factor above 32, n above 16384 (F64: above 8192), a row tile beyond
  *     96 KiB of LDS;
  *   - MIFFT_FLAG_DCT together with MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_FAITHFUL_STAGES or any keep bit;
- *   - MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT;
+ *   - MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND;
  *   - MIFFT_JIT=0 and an n without a precompiled instance: precompiled for 1024 points (F32 and F64, input of the plan's
  *     own float type); every other length is specialised at run time. */
 #define MIFFT_FLAG_DCT 4u
 #define MIFFT_FLAG_DCT_ORTHO 8u
+/* N-D DCT-II / DCT-III (scipy.fft.dctn / idctn of type 2 over the transformed dims; no reference counterpart).  ndim = 1 .. 6,
+ * in_components = 1 in both directions; x and out are both REAL tensors (batch, d0.., d{k-1}, 1) of one shape.  Every
+ * transformed dim gets the 1-D transform of MIFFT_FLAG_DCT above (forward: any in_dtype when the last dim is transformed;
+ * inverse: in_dtype == out_dtype in {F32, F64}); MIFFT_FLAG_DCT_ORTHO applies to each of them.  Keep bits
+ * (MIFFT_FLAG_KEEP_DIM) mean what they mean elsewhere: a kept dim is carried through like a batch dimension, its
+ * mifft_plan_stages() is 0 and its kernel name "none".
+ * One launch per transformed dim, innermost first (the 1-D factors of a separable transform commute, so forward and inverse
+ * plans run the same order): the first reads x and writes out, the others run in place on out.  No scratch
+ * (mifft_plan_scratch_bytes is 0); mifft_plan_in_bytes / out_bytes are batch * d0 * .. * d{k-1} real elements.
+ *   - a transformed LAST dim of n points runs the packed-row kernel of MIFFT_FLAG_DCT over the prod / n rows of every
+ *     batch entry, with its limits (even, 8 .. 16384, F64 up to 8192, n / 2 without a prime factor above 32);
+ *     mifft_plan_stages() reports the stages of its n / 2-point transform, `bases` factor n / 2;
+ *     the kernel is rows<n>[_f64]_dct2_<radices> / ..._dct3_<radices>;
+ *   - any other transformed dim of n points lies at a stride of S reals (S = the product of the dims after it), S even.  The
+ *     same memory viewed as complex elements at stride S / 2 is pairs of adjacent real columns u = x_a + i x_b, which the
+ *     in-place column tile moves coalesced.  Forward: the rows are permuted as they are loaded (v[j] = u[2j],
+ *     v[n-1-j] = u[2j+1]), Z = FFT_n(v), and with W = e^(-i pi k / 2n) the store separates V_a = (Z[k] + conj Z[n-k]) / 2 and
+ *     V_b = (Z[k] - conj Z[n-k]) / 2i and writes row k = (2 Re(W V_a), 2 Re(W V_b)), row n-k = (-2 Im(W V_a), -2 Im(W V_b)).
+ *     Inverse: the load forms Z[k] = conj(W) (X[k] - i X[n-k]) / 2 from rows k and n-k (X[n] := 0), the n-point inverse
+ *     follows and element j of its result is row 2j (j < ceil(n / 2)), element n-1-j row 2j+1.  Every n from 2 to 4096 whose
+ *     prime factors are at most 32, odd lengths included; mifft_plan_stages() reports n-point stages, `bases` factor n.
+ *     The kernel is cols<n>[_f64]_dct2_<radices>_jit / ..._dct3_<radices>_jit: compiled at run time only.
+ * mifft_plan_pass_geometry() works for both kinds of pass (a column pass counts tiles of pairs of columns).  Slab execs and
+ * whole_batch behave as for every other plan.  x and out need the alignment of one element only.
+ * in_components != 1 is MIFFT_ERR_BAD_COMPONENTS, a foreign in_dtype of an inverse plan MIFFT_ERR_BAD_DTYPE.
+ * MIFFT_ERR_UNSUPPORTED (with the reason), before any device work, for:
+ *   - MIFFT_FLAG_DCT_ND together with MIFFT_FLAG_DCT, MIFFT_FLAG_HALF_SPECTRUM or MIFFT_FLAG_FAITHFUL_STAGES;
+ *   - a transformed last dim outside the limits of the packed rows (above), or, under MIFFT_JIT=0, without a precompiled
+ *     instance (1024 points);
+ *   - a transformed other dim whose stride S is odd;
+ *   - a transformed other dim whose stride S is 2 (a trailing extent of 2: a single pair of columns is a row-shaped problem);
+ *   - a transformed other dim above 4096 points, one with a prime factor above 32, or one whose narrowest column tile does
+ *     not fit LDS (F64: 4096 points);
+ *   - a forward plan with in_dtype != out_dtype whose last dim is kept (its first pass is a column pass, which reads the
+ *     plan's own float type);
+ *   - MIFFT_JIT=0 with any transformed dim but the last. */
+#define MIFFT_FLAG_DCT_ND 16u
 
 typedef struct mifft_plan mifft_plan;
 

@@ -131,7 +131,10 @@ inline void check_layout_conditions_nd(const std::vector<int64_t>& in_layout, co
 // library: mifft_plan_create receives the logical real dims).  MIFFT_FLAG_KEEP_DIM(d) leaves dim d untransformed (its bases
 // list, when given, is empty).  MIFFT_FLAG_DCT (with MIFFT_FLAG_DCT_ORTHO for norm = "ortho") plans a DCT-II, or with
 // `inverse` its inverse, of real rows: its layouts are (batch, n, 1) on BOTH sides, which check_layout_conditions_nd refuses
-// (it wants a complex out_layout), so such a plan is created through mifft_plan_create itself.
+// (it wants a complex out_layout), so such a plan is created through mifft_plan_create itself.  The same holds for
+// MIFFT_FLAG_DCT_ND (16u), the N-D DCT over real (batch, d0.., 1) tensors, keep bits allowed.
+static_assert(MIFFT_FLAG_DCT_ND == 16u && (MIFFT_FLAG_DCT_ND & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_KEEP_MASK)) == 0,
+              "MIFFT_FLAG_DCT_ND is its own bit");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
