@@ -6,6 +6,10 @@ from .api import (  # noqa: F401
     FLAG_DCT,
     FLAG_DCT_ND,
     FLAG_DCT_ORTHO,
+    FLAG_STFT,
+    FLAG_STFT_CENTER_REFLECT,
+    FLAG_STFT_CENTER_ZEROS,
+    FLAG_STFT_HOP,
     DeviceContext,
     GPUTest,
     Plan,
@@ -22,8 +26,11 @@ from .api import (  # noqa: F401
     irfftn,
     ordered_bases,
     plan_fft,
+    plan_stft,
     reduce_dims,
     rfftn,
+    stft,
+    stft_frames,
     time_fft,
 )
 
@@ -31,4 +38,5 @@ __all__ = [
     "DeviceContext", "GPUTest", "Plan", "clear_plan_cache", "MifftError", "estimate_best_bases", "estimate_best_bases_nd",
     "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "reduce_dims", "rfftn", "time_fft", "dct", "idct",
     "FLAG_DCT", "FLAG_DCT_ORTHO", "FLAG_DCT_ND", "dctn", "idctn",
+    "FLAG_STFT", "FLAG_STFT_CENTER_REFLECT", "FLAG_STFT_CENTER_ZEROS", "FLAG_STFT_HOP", "plan_stft", "stft", "stft_frames",
 ]

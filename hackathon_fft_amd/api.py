@@ -16,6 +16,7 @@ from __future__ import annotations
 import collections
 import ctypes
 import enum
+import hashlib
 import threading
 from typing import Optional, Sequence
 
@@ -37,6 +38,10 @@ FLAG_HALF_SPECTRUM = 2  # MIFFT_FLAG_HALF_SPECTRUM: numpy's one-sided rfftn / ir
 FLAG_DCT = 4            # MIFFT_FLAG_DCT: DCT-II (inverse: its inverse) of real rows, (batch, n, 1) on both sides
 FLAG_DCT_ORTHO = 8      # MIFFT_FLAG_DCT_ORTHO: scipy's norm="ortho" of such a plan
 FLAG_DCT_ND = 16        # MIFFT_FLAG_DCT_ND: N-D DCT-II (inverse: its inverse) of real tensors, (batch, d0.., 1) on both sides
+FLAG_STFT = 32                 # MIFFT_FLAG_STFT: framed, windowed real signals, (batch, T, 1) -> (batch, F, n // 2 + 1, 2)
+FLAG_STFT_CENTER_REFLECT = 64  # MIFFT_FLAG_STFT_CENTER_REFLECT: frames centred, the signal reflected at both ends
+FLAG_STFT_CENTER_ZEROS = 128   # MIFFT_FLAG_STFT_CENTER_ZEROS: frames centred, zeros beyond both ends
+FLAG_STFT_HOP_MASK = 0xFFFF0000
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -46,6 +51,16 @@ def FLAG_KEEP_DIM(d: int) -> int:
 
 
 FLAG_KEEP_MASK = 0x3F00
+
+
+def FLAG_STFT_HOP(h: int) -> int:
+    """MIFFT_FLAG_STFT_HOP(h): the hop of an STFT plan, 1 .. 65535 samples"""
+    h = int(h)
+    if not 1 <= h <= 65535:
+        raise MifftError(ERR_UNSUPPORTED, f"the hop of an STFT plan is 1 .. 65535 samples, got {h}")
+    return h << 16
+
+
 ERR_UNSUPPORTED = -15   # MIFFT_ERR_UNSUPPORTED
 
 
@@ -179,6 +194,78 @@ def _check_dctn_layout(in_shape: tuple, out_shape: tuple) -> tuple:
     return dims
 
 
+_STFT_CENTER_FLAGS = {None: 0, "reflect": FLAG_STFT_CENTER_REFLECT, "constant": FLAG_STFT_CENTER_ZEROS}
+
+
+def _stft_center_flags(center) -> int:
+    """``center`` of an STFT plan as flag bits: None (frames start at multiples of the hop), "reflect" or "constant" """
+    if center is not None and not isinstance(center, str) or center not in _STFT_CENTER_FLAGS:
+        raise MifftError(ERR_UNSUPPORTED, f"center must be None, \"reflect\" or \"constant\", got {center!r}")
+    return _STFT_CENTER_FLAGS[center]
+
+
+def stft_frames(length: int, n_fft: int, hop_length: int, center=False) -> int:
+    """Frames torch.stft makes of ``length`` samples: 1 + (length - n_fft) // hop_length, centred (any true ``center``: the
+    signal is extended by n_fft // 2 at both ends) 1 + length // hop_length.  Pure host arithmetic."""
+    length, n_fft, hop_length = int(length), int(n_fft), int(hop_length)
+    if hop_length < 1:
+        raise MifftError(ERR_UNSUPPORTED, f"hop_length must be positive, got {hop_length}")
+    if center:
+        return 1 + length // hop_length
+    if length < n_fft:
+        raise MifftError(ERR_UNSUPPORTED, f"a signal of {length} samples is shorter than one frame of {n_fft}")
+    return 1 + (length - n_fft) // hop_length
+
+
+def _check_stft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> tuple:
+    """Layouts of an STFT plan (MIFFT_FLAG_STFT): x (batch, T, 1) real -> out (batch, F, n // 2 + 1, 2) with
+    F = stft_frames(T, n, hop, center); returns the dims (T, n), n = 2 (out_shape[2] - 1)."""
+    if len(in_shape) != 3 or len(out_shape) != 4:
+        raise MifftError(-1, f"STFT layouts are (batch, T, 1) -> (batch, F, n // 2 + 1, 2), got {in_shape} -> {out_shape}")
+    if in_shape[-1] != 1:
+        raise MifftError(-3, f"an STFT reads real signals (1 component), got {in_shape[-1]}")
+    if out_shape[-1] != 2:
+        raise MifftError(-3, f"an STFT writes complex bins (2 components), got {out_shape[-1]}")
+    if in_shape[0] != out_shape[0]:
+        raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
+    T, n = in_shape[1], 2 * (out_shape[2] - 1)
+    if n < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with frames of fewer than 8 points ({n}) is not supported")
+    FLAG_STFT_HOP(hop)
+    mode = _stft_center_flags(center)
+    if T < 2:
+        raise MifftError(-2, f"signals of {T} samples: at least 2")
+    if mode == FLAG_STFT_CENTER_REFLECT and n // 2 > T - 1:
+        raise MifftError(ERR_UNSUPPORTED, f"center=\"reflect\" needs n_fft // 2 <= T - 1 (one reflection), got n_fft = {n}, "
+                                          f"T = {T}")
+    frames = stft_frames(T, n, hop, mode != 0)
+    if out_shape[1] != frames:
+        raise MifftError(-2, f"{T} samples in frames of {n} every {hop} make {frames} frames, out has {out_shape[1]}")
+    return (T, n)
+
+
+def _window_f64(window, n_fft: int) -> "torch.Tensor":
+    """a window as n_fft float64 values on the host (a CUDA tensor is copied, which synchronises its stream)"""
+    w = torch.as_tensor(window).detach().to(device="cpu", dtype=torch.float64).contiguous()
+    if w.dim() != 1 or w.numel() != n_fft:
+        raise MifftError(-5, f"the window has {tuple(w.shape)} values, the frames {n_fft}")
+    return w
+
+
+def window_words(window) -> list:
+    """The window of an STFT plan as it travels through ``bases``: the IEEE binary64 bits of every value as two 32-bit words,
+    low word first (include/mifft.h, MIFFT_FLAG_STFT)."""
+    raw = torch.as_tensor(window).detach().to(device="cpu", dtype=torch.float64).contiguous().numpy().tobytes()
+    return [int.from_bytes(raw[i:i + 4], "little") for i in range(0, len(raw), 4)]
+
+
+def words_window(words) -> list:
+    """the inverse of window_words: the float64 values of a word list"""
+    words = [int(v) for v in words]
+    raw = b"".join((words[i] | (words[i + 1] << 32)).to_bytes(8, "little") for i in range(0, len(words), 2))
+    return (ctypes.c_double * (len(words) // 2)).from_buffer_copy(raw)[:]
+
+
 def _dct_norm_flags(norm) -> int:
     """scipy's ``norm`` of a DCT plan as flag bits: None / "backward" (the unnormalised forward) or "ortho" """
     if norm is None or norm == "backward":
@@ -213,16 +300,36 @@ class Plan:
     include/mifft.h.
     ``dctn=True`` (no reference counterpart): the N-D DCT-II (``inverse``: its inverse) over the dims of a real
     (batch, d0.., 1) tensor, ``axes`` and ``norm`` as above (MIFFT_FLAG_DCT_ND in include/mifft.h, _check_dctn_layout);
-    ``bases`` factor n // 2 for a transformed last dim and n for the others."""
+    ``bases`` factor n // 2 for a transformed last dim and n for the others.
+    ``stft_hop`` > 0 (no reference counterpart): the short-time Fourier transform of real signals, x (batch, T, 1) ->
+    out (batch, F, n // 2 + 1, 2), frames of n samples every ``stft_hop``; ``stft_center`` None / "reflect" / "constant";
+    ``stft_window`` None (rectangular) or n values, taken by value (MIFFT_FLAG_STFT in include/mifft.h, _check_stft_layout,
+    plan_stft).  ``bases`` of such a plan has two lists, an empty one and the radices of n (or an empty one: the default)."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
-                 dct: bool = False, norm=None, dctn: bool = False):
+                 dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
+        stft = int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT)
+        words = None
+        if stft:  # (with any other mode as well: the library refuses the pair)
+            if not int(stft_hop):
+                stft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
+                stft_center = {0: None, FLAG_STFT_CENTER_REFLECT: "reflect", FLAG_STFT_CENTER_ZEROS: "constant"}.get(
+                    int(flags) & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), stft_center)
+            stft_dims = _check_stft_layout(in_shape, out_shape, stft_hop, stft_center)
+            if axes is not None:
+                raise MifftError(ERR_UNSUPPORTED, "an STFT plan frames dim 0 and transforms dim 1: no axes")
+            if stft_window is not None:
+                words = window_words(_window_f64(stft_window, stft_dims[1]))
+            flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(stft_hop) | _stft_center_flags(stft_center) |
+                     (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0))
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
         dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
-        if dctn:  # (with dct or half_spectrum as well: the library refuses the pair)
+        if stft:
+            dims = stft_dims
+        elif dctn:  # (with dct or half_spectrum as well: the library refuses the pair)
             dims = _check_dctn_layout(in_shape, out_shape)
             flags = (int(flags) | FLAG_DCT_ND | _dct_norm_flags(norm) | (FLAG_DCT if dct else 0) |
                      (FLAG_HALF_SPECTRUM if half_spectrum else 0))
@@ -248,8 +355,16 @@ class Plan:
         self.half_spectrum = bool(half_spectrum)
         self.dct = dct
         self.dctn = dctn
+        self.stft = stft
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
-        if bases is not None:
+        if stft and (words is not None or bases is not None):  # (the window's words, then the radices of n)
+            if bases is not None and len(bases[0]) != 0:
+                raise MifftError(-5, "dim 0 of an STFT plan is framed, not transformed: its bases list must be empty")
+            radices = [int(b) for b in bases[1]] if bases is not None else []
+            flat = (words or []) + radices
+            c_flat = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+            c_len = (ctypes.c_int32 * 2)(len(words or []), len(radices))
+        elif bases is not None:
             flat = [int(b) for bs in bases for b in bs]
             c_flat = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
             c_len = (ctypes.c_int32 * len(dims))(*[len(bs) for bs in bases])
@@ -366,6 +481,34 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
                 dct=dct, norm=norm, dctn=dctn)
 
 
+def plan_stft(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, window=None, center=None,
+              ctx: Optional[DeviceContext] = None, whole_batch: int = 0) -> Plan:
+    """Plan of the short-time Fourier transform of ``batch`` real signals of ``length`` samples (no reference counterpart;
+    MIFFT_FLAG_STFT in include/mifft.h): frames of ``n_fft`` samples every ``hop_length``, multiplied by ``window`` (None:
+    rectangular; else n_fft values as a sequence, numpy array or tensor, taken by value when the plan is made) and
+    transformed to their n_fft // 2 + 1 non-negative bins.  ``center``: None (frame f starts at f * hop_length), "reflect" or
+    "constant" (frame f is centred on f * hop_length; the signal is reflected, or continued by zeros, beyond both ends: torch's
+    ``center=True`` with ``pad_mode``).  The plan has ``in_shape`` (batch, length, 1) and ``out_shape``
+    (batch, F, n_fft // 2 + 1, 2), F = stft_frames(length, n_fft, hop_length, center), both of ``dtype`` (float32 / float64),
+    and runs through ``fft(out, x, plan=plan)``, ``first=`` / ``count=`` included: one kernel launch, no padded copy, no tensor
+    of frames.  Every argument error is raised before any device work."""
+    batch, length, n_fft, hop_length = int(batch), int(length), int(n_fft), int(hop_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"an STFT plan reads and writes float32 or float64, got {dtype}")
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    FLAG_STFT_HOP(hop_length)
+    frames = stft_frames(length, n_fft, hop_length, _stft_center_flags(center) != 0)
+    in_shape, out_shape = (batch, length, 1), (batch, frames, n_fft // 2 + 1, 2)
+    _check_stft_layout(in_shape, out_shape, hop_length, center)
+    if window is not None:
+        window = _window_f64(window, n_fft)
+    if ctx is None:
+        ctx = DeviceContext()
+    return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, stft_hop=hop_length,
+                stft_center=center, stft_window=window)
+
+
 def _check_tensor(t: "torch.Tensor", shape: tuple, dtype, device: int, what: str) -> None:
     if not t.is_cuda or t.device.index != device:
         raise MifftError(-10, f"{what} must live on HIP device {device}, got {t.device}")
@@ -464,15 +607,20 @@ def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inver
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=bases,
                             inverse=inverse, faithful_stages=faithful_stages, ctx=DeviceContext(device),
                             half_spectrum=half_spectrum, axes=axes)
-        _PLAN_CACHE[key] = plan
-        while len(_PLAN_CACHE) > 1 and (len(_PLAN_CACHE) > _PLAN_CACHE_SIZE or
-                                        sum(q.scratch_bytes for q in _PLAN_CACHE.values()) > _PLAN_CACHE_SCRATCH_BYTES):
-            _, old = _PLAN_CACHE.popitem(last=False)
-            torch.cuda.synchronize(old.device)  # nothing enqueued with the evicted plan may still run
-            old.close()
+        _plan_cache_insert(key, plan)
     else:
         _PLAN_CACHE.move_to_end(key)
     return plan
+
+
+def _plan_cache_insert(key, plan: Plan) -> None:
+    """a new plan into the cache (under its lock), the oldest ones out while it is over its limits"""
+    _PLAN_CACHE[key] = plan
+    while len(_PLAN_CACHE) > 1 and (len(_PLAN_CACHE) > _PLAN_CACHE_SIZE or
+                                    sum(q.scratch_bytes for q in _PLAN_CACHE.values()) > _PLAN_CACHE_SCRATCH_BYTES):
+        _, old = _PLAN_CACHE.popitem(last=False)
+        torch.cuda.synchronize(old.device)  # nothing enqueued with the evicted plan may still run
+        old.close()
 
 
 def _prime_factors(n: int) -> list:
@@ -791,3 +939,78 @@ def idctn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=No
     """scipy.fft.idctn(x, type=2, norm=norm), the inverse of dctn under the same ``norm`` and ``dim``; the input is converted
     to ``out_dtype`` first."""
     return _dct_nd(x, type, norm, dim, out_dtype, True)
+
+
+def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None, window=None,
+         center: bool = True, pad_mode: str = "reflect", normalized: bool = False, onesided: bool = True, *,
+         out_dtype=None) -> "torch.Tensor":
+    """torch.stft(x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided=True, return_complex=True)
+    of a real ``x`` of shape (T,) or (..., T); the leading dims fold into the batch.  ``hop_length`` defaults to n_fft // 4,
+    ``win_length`` to n_fft; a shorter window is zero-padded on both sides to n_fft, as torch does; ``window=None`` is
+    rectangular; ``normalized=True`` multiplies by n_fft ** -0.5 (folded into the window table).  ``pad_mode`` is "reflect" or
+    "constant"; anything else, and ``onesided=False``, is MifftError -15.  Input that is not of ``out_dtype`` (default: that of
+    a float32 / float64 ``x``, else float64) is converted first.
+    Returns complex (..., n_fft // 2 + 1, F), torch's layout -- as a TRANSPOSED VIEW (``stride(-2) == 1``) of the frames-major
+    (..., F, n_fft // 2 + 1) tensor the kernel writes; call ``.contiguous()`` where the bins-major order is needed in memory.
+    One kernel launch: no padded copy of ``x``, no unfold, no tensor of frames (MIFFT_FLAG_STFT in include/mifft.h).
+    Plans are cached per (shape, dtype, n_fft, hop, centring, device, stream) AND the window's contents: every call hashes the
+    window's float64 values, so a window changed in place never meets a stale plan.  For a CUDA ``window`` that is one small
+    synchronising device-to-host copy per call: loops should make the plan once with ``plan_stft`` and call ``fft``."""
+    if not onesided:
+        raise MifftError(ERR_UNSUPPORTED, "stft: onesided=False is not supported")
+    if pad_mode not in ("reflect", "constant"):
+        raise MifftError(ERR_UNSUPPORTED, f"stft: pad_mode must be \"reflect\" or \"constant\", got {pad_mode!r}")
+    if x.is_complex():
+        raise MifftError(-3, "stft expects a real tensor")
+    if x.dim() < 1:
+        raise MifftError(-1, "stft expects a tensor of rank 1 or more: (T,) or (..., T)")
+    n_fft = int(n_fft)
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"stft with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    hop_length = n_fft // 4 if hop_length is None else int(hop_length)
+    FLAG_STFT_HOP(hop_length)
+    win_length = n_fft if win_length is None else int(win_length)
+    if not 0 < win_length <= n_fft:
+        raise MifftError(-2, f"stft: 0 < win_length <= n_fft, got win_length = {win_length}, n_fft = {n_fft}")
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if out_dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"stft: out_dtype must be float32 or float64, got {out_dtype}")
+    mode = (pad_mode if center else None)
+    logical = tuple(x.shape)
+    T = logical[-1]
+    batch = 1
+    for m in logical[:-1]:
+        batch *= m
+    frames = stft_frames(T, n_fft, hop_length, bool(center))
+    in_shape, out_shape = (batch, T, 1), (batch, frames, n_fft // 2 + 1, 2)
+    _check_stft_layout(in_shape, out_shape, hop_length, mode)
+    w = None
+    if window is not None or win_length < n_fft or normalized:
+        if window is None:
+            wl = torch.ones(win_length, dtype=torch.float64)
+        else:
+            wl = _window_f64(window, win_length)
+        left = (n_fft - win_length) // 2
+        w = torch.zeros(n_fft, dtype=torch.float64)
+        w[left:left + win_length] = wl
+        if normalized:
+            w *= float(n_fft) ** -0.5
+    device = DeviceContext(x.device.index if x.is_cuda else None).device
+    if not x.is_cuda or x.device.index != device:
+        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    xr = x.to(out_dtype).contiguous().reshape(in_shape)
+    out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
+    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
+    with _PLAN_CACHE_LOCK:
+        key = ("stft", out_dtype, in_shape, n_fft, hop_length, mode, digest, device,
+               int(torch.cuda.current_stream(device).cuda_stream))
+        plan = _PLAN_CACHE.get(key)
+        if plan is None:
+            plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, stft_hop=hop_length, stft_center=mode,
+                        stft_window=w)
+            _plan_cache_insert(key, plan)
+        else:
+            _PLAN_CACHE.move_to_end(key)
+        fft(out, xr, DeviceContext(device), plan=plan)
+    return torch.view_as_complex(out).reshape(logical[:-1] + (frames, n_fft // 2 + 1)).transpose(-1, -2)

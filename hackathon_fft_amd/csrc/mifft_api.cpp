@@ -29,10 +29,12 @@ int hip_error(hipError_t e, const char* what) {
 size_t Plan::in_elem_bytes() const { return dtype_size(in_dtype) * (size_t)in_components; }
 size_t Plan::out_elem_bytes() const { return dtype_size(out_dtype) * 2; }
 size_t Plan::in_row_bytes() const {
+    if (stft()) return (size_t)dims[0] * dtype_size(in_dtype);
     if (dct_any()) return (size_t)prod * dtype_size(in_dtype);
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
+    if (stft()) return (size_t)prod_half * out_elem_bytes();
     if (dct_any()) return (size_t)prod * dtype_size(out_dtype);
     if (!half_spectrum()) return (size_t)prod * out_elem_bytes();
     return inverse ? (size_t)prod * dtype_size(out_dtype) : (size_t)prod_half * out_elem_bytes();
@@ -214,6 +216,63 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         if (dims[i] < 2) return set_error(MIFFT_ERR_BAD_DIM, "no inner dimension should be of size 1");
     if ((bases_flat == nullptr) != (bases_len == nullptr))
         return set_error(MIFFT_ERR_NULL, "bases_flat and bases_len must both be given or both be NULL");
+    // ---- STFT plans (MIFFT_FLAG_STFT; stft.cpp): their own route from here to the end.  Everything that can be refused
+    //      without a device first; `bases` carries the window and the radices of dim 1 ----
+    {
+        std::string why;
+        const int rc = stft_flag_check(flags, why);
+        if (rc) return set_error(rc, why);
+    }
+    if (flags & MIFFT_FLAG_STFT) {
+        mifft_plan* h = new mifft_plan();
+        Plan& p = h->p;
+        p.device = device;
+        p.in_dtype = in_dtype;
+        p.out_dtype = out_dtype;
+        p.ndim = ndim;
+        for (int i = 0; i < ndim; ++i) p.dims[i] = dims[i];
+        p.batch = batch;
+        p.sel_batch = whole_batch;
+        p.in_components = in_components;
+        p.inverse = inverse ? 1 : 0;
+        p.flags = flags;
+        auto fail = [&](int rc, const std::string& why) {
+            free_plan_device(p);
+            delete h;
+            return rc == MIFFT_ERR_HIP ? rc : set_error(rc, why);
+        };
+        std::string why;
+        int rc = stft_check(p, why);
+        if (rc) return fail(rc, why);
+        const int64_t n = dims[1];
+        p.prod = p.stft_frames() * n;  // (the rows the one pass transforms, and what it stores)
+        p.prod_half = p.stft_frames() * (n / 2 + 1);
+        std::vector<double> window;
+        std::vector<uint64_t> user;
+        rc = stft_unpack_bases(n, bases_flat, bases_len, window, user, why);
+        if (rc) return fail(rc, why);
+        if (user.empty()) user = plan_estimate_bases((uint64_t)n, /*gpu_target=*/true);
+        std::vector<std::vector<uint32_t>> ordered(2), processed(2);
+        rc = plan_ordered_bases((uint64_t)n, user, ordered[1], processed[1], why);
+        if (rc) return fail(rc, why);
+        p.stage_radices = ordered;  // (dim 0 is framed, not transformed: no stages)
+        const int ndev = device_count_quiet();
+        if (device < 0 || device >= ndev)
+            return fail(MIFFT_ERR_NO_DEVICE, "libmifft has no CPU path: device " + std::to_string(device) +
+                                                 " is not a usable HIP device (" + std::to_string(ndev) + " visible)");
+        DeviceGuard guard(device);
+        if (guard.err != hipSuccess) {
+            delete h;
+            return hip_error(guard.err, "hipSetDevice");
+        }
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess) p.num_cus = prop.multiProcessorCount;
+        config_refresh();
+        rc = build_stft(p, ordered[1], processed[1], window, why);
+        if (rc) return fail(rc, why);
+        *out_plan = h;
+        return MIFFT_OK;
+    }
     // ---- DCT plans (MIFFT_FLAG_DCT; dct.cpp): everything that can be refused without a device, before anything else ----
     if ((flags & MIFFT_FLAG_DCT_ORTHO) && !(flags & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ND)))
         return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND");
@@ -750,6 +809,7 @@ int mifft_plan_stages(const mifft_plan* plan, int dim, uint32_t* radices_out, in
 const char* mifft_plan_kernel_name(const mifft_plan* plan, int dim) {
     if (!plan) return "";
     if (dim >= 0 && dim < plan->p.ndim && plan->p.kept(dim)) return "none";
+    if (dim == 0 && plan->p.stft()) return "none";  // (framed, not transformed)
     for (const DimPass& ps : plan->p.passes)
         if (ps.dim_index == dim || ps.dim_index2 == dim) return ps.kernel_name;
     return "";
@@ -760,6 +820,7 @@ int mifft_plan_pass_geometry(const mifft_plan* plan, int dim, int64_t count, int
     if (dim < 0 || dim >= plan->p.ndim) return set_error(MIFFT_ERR_BAD_RANK, "dim out of range");
     if (count < 1) return set_error(MIFFT_ERR_BAD_BATCH, "count must be positive");
     if (plan->p.kept(dim)) return set_error(MIFFT_ERR_UNSUPPORTED, "a kept dim has no pass");
+    if (dim == 0 && plan->p.stft()) return set_error(MIFFT_ERR_UNSUPPORTED, "dim 0 of an STFT plan is framed: it has no pass");
     const DimPass* found = nullptr;
     for (const DimPass& ps : plan->p.passes)
         if (ps.dim_index == dim || ps.dim_index2 == dim) {

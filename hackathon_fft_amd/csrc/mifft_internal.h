@@ -98,6 +98,9 @@ struct DimPass {
     // and of the other bins (TileParams::dct_s0 / dct_s1)
     int dct = 0;
     double dct_s0 = 1.0, dct_s1 = 1.0;
+    // TileCfg::STFT of a packed-row pass: the rows are the `outer` frames of every batch entry (hop, length and centring are the
+    // plan's); d_aux2 holds the window, N values of the plan's float type
+    bool stft = false;
     int64_t half_pitch = 0;  // R2C / C2R: row pitch (complex elements) of the half-spectrum side; 0 = N (full-spectrum rows)
     int store_lim = 0;
     bool ilv = false;  // interleaved block tile (TileCfg::ILV): `inner` (< 128 B of elements) transforms per block, launched as rows
@@ -156,6 +159,12 @@ struct Plan {
     bool dct_nd() const { return (flags & MIFFT_FLAG_DCT_ND) != 0; }
     bool dct_any() const { return dct() || dct_nd(); }
     double dct_exec_bytes() const { return size_batch() * (double)prod * (double)(out_elem_bytes() / 2) * 2.0; }
+    // MIFFT_FLAG_STFT: dims = {T, n}; x is (batch, T, 1) real, out (batch, F, n / 2 + 1, 2), F = stft_frames() frames of n
+    // samples every stft_hop(); stft_center(): 0 none, 1 reflect, 2 zeros (TileParams::stft_center)
+    bool stft() const { return (flags & MIFFT_FLAG_STFT) != 0; }
+    int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
+    int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
+    int64_t stft_frames() const { return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop(); }
     // bytes of ONE transform (one batch entry) of x, out and the plan scratch: the slab offsets and the alias check of
     // mifft_exec_batch and the size queries.  Without the flag: prod * in_elem_bytes(), prod * out_elem_bytes() twice.
     size_t in_row_bytes() const;
@@ -274,6 +283,19 @@ bool select_jit_dct_cols(const Plan& plan, DimPass& pass, std::string& why_not);
 int dctn_check(const Plan& plan, std::string& why);
 int build_dctn(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                const std::vector<std::vector<uint32_t>>& processed, std::string& why);
+// plans with MIFFT_FLAG_STFT (stft.cpp): the checks that need no device (flags, shape, the window carried in `bases`), then
+// the single pass.  select_jit_stft_rows is the packed-row kernel with TileCfg::STFT (kernels_jit.cpp; compiled at run time
+// only), stft_rows_supported the same check without a device.  stft_flag_check: the STFT bits of a plan WITHOUT the flag.
+bool stft_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_stft_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+int stft_flag_check(uint32_t flags, std::string& why);
+int stft_check(const Plan& plan, std::string& why);
+// the window of such a plan from bases_flat / bases_len (2 n words: the binary64 bits of w[0 .. n-1], low word first; none:
+// rectangular, `window` left empty) and the user radices of the n-point transform (none: `radices` left empty)
+int stft_unpack_bases(int64_t n, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+                      std::vector<uint64_t>& radices, std::string& why);
+int build_stft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+               const std::vector<double>& window, std::string& why);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

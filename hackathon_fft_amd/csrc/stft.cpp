@@ -1,0 +1,171 @@
+// stft.cpp -- the plans with MIFFT_FLAG_STFT (torch.stft of real signals, the frames leading; include/mifft.h).
+//
+// One launch, no scratch, no padded copy and no tensor of frames: the packed real-row kernel of the frame length with
+// TileCfg::STFT set, whose load takes row r from frame r % F of batch entry r / F of the signal, reflected or zero-extended at
+// the ends of a centred plan, and multiplies it by the window (tile_kernel.h).  x is (batch, T, 1) real, out
+// (batch, F, n / 2 + 1, 2); the window travels through `bases` as host data and lives in the plan as a device table of the
+// plan's float type.
+#include <cmath>
+#include <cstring>
+
+#include "mifft_config.h"
+#include "mifft_internal.h"
+
+namespace mifft {
+
+// the STFT bits of a plan without MIFFT_FLAG_STFT
+int stft_flag_check(uint32_t flags, std::string& why) {
+    if (flags & MIFFT_FLAG_STFT) return MIFFT_OK;
+    if (flags & MIFFT_FLAG_STFT_HOP_MASK) {
+        why = "a hop (MIFFT_FLAG_STFT_HOP) without MIFFT_FLAG_STFT";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (flags & (MIFFT_FLAG_STFT_CENTER_REFLECT | MIFFT_FLAG_STFT_CENTER_ZEROS)) {
+        why = "a centre bit (MIFFT_FLAG_STFT_CENTER_REFLECT / MIFFT_FLAG_STFT_CENTER_ZEROS) without MIFFT_FLAG_STFT";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    return MIFFT_OK;
+}
+
+// checks that need no device: MIFFT_OK, or the status and its reason
+int stft_check(const Plan& p, std::string& why) {
+    const struct {
+        uint32_t bits;
+        const char* what;
+    } other[] = {{MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no STFT to be faithful to"},
+                 {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an STFT plan stores the half spectrum of every frame anyway"},
+                 {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
+                 {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
+                 {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an STFT plan frames dim 0 and transforms dim 1"}};
+    for (const auto& o : other)
+        if (p.flags & o.bits) {
+            why = std::string("MIFFT_FLAG_STFT with ") + o.what;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+    if (p.stft_hop() == 0) {
+        why = "MIFFT_FLAG_STFT with hop 0: MIFFT_FLAG_STFT_HOP(h) carries the hop, 1 .. 65535";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if ((p.flags & MIFFT_FLAG_STFT_CENTER_REFLECT) && (p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS)) {
+        why = "both centre bits: MIFFT_FLAG_STFT_CENTER_REFLECT and MIFFT_FLAG_STFT_CENTER_ZEROS exclude each other";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.ndim != 2) {
+        why = "MIFFT_FLAG_STFT frames the signals of a (batch, T, 1) tensor: ndim must be 2 (dims = {T, n}), not " +
+              std::to_string(p.ndim);
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.inverse) {
+        why = "the inverse STFT is not routed";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 1) {
+        why = "an STFT reads real signals (in_components = 1)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.in_dtype != p.out_dtype) {
+        why = "an STFT reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    const int64_t T = p.dims[0], n = p.dims[1];
+    if (T >= (1ll << 31)) {
+        why = "signals of 2^31 samples or more (" + std::to_string(T) + "): the frames are addressed in 32 bits";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (n % 2 != 0) {
+        why = "STFT with an odd frame length (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (n < 8) {
+        why = "STFT with frames of fewer than 8 points (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!stft_rows_supported(p, n, w)) {
+        why = "STFT with frames of " + std::to_string(n) + " points: " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (!p.stft_center() && T < n) {
+        why = "signals of " + std::to_string(T) + " samples are shorter than one frame of " + std::to_string(n) +
+              " (T < n without a centre bit)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.stft_center() == 1 && n / 2 > T - 1) {
+        why = "MIFFT_FLAG_STFT_CENTER_REFLECT needs n / 2 <= T - 1 (one reflection): n = " + std::to_string(n) +
+              ", T = " + std::to_string(T);
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.stft_frames() >= (1ll << 31) - 64) {  // (hop 1 on a signal just below 2^31 samples)
+        why = "2^31 frames per signal or more: the frames are counted in 32 bits";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    return MIFFT_OK;
+}
+
+int stft_unpack_bases(int64_t n, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+                      std::vector<uint64_t>& radices, std::string& why) {
+    window.clear();
+    radices.clear();
+    if (!bases_flat || !bases_len) return MIFFT_OK;
+    if (bases_len[0] != 0 && (int64_t)bases_len[0] != 2 * n) {
+        why = "bases_len[0] of an STFT plan is 0 (rectangular window) or 2 n = " + std::to_string(2 * n) +
+              " words of window, not " + std::to_string(bases_len[0]);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (bases_len[1] < 0) {
+        why = "negative bases_len";
+        return MIFFT_ERR_NO_BASES;
+    }
+    if (bases_len[0]) {
+        window.resize((size_t)n);
+        for (int64_t j = 0; j < n; ++j) {
+            const uint64_t bits = (uint64_t)bases_flat[2 * j] | ((uint64_t)bases_flat[2 * j + 1] << 32);
+            double v;
+            memcpy(&v, &bits, sizeof v);
+            if (!std::isfinite(v)) {
+                why = "window value " + std::to_string(j) + " is not finite";
+                return MIFFT_ERR_BAD_BASES;
+            }
+            window[(size_t)j] = v;
+        }
+    }
+    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    return MIFFT_OK;
+}
+
+// the window in the plan's float type: n values, read by the kernel as n / 2 packed pairs
+template <typename T>
+static hipError_t upload_window_t(int64_t n, const std::vector<double>& window, void** d_table) {
+    std::vector<T> tab((size_t)n, (T)1);
+    for (size_t j = 0; j < window.size(); ++j) tab[j] = (T)window[j];
+    hipError_t e = hipMalloc(d_table, tab.size() * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(*d_table, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
+// the one pass: dim 1 (n points) over the F frames of every batch entry
+int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+               const std::vector<double>& window, std::string& why) {
+    const int64_t n = p.dims[1];
+    DimPass ps;
+    ps.dim_index = 1;
+    ps.N = n;
+    ps.inner = 1;
+    ps.outer = p.stft_frames();
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    ps.half_pitch = n / 2 + 1;
+    if (!select_jit_stft_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    // the passes run n / 2 points; the unpacking needs W_n^k, forward (as a half-spectrum row pass); the window
+    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    if (e == hipSuccess)
+        e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(n, window, &ps.d_aux2) : upload_window_t<float>(n, window, &ps.d_aux2);
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "STFT table upload");
+    return MIFFT_OK;
+}
+
+}  // namespace mifft

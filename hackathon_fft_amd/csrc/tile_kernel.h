@@ -96,6 +96,14 @@ MIFFT_DEV T gload_real(const T* p) {
     else
         return *p;
 }
+// two adjacent reals at an address aligned to ONE element (the frames of TileCfg::STFT start at any sample: the hop may be
+// odd), as one access that the hardware's unaligned global accesses serve
+template <typename T>
+MIFFT_DEV cpx<T> gload_pair(const T* p) {
+    typedef T vec2u __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    const vec2u v = *(const vec2u*)p;
+    return {v.x, v.y};
+}
 template <bool NT, typename T>
 MIFFT_DEV void gstore(cpx<T>* p, cpx<T> v) {
     if constexpr (NT) {
@@ -175,6 +183,12 @@ struct TileParams {
     // bins are stored (DCT = 2) or loaded (DCT = 3)
     const void* dct_tw;
     double dct_s0, dct_s1;
+    // STFT configurations: logical row r of the launch is frame r % stft_frames of batch entry r / stft_frames, entries of
+    // stft_len reals; the frame starts at sample frame * stft_hop - (stft_center ? N : 0) of its entry (N = half the frame
+    // length) and is multiplied by stft_win, 2 N values of type T.  stft_center: 0 no frame leaves its entry, 1 the signal is
+    // reflected at both ends (N <= stft_len - 1: one reflection), 2 zeros beyond both ends.
+    const void* stft_win;
+    int stft_frames, stft_hop, stft_len, stft_center;
 };
 
 MIFFT_DEV long long tile_id(const TileParams& p, long long t) { return p.reverse ? p.n_tiles - 1 - t : t; }
@@ -262,7 +276,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
-          int ILV_ = 0, int DCT_ = 0>
+          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -430,6 +444,17 @@ struct TileCfg {
 #else
     static constexpr bool DCT_QUADS = DCT_ != 0 && !COLS_ && N_ % 2 == 0;
 #endif
+    // STFT (torch.stft over real signals): an R2C tile whose rows are the overlapping FRAMES of a signal instead of the rows of
+    // a tensor.  Only the load differs: row r = r0 + c of the launch is frame r % F of batch entry r / F, its packed element m
+    // the two reals at s = frame * hop - (centred ? N : 0) + 2 m and s + 1 of that entry, times the window's values 2 m and
+    // 2 m + 1 (TileParams::stft_*).  A row that lies inside its entry loads every pair with one access, aligned to one element
+    // like the DCT rows below; a row that reaches beyond either end (centred plans only) loads real by real with the index
+    // reflected (i < 0 -> -i, i > T - 1 -> 2 (T - 1) - i) or replaced by zero.  The choice is per row.  Neighbouring frames
+    // re-read the same lines through L2 and the Infinity Cache; nothing outside [0, T) of an entry of the launch is touched.
+    // The passes, the unpacking store (one row of N + 1 bins per frame) and the persistent walk are the R2C tile's.
+    static constexpr bool STFT = STFT_;
+    static_assert(!STFT_ || (R2C_ && !FIRST_DIRECT_ && DCT_ == 0 && same_t<IT_, T_>::value),
+                  "STFT: packed real rows of the plan's own float type, staged in LDS by the framing load");
     static constexpr int CPITCH = TSTORE_ ? TILE_ + 1 : TILE_;
     static_assert(!TSTORE_ || (COLS_ && !LAST_DIRECT_ && FIRST_DIRECT_), "TSTORE: column tile, last pass left in LDS");
     static constexpr int DATA_ELEMS = COLS_ ? N_ * CPITCH : LD * TILE_;
@@ -1603,6 +1628,43 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     ldr[2 * lds_index<C, -1>(c, j >> 1) + (j & 1)] = x.x;
                     ldr[2 * lds_index<C, -1>(c, q >> 1) + (q & 1)] = x.y;
                 }
+            }
+            __syncthreads();
+        } else if constexpr (C::STFT) {
+            // (b, frame) of the tile's first row once, uniform; a row further on wraps into the entries that follow
+            const long long r0 = base / C::N, b0 = r0 / p.stft_frames;
+            const int fr0 = (int)(r0 - b0 * p.stft_frames);
+            const int F = p.stft_frames, hop = p.stft_hop, len = p.stft_len, mode = p.stft_center;
+            const int last_start = len - 2 * C::N;  // the last sample a frame may start at and stay inside its entry
+            const T* x0 = (const T*)p.in + b0 * len;
+            const V* win = (const V*)p.stft_win;
+            for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                const int c = f / C::N, m = f - c * C::N;
+                int fr = fr0 + c, db = 0;
+                if (fr >= F) {
+                    db = fr / F;
+                    fr -= db * F;
+                }
+                const T* xe = x0 + (long long)db * len;
+                const int s0 = fr * hop - (mode ? C::N : 0);  // (fr * hop <= len: 32 bits hold it)
+                V x;
+                if (s0 >= 0 && s0 <= last_start) {
+                    x = gload_pair(xe + s0 + 2 * m);
+                } else {
+                    T v[2];
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        long long i = (long long)s0 + 2 * m + q;
+                        const bool outside = i < 0 || i > len - 1;
+                        if (i < 0) i = -i;
+                        if (i > len - 1) i = 2 * ((long long)len - 1) - i;
+                        v[q] = (T)0;
+                        if (!outside || mode == 1) v[q] = xe[i];  // (zeros beyond the ends: no load at all)
+                    }
+                    x = {v[0], v[1]};
+                }
+                const V w = win[m];
+                lds[lds_index<C, -1>(c, m)] = {x.x * w.x, x.y * w.y};
             }
             __syncthreads();
         } else if constexpr (!C::FIRST_DIRECT) {

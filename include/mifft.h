@@ -208,6 +208,45 @@ typedef enum {
  *     plan's own float type);
  *   - MIFFT_JIT=0 with any transformed dim but the last. */
 #define MIFFT_FLAG_DCT_ND 16u
+/* Short-time Fourier transform of real signals (torch.stft(..., onesided=True, return_complex=True) with the frames leading; no
+ * reference counterpart).  ndim = 2, dims = {T, n}: T samples per batch entry, frames of n samples taken every `hop` samples
+ * (MIFFT_FLAG_STFT_HOP(hop), 1 .. 65535).  in_components = 1, inverse = 0, in_dtype == out_dtype in {F32, F64}:
+ *       x   (batch, T, 1)  ->  out (batch, F, n / 2 + 1, 2),    out[b, f, k] = sum_j w[j] x~[b, f * hop + j - c] e^(-2 pi i j k / n)
+ * with c = 0 and F = 1 + (T - n) / hop without a centre bit (samples after the last frame are never read), c = n / 2 and
+ * F = 1 + T / hop with one (integer divisions); x~ is x, continued beyond both ends by reflection without repeating the end
+ * samples (MIFFT_FLAG_STFT_CENTER_REFLECT: numpy.pad mode "reflect", torch's pad_mode default) or by zeros
+ * (MIFFT_FLAG_STFT_CENTER_ZEROS: torch's pad_mode "constant").  No padded copy of x and no tensor of frames exist: the frames
+ * are formed in the load of the one kernel the plan launches, the packed real-row kernel of n points with a framing,
+ * windowing load (kernel rows<n>[_f64]_r2c_<radices>_stft_jit: compiled at run time only), which writes the spectrogram once
+ * and reads x through the caches, overlapping frames included.
+ * `bases_flat` / `bases_len`, when given, have the plan's two entries, and carry the window in the first:
+ *   - bases_len[0] is 0 (rectangular window) or 2 n: the IEEE binary64 bits of w[0 .. n-1], each as two 32-bit words, low
+ *     word first.  Host data, taken by value: the plan rounds it to its float type and keeps its own device copy;
+ *   - bases_len[1] is 0 (the default radix estimate for n: allowed in STFT plans only) or the radices of dim 1, which
+ *     multiply to n as those of a half-spectrum plan.
+ * NULL / NULL: a rectangular window and the default radices.
+ * mifft_plan_stages(0) is 0 and mifft_plan_kernel_name(0) "none" (dim 0 is framed, not transformed); dim 1 reports the n-point
+ * stages and the kernel.  mifft_plan_num_launches() is 1, mifft_plan_scratch_bytes() 0, mifft_plan_in_bytes() batch * T
+ * elements, mifft_plan_out_bytes() batch * F * (n / 2 + 1) complex; mifft_exec_batch(first, count) offsets x by first * T
+ * reals and out by first * F * (n / 2 + 1) complex and touches no other entry; mifft_plan_pass_geometry(1) counts rows of
+ * count * F frames; whole_batch behaves as for every other plan.  x needs the alignment of one element only.
+ * Refused before any device work, the reason in mifft_last_error().  MIFFT_ERR_UNSUPPORTED:
+ *   - a hop field without MIFFT_FLAG_STFT, or the flag with hop 0; a centre bit without the flag, or both centre bits;
+ *   - MIFFT_FLAG_STFT with MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT, MIFFT_FLAG_DCT_ND,
+ *     MIFFT_FLAG_DCT_ORTHO or a keep bit;
+ *   - ndim != 2;  inverse != 0 (the inverse STFT is not routed);
+ *   - n outside the limits of the packed rows: odd, below 8, above 16384 (F64: 8192), n / 2 with a prime factor above 32, a
+ *     row tile beyond 96 KiB of LDS;
+ *   - T < n without a centre bit;  n / 2 > T - 1 with MIFFT_FLAG_STFT_CENTER_REFLECT (one reflection must reach);
+ *   - MIFFT_JIT=0 (no precompiled instances).
+ * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_BAD_BASES: a
+ * bases_len[0] other than 0 or 2 n, a window value that is not finite (or radices that do not multiply to n).
+ * MIFFT_ERR_TOO_LARGE: T >= 2^31 (or as many frames per entry). */
+#define MIFFT_FLAG_STFT 32u
+#define MIFFT_FLAG_STFT_CENTER_REFLECT 64u   /* frames centred, signal reflected at both ends */
+#define MIFFT_FLAG_STFT_CENTER_ZEROS 128u    /* frames centred, zeros beyond both ends */
+#define MIFFT_FLAG_STFT_HOP(h) ((uint32_t)(h) << 16)   /* 1 .. 65535 */
+#define MIFFT_FLAG_STFT_HOP_MASK 0xFFFF0000u
 
 typedef struct mifft_plan mifft_plan;
 

@@ -135,6 +135,16 @@ inline void check_layout_conditions_nd(const std::vector<int64_t>& in_layout, co
 // MIFFT_FLAG_DCT_ND (16u), the N-D DCT over real (batch, d0.., 1) tensors, keep bits allowed.
 static_assert(MIFFT_FLAG_DCT_ND == 16u && (MIFFT_FLAG_DCT_ND & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_KEEP_MASK)) == 0,
               "MIFFT_FLAG_DCT_ND is its own bit");
+// MIFFT_FLAG_STFT (32u) with MIFFT_FLAG_STFT_HOP(hop) and at most one of MIFFT_FLAG_STFT_CENTER_REFLECT (64u) /
+// MIFFT_FLAG_STFT_CENTER_ZEROS (128u) plans the short-time Fourier transform of real signals: x (batch, T, 1) ->
+// out (batch, F, n / 2 + 1, 2), dims = {T, n}.  The two layouts differ before the last dimension and `bases` carries the window
+// (include/mifft.h), so such a plan, too, is created through mifft_plan_create itself.
+static_assert(MIFFT_FLAG_STFT == 32u && MIFFT_FLAG_STFT_CENTER_REFLECT == 64u && MIFFT_FLAG_STFT_CENTER_ZEROS == 128u &&
+                  MIFFT_FLAG_STFT_HOP(1) == 0x10000u && MIFFT_FLAG_STFT_HOP_MASK == 0xFFFF0000u &&
+                  ((MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_CENTER_REFLECT | MIFFT_FLAG_STFT_CENTER_ZEROS | MIFFT_FLAG_STFT_HOP_MASK) &
+                   (MIFFT_FLAG_KEEP_MASK | MIFFT_FLAG_DCT_ND | MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_HALF_SPECTRUM |
+                    MIFFT_FLAG_FAITHFUL_STAGES)) == 0,
+              "the STFT bits are their own");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
