@@ -6,6 +6,7 @@ from .api import (  # noqa: F401
     FLAG_DCT,
     FLAG_DCT_ND,
     FLAG_DCT_ORTHO,
+    FLAG_ISTFT,
     FLAG_STFT,
     FLAG_STFT_CENTER_REFLECT,
     FLAG_STFT_CENTER_ZEROS,
@@ -24,8 +25,12 @@ from .api import (  # noqa: F401
     idctn,
     ifftn,
     irfftn,
+    istft,
+    istft_length,
+    istft_schedule,
     ordered_bases,
     plan_fft,
+    plan_istft,
     plan_stft,
     reduce_dims,
     rfftn,
@@ -39,4 +44,5 @@ __all__ = [
     "fft", "fftn", "ifftn", "irfftn", "ordered_bases", "plan_fft", "reduce_dims", "rfftn", "time_fft", "dct", "idct",
     "FLAG_DCT", "FLAG_DCT_ORTHO", "FLAG_DCT_ND", "dctn", "idctn",
     "FLAG_STFT", "FLAG_STFT_CENTER_REFLECT", "FLAG_STFT_CENTER_ZEROS", "FLAG_STFT_HOP", "plan_stft", "stft", "stft_frames",
+    "FLAG_ISTFT", "plan_istft", "istft", "istft_length", "istft_schedule",
 ]

@@ -42,6 +42,7 @@ FLAG_STFT = 32                 # MIFFT_FLAG_STFT: framed, windowed real signals,
 FLAG_STFT_CENTER_REFLECT = 64  # MIFFT_FLAG_STFT_CENTER_REFLECT: frames centred, the signal reflected at both ends
 FLAG_STFT_CENTER_ZEROS = 128   # MIFFT_FLAG_STFT_CENTER_ZEROS: frames centred, zeros beyond both ends
 FLAG_STFT_HOP_MASK = 0xFFFF0000
+FLAG_ISTFT = 0x4000            # MIFFT_FLAG_ISTFT: overlap-added frames, (batch, F, n // 2 + 1, 2) -> (batch, T, 1); hop and centre bits shared
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -244,6 +245,54 @@ def _check_stft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> t
     return (T, n)
 
 
+def istft_length(frames: int, n_fft: int, hop_length: int, center=False) -> int:
+    """Samples torch.istft returns by default for ``frames`` frames: n_fft + hop_length * (frames - 1), less n_fft // 2 at both
+    ends when centred.  Pure host arithmetic."""
+    frames, n_fft, hop_length = int(frames), int(n_fft), int(hop_length)
+    if hop_length < 1:
+        raise MifftError(ERR_UNSUPPORTED, f"hop_length must be positive, got {hop_length}")
+    if frames < 1:
+        raise MifftError(-2, f"at least one frame, got {frames}")
+    return n_fft + hop_length * (frames - 1) - (2 * (n_fft // 2) if center else 0)
+
+
+def _istft_center_flags(center) -> int:
+    """``center`` of an inverse STFT plan as flag bits: None / False (uncentred), True / "reflect" or "constant" (centred: the
+    two bits mean the same here, the first and last n // 2 samples are trimmed)"""
+    if center is None or center is False:
+        return 0
+    if center is True:
+        return FLAG_STFT_CENTER_REFLECT
+    return _stft_center_flags(center)
+
+
+def _check_istft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> tuple:
+    """Layouts of an inverse STFT plan (MIFFT_FLAG_ISTFT): x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real with
+    2 <= T <= n + hop (F - 1) - (centred: n // 2); returns the dims (T, F, n), n = 2 (in_shape[2] - 1)."""
+    if len(in_shape) != 4 or len(out_shape) != 3:
+        raise MifftError(-1, f"inverse STFT layouts are (batch, F, n // 2 + 1, 2) -> (batch, T, 1), got {in_shape} -> {out_shape}")
+    if in_shape[-1] != 2:
+        raise MifftError(-3, f"an inverse STFT reads complex bins (2 components), got {in_shape[-1]}")
+    if out_shape[-1] != 1:
+        raise MifftError(-3, f"an inverse STFT writes real signals (1 component), got {out_shape[-1]}")
+    if in_shape[0] != out_shape[0]:
+        raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
+    F, n, T = in_shape[1], 2 * (in_shape[2] - 1), out_shape[1]
+    if n < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with frames of fewer than 8 points ({n}) is not supported")
+    FLAG_STFT_HOP(hop)
+    if hop > n:
+        raise MifftError(ERR_UNSUPPORTED, f"hop_length {hop} > n_fft {n}: gaps between the frames")
+    centred = _istft_center_flags(center) != 0
+    if F < 1:
+        raise MifftError(-2, f"at least one frame, got {F}")
+    covered = n + hop * (F - 1) - (n // 2 if centred else 0)
+    if not 2 <= T <= covered:
+        raise MifftError(-2, f"{F} frames of {n} every {hop} cover 2 .. {covered} output samples, out has {T} "
+                             f"(a longer output is not zero-padded)")
+    return (T, F, n)
+
+
 def _window_f64(window, n_fft: int) -> "torch.Tensor":
     """a window as n_fft float64 values on the host (a CUDA tensor is copied, which synchronises its stream)"""
     w = torch.as_tensor(window).detach().to(device="cpu", dtype=torch.float64).contiguous()
@@ -304,14 +353,39 @@ class Plan:
     ``stft_hop`` > 0 (no reference counterpart): the short-time Fourier transform of real signals, x (batch, T, 1) ->
     out (batch, F, n // 2 + 1, 2), frames of n samples every ``stft_hop``; ``stft_center`` None / "reflect" / "constant";
     ``stft_window`` None (rectangular) or n values, taken by value (MIFFT_FLAG_STFT in include/mifft.h, _check_stft_layout,
-    plan_stft).  ``bases`` of such a plan has two lists, an empty one and the radices of n (or an empty one: the default)."""
+    plan_stft).  ``bases`` of such a plan has two lists, an empty one and the radices of n (or an empty one: the default).
+    ``istft_hop`` > 0 (no reference counterpart): the inverse, x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real,
+    ``inverse=True`` implied; ``stft_center`` None / False or True / "reflect" / "constant" (centred: n // 2 samples trimmed
+    at both ends), ``stft_window`` as above, ``istft_gain`` a factor on the synthesis window that stays out of the envelope
+    (MIFFT_FLAG_ISTFT in include/mifft.h, _check_istft_layout, plan_istft).  ``bases`` has three lists: two empty ones and
+    the radices of n (or an empty one)."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
-                 dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None):
+                 dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
+                 istft_hop: int = 0, istft_gain: float = 1.0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         stft = int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT)
+        istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
         words = None
+        if istft:  # (with any other mode as well: the library refuses the pair)
+            if not int(istft_hop):
+                istft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
+                if stft_center is None:
+                    stft_center = {0: None, FLAG_STFT_CENTER_ZEROS: "constant"}.get(
+                        int(flags) & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), "reflect")
+            istft_dims = _check_istft_layout(in_shape, out_shape, istft_hop, stft_center)
+            if axes is not None:
+                raise MifftError(ERR_UNSUPPORTED, "an inverse STFT plan transforms dim 2 and overlap-adds dim 1: no axes")
+            gain = float(istft_gain)
+            if stft_window is not None or gain != 1.0:
+                w = torch.ones(istft_dims[2], dtype=torch.float64) if stft_window is None else _window_f64(stft_window, istft_dims[2])
+                words = window_words(w) + (window_words([gain]) if gain != 1.0 else [])
+            inverse = True
+            flags = (int(flags) | FLAG_ISTFT | FLAG_STFT_HOP(istft_hop) | _istft_center_flags(stft_center) |
+                     (FLAG_STFT if stft else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
+                     (FLAG_HALF_SPECTRUM if half_spectrum else 0))
+            stft = False
         if stft:  # (with any other mode as well: the library refuses the pair)
             if not int(stft_hop):
                 stft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
@@ -327,7 +401,9 @@ class Plan:
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
         dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
-        if stft:
+        if istft:
+            dims = istft_dims
+        elif stft:
             dims = stft_dims
         elif dctn:  # (with dct or half_spectrum as well: the library refuses the pair)
             dims = _check_dctn_layout(in_shape, out_shape)
@@ -356,8 +432,17 @@ class Plan:
         self.dct = dct
         self.dctn = dctn
         self.stft = stft
+        self.istft = istft
+        self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
-        if stft and (words is not None or bases is not None):  # (the window's words, then the radices of n)
+        if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
+            if bases is not None and (len(bases[0]) != 0 or len(bases[1]) != 0):
+                raise MifftError(-5, "dims 0 and 1 of an inverse STFT plan are not transformed: their bases lists must be empty")
+            radices = [int(b) for b in bases[2]] if bases is not None else []
+            flat = (words or []) + radices
+            c_flat = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+            c_len = (ctypes.c_int32 * 3)(len(words or []), 0, len(radices))
+        elif stft and (words is not None or bases is not None):  # (the window's words, then the radices of n)
             if bases is not None and len(bases[0]) != 0:
                 raise MifftError(-5, "dim 0 of an STFT plan is framed, not transformed: its bases list must be empty")
             radices = [int(b) for b in bases[1]] if bases is not None else []
@@ -381,7 +466,7 @@ class Plan:
     # -- introspection ------------------------------------------------------
     @property
     def ndim(self) -> int:
-        return len(self.out_shape) - 2
+        return self._ndim
 
     def stages(self, dim: int) -> list:
         out = (ctypes.c_uint32 * 64)()
@@ -507,6 +592,65 @@ def plan_stft(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, wi
         ctx = DeviceContext()
     return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, stft_hop=hop_length,
                 stft_center=center, stft_window=window)
+
+
+def plan_istft(dtype, batch: int, frames: int, n_fft: int, hop_length: int, *, window=None, center=False,
+               normalized: bool = False, length: Optional[int] = None, ctx: Optional[DeviceContext] = None,
+               whole_batch: int = 0) -> Plan:
+    """Plan of the inverse short-time Fourier transform with real output (no reference counterpart; MIFFT_FLAG_ISTFT in
+    include/mifft.h; torch.istft's semantics): ``frames`` half spectra of ``n_fft // 2 + 1`` bins per batch entry are
+    transformed back, multiplied by ``window`` (None: rectangular; else n_fft values, taken by value), overlap-added every
+    ``hop_length`` samples and divided by the overlap-added squared window.  ``center``: the first and last n_fft // 2
+    samples are trimmed (None / False, or True / "reflect" / "constant").  ``normalized``: the frames are multiplied by
+    sqrt(n_fft).  ``length``: output samples per entry, default istft_length(frames, n_fft, hop_length, center); it may be
+    shorter, never longer (no zero-padding).  The plan has ``in_shape`` (batch, frames, n_fft // 2 + 1, 2) and ``out_shape``
+    (batch, length, 1), both of ``dtype`` (float32 / float64), and runs through ``fft(out, X, plan=plan)``, ``first=`` /
+    ``count=`` included: one kernel launch, no tensor of frames, no memset; an entry's result is bit-identical for any batch
+    and slab.  Every argument error is raised before any device work; a window that breaks the nonzero overlap-add condition
+    in the output range is refused (-15)."""
+    batch, frames, n_fft, hop_length = int(batch), int(frames), int(n_fft), int(hop_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"an inverse STFT plan reads and writes float32 or float64, got {dtype}")
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    FLAG_STFT_HOP(hop_length)
+    centred = _istft_center_flags(center) != 0
+    T = istft_length(frames, n_fft, hop_length, centred) if length is None else int(length)
+    in_shape, out_shape = (batch, frames, n_fft // 2 + 1, 2), (batch, T, 1)
+    _check_istft_layout(in_shape, out_shape, hop_length, center)
+    if window is not None:
+        window = _window_f64(window, n_fft)
+    if ctx is None:
+        ctx = DeviceContext()
+    return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, istft_hop=hop_length,
+                stft_center=center, stft_window=window, istft_gain=float(n_fft) ** 0.5 if normalized else 1.0)
+
+
+def istft_schedule(plan: Plan, count: Optional[int] = None) -> list:
+    """The walk of an inverse STFT plan's one launch over ``count`` batch entries (default: the whole batch), from
+    ``pass_geometry(2, count)`` by host arithmetic alone: for every workgroup ``(first_tile, run_tiles, warmup_tiles)``.
+    Tile t is tile t % tiles_per_entry of entry t // tiles_per_entry, tiles_per_entry = ceil(F / TILE) (the last tile of an
+    entry is ragged); workgroup w owns the ascending run [first_tile, first_tile + run_tiles), lengths differing by one at
+    most; a run that starts inside an entry at tile g first recomputes warmup_tiles = min(g, ceil((K - 1) / TILE)) tiles before
+    it with the stores suppressed, K = ceil(n_fft / hop) the frames that cover one sample."""
+    if not getattr(plan, "istft", False):
+        raise MifftError(ERR_UNSUPPORTED, "istft_schedule describes inverse STFT plans only")
+    tile, _, n_tiles, grid = plan.pass_geometry(2, count)
+    frames, n_fft = plan.in_shape[1], 2 * (plan.in_shape[2] - 1)
+    hop = (plan.flags & FLAG_STFT_HOP_MASK) >> 16
+    return _istft_schedule(tile, n_tiles, grid, frames, n_fft, hop)
+
+
+def _istft_schedule(tile: int, n_tiles: int, grid: int, frames: int, n_fft: int, hop: int) -> list:
+    tpe = -(-frames // tile)
+    K = -(-n_fft // hop)
+    W = -(-(K - 1) // tile)
+    length, rem = divmod(n_tiles, grid)
+    runs = []
+    for w in range(grid):
+        first = w * length + min(w, rem)
+        runs.append((first, length + (1 if w < rem else 0), min(first % tpe, W)))
+    return runs
 
 
 def _check_tensor(t: "torch.Tensor", shape: tuple, dtype, device: int, what: str) -> None:
@@ -1014,3 +1158,82 @@ def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_le
             _PLAN_CACHE.move_to_end(key)
         fft(out, xr, DeviceContext(device), plan=plan)
     return torch.view_as_complex(out).reshape(logical[:-1] + (frames, n_fft // 2 + 1)).transpose(-1, -2)
+
+
+def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None, window=None,
+          center: bool = True, normalized: bool = False, onesided: Optional[bool] = None, length: Optional[int] = None,
+          return_complex: bool = False, *, out_dtype=None) -> "torch.Tensor":
+    """torch.istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided=True, length, return_complex=False)
+    of a complex ``X`` of shape (n_fft // 2 + 1, F) or (..., n_fft // 2 + 1, F), torch's layout; the leading dims fold into
+    the batch.  ``hop_length`` defaults to n_fft // 4, ``win_length`` to n_fft; a shorter window is zero-padded on both sides
+    to n_fft, as torch does; ``window=None`` is rectangular.  Returns real (..., length), ``length`` defaulting to
+    istft_length(F, n_fft, hop_length, center).  ``onesided=False``, ``return_complex=True``, an odd n_fft and a ``length``
+    beyond what the frames cover (torch zero-pads) are MifftError -15; so is a window whose squared overlap-add vanishes in
+    the output range (torch raises for it too).  Input that is not of ``out_dtype``'s complex type (default: that of a
+    complex64 / complex128 ``X``) is converted first.
+    The kernel reads frames-major (..., F, n_fft // 2 + 1) memory: when ``X.transpose(-1, -2)`` is contiguous -- exactly the
+    view ``stft`` returns -- X is used as it lies, with no copy; otherwise ONE transposing copy is made first.
+    One kernel launch: no tensor of frames, no fold, no memset (MIFFT_FLAG_ISTFT in include/mifft.h).  Plans are cached like
+    ``stft``'s: per (shape, dtype, n_fft, hop, centring, length, gain, device, stream) AND the window's contents."""
+    if onesided is not None and not onesided:
+        raise MifftError(ERR_UNSUPPORTED, "istft: onesided=False is not supported")
+    if return_complex:
+        raise MifftError(ERR_UNSUPPORTED, "istft: return_complex=True is not supported")
+    if not X.is_complex():
+        raise MifftError(-3, "istft expects a complex tensor")
+    if X.dim() < 2:
+        raise MifftError(-1, "istft expects a tensor of rank 2 or more: (n_fft // 2 + 1, F) or (..., n_fft // 2 + 1, F)")
+    n_fft = int(n_fft)
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"istft with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    if X.shape[-2] != n_fft // 2 + 1:
+        raise MifftError(-2, f"istft: X has {X.shape[-2]} bins, n_fft = {n_fft} needs {n_fft // 2 + 1}")
+    hop_length = n_fft // 4 if hop_length is None else int(hop_length)
+    FLAG_STFT_HOP(hop_length)
+    win_length = n_fft if win_length is None else int(win_length)
+    if not 0 < win_length <= n_fft:
+        raise MifftError(-2, f"istft: 0 < win_length <= n_fft, got win_length = {win_length}, n_fft = {n_fft}")
+    if out_dtype is None:
+        out_dtype = {torch.complex64: torch.float32, torch.complex128: torch.float64}.get(X.dtype, torch.float64)
+    if out_dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"istft: out_dtype must be float32 or float64, got {out_dtype}")
+    logical = tuple(X.shape)
+    frames = logical[-1]
+    batch = 1
+    for m in logical[:-2]:
+        batch *= m
+    covered = istft_length(frames, n_fft, hop_length, False) - (n_fft // 2 if center else 0)
+    T = istft_length(frames, n_fft, hop_length, bool(center)) if length is None else int(length)
+    if T > covered:
+        raise MifftError(ERR_UNSUPPORTED, f"istft: length = {T} beyond the {covered} samples the frames cover (zero-padding "
+                                          f"is not supported)")
+    in_shape, out_shape = (batch, frames, n_fft // 2 + 1, 2), (batch, T, 1)
+    _check_istft_layout(in_shape, out_shape, hop_length, bool(center))
+    w = None
+    if window is not None or win_length < n_fft:
+        wl = torch.ones(win_length, dtype=torch.float64) if window is None else _window_f64(window, win_length)
+        left = (n_fft - win_length) // 2
+        w = torch.zeros(n_fft, dtype=torch.float64)
+        w[left:left + win_length] = wl
+    gain = float(n_fft) ** 0.5 if normalized else 1.0
+    device = DeviceContext(X.device.index if X.is_cuda else None).device
+    if not X.is_cuda or X.device.index != device:
+        raise MifftError(-10, f"X must live on HIP device {device}, got {X.device}")
+    ctype = torch.complex64 if out_dtype == torch.float32 else torch.complex128
+    # frames-major memory: a no-op for the view stft returns, one transposing copy otherwise
+    xf = X.to(ctype).transpose(-1, -2).contiguous()
+    xr = torch.view_as_real(xf).reshape(in_shape)
+    out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
+    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
+    with _PLAN_CACHE_LOCK:
+        key = ("istft", out_dtype, in_shape, n_fft, hop_length, bool(center), T, gain, digest, device,
+               int(torch.cuda.current_stream(device).cuda_stream))
+        plan = _PLAN_CACHE.get(key)
+        if plan is None:
+            plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, istft_hop=hop_length,
+                        stft_center=bool(center), stft_window=w, istft_gain=gain)
+            _plan_cache_insert(key, plan)
+        else:
+            _PLAN_CACHE.move_to_end(key)
+        fft(out, xr, DeviceContext(device), plan=plan)
+    return out.reshape(logical[:-2] + (T,))

@@ -1,0 +1,238 @@
+// istft.cpp -- the plans with MIFFT_FLAG_ISTFT (torch.istft with real output, the frames leading; include/mifft.h).
+//
+// One launch, no scratch, no memset and no tensor of frames: the C2R row kernel of the frame length with TileCfg::ISTFT set,
+// whose rows are TILE consecutive frames of one batch entry and whose store multiplies by the synthesis window, overlap-adds
+// the frames in LDS, carries the unfinished samples to the workgroup's next tile, divides by the window envelope and writes
+// every output sample once (tile_kernel.h).  x is (batch, F, n / 2 + 1, 2), out (batch, T, 1) real.  The window and the gain
+// travel through `bases` as host data; the plan keeps gain * w[j] / n with the sign of the kernel's conjugation (the 1 / n is
+// folded into this table: the pass's own scale is not applied) and 1 / sum w^2 at every padded sample as device tables of its
+// float type, both computed in binary64 and rounded once.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "mifft_config.h"
+#include "mifft_internal.h"
+
+namespace mifft {
+
+static bool read_f64(const uint32_t* words, double& v) {
+    const uint64_t bits = (uint64_t)words[0] | ((uint64_t)words[1] << 32);
+    memcpy(&v, &bits, sizeof v);
+    return std::isfinite(v);
+}
+
+// sum over the frames that cover padded sample u of w[u - f hop]^2, ascending f
+static double envelope_at(const std::vector<double>& window, int64_t n, int64_t hop, int64_t F, int64_t u) {
+    const int64_t f_hi = std::min<int64_t>(F - 1, u / hop), f_lo = u < n ? 0 : (u - n) / hop + 1;
+    double s = 0.0;
+    for (int64_t f = f_lo; f <= f_hi; ++f) {
+        const double w = window.empty() ? 1.0 : window[(size_t)(u - f * hop)];
+        s += w * w;
+    }
+    return s;
+}
+
+// From u = n on and below F hop every padded sample is covered by the same window values as the one a hop before it, summed
+// in the same order: the envelope there repeats with period hop.  `middle` says whether u has such a twin a hop before it.
+static bool envelope_repeats(int64_t n, int64_t hop, int64_t F, int64_t u) { return u >= n + hop && u < F * hop; }
+
+// the first stored sample u in [c, c + T) whose envelope is below `tiny` in absolute value, or -1: the head, the tail and ONE
+// period of the repeating middle are evaluated, O(n^2 / hop) whatever the length
+static int64_t envelope_first_below(const std::vector<double>& window, int64_t n, int64_t hop, int64_t F, int64_t c, int64_t T,
+                                    double tiny) {
+    int64_t first = -1;
+    auto visit = [&](int64_t u) {
+        if ((first < 0 || u < first) && std::fabs(envelope_at(window, n, hop, F, u)) < tiny) first = u;
+    };
+    const int64_t lo = c, hi = c + T;                       // [lo, hi)
+    const int64_t m0 = std::max(lo, n + hop), m1 = std::min(hi, F * hop);  // the repeating samples among them
+    for (int64_t u = lo; u < std::min(hi, n + hop); ++u) visit(u);
+    for (int64_t u = std::max(lo, std::max(F * hop, n + hop)); u < hi; ++u) visit(u);
+    for (int64_t u = m0; u < std::min(m1, m0 + hop); ++u) visit(u);  // one period stands for all of them
+    return first;
+}
+
+// checks that need no device: MIFFT_OK, or the status and its reason; the window, the gain and the user radices on the way
+int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
+                std::vector<uint64_t>& radices, std::string& why) {
+    window.clear();
+    radices.clear();
+    gain = 1.0;
+    const struct {
+        uint32_t bits;
+        const char* what;
+    } other[] = {// (MIFFT_FLAG_STFT beside this bit never gets here: stft_check refuses the pair)
+                 {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no inverse STFT to be faithful to"},
+                 {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an inverse STFT plan reads the half spectrum of every frame anyway"},
+                 {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
+                 {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
+                 {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an inverse STFT plan transforms dim 2 and overlap-adds dim 1"}};
+    for (const auto& o : other)
+        if (p.flags & o.bits) {
+            why = std::string("MIFFT_FLAG_ISTFT with ") + o.what;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+    if (!p.inverse) {
+        why = "MIFFT_FLAG_ISTFT with inverse = 0: the forward transform is MIFFT_FLAG_STFT";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.ndim != 3) {
+        why = "MIFFT_FLAG_ISTFT overlap-adds the frames of a (batch, F, n / 2 + 1, 2) tensor: ndim must be 3 (dims = {T, F, n}), not " +
+              std::to_string(p.ndim);
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if ((p.flags & MIFFT_FLAG_STFT_CENTER_REFLECT) && (p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS)) {
+        why = "both centre bits: MIFFT_FLAG_STFT_CENTER_REFLECT and MIFFT_FLAG_STFT_CENTER_ZEROS exclude each other";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    const int64_t T = p.dims[0], F = p.dims[1], n = p.dims[2], hop = p.stft_hop();
+    if (hop == 0) {
+        why = "MIFFT_FLAG_ISTFT with hop 0: MIFFT_FLAG_STFT_HOP(h) carries the hop, 1 .. n";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (hop > n) {
+        why = "MIFFT_FLAG_ISTFT with hop " + std::to_string(hop) + " > n = " + std::to_string(n) +
+              ": gaps between the frames, where the window envelope is zero";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 2) {
+        why = "an inverse STFT reads complex frames (in_components = 2)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.in_dtype != p.out_dtype) {
+        why = "an inverse STFT reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    if (n % 2 != 0) {
+        why = "STFT with an odd frame length (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (n < 8) {
+        why = "STFT with frames of fewer than 8 points (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!istft_rows_supported(p, n, w)) {
+        why = "STFT with frames of " + std::to_string(n) + " points: " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (F < 1) {
+        why = "an inverse STFT needs at least one frame (dims[1] = " + std::to_string(F) + ")";
+        return MIFFT_ERR_BAD_DIM;
+    }
+    if (F > (1ll << 26)) {  // (before L is formed: L = n + hop (F - 1) stays far inside 64 bits)
+        why = "more than 2^26 frames per entry: the envelope table has one entry per padded sample";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    const int64_t L = p.istft_padded_len(), c = p.istft_trim();
+    if (L > (1ll << 26)) {
+        why = "frames that cover " + std::to_string(L) + " samples per entry: the envelope table (one entry per padded sample) is " +
+              "limited to 2^26";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (T < 1 || T > L - c) {
+        why = "T = " + std::to_string(T) + " output samples, but the frames cover 1 .. " + std::to_string(L - c) +
+              " (n + hop (F - 1)" + (c ? " - n / 2" : "") + "): a longer output is not zero-padded";
+        return MIFFT_ERR_BAD_DIM;
+    }
+    // ---- `bases`: window [+ gain], nothing for dim 1, the radices of n ----
+    if (bases_flat && bases_len) {
+        const int64_t l0 = bases_len[0];
+        if (l0 != 0 && l0 != 2 * n && l0 != 2 * n + 2) {
+            why = "bases_len[0] of an inverse STFT plan is 0 (rectangular window), 2 n = " + std::to_string(2 * n) +
+                  " words of window, or 2 n + 2 (window and gain), not " + std::to_string(l0);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (bases_len[1] != 0 || bases_len[2] < 0) {
+            why = "bases_len[1] of an inverse STFT plan is 0 (dim 1 is overlap-added, not transformed) and bases_len[2] the radices of n";
+            return bases_len[2] < 0 ? MIFFT_ERR_NO_BASES : MIFFT_ERR_BAD_BASES;
+        }
+        if (l0) {
+            window.resize((size_t)n);
+            for (int64_t j = 0; j < n; ++j)
+                if (!read_f64(bases_flat + 2 * j, window[(size_t)j])) {
+                    why = "window value " + std::to_string(j) + " is not finite";
+                    return MIFFT_ERR_BAD_BASES;
+                }
+            if (l0 == 2 * n + 2 && !read_f64(bases_flat + 2 * n, gain)) {
+                why = "the gain is not finite";
+                return MIFFT_ERR_BAD_BASES;
+            }
+        }
+        for (int k = 0; k < bases_len[2]; ++k) radices.push_back(bases_flat[l0 + k]);
+    }
+    // ---- NOLA over the samples the plan stores (torch.istft: window_envelop.abs().min() over [c, c + T) against 1e-11) ----
+    const int64_t bare = envelope_first_below(window, n, hop, F, c, T, 1e-11);
+    if (bare >= 0) {
+        why = "the window's squared overlap-add is zero at output sample " + std::to_string(bare - c) +
+              " (nonzero overlap-add condition: below 1e-11)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    return MIFFT_OK;
+}
+
+template <typename T>
+static hipError_t upload_t(const std::vector<T>& tab, void** d_table) {
+    hipError_t e = hipMalloc(d_table, tab.size() * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(*d_table, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
+// the synthesis table and the reciprocal envelope, formed in binary64 and rounded once to the plan's type T (the only host
+// copy of the L-entry table is of that type; a repeating sample copies its twin's rounded value, which is the same rounding)
+template <typename T>
+static hipError_t upload_tables_t(int64_t n, int64_t hop, int64_t F, const std::vector<double>& window, double gain, void** d_ws,
+                                  void** d_env) {
+    const int64_t L = n + hop * (F - 1);
+    std::vector<T> ws((size_t)n), inv((size_t)L);
+    // the kernel's last pass leaves conj(z) of the packed frame z_m = y[2m] + i y[2m+1], unscaled: odd reals negated, 1 / n here
+    for (int64_t j = 0; j < n; ++j)
+        ws[(size_t)j] = (T)(((j & 1) ? -gain : gain) * (window.empty() ? 1.0 : window[(size_t)j]) / (double)n);
+    // (samples outside the stored range may have a zero envelope: their entries are never read)
+    for (int64_t u = 0; u < L; ++u) {
+        if (envelope_repeats(n, hop, F, u)) {
+            inv[(size_t)u] = inv[(size_t)(u - hop)];
+            continue;
+        }
+        const double e = envelope_at(window, n, hop, F, u);
+        inv[(size_t)u] = (T)(e != 0.0 ? 1.0 / e : 0.0);
+    }
+    hipError_t e = upload_t<T>(ws, d_ws);
+    if (e == hipSuccess) e = upload_t<T>(inv, d_env);
+    return e;
+}
+
+// the one pass: dim 2 (n points) over the F frames of every batch entry
+int build_istft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+                const std::vector<double>& window, double gain, std::string& why) {
+    const int64_t F = p.dims[1], n = p.dims[2], hop = p.stft_hop();
+    DimPass ps;
+    ps.dim_index = 2;
+    ps.N = n;
+    ps.inner = 1;
+    ps.outer = F;
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    ps.half_pitch = n / 2 + 1;
+    if (!select_jit_istft_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    // the passes run n / 2 points; the fold needs W_n^k, forward (as a half-spectrum row pass)
+    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, true, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    if (e == hipSuccess) {
+        try {
+            e = p.out_dtype == MIFFT_F64 ? upload_tables_t<double>(n, hop, F, window, gain, &ps.d_aux2, &ps.d_aux3)
+                                         : upload_tables_t<float>(n, hop, F, window, gain, &ps.d_aux2, &ps.d_aux3);
+        } catch (const std::bad_alloc&) {  // (up to 2^26 entries on the host)
+            e = hipErrorOutOfMemory;
+        }
+    }
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "inverse STFT table upload");
+    return MIFFT_OK;
+}
+
+}  // namespace mifft

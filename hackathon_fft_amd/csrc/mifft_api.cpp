@@ -30,11 +30,13 @@ size_t Plan::in_elem_bytes() const { return dtype_size(in_dtype) * (size_t)in_co
 size_t Plan::out_elem_bytes() const { return dtype_size(out_dtype) * 2; }
 size_t Plan::in_row_bytes() const {
     if (stft()) return (size_t)dims[0] * dtype_size(in_dtype);
+    if (istft()) return (size_t)prod_half * in_elem_bytes();
     if (dct_any()) return (size_t)prod * dtype_size(in_dtype);
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
     if (stft()) return (size_t)prod_half * out_elem_bytes();
+    if (istft()) return (size_t)dims[0] * dtype_size(out_dtype);
     if (dct_any()) return (size_t)prod * dtype_size(out_dtype);
     if (!half_spectrum()) return (size_t)prod * out_elem_bytes();
     return inverse ? (size_t)prod * dtype_size(out_dtype) : (size_t)prod_half * out_elem_bytes();
@@ -212,18 +214,22 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         return set_error(MIFFT_ERR_BAD_DTYPE, "out_dtype must be floating point");
     if (dtype_size(in_dtype) == 0) return set_error(MIFFT_ERR_BAD_DTYPE, "unsupported in_dtype");
     if (batch < 0) return set_error(MIFFT_ERR_BAD_BATCH, "batch must be >= 0");
-    for (int i = 0; i < ndim; ++i)
+    for (int i = 0; i < ndim; ++i) {
+        if (i == 1 && ndim == 3 && (flags & MIFFT_FLAG_ISTFT) && dims[i] == 1) continue;  // (one frame: istft.cpp)
         if (dims[i] < 2) return set_error(MIFFT_ERR_BAD_DIM, "no inner dimension should be of size 1");
+    }
     if ((bases_flat == nullptr) != (bases_len == nullptr))
         return set_error(MIFFT_ERR_NULL, "bases_flat and bases_len must both be given or both be NULL");
-    // ---- STFT plans (MIFFT_FLAG_STFT; stft.cpp): their own route from here to the end.  Everything that can be refused
-    //      without a device first; `bases` carries the window and the radices of dim 1 ----
+    // ---- STFT and inverse STFT plans (MIFFT_FLAG_STFT, stft.cpp; MIFFT_FLAG_ISTFT, istft.cpp): their own route from here to
+    //      the end.  Everything that can be refused without a device first; `bases` carries the window and the radices of
+    //      the one transformed dim, the last ----
     {
         std::string why;
         const int rc = stft_flag_check(flags, why);
         if (rc) return set_error(rc, why);
     }
-    if (flags & MIFFT_FLAG_STFT) {
+    if (flags & (MIFFT_FLAG_STFT | MIFFT_FLAG_ISTFT)) {
+        const bool fwd = (flags & MIFFT_FLAG_STFT) != 0;  // (both bits: stft_check refuses the pair)
         mifft_plan* h = new mifft_plan();
         Plan& p = h->p;
         p.device = device;
@@ -242,20 +248,24 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
             return rc == MIFFT_ERR_HIP ? rc : set_error(rc, why);
         };
         std::string why;
-        int rc = stft_check(p, why);
-        if (rc) return fail(rc, why);
-        const int64_t n = dims[1];
-        p.prod = p.stft_frames() * n;  // (the rows the one pass transforms, and what it stores)
-        p.prod_half = p.stft_frames() * (n / 2 + 1);
         std::vector<double> window;
         std::vector<uint64_t> user;
-        rc = stft_unpack_bases(n, bases_flat, bases_len, window, user, why);
+        double gain = 1.0;
+        int rc = fwd ? stft_check(p, why) : istft_check(p, bases_flat, bases_len, window, gain, user, why);
         if (rc) return fail(rc, why);
+        const int td = ndim - 1;  // the transformed dim
+        const int64_t n = dims[td], frames = fwd ? p.stft_frames() : dims[1];
+        p.prod = frames * n;  // (the rows the one pass transforms)
+        p.prod_half = frames * (n / 2 + 1);
+        if (fwd) {
+            rc = stft_unpack_bases(n, bases_flat, bases_len, window, user, why);
+            if (rc) return fail(rc, why);
+        }
         if (user.empty()) user = plan_estimate_bases((uint64_t)n, /*gpu_target=*/true);
-        std::vector<std::vector<uint32_t>> ordered(2), processed(2);
-        rc = plan_ordered_bases((uint64_t)n, user, ordered[1], processed[1], why);
+        std::vector<std::vector<uint32_t>> ordered((size_t)ndim), processed((size_t)ndim);
+        rc = plan_ordered_bases((uint64_t)n, user, ordered[td], processed[td], why);
         if (rc) return fail(rc, why);
-        p.stage_radices = ordered;  // (dim 0 is framed, not transformed: no stages)
+        p.stage_radices = ordered;  // (the other dims are framed / overlap-added, not transformed: no stages)
         const int ndev = device_count_quiet();
         if (device < 0 || device >= ndev)
             return fail(MIFFT_ERR_NO_DEVICE, "libmifft has no CPU path: device " + std::to_string(device) +
@@ -268,7 +278,8 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) p.num_cus = prop.multiProcessorCount;
         config_refresh();
-        rc = build_stft(p, ordered[1], processed[1], window, why);
+        rc = fwd ? build_stft(p, ordered[td], processed[td], window, why)
+                 : build_istft(p, ordered[td], processed[td], window, gain, why);
         if (rc) return fail(rc, why);
         *out_plan = h;
         return MIFFT_OK;
@@ -810,6 +821,7 @@ const char* mifft_plan_kernel_name(const mifft_plan* plan, int dim) {
     if (!plan) return "";
     if (dim >= 0 && dim < plan->p.ndim && plan->p.kept(dim)) return "none";
     if (dim == 0 && plan->p.stft()) return "none";  // (framed, not transformed)
+    if (dim >= 0 && dim < 2 && plan->p.istft()) return "none";  // (samples and frames: overlap-added, not transformed)
     for (const DimPass& ps : plan->p.passes)
         if (ps.dim_index == dim || ps.dim_index2 == dim) return ps.kernel_name;
     return "";
@@ -821,6 +833,8 @@ int mifft_plan_pass_geometry(const mifft_plan* plan, int dim, int64_t count, int
     if (count < 1) return set_error(MIFFT_ERR_BAD_BATCH, "count must be positive");
     if (plan->p.kept(dim)) return set_error(MIFFT_ERR_UNSUPPORTED, "a kept dim has no pass");
     if (dim == 0 && plan->p.stft()) return set_error(MIFFT_ERR_UNSUPPORTED, "dim 0 of an STFT plan is framed: it has no pass");
+    if (dim < 2 && plan->p.istft())
+        return set_error(MIFFT_ERR_UNSUPPORTED, "dims 0 and 1 of an inverse STFT plan are overlap-added: they have no pass");
     const DimPass* found = nullptr;
     for (const DimPass& ps : plan->p.passes)
         if (ps.dim_index == dim || ps.dim_index2 == dim) {

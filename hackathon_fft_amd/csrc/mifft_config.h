@@ -54,6 +54,13 @@ struct Config {
     // 509 0.57 -> 0.26, 1019 1.11 -> 0.32, 2039 2.16 -> 0.48; below, the cooperative pass wins: 83 0.142 against 0.295)
     int rader_pad_min = 200;
 
+    // inverse STFT (TileCfg::ISTFT): the grid is at most n_tiles / istft_min_run workgroups, so that a run that starts inside
+    // an entry spreads its warm-up tiles over at least that many of its own.  Measured (profiles/r10_istft.txt;
+    // lab: MIFFT_ISTFT_MIN_RUN): with a few hundred tiles, where the constant decides the grid, 1 is 25-30 % ahead of 2 and
+    // every doubling loses more -- more workgroups beat fewer warm-up tiles; with thousands of tiles 1, 2 (and 4) give the
+    // same full grid
+    int istft_min_run = 1;
+
     // ---- Infinity-Cache policy of N-D schedules: bit 0 non-temporal first pass, bit 1 alternating walk ----
     int nd_mode = 3;
 
@@ -122,6 +129,7 @@ inline Config load_config() {
     if (const char* v = env("MIFFT_DCT_COLS_DIRECT")) c.dct_cols_direct = v[0] != '0';
     if (const char* v = env("MIFFT_RADER_MIN")) c.rader_min = c.rader_min_pair = atoi(v);
     if (const char* v = env("MIFFT_RADER_PAD_MIN")) c.rader_pad_min = atoi(v);
+    if (const char* v = env("MIFFT_ISTFT_MIN_RUN")) c.istft_min_run = atoi(v) > 0 ? atoi(v) : 1;
 #endif
 #ifdef MIFFT_TESTING
     if (const char* v = env("MIFFT_TEST_FAIL_SCRATCH_ALLOC")) c.test_fail_scratch_alloc = v[0] == '1';

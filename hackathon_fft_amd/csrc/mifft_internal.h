@@ -101,6 +101,10 @@ struct DimPass {
     // TileCfg::STFT of a packed-row pass: the rows are the `outer` frames of every batch entry (hop, length and centring are the
     // plan's); d_aux2 holds the window, N values of the plan's float type
     bool stft = false;
+    // TileCfg::ISTFT of a C2R pass: `outer` frames per batch entry are overlap-added into dims[0] samples; d_aux2 holds the
+    // synthesis table (N values), d_aux3 the reciprocal envelope (N + hop (outer - 1) values), both of the plan's float type
+    bool istft = false;
+    int istft_min_run = 1;  // (Config::istft_min_run when the pass was built: the grid is at most n_tiles / istft_min_run)
     int64_t half_pitch = 0;  // R2C / C2R: row pitch (complex elements) of the half-spectrum side; 0 = N (full-spectrum rows)
     int store_lim = 0;
     bool ilv = false;  // interleaved block tile (TileCfg::ILV): `inner` (< 128 B of elements) transforms per block, launched as rows
@@ -165,6 +169,12 @@ struct Plan {
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
     int64_t stft_frames() const { return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop(); }
+    // MIFFT_FLAG_ISTFT: dims = {T, F, n}; x is (batch, F, n / 2 + 1, 2), out (batch, T, 1) real: F frames of n samples every
+    // stft_hop() overlap-added over istft_padded_len() samples, of which T from istft_trim() on are stored
+    bool istft() const { return (flags & MIFFT_FLAG_ISTFT) != 0; }
+    bool istft_centered() const { return (flags & (MIFFT_FLAG_STFT_CENTER_REFLECT | MIFFT_FLAG_STFT_CENTER_ZEROS)) != 0; }
+    int64_t istft_padded_len() const { return dims[2] + stft_hop() * (dims[1] - 1); }
+    int64_t istft_trim() const { return istft_centered() ? dims[2] / 2 : 0; }
     // bytes of ONE transform (one batch entry) of x, out and the plan scratch: the slab offsets and the alias check of
     // mifft_exec_batch and the size queries.  Without the flag: prod * in_elem_bytes(), prod * out_elem_bytes() twice.
     size_t in_row_bytes() const;
@@ -296,6 +306,17 @@ int stft_unpack_bases(int64_t n, const uint32_t* bases_flat, const int32_t* base
                       std::vector<uint64_t>& radices, std::string& why);
 int build_stft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                const std::vector<double>& window, std::string& why);
+// plans with MIFFT_FLAG_ISTFT (istft.cpp), in the same manner: istft_check needs no device and leaves the window (empty:
+// rectangular), the gain and the user radices in its outputs; it refuses a window whose squared overlap-add is zero
+// somewhere in the samples the plan stores.  select_jit_istft_rows is the C2R kernel with TileCfg::ISTFT (run time only),
+// istft_rows_supported the same check without a device; Config::istft_min_run, copied to DimPass::istft_min_run when the pass is
+// built, enters the grid (tile_launch_geometry).
+bool istft_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_istft_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+int istft_check(const Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+                double& gain, std::vector<uint64_t>& radices, std::string& why);
+int build_istft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+                const std::vector<double>& window, double gain, std::string& why);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

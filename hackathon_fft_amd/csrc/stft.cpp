@@ -13,9 +13,9 @@
 
 namespace mifft {
 
-// the STFT bits of a plan without MIFFT_FLAG_STFT
+// the STFT bits of a plan with neither mode bit (MIFFT_FLAG_STFT, MIFFT_FLAG_ISTFT)
 int stft_flag_check(uint32_t flags, std::string& why) {
-    if (flags & MIFFT_FLAG_STFT) return MIFFT_OK;
+    if (flags & (MIFFT_FLAG_STFT | MIFFT_FLAG_ISTFT)) return MIFFT_OK;
     if (flags & MIFFT_FLAG_STFT_HOP_MASK) {
         why = "a hop (MIFFT_FLAG_STFT_HOP) without MIFFT_FLAG_STFT";
         return MIFFT_ERR_UNSUPPORTED;
@@ -37,7 +37,8 @@ int stft_check(const Plan& p, std::string& why) {
                  {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
                  {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
                  {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
-                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an STFT plan frames dim 0 and transforms dim 1"}};
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an STFT plan frames dim 0 and transforms dim 1"},
+                 {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
     for (const auto& o : other)
         if (p.flags & o.bits) {
             why = std::string("MIFFT_FLAG_STFT with ") + o.what;

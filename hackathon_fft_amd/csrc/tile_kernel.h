@@ -189,6 +189,10 @@ struct TileParams {
     // reflected at both ends (N <= stft_len - 1: one reflection), 2 zeros beyond both ends.
     const void* stft_win;
     int stft_frames, stft_hop, stft_len, stft_center;
+    // ISTFT configurations reuse the four integers (frames per entry F, hop, output samples per entry T, centred or not) and
+    // stft_win (the synthesis table, below); tiles_per_outer is the tiles of ONE entry, ceil(F / TILE), and istft_env the
+    // reciprocal envelope 1 / sum w^2 at every padded sample 0 .. 2 N + hop (F - 1) - 1, type T
+    const void* istft_env;
 };
 
 MIFFT_DEV long long tile_id(const TileParams& p, long long t) { return p.reverse ? p.n_tiles - 1 - t : t; }
@@ -276,7 +280,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
-          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false>
+          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -455,6 +459,24 @@ struct TileCfg {
     static constexpr bool STFT = STFT_;
     static_assert(!STFT_ || (R2C_ && !FIRST_DIRECT_ && DCT_ == 0 && same_t<IT_, T_>::value),
                   "STFT: packed real rows of the plan's own float type, staged in LDS by the framing load");
+    // ISTFT (torch.istft, real output): a C2R tile whose rows are TILE consecutive FRAMES of ONE batch entry and whose store
+    // overlap-adds them.  Load and passes are the C2R tile's (row r of entry b is spectrogram row b F + r); the last pass
+    // leaves conj(z) of the packed frames in LDS, unscaled.  The store has one work item per padded sample
+    // u in [f0 hop, (f0 + nv - 1) hop + 2 N) of the tile's frames f0 .. f0 + nv - 1: it starts from the partial sum the
+    // earlier tiles of the entry left in `carry` (2 N - hop reals behind the tables; exact zero in the first tile of an entry
+    // and beyond the carry), adds ws[j] y_f[j], j = u - f hop, for the tile's frames that cover u in ASCENDING f, each term
+    // one fma, and either finishes the sample -- u < (f0 + nv) hop, or the tile is the last of its entry: times
+    // istft_env[u], stored to out[b, u - c] when that lies in [0, T) -- or leaves it in the carry at u - (f0 + nv) hop.
+    // ws (stft_win) is gain * w[j] / 2N with the sign of the conjugation folded in (odd j negative), so a term is one fma
+    // on the LDS slot as it stands.  The carry moves towards lower indices: the samples are walked in ascending chunks of
+    // THREADS with a barrier between a chunk's reads and its writes.  A workgroup owns one contiguous ascending run of tiles
+    // (lengths differ by one at most); a run that starts inside an entry first recomputes the W tiles before it with the
+    // stores suppressed (tile_kernel), so every sample is summed in ascending frame order from an exact zero whatever the
+    // partition, and the result of an entry does not depend on the grid.  Every output sample is written exactly once, with
+    // a plain store; nothing outside [0, T) of an entry of the launch is touched.
+    static constexpr bool ISTFT = ISTFT_;
+    static_assert(!ISTFT_ || (C2R_ && !LAST_DIRECT_ && DCT_ == 0 && !STFT_ && ROWPAD_ == 0),
+                  "ISTFT: folded rows whose last pass stays in LDS for the overlap-add");
     static constexpr int CPITCH = TSTORE_ ? TILE_ + 1 : TILE_;
     static_assert(!TSTORE_ || (COLS_ && !LAST_DIRECT_ && FIRST_DIRECT_), "TSTORE: column tile, last pass left in LDS");
     static constexpr int DATA_ELEMS = COLS_ ? N_ * CPITCH : LD * TILE_;
@@ -492,10 +514,13 @@ struct TileCfg {
     static constexpr bool HERM_RUNS = HERM_ && !XCD_CHUNK;
     static constexpr int HERM_OFF = DATA_ELEMS + TWL_TOTAL + CS_ELEMS;
     static constexpr int HERM_ELEMS = HERM_RUNS ? N_ : 0;
+    // ISTFT: the carry, 2 N - hop <= 2 N reals, where the Hermitian column would be (C2R excludes HERM)
+    static constexpr int ISTFT_OFF = HERM_OFF;
+    static constexpr int ISTFT_ELEMS = ISTFT_ ? N_ : 0;
     static_assert(!(HERM_ && DMA_), "HERM: no staging buffer");
     static constexpr size_t LDS_BYTES =
         DMA_ ? (size_t)(STAGE_OFF + STAGE_ELEMS) * 2 * sizeof(T_)
-             : (size_t)(DATA_ELEMS + TWL_TOTAL + CS_ELEMS + HERM_ELEMS) * 2 * sizeof(T_);
+             : (size_t)(DATA_ELEMS + TWL_TOTAL + CS_ELEMS + HERM_ELEMS + ISTFT_ELEMS) * 2 * sizeof(T_);
     static_assert(P(NP_) == N_, "radices must multiply to N");
     static_assert(LDS_BYTES <= 160 * 1024, "tile + twiddle table exceed the CU's 160 KiB of LDS");
 };
@@ -1398,8 +1423,19 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
         t_end = t + len + (w < rem ? 1 : 0);
         t_step = 1;
     }
-    // (runs: position t of the order is tile n_tiles - 1 - t, whatever p.reverse says)
-    auto tile_at = [&](long long pos) { return C::HERM_RUNS ? p.n_tiles - 1 - pos : tile_id(p, pos); };
+    if constexpr (C::ISTFT) {  // the same runs in ASCENDING order, after the warm-up tiles of a run that starts inside an entry:
+                               // the W tiles before it, W = min(g, ceil((K - 1) / TILE)), K = ceil(2 N / hop) frames per sample
+        const long long len = p.n_tiles / gridDim.x, rem = p.n_tiles - len * gridDim.x, w = blockIdx.x;
+        run_begin = w * len + (w < rem ? w : rem);
+        t_end = run_begin + len + (w < rem ? 1 : 0);
+        t_step = 1;
+        const long long g = run_begin % p.tiles_per_outer;
+        const long long K = (2 * C::N + p.stft_hop - 1) / p.stft_hop, W = (K - 1 + C::TILE - 1) / C::TILE;
+        t = run_begin - (W < g ? W : g);
+    }
+    const long long t_first = t;
+    // (runs: position t of the order is tile n_tiles - 1 - t, whatever p.reverse says; ISTFT: tile t)
+    auto tile_at = [&](long long pos) { return C::ISTFT ? pos : C::HERM_RUNS ? p.n_tiles - 1 - pos : tile_id(p, pos); };
     if constexpr (C::XCD_CHUNK) {
         if (gridDim.x >= 8) {  // (smaller grids: some XCD would own tiles but no workgroup)
             const long long x = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -1453,6 +1489,13 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 const bool in = t > run_begin && in_row + 1 < p.herm_tpr && nxt % p.herm_d2 != 0 && herm_twice(p, nxt);
                 fs_row |= (in ? 1 << 30 : 0) | (out ? (int)(1u << 31) : 0);
             }
+        } else if constexpr (C::ISTFT) {  // tile g of entry b: frames f0 = g TILE .. of that entry, never beyond it
+            const long long b = tt / p.tiles_per_outer;
+            const int f0 = (int)(tt - b * p.tiles_per_outer) * C::TILE;
+            nv = p.stft_frames - f0 < C::TILE ? p.stft_frames - f0 : C::TILE;
+            base = (b * p.stft_frames + f0) * C::N;
+            obase = b;
+            fs_row = f0;
         } else {
             tile_geom<C>(p, tt, base, nv);
         }
@@ -1853,6 +1896,44 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             __syncthreads();
         } else if constexpr (C::ILV > 0) {
             ilv_store<C>(p, lds, base, nv * C::N, tid);
+            __syncthreads();
+        } else if constexpr (C::ISTFT) {
+            // conj(z) of the packed frames lies in LDS: real j of frame r is component j & 1 of element j >> 1 of row r
+            // (adjacent lanes read adjacent slots), its sign and the 1 / 2N part of ws
+            constexpr int NN = 2 * C::N;
+            const int hop = p.stft_hop, len = p.stft_len, cen = p.stft_center ? C::N : 0, f0 = fs_row;
+            const bool last = f0 + nv >= p.stft_frames, warm = t < run_begin;
+            const int span = (nv - 1) * hop + NN;                        // samples the tile's frames touch, from f0 hop on
+            const int done = last ? span : nv * hop;                     // finished here; the rest goes to the carry
+            const int ncarry = (f0 == 0 || t == t_first) ? 0 : NN - hop;  // partial sums waiting (a run starts from zero)
+            const int u0 = f0 * hop;                                      // (< 2^26, istft_check)
+            const T* ldr = (const T*)lds;
+            T* carry = (T*)(lds + C::ISTFT_OFF);
+            const T* ws = (const T*)p.stft_win;
+            const T* env = (const T*)p.istft_env;
+            T* outb = (T*)p.out + obase * len;
+            for (int i0 = 0; i0 < span; i0 += C::THREADS) {
+                const int i = i0 + tid;
+                T acc = (T)0;
+                if (i < span) {
+                    if (i < ncarry) acc = carry[i];
+                    int r_hi = i / hop;
+                    if (r_hi > nv - 1) r_hi = nv - 1;
+                    for (int r = i < NN ? 0 : (i - NN) / hop + 1; r <= r_hi; ++r) {
+                        const int j = i - r * hop;
+                        acc = fma_t(ws[j], ldr[2 * lds_index<C, C::NP - 1>(r, j >> 1) + (j & 1)], acc);
+                    }
+                }
+                if (!last) __syncthreads();  // (uniform) this chunk's carry reads before its carry writes
+                if (i < span) {
+                    if (i >= done) {
+                        carry[i - done] = acc;
+                    } else {
+                        const int u = u0 + i;
+                        if (!warm && u >= cen && u < cen + len) outb[u - cen] = acc * env[u];
+                    }
+                }
+            }
             __syncthreads();
         } else if constexpr (C::DCT == 3 && !C::COLS) {
             // conj(z) of the packed row z_j = v[2j] + i v[2j+1] lies in LDS, already scaled: x[2j] is slot j of v, x[2j+1]

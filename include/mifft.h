@@ -234,7 +234,7 @@ typedef enum {
  *   - a hop field without MIFFT_FLAG_STFT, or the flag with hop 0; a centre bit without the flag, or both centre bits;
  *   - MIFFT_FLAG_STFT with MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT, MIFFT_FLAG_DCT_ND,
  *     MIFFT_FLAG_DCT_ORTHO or a keep bit;
- *   - ndim != 2;  inverse != 0 (the inverse STFT is not routed);
+ *   - ndim != 2;  inverse != 0 (the inverse STFT is not routed through this bit: MIFFT_FLAG_ISTFT, below);
  *   - n outside the limits of the packed rows: odd, below 8, above 16384 (F64: 8192), n / 2 with a prime factor above 32, a
  *     row tile beyond 96 KiB of LDS;
  *   - T < n without a centre bit;  n / 2 > T - 1 with MIFFT_FLAG_STFT_CENTER_REFLECT (one reflection must reach);
@@ -247,6 +247,48 @@ typedef enum {
 #define MIFFT_FLAG_STFT_CENTER_ZEROS 128u    /* frames centred, zeros beyond both ends */
 #define MIFFT_FLAG_STFT_HOP(h) ((uint32_t)(h) << 16)   /* 1 .. 65535 */
 #define MIFFT_FLAG_STFT_HOP_MASK 0xFFFF0000u
+/* Inverse short-time Fourier transform with real output (torch.istft(..., onesided=True), the frames leading; no reference
+ * counterpart).  Its own mode bit: MIFFT_FLAG_STFT with inverse = 1 stays refused.  It reuses MIFFT_FLAG_STFT_HOP(hop) and
+ * the two centre bits -- either one means "centred: the first and last n / 2 samples are trimmed", both together are refused.
+ * ndim = 3, dims = {T, F, n}: T output samples per batch entry, F frames (F = 1 is allowed: for this mode only the "no
+ * dimension of size 1" rule skips dims[1]) of n points every `hop` samples, 1 <= hop <= n.  inverse = 1, in_components = 2,
+ * in_dtype == out_dtype in {F32, F64}:
+ *       x (batch, F, n / 2 + 1, 2)  ->  out (batch, T, 1),
+ *       out[b, t] = sum_f ws[j] y_f[j] / sum_f w[j]^2,    j = t + c - f * hop,  0 <= j < n,
+ * the sums over the frames that cover t; y_f is the n-point inverse real transform (with its 1 / n) of frame f, the imaginary
+ * parts of bins 0 and n / 2 ignored as by a half-spectrum inverse; c = n / 2 when centred, else 0; ws = gain * w.
+ * With L = n + hop * (F - 1), 2 <= T <= L - c (torch would zero-pad a longer output; this plan refuses it; T = 1 falls to
+ * the rule that no dimension but F is of size 1).
+ * ONE kernel launch, no scratch, no memset and no tensor of frames: the C2R row kernel of n points over TILE consecutive
+ * frames of one entry, whose store overlap-adds the frames in LDS, carries the unfinished samples in LDS to the next tile,
+ * divides by the envelope and writes every output sample exactly once with a plain store (kernel
+ * rows<n>[_f64]_c2r_<radices>_istft_jit: compiled at run time only).  Every sample is summed in ascending frame order, so the
+ * result of an entry is bit-identical for any batch, first / count and grid.
+ * `bases_flat` / `bases_len`, when given, have the plan's three entries:
+ *   - bases_len[0] is 0 (rectangular window, gain 1), 2 n (the binary64 words of w[0 .. n-1] as in an STFT plan) or 2 n + 2
+ *     (w, then one binary64 gain; torch's normalized=True is gain = sqrt(n); the gain does not enter the envelope);
+ *   - bases_len[1] is 0;  bases_len[2] is 0 (the default radix estimate for n) or the radices of n.
+ * The plan keeps ws[j] / n (rounded once from binary64; the 1 / n is folded into this table, not applied as the pass's scale)
+ * and 1 / sum w^2 at all L padded samples as device tables of its float type.
+ * mifft_plan_stages / mifft_plan_kernel_name report nothing / "none" for dims 0 and 1 and the n-point stages and the kernel
+ * for dim 2; mifft_plan_num_launches() is 1, mifft_plan_scratch_bytes() 0; mifft_plan_in_bytes() / _out_bytes() the two
+ * tensors; mifft_exec_batch(first, count) offsets both by whole entries; mifft_plan_pass_geometry(2, count) reports
+ * {TILE, threads, n_tiles = count * ceil(F / TILE), grid}: tiles never span entries, and workgroup w of the grid
+ * min(CUs * per_cu, max(1, n_tiles / istft_min_run)) (a constant of the library's mifft_config.h) owns the ascending run of tiles from w * len + min(w, rem) on
+ * (len = n_tiles / grid, rem = n_tiles % grid; one more tile for w < rem).  whole_batch behaves as for every other plan.
+ * Refused before any device work, the reason in mifft_last_error().  MIFFT_ERR_UNSUPPORTED:
+ *   - MIFFT_FLAG_ISTFT with MIFFT_FLAG_STFT, MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT,
+ *     MIFFT_FLAG_DCT_ND, MIFFT_FLAG_DCT_ORTHO or a keep bit;  inverse = 0;  ndim != 3;  both centre bits;
+ *   - hop 0, or hop > n (gaps between the frames: the envelope would be zero there);
+ *   - n outside the limits of the packed rows (as for MIFFT_FLAG_STFT), or a tile and carry beyond the CU's LDS;
+ *   - a window whose squared overlap-add falls below 1e-11 in absolute value at one of the samples t + c, 0 <= t < T
+ *     (torch's own NOLA threshold and range): the reason names the "overlap-add" condition;
+ *   - MIFFT_JIT=0 (no precompiled instances).
+ * MIFFT_ERR_BAD_DIM: T < 2 or T > L - c.  MIFFT_ERR_TOO_LARGE: L > 2^26 (the envelope table has L entries).
+ * MIFFT_ERR_BAD_COMPONENTS: in_components != 2.  MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_BASES: a
+ * bases_len[0] other than 0, 2 n or 2 n + 2, a non-zero bases_len[1], a window value or gain that is not finite (or radices
+ * that do not multiply to n). */
+#define MIFFT_FLAG_ISTFT 0x4000u
 
 typedef struct mifft_plan mifft_plan;
 

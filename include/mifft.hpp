@@ -145,6 +145,14 @@ static_assert(MIFFT_FLAG_STFT == 32u && MIFFT_FLAG_STFT_CENTER_REFLECT == 64u &&
                    (MIFFT_FLAG_KEEP_MASK | MIFFT_FLAG_DCT_ND | MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_HALF_SPECTRUM |
                     MIFFT_FLAG_FAITHFUL_STAGES)) == 0,
               "the STFT bits are their own");
+// MIFFT_FLAG_ISTFT (0x4000u) with MIFFT_FLAG_STFT_HOP(hop) and at most one centre bit plans the inverse, real output:
+// x (batch, F, n / 2 + 1, 2) -> out (batch, T, 1), dims = {T, F, n}; `bases` carries the window and a gain (include/mifft.h).
+// Created through mifft_plan_create itself, as the forward.
+static_assert(MIFFT_FLAG_ISTFT == 0x4000u &&
+                  (MIFFT_FLAG_ISTFT & (MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_CENTER_REFLECT | MIFFT_FLAG_STFT_CENTER_ZEROS |
+                                       MIFFT_FLAG_STFT_HOP_MASK | MIFFT_FLAG_KEEP_MASK | MIFFT_FLAG_DCT_ND | MIFFT_FLAG_DCT |
+                                       MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_HALF_SPECTRUM | MIFFT_FLAG_FAITHFUL_STAGES)) == 0,
+              "MIFFT_FLAG_ISTFT is its own bit");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
