@@ -43,6 +43,7 @@ FLAG_STFT_CENTER_REFLECT = 64  # MIFFT_FLAG_STFT_CENTER_REFLECT: frames centred,
 FLAG_STFT_CENTER_ZEROS = 128   # MIFFT_FLAG_STFT_CENTER_ZEROS: frames centred, zeros beyond both ends
 FLAG_STFT_HOP_MASK = 0xFFFF0000
 FLAG_ISTFT = 0x4000            # MIFFT_FLAG_ISTFT: overlap-added frames, (batch, F, n // 2 + 1, 2) -> (batch, T, 1); hop and centre bits shared
+FLAG_STFT_POWER = 0x8000       # MIFFT_FLAG_STFT_POWER: beside FLAG_STFT, real |X| ** power or its filterbanked bands instead of X
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -245,6 +246,50 @@ def _check_stft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> t
     return (T, n)
 
 
+def _spec_power(power) -> int:
+    """``power`` of a spectrogram plan: 1 (magnitude) or 2 (power)"""
+    if isinstance(power, bool) or not isinstance(power, (int, float)) or power not in (1, 2):
+        raise MifftError(ERR_UNSUPPORTED, f"power must be 1 (magnitude) or 2 (power), got {power!r}")
+    return int(power)
+
+
+def _fb_f64(fb, bins: Optional[int] = None) -> "torch.Tensor":
+    """a filterbank as a (bins, M) float64 matrix on the host (a CUDA tensor is copied, which synchronises its stream)"""
+    t = torch.as_tensor(fb)
+    if t.is_complex():
+        raise MifftError(-3, "the filterbank must be real")
+    t = t.detach().to(device="cpu", dtype=torch.float64).contiguous()
+    if t.dim() != 2 or t.shape[1] < 1 or (bins is not None and t.shape[0] != bins):
+        want = "n_fft // 2 + 1" if bins is None else str(bins)
+        raise MifftError(-2, f"the filterbank is {tuple(t.shape)}, expected ({want}, M): one row per bin, one column per band "
+                             f"(a librosa-style (M, bins) matrix must be transposed)")
+    return t
+
+
+def _f64_words(values) -> list:
+    """float64 values as they travel through ``bases`` (window_words, for long tables)"""
+    import numpy as np
+    a = torch.as_tensor(values).detach().to(device="cpu", dtype=torch.float64).contiguous().numpy()
+    return np.frombuffer(a.tobytes(), dtype="<u4").tolist()
+
+
+def _check_spec_layout(in_shape: tuple, out_shape: tuple, hop: int, center, fb) -> tuple:
+    """Layouts of a spectrogram plan (MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_POWER): x (batch, T, 1) real -> out
+    (batch, F, n // 2 + 1, 1) real, or (batch, F, M, 1) with a filterbank ``fb`` of shape (n // 2 + 1, M); returns the dims
+    (T, n)."""
+    if len(out_shape) != 4:
+        raise MifftError(-1, f"spectrogram layouts are (batch, T, 1) -> (batch, F, n // 2 + 1 or M, 1), got {in_shape} -> "
+                             f"{out_shape}")
+    if out_shape[-1] != 1:
+        raise MifftError(-3, f"a spectrogram plan writes real values (1 component), got {out_shape[-1]}")
+    bins = out_shape[2]
+    if fb is not None:
+        bins = int(fb.shape[0])
+        if out_shape[2] != fb.shape[1]:
+            raise MifftError(-2, f"a filterbank of {tuple(fb.shape)} makes {fb.shape[1]} bands, out has {out_shape[2]}")
+    return _check_stft_layout(in_shape, out_shape[:2] + (bins, 2), hop, center)
+
+
 def istft_length(frames: int, n_fft: int, hop_length: int, center=False) -> int:
     """Samples torch.istft returns by default for ``frames`` frames: n_fft + hop_length * (frames - 1), less n_fft // 2 at both
     ends when centred.  Pure host arithmetic."""
@@ -354,6 +399,10 @@ class Plan:
     out (batch, F, n // 2 + 1, 2), frames of n samples every ``stft_hop``; ``stft_center`` None / "reflect" / "constant";
     ``stft_window`` None (rectangular) or n values, taken by value (MIFFT_FLAG_STFT in include/mifft.h, _check_stft_layout,
     plan_stft).  ``bases`` of such a plan has two lists, an empty one and the radices of n (or an empty one: the default).
+    ``stft_power`` 1 or 2 beside ``stft_hop`` (no reference counterpart): the same plan stores abs(X) ** stft_power, real,
+    out (batch, F, n // 2 + 1, 1) -- or, with ``stft_fb`` of shape (n // 2 + 1, M), taken by value as float64, the M bands
+    fb.T @ abs(X) ** stft_power per frame, out (batch, F, M, 1), n taken from the filterbank's rows (MIFFT_FLAG_STFT_POWER in
+    include/mifft.h, _check_spec_layout, plan_spectrogram).  None: the complex STFT plan.
     ``istft_hop`` > 0 (no reference counterpart): the inverse, x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real,
     ``inverse=True`` implied; ``stft_center`` None / False or True / "reflect" / "constant" (centred: n // 2 samples trimmed
     at both ends), ``stft_window`` as above, ``istft_gain`` a factor on the synthesis window that stays out of the envelope
@@ -363,7 +412,7 @@ class Plan:
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
-                 istft_hop: int = 0, istft_gain: float = 1.0):
+                 istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         stft = int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT)
         istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
@@ -391,11 +440,23 @@ class Plan:
                 stft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
                 stft_center = {0: None, FLAG_STFT_CENTER_REFLECT: "reflect", FLAG_STFT_CENTER_ZEROS: "constant"}.get(
                     int(flags) & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), stft_center)
-            stft_dims = _check_stft_layout(in_shape, out_shape, stft_hop, stft_center)
+            if stft_power is None:
+                if stft_fb is not None:
+                    raise MifftError(ERR_UNSUPPORTED, "stft_fb without stft_power: a filterbank applies to abs(X) ** power")
+                stft_dims = _check_stft_layout(in_shape, out_shape, stft_hop, stft_center)
+            else:
+                power = _spec_power(stft_power)
+                fbm = None if stft_fb is None else _fb_f64(stft_fb)
+                stft_dims = _check_spec_layout(in_shape, out_shape, stft_hop, stft_center, fbm)
             if axes is not None:
                 raise MifftError(ERR_UNSUPPORTED, "an STFT plan frames dim 0 and transforms dim 1: no axes")
             if stft_window is not None:
                 words = window_words(_window_f64(stft_window, stft_dims[1]))
+            if stft_power is not None:  # (the window written out, the power, the filterbank row by row)
+                words = (words or _f64_words(torch.ones(stft_dims[1], dtype=torch.float64))) + _f64_words([float(power)])
+                if fbm is not None:
+                    words = words + _f64_words(fbm)
+                flags = int(flags) | FLAG_STFT_POWER
             flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(stft_hop) | _stft_center_flags(stft_center) |
                      (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0))
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
@@ -433,6 +494,7 @@ class Plan:
         self.dctn = dctn
         self.stft = stft
         self.istft = istft
+        self.spectrogram = stft and stft_power is not None
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
@@ -592,6 +654,41 @@ def plan_stft(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, wi
         ctx = DeviceContext()
     return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, stft_hop=hop_length,
                 stft_center=center, stft_window=window)
+
+
+def plan_spectrogram(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, window=None, center=None,
+                     power=2.0, fb=None, ctx: Optional[DeviceContext] = None, whole_batch: int = 0) -> Plan:
+    """Plan of the magnitude (``power=1``) or power (``power=2``) spectrogram of ``batch`` real signals of ``length`` samples
+    (no reference counterpart; MIFFT_FLAG_STFT_POWER in include/mifft.h): plan_stft's frames, window and ``center``, but the
+    one kernel stores abs(X) ** power as reals -- out_shape (batch, F, n_fft // 2 + 1, 1) -- or, with a filterbank ``fb`` of
+    shape (n_fft // 2 + 1, M) (any real tensor or array, taken by value as float64; the orientation of
+    torchaudio.functional.melscale_fbanks -- a librosa-style (M, n_fft // 2 + 1) matrix must be transposed by the caller), the
+    M bands fb.T @ abs(X) ** power of every frame, out_shape (batch, F, M, 1).  The complex spectrogram is never written.  The
+    filterbank is applied band by band over the span of each column's non-zero rows, so its cost follows the spans: a dense
+    matrix is correct but slow.  No log / dB stage and no mel-filter generator.  Runs through ``fft(out, x, plan=plan)``,
+    ``first=`` / ``count=`` included; a frame's result is bit-identical for any batch and slab.  Every argument error is raised
+    before any device work: ``power`` other than 1 or 2 is -15, a filterbank of another shape -2."""
+    batch, length, n_fft, hop_length = int(batch), int(length), int(n_fft), int(hop_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"a spectrogram plan reads and writes float32 or float64, got {dtype}")
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    if power is None:
+        raise MifftError(ERR_UNSUPPORTED, "power=None is the complex STFT: use plan_stft")
+    power = _spec_power(power)
+    FLAG_STFT_HOP(hop_length)
+    frames = stft_frames(length, n_fft, hop_length, _stft_center_flags(center) != 0)
+    if fb is not None:
+        fb = _fb_f64(fb, n_fft // 2 + 1)
+    in_shape = (batch, length, 1)
+    out_shape = (batch, frames, n_fft // 2 + 1 if fb is None else int(fb.shape[1]), 1)
+    _check_spec_layout(in_shape, out_shape, hop_length, center, fb)
+    if window is not None:
+        window = _window_f64(window, n_fft)
+    if ctx is None:
+        ctx = DeviceContext()
+    return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, stft_hop=hop_length,
+                stft_center=center, stft_window=window, stft_power=power, stft_fb=fb)
 
 
 def plan_istft(dtype, batch: int, frames: int, n_fft: int, hop_length: int, *, window=None, center=False,
@@ -1100,26 +1197,33 @@ def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_le
     Plans are cached per (shape, dtype, n_fft, hop, centring, device, stream) AND the window's contents: every call hashes the
     window's float64 values, so a window changed in place never meets a stale plan.  For a CUDA ``window`` that is one small
     synchronising device-to-host copy per call: loops should make the plan once with ``plan_stft`` and call ``fft``."""
+    return _stft_run("stft", x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype,
+                     None, None)
+
+
+def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype, power,
+              fb) -> "torch.Tensor":
+    """stft (``power`` None) and spectrogram (``power`` 1 or 2, ``fb`` None or a (n_fft // 2 + 1, M) float64 host matrix)"""
     if not onesided:
-        raise MifftError(ERR_UNSUPPORTED, "stft: onesided=False is not supported")
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: onesided=False is not supported")
     if pad_mode not in ("reflect", "constant"):
-        raise MifftError(ERR_UNSUPPORTED, f"stft: pad_mode must be \"reflect\" or \"constant\", got {pad_mode!r}")
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: pad_mode must be \"reflect\" or \"constant\", got {pad_mode!r}")
     if x.is_complex():
-        raise MifftError(-3, "stft expects a real tensor")
+        raise MifftError(-3, f"{who} expects a real tensor")
     if x.dim() < 1:
-        raise MifftError(-1, "stft expects a tensor of rank 1 or more: (T,) or (..., T)")
+        raise MifftError(-1, f"{who} expects a tensor of rank 1 or more: (T,) or (..., T)")
     n_fft = int(n_fft)
     if n_fft % 2 or n_fft < 8:
-        raise MifftError(ERR_UNSUPPORTED, f"stft with an odd n_fft or one below 8 ({n_fft}) is not supported")
+        raise MifftError(ERR_UNSUPPORTED, f"{who} with an odd n_fft or one below 8 ({n_fft}) is not supported")
     hop_length = n_fft // 4 if hop_length is None else int(hop_length)
     FLAG_STFT_HOP(hop_length)
     win_length = n_fft if win_length is None else int(win_length)
     if not 0 < win_length <= n_fft:
-        raise MifftError(-2, f"stft: 0 < win_length <= n_fft, got win_length = {win_length}, n_fft = {n_fft}")
+        raise MifftError(-2, f"{who}: 0 < win_length <= n_fft, got win_length = {win_length}, n_fft = {n_fft}")
     if out_dtype is None:
         out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
     if out_dtype not in _OUT_DTYPES:
-        raise MifftError(-4, f"stft: out_dtype must be float32 or float64, got {out_dtype}")
+        raise MifftError(-4, f"{who}: out_dtype must be float32 or float64, got {out_dtype}")
     mode = (pad_mode if center else None)
     logical = tuple(x.shape)
     T = logical[-1]
@@ -1127,8 +1231,12 @@ def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_le
     for m in logical[:-1]:
         batch *= m
     frames = stft_frames(T, n_fft, hop_length, bool(center))
-    in_shape, out_shape = (batch, T, 1), (batch, frames, n_fft // 2 + 1, 2)
-    _check_stft_layout(in_shape, out_shape, hop_length, mode)
+    bins = n_fft // 2 + 1
+    if fb is not None:
+        fb = _fb_f64(fb, bins)
+    width = bins if fb is None else int(fb.shape[1])
+    in_shape, out_shape = (batch, T, 1), (batch, frames, width, 2 if power is None else 1)
+    _check_stft_layout(in_shape, (batch, frames, bins, 2), hop_length, mode)
     w = None
     if window is not None or win_length < n_fft or normalized:
         if window is None:
@@ -1149,15 +1257,43 @@ def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_le
     with _PLAN_CACHE_LOCK:
         key = ("stft", out_dtype, in_shape, n_fft, hop_length, mode, digest, device,
                int(torch.cuda.current_stream(device).cuda_stream))
+        if power is not None:  # (the stft key as it has always been, then what the spectrogram adds)
+            key += (power, None if fb is None else (tuple(fb.shape), hashlib.sha1(fb.numpy().tobytes()).digest()))
         plan = _PLAN_CACHE.get(key)
         if plan is None:
             plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, stft_hop=hop_length, stft_center=mode,
-                        stft_window=w)
+                        stft_window=w, stft_power=power, stft_fb=fb)
             _plan_cache_insert(key, plan)
         else:
             _PLAN_CACHE.move_to_end(key)
         fft(out, xr, DeviceContext(device), plan=plan)
+    if power is not None:
+        return out.reshape(logical[:-1] + (frames, width)).transpose(-1, -2)
     return torch.view_as_complex(out).reshape(logical[:-1] + (frames, n_fft // 2 + 1)).transpose(-1, -2)
+
+
+def spectrogram(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None,
+                window=None, center: bool = True, pad_mode: str = "reflect", normalized: bool = False, power=2.0, *,
+                fb=None, out_dtype=None, onesided: bool = True) -> "torch.Tensor":
+    """torch.stft(x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided=True,
+    return_complex=True).abs().pow(power) of a real ``x`` of shape (T,) or (..., T), ``power`` 1 (magnitude) or 2 (power), in one
+    kernel launch that never writes the complex spectrogram; every argument it shares with ``stft`` means what it means
+    there.  ``normalized=True`` is torch.stft's, a factor n_fft ** -0.5 on X -- not torchaudio's window normalisation.
+    ``fb``: a filterbank of shape (n_fft // 2 + 1, M), any real tensor or array on any device, taken by value as float64 like
+    the window; the result is then (fb.T @ .) along the frequency dim, M bands per frame.  That is the orientation of
+    torchaudio.functional.melscale_fbanks; a librosa-style (M, n_fft // 2 + 1) matrix must be transposed by the caller.  The
+    bands are summed over the span of each column's non-zero rows: a dense matrix is correct but slow.  There is no log / dB
+    stage and no mel-filter generator here: the filterbanked output is small, an elementwise pass over it is cheap.
+    Returns real (..., n_fft // 2 + 1 or M, F) as a TRANSPOSED VIEW (``stride(-2) == 1``) of the frames-major tensor the kernel
+    writes, exactly as ``stft`` does.  ``power`` other than 1 or 2 is MifftError -15; so is ``power=None``: the complex
+    spectrogram is ``stft``.  A filterbank of another shape is -2.  Plans are cached as those of ``stft``, the key extended by
+    the power and a digest of the filterbank's values, so a filterbank changed in place never meets a stale plan; loops should
+    make the plan once with ``plan_spectrogram`` and call ``fft``."""
+    if power is None:
+        raise MifftError(ERR_UNSUPPORTED, "spectrogram: power=None is the complex spectrogram: use stft")
+    power = _spec_power(power)
+    return _stft_run("spectrogram", x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided,
+                     out_dtype, power, fb)
 
 
 def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None, window=None,

@@ -35,6 +35,7 @@ size_t Plan::in_row_bytes() const {
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
+    if (stft() && spec_power) return (size_t)(stft_frames() * stft_out_width()) * dtype_size(out_dtype);
     if (stft()) return (size_t)prod_half * out_elem_bytes();
     if (istft()) return (size_t)dims[0] * dtype_size(out_dtype);
     if (dct_any()) return (size_t)prod * dtype_size(out_dtype);
@@ -248,7 +249,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
             return rc == MIFFT_ERR_HIP ? rc : set_error(rc, why);
         };
         std::string why;
-        std::vector<double> window;
+        std::vector<double> window, fb;
         std::vector<uint64_t> user;
         double gain = 1.0;
         int rc = fwd ? stft_check(p, why) : istft_check(p, bases_flat, bases_len, window, gain, user, why);
@@ -258,7 +259,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         p.prod = frames * n;  // (the rows the one pass transforms)
         p.prod_half = frames * (n / 2 + 1);
         if (fwd) {
-            rc = stft_unpack_bases(n, bases_flat, bases_len, window, user, why);
+            rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, user, why);
             if (rc) return fail(rc, why);
         }
         if (user.empty()) user = plan_estimate_bases((uint64_t)n, /*gpu_target=*/true);
@@ -278,7 +279,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) p.num_cus = prop.multiProcessorCount;
         config_refresh();
-        rc = fwd ? build_stft(p, ordered[td], processed[td], window, why)
+        rc = fwd ? build_stft(p, ordered[td], processed[td], window, fb, why)
                  : build_istft(p, ordered[td], processed[td], window, gain, why);
         if (rc) return fail(rc, why);
         *out_plan = h;

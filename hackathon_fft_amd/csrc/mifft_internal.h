@@ -169,6 +169,12 @@ struct Plan {
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
     int64_t stft_frames() const { return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop(); }
+    // MIFFT_FLAG_STFT_POWER on such a plan: out is real, (batch, F, n / 2 + 1, 1) of |X|^spec_power (1 or 2), or
+    // (batch, F, spec_bands, 1) after a filterbank of spec_bands > 0 bands; stft_out_width() reals per frame.  0: the flag is
+    // not set.  Filled by stft_unpack_bases.
+    int spec_power = 0;
+    int64_t spec_bands = 0;
+    int64_t stft_out_width() const { return spec_bands > 0 ? spec_bands : dims[1] / 2 + 1; }
     // MIFFT_FLAG_ISTFT: dims = {T, F, n}; x is (batch, F, n / 2 + 1, 2), out (batch, T, 1) real: F frames of n samples every
     // stft_hop() overlap-added over istft_padded_len() samples, of which T from istft_trim() on are stored
     bool istft() const { return (flags & MIFFT_FLAG_ISTFT) != 0; }
@@ -301,11 +307,16 @@ bool select_jit_stft_rows(const Plan& plan, DimPass& pass, std::string& why_not)
 int stft_flag_check(uint32_t flags, std::string& why);
 int stft_check(const Plan& plan, std::string& why);
 // the window of such a plan from bases_flat / bases_len (2 n words: the binary64 bits of w[0 .. n-1], low word first; none:
-// rectangular, `window` left empty) and the user radices of the n-point transform (none: `radices` left empty)
-int stft_unpack_bases(int64_t n, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                      std::vector<uint64_t>& radices, std::string& why);
+// rectangular, `window` left empty) and the user radices of the n-point transform (none: `radices` left empty).  With
+// MIFFT_FLAG_STFT_POWER also the power and the filterbank (row-major (n / 2 + 1, M); M = 0: `fb` left empty), which set
+// plan.spec_power and plan.spec_bands.
+int stft_unpack_bases(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+                      std::vector<double>& fb, std::vector<uint64_t>& radices, std::string& why);
 int build_stft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, std::string& why);
+               const std::vector<double>& window, const std::vector<double>& fb, std::string& why);
+// the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
+// count of ints, then the weights in the plan's float type
+inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }
 // plans with MIFFT_FLAG_ISTFT (istft.cpp), in the same manner: istft_check needs no device and leaves the window (empty:
 // rectangular), the gain and the user radices in its outputs; it refuses a window whose squared overlap-add is zero
 // somewhere in the samples the plan stores.  select_jit_istft_rows is the C2R kernel with TileCfg::ISTFT (run time only),

@@ -5,6 +5,11 @@
 // the ends of a centred plan, and multiplies it by the window (tile_kernel.h).  x is (batch, T, 1) real, out
 // (batch, F, n / 2 + 1, 2); the window travels through `bases` as host data and lives in the plan as a device table of the
 // plan's float type.
+//
+// With MIFFT_FLAG_STFT_POWER the same launch stores |X| or |X|^2 as reals (TileCfg::SPEC), (batch, F, n / 2 + 1, 1), or the
+// product of that with a filterbank (TileCfg::FB), (batch, F, M, 1): `bases` then carries the window, the power and the
+// (n / 2 + 1, M) matrix, which is banded here -- per column the span from its first to its last non-zero row -- and lives in
+// the plan as one device table.
 #include <cmath>
 #include <cstring>
 
@@ -15,6 +20,11 @@ namespace mifft {
 
 // the STFT bits of a plan with neither mode bit (MIFFT_FLAG_STFT, MIFFT_FLAG_ISTFT)
 int stft_flag_check(uint32_t flags, std::string& why) {
+    if ((flags & MIFFT_FLAG_STFT_POWER) && !(flags & MIFFT_FLAG_STFT)) {
+        why = (flags & MIFFT_FLAG_ISTFT) ? "MIFFT_FLAG_STFT_POWER with MIFFT_FLAG_ISTFT: a magnitude or power spectrogram has no inverse"
+                                         : "MIFFT_FLAG_STFT_POWER without MIFFT_FLAG_STFT";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
     if (flags & (MIFFT_FLAG_STFT | MIFFT_FLAG_ISTFT)) return MIFFT_OK;
     if (flags & MIFFT_FLAG_STFT_HOP_MASK) {
         why = "a hop (MIFFT_FLAG_STFT_HOP) without MIFFT_FLAG_STFT";
@@ -104,15 +114,43 @@ int stft_check(const Plan& p, std::string& why) {
     return MIFFT_OK;
 }
 
-int stft_unpack_bases(int64_t n, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                      std::vector<uint64_t>& radices, std::string& why) {
+static double word_pair(const uint32_t* w) {
+    const uint64_t bits = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    double v;
+    memcpy(&v, &bits, sizeof v);
+    return v;
+}
+
+int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+                      std::vector<double>& fb, std::vector<uint64_t>& radices, std::string& why) {
+    const int64_t n = p.dims[1], K = n / 2 + 1;
+    const bool spec = (p.flags & MIFFT_FLAG_STFT_POWER) != 0;
     window.clear();
+    fb.clear();
     radices.clear();
-    if (!bases_flat || !bases_len) return MIFFT_OK;
-    if (bases_len[0] != 0 && (int64_t)bases_len[0] != 2 * n) {
-        why = "bases_len[0] of an STFT plan is 0 (rectangular window) or 2 n = " + std::to_string(2 * n) +
-              " words of window, not " + std::to_string(bases_len[0]);
-        return MIFFT_ERR_BAD_BASES;
+    p.spec_power = 0;
+    p.spec_bands = 0;
+    if (spec) {  // the window written out, the power, and M columns of K weights: 2 n + 2 + 2 M K words
+        const int64_t len0 = bases_len ? (int64_t)bases_len[0] : 0, rest = len0 - 2 * n - 2;
+        if (!bases_flat || !bases_len || rest < 0 || rest % (2 * K) != 0) {
+            why = "bases_len[0] of a plan with MIFFT_FLAG_STFT_POWER is 2 n + 2 + 2 M K = " + std::to_string(2 * n + 2) + " + " +
+                  std::to_string(2 * K) + " M words (the window, the power, an (n / 2 + 1, M) filterbank; M >= 0), not " +
+                  (bases_len ? std::to_string(bases_len[0]) : std::string("absent (bases is NULL)"));
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (rest / (2 * K) > MIFFT_STFT_MAX_BANDS) {
+            why = "a filterbank of " + std::to_string(rest / (2 * K)) + " bands: at most MIFFT_STFT_MAX_BANDS = " +
+                  std::to_string(MIFFT_STFT_MAX_BANDS);
+            return MIFFT_ERR_TOO_LARGE;
+        }
+        p.spec_bands = rest / (2 * K);
+    } else {
+        if (!bases_flat || !bases_len) return MIFFT_OK;
+        if (bases_len[0] != 0 && (int64_t)bases_len[0] != 2 * n) {
+            why = "bases_len[0] of an STFT plan is 0 (rectangular window) or 2 n = " + std::to_string(2 * n) +
+                  " words of window, not " + std::to_string(bases_len[0]);
+            return MIFFT_ERR_BAD_BASES;
+        }
     }
     if (bases_len[1] < 0) {
         why = "negative bases_len";
@@ -121,14 +159,30 @@ int stft_unpack_bases(int64_t n, const uint32_t* bases_flat, const int32_t* base
     if (bases_len[0]) {
         window.resize((size_t)n);
         for (int64_t j = 0; j < n; ++j) {
-            const uint64_t bits = (uint64_t)bases_flat[2 * j] | ((uint64_t)bases_flat[2 * j + 1] << 32);
-            double v;
-            memcpy(&v, &bits, sizeof v);
+            const double v = word_pair(bases_flat + 2 * j);
             if (!std::isfinite(v)) {
                 why = "window value " + std::to_string(j) + " is not finite";
                 return MIFFT_ERR_BAD_BASES;
             }
             window[(size_t)j] = v;
+        }
+    }
+    if (spec) {
+        const double power = word_pair(bases_flat + 2 * n);
+        if (!(power == 1.0 || power == 2.0)) {  // (NaN included)
+            why = "the power of a plan with MIFFT_FLAG_STFT_POWER is 1 (magnitude) or 2 (power), not " + std::to_string(power);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        p.spec_power = (int)power;
+        fb.resize((size_t)(K * p.spec_bands));
+        for (size_t i = 0; i < fb.size(); ++i) {
+            const double v = word_pair(bases_flat + 2 * n + 2 + 2 * i);
+            if (!std::isfinite(v)) {
+                why = "filterbank weight (" + std::to_string(i / (size_t)p.spec_bands) + ", " +
+                      std::to_string(i % (size_t)p.spec_bands) + ") is not finite";
+                return MIFFT_ERR_BAD_BASES;
+            }
+            fb[i] = v;
         }
     }
     for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
@@ -145,9 +199,36 @@ static hipError_t upload_window_t(int64_t n, const std::vector<double>& window, 
     return e;
 }
 
+// the (K, M) filterbank as bands: per column lo = its first non-zero row and len = its last non-zero row - lo + 1 (zeros in
+// between stay inside the span; a column of zeros has len 0), off = where its len weights start.  One device table: lo[M],
+// len[M], off[M] (int32, padded to an even count), then the weights, rounded once to T.
+template <typename T>
+static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>& fb, void** d_table) {
+    std::vector<int32_t> head((size_t)spec_table_ints(M), 0);
+    std::vector<T> wt;
+    for (int64_t m = 0; m < M; ++m) {
+        int64_t lo = 0, hi = -1;
+        for (int64_t k = 0; k < K; ++k)
+            if (fb[(size_t)(k * M + m)] != 0.0) {
+                if (hi < 0) lo = k;
+                hi = k;
+            }
+        const int64_t len = hi < 0 ? 0 : hi - lo + 1;
+        head[(size_t)m] = (int32_t)lo;
+        head[(size_t)(M + m)] = (int32_t)len;
+        head[(size_t)(2 * M + m)] = (int32_t)wt.size();  // (<= M K < 2^30: bases_len is an int32 of 2 M K words and more)
+        for (int64_t j = 0; j < len; ++j) wt.push_back((T)fb[(size_t)((lo + j) * M + m)]);
+    }
+    const size_t hb = head.size() * sizeof(int32_t), wb = wt.size() * sizeof(T);
+    hipError_t e = hipMalloc(d_table, hb + (wb ? wb : sizeof(T)));
+    if (e == hipSuccess) e = hipMemcpy(*d_table, head.data(), hb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && wb) e = hipMemcpy((char*)*d_table + hb, wt.data(), wb, hipMemcpyHostToDevice);
+    return e;
+}
+
 // the one pass: dim 1 (n points) over the F frames of every batch entry
 int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, std::string& why) {
+               const std::vector<double>& window, const std::vector<double>& fb, std::string& why) {
     const int64_t n = p.dims[1];
     DimPass ps;
     ps.dim_index = 1;
@@ -164,6 +245,9 @@ int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
     if (e == hipSuccess)
         e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(n, window, &ps.d_aux2) : upload_window_t<float>(n, window, &ps.d_aux2);
+    if (e == hipSuccess && p.spec_bands > 0)
+        e = p.out_dtype == MIFFT_F64 ? upload_bands_t<double>(n / 2 + 1, p.spec_bands, fb, &ps.d_aux3)
+                                     : upload_bands_t<float>(n / 2 + 1, p.spec_bands, fb, &ps.d_aux3);
     p.passes.push_back(ps);
     if (e != hipSuccess) return hip_error(e, "STFT table upload");
     return MIFFT_OK;

@@ -114,6 +114,19 @@ MIFFT_DEV void gstore(cpx<T>* p, cpx<T> v) {
     }
 }
 
+// one real at an address aligned to one element (the rows of a TileCfg::SPEC store are N + 1 reals wide)
+template <bool NT, typename T>
+MIFFT_DEV void gstore_real(T* p, T v) {
+    if constexpr (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
+// the correctly rounded square root (sqrtf / sqrt without a header: this file is also compiled by hipRTC)
+MIFFT_DEV float sqrt_t(float v) { return __builtin_sqrtf(v); }
+MIFFT_DEV double sqrt_t(double v) { return __builtin_sqrt(v); }
+
 template <class A, class B> struct same_t { static constexpr bool value = false; };
 template <class A> struct same_t<A, A> { static constexpr bool value = true; };
 
@@ -193,6 +206,14 @@ struct TileParams {
     // stft_win (the synthesis table, below); tiles_per_outer is the tiles of ONE entry, ceil(F / TILE), and istft_env the
     // reciprocal envelope 1 / sum w^2 at every padded sample 0 .. 2 N + hop (F - 1) - 1, type T
     const void* istft_env;
+    // SPEC configurations with a filterbank (TileCfg::FB): band m < spec_bands is sum_j spec_wt[spec_off[m] + j] *
+    // P[spec_lo[m] + j], j < spec_len[m] (spec_lo[m] + spec_len[m] <= N + 1; weights of type T).  Without one the four
+    // pointers are null and spec_bands is 0.
+    const void* spec_wt;
+    const int* spec_lo;
+    const int* spec_len;
+    const int* spec_off;
+    int spec_bands;
 };
 
 MIFFT_DEV long long tile_id(const TileParams& p, long long t) { return p.reverse ? p.n_tiles - 1 - t : t; }
@@ -280,7 +301,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
-          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false>
+          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -474,6 +495,24 @@ struct TileCfg {
     // stores suppressed (tile_kernel), so every sample is summed in ascending frame order from an exact zero whatever the
     // partition, and the result of an entry does not depend on the grid.  Every output sample is written exactly once, with
     // a plain store; nothing outside [0, T) of an entry of the launch is touched.
+    // SPEC (spectrogram: |X| or |X|^2 of an STFT tile, 1 magnitude, 2 power): only the store differs.  The work item of the
+    // pair (k, N - k) holds a = X[k] and b = X[N-k]; instead of two complex bins it writes two reals, a.x^2 + a.y^2 (one
+    // product and one fma) or its sqrt, into a row of N + 1 reals per frame -- half the bytes, and the complex spectrogram
+    // never exists.  Rows of N + 1 reals start at any element, so the stores are aligned to one element.
+    // FB (with SPEC): a banded filterbank of spec_bands bands follows in the same launch.  The pair's work item leaves its
+    // two reals IN PLACE -- P[k] in .x of slot k for k < N, P[N] in .y of slot 0; it is the only reader of those slots, so
+    // no LDS is added and every length that plans as an STFT plans here -- and stores nothing.  After a barrier one work
+    // item per (row c < nv, band m), m fastest, sums spec_wt[off[m] + j] * P[c][lo[m] + j] over ascending j, one fma per
+    // term from an exact zero, and stores out[(row0 + c) * spec_bands + m]: a row's stores are contiguous, a band without
+    // bins stores an exact 0, rows c >= nv store nothing.  The order of summation is fixed per frame, so a frame's result
+    // does not depend on batch, slab or grid.  The band tables are read from global memory (TileParams::spec_*): a few
+    // hundred bytes that every workgroup re-reads, resident in L2 and the vector L1 after the first tile, whereas a copy
+    // in LDS would not fit beside the longest rows, which fill it.  The cost is proportional to the spans of the bands: a
+    // dense matrix is correct but slow (no MFMA: a mel filter spans a handful of bins).
+    static constexpr int SPEC = SPEC_;
+    static constexpr bool FB = FB_;
+    static_assert(SPEC_ >= 0 && SPEC_ <= 2 && (SPEC_ == 0 || STFT_) && (!FB_ || SPEC_ != 0),
+                  "SPEC: the magnitude / power store of an STFT tile; FB: its filterbank");
     static constexpr bool ISTFT = ISTFT_;
     static_assert(!ISTFT_ || (C2R_ && !LAST_DIRECT_ && DCT_ == 0 && !STFT_ && ROWPAD_ == 0),
                   "ISTFT: folded rows whose last pass stays in LDS for the overlap-add");
@@ -1883,6 +1922,27 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     }
                     continue;
                 }
+                if constexpr (C::SPEC != 0) {
+                    // |a|^2 and |b|^2, or their square roots: bins k and N - k of the frame (k = 0: bins 0 and N; 2 k = N: one bin)
+                    T pa = fma_t(a.y, a.y, a.x * a.x), pb = fma_t(b.y, b.y, b.x * b.x);
+                    if constexpr (C::SPEC == 1) {
+                        pa = sqrt_t(pa);
+                        pb = sqrt_t(pb);
+                    }
+                    if constexpr (C::FB) {  // in place: this work item is the only reader of slots k and m
+                        if (k == 0) {
+                            lds[lds_index<C, C::NP - 1>(c, 0)] = {pa, pb};
+                        } else {
+                            lds[lds_index<C, C::NP - 1>(c, k)].x = pa;
+                            if (2 * k != C::N) lds[lds_index<C, C::NP - 1>(c, m)].x = pb;
+                        }
+                    } else {
+                        T* row = (T*)p.out + (row0 + c) * (C::N + 1);
+                        gstore_real<(C::NT & 2) != 0>(row + k, pa);
+                        if (2 * k != C::N) gstore_real<(C::NT & 2) != 0>(row + C::N - k, pb);
+                    }
+                    continue;
+                }
                 if (p.inverse) {  // the inverse of a real row: conj(X) / 2N
                     a.x *= (T)p.scale;
                     a.y *= -(T)p.scale;
@@ -1892,6 +1952,25 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 V* row = gout + (row0 + c) * p.half_pitch;
                 gstore<(C::NT & 2) != 0>(row + k, a);
                 if (2 * k != C::N) gstore<(C::NT & 2) != 0>(row + C::N - k, b);
+            }
+            if constexpr (C::FB) {
+                // P of the tile's frames lies in LDS: one work item per (row, band), the bands of a row over adjacent lanes
+                __syncthreads();
+                const int M = p.spec_bands;
+                const T* wt = (const T*)p.spec_wt;
+                T* orow = (T*)p.out + row0 * M;
+                for (int f = tid; f < nv * M; f += C::THREADS) {
+                    const int c = f / M, mb = f - c * M;
+                    const int lo = p.spec_lo[mb], len = p.spec_len[mb];
+                    const T* wb = wt + p.spec_off[mb];
+                    T acc = (T)0;
+                    for (int j = 0; j < len; ++j) {
+                        const int bin = lo + j;  // (<= N: bin N is the .y of slot 0)
+                        const V s = lds[lds_index<C, C::NP - 1>(c, bin == C::N ? 0 : bin)];
+                        acc = fma_t(wb[j], bin == C::N ? s.y : s.x, acc);
+                    }
+                    gstore_real<(C::NT & 2) != 0>(orow + f, acc);
+                }
             }
             __syncthreads();
         } else if constexpr (C::ILV > 0) {

@@ -289,6 +289,35 @@ typedef enum {
  * bases_len[0] other than 0, 2 n or 2 n + 2, a non-zero bases_len[1], a window value or gain that is not finite (or radices
  * that do not multiply to n). */
 #define MIFFT_FLAG_ISTFT 0x4000u
+/* Magnitude, power or filterbanked (mel) spectrogram: a modifier of MIFFT_FLAG_STFT (torch.stft(...).abs().pow(power), then
+ * fb.T @ . along the frequencies; no reference counterpart).  dims, hop, centre bits, dtype rules and every refusal of an
+ * STFT plan are unchanged; the output is REAL,
+ *       x (batch, T, 1)  ->  out (batch, F, n / 2 + 1, 1),    out[b, f, k] = |X[b, f, k]|^power          (M = 0)
+ *       x (batch, T, 1)  ->  out (batch, F, M, 1),            out[b, f, m] = sum_k fb[k, m] |X[b, f, k]|^power   (M > 0)
+ * with X the bins of the STFT plan above, K = n / 2 + 1.  The modulus (power 1: a correctly rounded sqrt of re^2 + im^2; the
+ * squares are not rescaled as hypot would) and the filterbank are folded into the store of the STFT plan's one kernel (kernel
+ * rows<n>[_f64]_r2c_<radices>_stft_p<power>[_fb]_jit): the complex spectrogram is never written, no second launch, no scratch.
+ * `bases_flat` / `bases_len` must be given, with the plan's two entries:
+ *   - bases_len[0] is 2 n + 2 + 2 M K for an integer M >= 0, all values as IEEE binary64 in two 32-bit words, low word first,
+ *     in this order: the window w[0 .. n-1] (a rectangular one is written out as ones); one `power`, exactly 1.0 or 2.0; if
+ *     M > 0 the filterbank, row-major (K, M) -- the orientation of torchaudio.functional.melscale_fbanks; a librosa-style
+ *     (M, K) matrix is transposed by the caller.  Host data, taken by value;
+ *   - bases_len[1] as in an STFT plan.
+ * The library bands the matrix: of column m it keeps the rows lo = its first non-zero row .. its last non-zero row (zeros in
+ * between stay inside the span; a column of zeros keeps nothing and yields an exact 0), the weights rounded once to the plan's
+ * float type.  out[b, f, m] is summed over the kept rows in ascending k, one fused multiply-add per term from an exact zero,
+ * so a frame's result is bit-identical for any batch, first / count and grid.  The cost of the filterbank is proportional to
+ * the sum of the spans: a dense matrix is correct but slow (there is no matrix-core path; a mel filter spans a handful of
+ * bins).  Weights may be of either sign.  No log / dB stage and no mel-filter generator: out of scope.
+ * mifft_plan_out_bytes() is batch * F * (M ? M : K) elements; mifft_exec_batch(first, count) offsets out by first * F *
+ * (M ? M : K) reals; mifft_plan_pass_geometry(1), mifft_plan_num_launches() (1), mifft_plan_scratch_bytes() (0) and
+ * mifft_plan_in_bytes() are the STFT plan's.
+ * MIFFT_ERR_UNSUPPORTED, before any device work: the bit without MIFFT_FLAG_STFT (alone, or with MIFFT_FLAG_ISTFT); every
+ * refusal of an STFT plan, MIFFT_JIT=0 included.  MIFFT_ERR_BAD_BASES: a bases_len[0] of any other length (the reason names
+ * bases_len[0]; NULL bases included: the power has to be given), a power other than 1 or 2 (the reason names the power), a
+ * window value, power or filterbank weight that is not finite.  MIFFT_ERR_TOO_LARGE: M > MIFFT_STFT_MAX_BANDS. */
+#define MIFFT_FLAG_STFT_POWER 0x8000u
+#define MIFFT_STFT_MAX_BANDS 32768
 
 typedef struct mifft_plan mifft_plan;
 

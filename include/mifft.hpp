@@ -153,6 +153,15 @@ static_assert(MIFFT_FLAG_ISTFT == 0x4000u &&
                                        MIFFT_FLAG_STFT_HOP_MASK | MIFFT_FLAG_KEEP_MASK | MIFFT_FLAG_DCT_ND | MIFFT_FLAG_DCT |
                                        MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_HALF_SPECTRUM | MIFFT_FLAG_FAITHFUL_STAGES)) == 0,
               "MIFFT_FLAG_ISTFT is its own bit");
+// MIFFT_FLAG_STFT_POWER (0x8000u) beside MIFFT_FLAG_STFT: the same plan with a REAL output, |X|^power (1 or 2) as
+// (batch, F, n / 2 + 1, 1), or its product with an (n / 2 + 1, M) filterbank as (batch, F, M, 1); `bases` carries the window,
+// the power and the filterbank (include/mifft.h).  Created through mifft_plan_create itself, as the STFT plan.
+static_assert(MIFFT_FLAG_STFT_POWER == 0x8000u &&
+                  (MIFFT_FLAG_STFT_POWER & (MIFFT_FLAG_ISTFT | MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_CENTER_REFLECT |
+                                            MIFFT_FLAG_STFT_CENTER_ZEROS | MIFFT_FLAG_STFT_HOP_MASK | MIFFT_FLAG_KEEP_MASK |
+                                            MIFFT_FLAG_DCT_ND | MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_HALF_SPECTRUM |
+                                            MIFFT_FLAG_FAITHFUL_STAGES)) == 0,
+              "MIFFT_FLAG_STFT_POWER is its own bit");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
