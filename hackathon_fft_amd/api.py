@@ -44,6 +44,9 @@ FLAG_STFT_CENTER_ZEROS = 128   # MIFFT_FLAG_STFT_CENTER_ZEROS: frames centred, z
 FLAG_STFT_HOP_MASK = 0xFFFF0000
 FLAG_ISTFT = 0x4000            # MIFFT_FLAG_ISTFT: overlap-added frames, (batch, F, n // 2 + 1, 2) -> (batch, T, 1); hop and centre bits shared
 FLAG_STFT_POWER = 0x8000       # MIFFT_FLAG_STFT_POWER: beside FLAG_STFT, real |X| ** power or its filterbanked bands instead of X
+STFT_EXT_TAG_LO = 0x46465401   # MIFFT_STFT_EXT_TAG_LO / _HI: the NaN in the power slot that selects the extended payload of such
+STFT_EXT_TAG_HI = 0x7FF84D49   # a plan (log stage, matrix after the bands)
+STFT_MAX_BANDS = 32768         # MIFFT_STFT_MAX_BANDS
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -273,10 +276,10 @@ def _f64_words(values) -> list:
     return np.frombuffer(a.tobytes(), dtype="<u4").tolist()
 
 
-def _check_spec_layout(in_shape: tuple, out_shape: tuple, hop: int, center, fb) -> tuple:
+def _check_spec_layout(in_shape: tuple, out_shape: tuple, hop: int, center, fb, post=None) -> tuple:
     """Layouts of a spectrogram plan (MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_POWER): x (batch, T, 1) real -> out
-    (batch, F, n // 2 + 1, 1) real, or (batch, F, M, 1) with a filterbank ``fb`` of shape (n // 2 + 1, M); returns the dims
-    (T, n)."""
+    (batch, F, n // 2 + 1, 1) real, or (batch, F, M, 1) with a filterbank ``fb`` of shape (n // 2 + 1, M), or (batch, F, Q, 1)
+    with an (M, Q) matrix ``post`` after it; returns the dims (T, n)."""
     if len(out_shape) != 4:
         raise MifftError(-1, f"spectrogram layouts are (batch, T, 1) -> (batch, F, n // 2 + 1 or M, 1), got {in_shape} -> "
                              f"{out_shape}")
@@ -285,9 +288,77 @@ def _check_spec_layout(in_shape: tuple, out_shape: tuple, hop: int, center, fb) 
     bins = out_shape[2]
     if fb is not None:
         bins = int(fb.shape[0])
-        if out_shape[2] != fb.shape[1]:
+        if post is not None:
+            if out_shape[2] != post.shape[1]:
+                raise MifftError(-2, f"a matrix post of {tuple(post.shape)} makes {post.shape[1]} values, out has {out_shape[2]}")
+        elif out_shape[2] != fb.shape[1]:
             raise MifftError(-2, f"a filterbank of {tuple(fb.shape)} makes {fb.shape[1]} bands, out has {out_shape[2]}")
     return _check_stft_layout(in_shape, out_shape[:2] + (bins, 2), hop, center)
+
+
+def _spec_log(log, what: str = "stft_log") -> tuple:
+    """the log stage of a spectrogram plan as four floats (add, amin, a, c): y = a * log2(max(v + add, amin)) + c"""
+    import math
+    try:
+        vals = tuple(float(v) for v in log)
+    except (TypeError, ValueError):
+        vals = ()
+    if len(vals) != 4:
+        raise MifftError(ERR_UNSUPPORTED, f"{what} is (add, amin, a, c), four numbers, got {log!r}")
+    add, amin, a, c = vals
+    if not math.isfinite(add) or add < 0:
+        raise MifftError(-5, f"add (eps) of the log stage is finite and not negative, got {add!r}")
+    if not (amin > 0 and math.isfinite(amin)):
+        raise MifftError(-5, f"amin of the log stage is positive and finite, got {amin!r}")
+    if not math.isfinite(a) or a == 0:
+        raise MifftError(-5, f"a of the log stage is finite and not zero, got {a!r}")
+    if not math.isfinite(c):
+        raise MifftError(-5, f"c of the log stage is finite, got {c!r}")
+    return vals
+
+
+def _post_f64(post, bands: Optional[int]) -> "torch.Tensor":
+    """the matrix after the bands as an (M, Q) float64 matrix on the host (a CUDA tensor is copied, which synchronises)"""
+    t = torch.as_tensor(post)
+    if t.is_complex():
+        raise MifftError(-3, "post must be real")
+    t = t.detach().to(device="cpu", dtype=torch.float64).contiguous()
+    if bands is None:
+        raise MifftError(ERR_UNSUPPORTED, "post without fb: the matrix applies to the bands of a filterbank")
+    if t.dim() != 2 or t.shape[1] < 1 or t.shape[0] != bands:
+        raise MifftError(-2, f"post is {tuple(t.shape)}, expected ({bands}, Q): one row per band of the filterbank, one column "
+                             f"per output")
+    if t.shape[1] > STFT_MAX_BANDS:
+        raise MifftError(-9, f"post has {t.shape[1]} columns: at most {STFT_MAX_BANDS}")
+    return t
+
+
+_LOG_KINDS = ("log", "log10", "db")
+
+
+def _log_stage(log, amin, eps, ref, power: int) -> Optional[tuple]:
+    """``log`` / ``amin`` / ``eps`` / ``ref`` of plan_spectrogram and spectrogram as the (add, amin, a, c) of the plan"""
+    import math
+    if log is None:
+        if ref != 1.0:
+            raise MifftError(ERR_UNSUPPORTED, "ref without log=\"db\"")
+        return None
+    if not isinstance(log, str) or log not in _LOG_KINDS:
+        raise MifftError(ERR_UNSUPPORTED, f"log must be None, \"log\", \"log10\" or \"db\", got {log!r}")
+    try:
+        amin, eps, ref = float(amin), float(eps), float(ref)
+    except (TypeError, ValueError):
+        raise MifftError(ERR_UNSUPPORTED, f"amin, eps and ref are numbers, got {amin!r}, {eps!r}, {ref!r}") from None
+    if log != "db":
+        if ref != 1.0:
+            raise MifftError(ERR_UNSUPPORTED, f"ref belongs to log=\"db\", not to log={log!r}")
+        return _spec_log((eps, amin, math.log(2.0) if log == "log" else math.log10(2.0), 0.0), "log")
+    if not (ref > 0 and math.isfinite(ref)):
+        raise MifftError(-5, f"ref of log=\"db\" is positive and finite, got {ref!r}")
+    if not (amin > 0 and math.isfinite(amin)):
+        raise MifftError(-5, f"amin of the log stage is positive and finite, got {amin!r}")
+    mult = 10.0 if power == 2 else 20.0
+    return _spec_log((eps, amin, mult * math.log10(2.0), -mult * math.log10(max(amin, ref))), "log")
 
 
 def istft_length(frames: int, n_fft: int, hop_length: int, center=False) -> int:
@@ -403,6 +474,10 @@ class Plan:
     out (batch, F, n // 2 + 1, 1) -- or, with ``stft_fb`` of shape (n // 2 + 1, M), taken by value as float64, the M bands
     fb.T @ abs(X) ** stft_power per frame, out (batch, F, M, 1), n taken from the filterbank's rows (MIFFT_FLAG_STFT_POWER in
     include/mifft.h, _check_spec_layout, plan_spectrogram).  None: the complex STFT plan.
+    ``stft_log`` (add, amin, a, c) beside ``stft_power``: every value v the plan would store becomes
+    a * log2(max(v + add, amin)) + c first; ``stft_post`` an (M, Q) real matrix beside ``stft_fb``, taken by value as float64:
+    the plan stores post.T @ (the M bands, after the log stage if any), out (batch, F, Q, 1).  Either one travels in the tagged
+    payload (MIFFT_STFT_EXT_TAG in include/mifft.h); without them the plan builds the words it has always built.
     ``istft_hop`` > 0 (no reference counterpart): the inverse, x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real,
     ``inverse=True`` implied; ``stft_center`` None / False or True / "reflect" / "constant" (centred: n // 2 samples trimmed
     at both ends), ``stft_window`` as above, ``istft_gain`` a factor on the synthesis window that stays out of the envelope
@@ -412,7 +487,8 @@ class Plan:
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
-                 istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None):
+                 istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
+                 stft_post=None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         stft = int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT)
         istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
@@ -443,19 +519,31 @@ class Plan:
             if stft_power is None:
                 if stft_fb is not None:
                     raise MifftError(ERR_UNSUPPORTED, "stft_fb without stft_power: a filterbank applies to abs(X) ** power")
+                if stft_log is not None or stft_post is not None:
+                    raise MifftError(ERR_UNSUPPORTED, "stft_log / stft_post without stft_power: they follow abs(X) ** power")
                 stft_dims = _check_stft_layout(in_shape, out_shape, stft_hop, stft_center)
             else:
                 power = _spec_power(stft_power)
                 fbm = None if stft_fb is None else _fb_f64(stft_fb)
-                stft_dims = _check_spec_layout(in_shape, out_shape, stft_hop, stft_center, fbm)
+                logv = None if stft_log is None else _spec_log(stft_log)
+                postm = None if stft_post is None else _post_f64(stft_post, None if fbm is None else int(fbm.shape[1]))
+                stft_dims = _check_spec_layout(in_shape, out_shape, stft_hop, stft_center, fbm, postm)
             if axes is not None:
                 raise MifftError(ERR_UNSUPPORTED, "an STFT plan frames dim 0 and transforms dim 1: no axes")
             if stft_window is not None:
                 words = window_words(_window_f64(stft_window, stft_dims[1]))
             if stft_power is not None:  # (the window written out, the power, the filterbank row by row)
-                words = (words or _f64_words(torch.ones(stft_dims[1], dtype=torch.float64))) + _f64_words([float(power)])
+                words = words or _f64_words(torch.ones(stft_dims[1], dtype=torch.float64))
+                if logv is None and postm is None:
+                    words = words + _f64_words([float(power)])
+                else:  # (the tagged payload: TAG | power | M | Q | log | add | amin | a | c, then fb and post)
+                    head = [float(power), 0.0 if fbm is None else float(fbm.shape[1]), 0.0 if postm is None else float(postm.shape[1]),
+                            0.0 if logv is None else 1.0] + list(logv or (0.0, 0.0, 0.0, 0.0))
+                    words = words + [STFT_EXT_TAG_LO, STFT_EXT_TAG_HI] + _f64_words(torch.tensor(head, dtype=torch.float64))
                 if fbm is not None:
                     words = words + _f64_words(fbm)
+                if postm is not None:
+                    words = words + _f64_words(postm)
                 flags = int(flags) | FLAG_STFT_POWER
             flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(stft_hop) | _stft_center_flags(stft_center) |
                      (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0))
@@ -657,7 +745,8 @@ def plan_stft(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, wi
 
 
 def plan_spectrogram(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, window=None, center=None,
-                     power=2.0, fb=None, ctx: Optional[DeviceContext] = None, whole_batch: int = 0) -> Plan:
+                     power=2.0, fb=None, ctx: Optional[DeviceContext] = None, whole_batch: int = 0, log=None,
+                     amin: float = 1e-10, eps: float = 0.0, ref: float = 1.0, post=None) -> Plan:
     """Plan of the magnitude (``power=1``) or power (``power=2``) spectrogram of ``batch`` real signals of ``length`` samples
     (no reference counterpart; MIFFT_FLAG_STFT_POWER in include/mifft.h): plan_stft's frames, window and ``center``, but the
     one kernel stores abs(X) ** power as reals -- out_shape (batch, F, n_fft // 2 + 1, 1) -- or, with a filterbank ``fb`` of
@@ -665,9 +754,18 @@ def plan_spectrogram(dtype, batch: int, length: int, n_fft: int, hop_length: int
     torchaudio.functional.melscale_fbanks -- a librosa-style (M, n_fft // 2 + 1) matrix must be transposed by the caller), the
     M bands fb.T @ abs(X) ** power of every frame, out_shape (batch, F, M, 1).  The complex spectrogram is never written.  The
     filterbank is applied band by band over the span of each column's non-zero rows, so its cost follows the spans: a dense
-    matrix is correct but slow.  No log / dB stage and no mel-filter generator.  Runs through ``fft(out, x, plan=plan)``,
-    ``first=`` / ``count=`` included; a frame's result is bit-identical for any batch and slab.  Every argument error is raised
-    before any device work: ``power`` other than 1 or 2 is -15, a filterbank of another shape -2."""
+    matrix is correct but slow.  ``melscale_fbanks`` makes a mel filterbank.
+    ``log``: None, or a stage on every value v the plan would store, in the same launch -- "log": ln(max(v + eps, amin));
+    "log10": the same in base 10 (Whisper's log10(max(mel, 1e-10)) is the default ``amin``); "db": torchaudio's
+    amplitude_to_DB without top_db, mult * log10(max(v + eps, amin)) - mult * log10(max(amin, ref)) with mult 10 for
+    ``power=2`` and 20 for ``power=1``.  ``ref`` with any other ``log`` is refused.  There is no ``top_db`` and no Whisper
+    ``max - 8`` clamp: both need the maximum over a whole entry; apply them to the small output, e.g.
+    ``y = torch.maximum(y, y.amax(dim=(-2, -1), keepdim=True) - 80.0)``.
+    ``post``: an (M, Q) real matrix (needs ``fb``; taken by value as float64), applied to the M bands of every frame after the
+    log stage, out_shape (batch, F, Q, 1): with ``create_dct`` the MFCC.  Needs M <= n_fft // 2 - 1.
+    Runs through ``fft(out, x, plan=plan)``, ``first=`` / ``count=`` included; a frame's result is bit-identical for any batch
+    and slab.  Every argument error is raised before any device work: ``power`` other than 1 or 2 is -15, a filterbank of
+    another shape -2, an unknown ``log`` -15, a ``post`` of another row count than M -2, ``post`` without ``fb`` -15."""
     batch, length, n_fft, hop_length = int(batch), int(length), int(n_fft), int(hop_length)
     if dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"a spectrogram plan reads and writes float32 or float64, got {dtype}")
@@ -680,15 +778,19 @@ def plan_spectrogram(dtype, batch: int, length: int, n_fft: int, hop_length: int
     frames = stft_frames(length, n_fft, hop_length, _stft_center_flags(center) != 0)
     if fb is not None:
         fb = _fb_f64(fb, n_fft // 2 + 1)
+    logv = _log_stage(log, amin, eps, ref, power)
+    if post is not None:
+        post = _post_f64(post, None if fb is None else int(fb.shape[1]))
     in_shape = (batch, length, 1)
-    out_shape = (batch, frames, n_fft // 2 + 1 if fb is None else int(fb.shape[1]), 1)
-    _check_spec_layout(in_shape, out_shape, hop_length, center, fb)
+    width = n_fft // 2 + 1 if fb is None else int(fb.shape[1])
+    out_shape = (batch, frames, width if post is None else int(post.shape[1]), 1)
+    _check_spec_layout(in_shape, out_shape, hop_length, center, fb, post)
     if window is not None:
         window = _window_f64(window, n_fft)
     if ctx is None:
         ctx = DeviceContext()
     return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, stft_hop=hop_length,
-                stft_center=center, stft_window=window, stft_power=power, stft_fb=fb)
+                stft_center=center, stft_window=window, stft_power=power, stft_fb=fb, stft_log=logv, stft_post=post)
 
 
 def plan_istft(dtype, batch: int, frames: int, n_fft: int, hop_length: int, *, window=None, center=False,
@@ -1202,8 +1304,9 @@ def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_le
 
 
 def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype, power,
-              fb) -> "torch.Tensor":
-    """stft (``power`` None) and spectrogram (``power`` 1 or 2, ``fb`` None or a (n_fft // 2 + 1, M) float64 host matrix)"""
+              fb, logv=None, post=None) -> "torch.Tensor":
+    """stft (``power`` None) and spectrogram (``power`` 1 or 2, ``fb`` None or a (n_fft // 2 + 1, M) float64 host matrix,
+    ``logv`` None or (add, amin, a, c), ``post`` None or an (M, Q) matrix)"""
     if not onesided:
         raise MifftError(ERR_UNSUPPORTED, f"{who}: onesided=False is not supported")
     if pad_mode not in ("reflect", "constant"):
@@ -1235,6 +1338,9 @@ def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mo
     if fb is not None:
         fb = _fb_f64(fb, bins)
     width = bins if fb is None else int(fb.shape[1])
+    if post is not None:
+        post = _post_f64(post, None if fb is None else width)
+        width = int(post.shape[1])
     in_shape, out_shape = (batch, T, 1), (batch, frames, width, 2 if power is None else 1)
     _check_stft_layout(in_shape, (batch, frames, bins, 2), hop_length, mode)
     w = None
@@ -1259,10 +1365,12 @@ def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mo
                int(torch.cuda.current_stream(device).cuda_stream))
         if power is not None:  # (the stft key as it has always been, then what the spectrogram adds)
             key += (power, None if fb is None else (tuple(fb.shape), hashlib.sha1(fb.numpy().tobytes()).digest()))
+        if logv is not None or post is not None:  # (and what the log stage and the matrix after the bands add)
+            key += (logv, None if post is None else (tuple(post.shape), hashlib.sha1(post.numpy().tobytes()).digest()))
         plan = _PLAN_CACHE.get(key)
         if plan is None:
             plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, stft_hop=hop_length, stft_center=mode,
-                        stft_window=w, stft_power=power, stft_fb=fb)
+                        stft_window=w, stft_power=power, stft_fb=fb, stft_log=logv, stft_post=post)
             _plan_cache_insert(key, plan)
         else:
             _PLAN_CACHE.move_to_end(key)
@@ -1274,7 +1382,8 @@ def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mo
 
 def spectrogram(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None,
                 window=None, center: bool = True, pad_mode: str = "reflect", normalized: bool = False, power=2.0, *,
-                fb=None, out_dtype=None, onesided: bool = True) -> "torch.Tensor":
+                fb=None, out_dtype=None, onesided: bool = True, log=None, amin: float = 1e-10, eps: float = 0.0,
+                ref: float = 1.0, post=None) -> "torch.Tensor":
     """torch.stft(x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided=True,
     return_complex=True).abs().pow(power) of a real ``x`` of shape (T,) or (..., T), ``power`` 1 (magnitude) or 2 (power), in one
     kernel launch that never writes the complex spectrogram; every argument it shares with ``stft`` means what it means
@@ -1282,18 +1391,122 @@ def spectrogram(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None,
     ``fb``: a filterbank of shape (n_fft // 2 + 1, M), any real tensor or array on any device, taken by value as float64 like
     the window; the result is then (fb.T @ .) along the frequency dim, M bands per frame.  That is the orientation of
     torchaudio.functional.melscale_fbanks; a librosa-style (M, n_fft // 2 + 1) matrix must be transposed by the caller.  The
-    bands are summed over the span of each column's non-zero rows: a dense matrix is correct but slow.  There is no log / dB
-    stage and no mel-filter generator here: the filterbanked output is small, an elementwise pass over it is cheap.
-    Returns real (..., n_fft // 2 + 1 or M, F) as a TRANSPOSED VIEW (``stride(-2) == 1``) of the frames-major tensor the kernel
+    bands are summed over the span of each column's non-zero rows: a dense matrix is correct but slow.  ``melscale_fbanks``
+    makes a mel filterbank.
+    ``log`` / ``amin`` / ``eps`` / ``ref``: a log stage in the same launch, as in ``plan_spectrogram`` -- "log":
+    ln(max(v + eps, amin)); "log10": base 10; "db": torchaudio's amplitude_to_DB(v, multiplier 10 for ``power=2`` / 20 for
+    ``power=1``, amin, db_multiplier=log10(max(amin, ref))) without top_db.  ``ref`` with any other ``log`` is -15.  There is
+    no ``top_db`` and no Whisper ``max - 8`` clamp, which need the maximum over a whole entry; on the small output that is one
+    line, ``y = torch.maximum(y, y.amax(dim=(-2, -1), keepdim=True) - 80.0)`` (Whisper: ``- 8.0`` on log10).
+    ``post``: an (M, Q) real matrix after the bands (and the log stage), taken by value as float64; needs ``fb`` and
+    M <= n_fft // 2 - 1; the result has Q values per frame.  With ``create_dct`` that is the MFCC (``mfcc``).
+    Returns real (..., n_fft // 2 + 1 or M or Q, F) as a TRANSPOSED VIEW (``stride(-2) == 1``) of the frames-major tensor the kernel
     writes, exactly as ``stft`` does.  ``power`` other than 1 or 2 is MifftError -15; so is ``power=None``: the complex
     spectrogram is ``stft``.  A filterbank of another shape is -2.  Plans are cached as those of ``stft``, the key extended by
-    the power and a digest of the filterbank's values, so a filterbank changed in place never meets a stale plan; loops should
-    make the plan once with ``plan_spectrogram`` and call ``fft``."""
+    the power and a digest of the filterbank's values (and of ``post``, and the log stage), so a matrix changed in place never
+    meets a stale plan; loops should make the plan once with ``plan_spectrogram`` and call ``fft``."""
     if power is None:
         raise MifftError(ERR_UNSUPPORTED, "spectrogram: power=None is the complex spectrogram: use stft")
     power = _spec_power(power)
+    logv = _log_stage(log, amin, eps, ref, power)
+    if post is not None and fb is None:
+        _post_f64(post, None)
     return _stft_run("spectrogram", x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided,
-                     out_dtype, power, fb)
+                     out_dtype, power, fb, logv, post)
+
+
+def _mel(f, scale: str):
+    import numpy as np
+    f = np.asarray(f, dtype=np.float64)
+    if scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    return np.where(f >= 1000.0, 15.0 + 27.0 * np.log(np.maximum(f, 1000.0) / 1000.0) / np.log(6.4), 3.0 * f / 200.0)
+
+
+def _mel_to_hz(m, scale: str):
+    import numpy as np
+    m = np.asarray(m, dtype=np.float64)
+    if scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m >= 15.0, 1000.0 * np.exp(np.log(6.4) * (np.maximum(m, 15.0) - 15.0) / 27.0), 200.0 * m / 3.0)
+
+
+def melscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int, norm=None,
+                    mel_scale: str = "htk") -> "torch.Tensor":
+    """The triangular mel filterbank of torchaudio.functional.melscale_fbanks as a float64 (n_freqs, n_mels) host tensor, the
+    orientation ``fb=`` takes.  Pure host arithmetic, by this definition and no other:
+        all_freqs = linspace(0, sample_rate // 2, n_freqs); m_pts = linspace(mel(f_min), mel(f_max), n_mels + 2); f_pts = hz(m_pts)
+        fb[k, m] = max(0, min((all_freqs[k] - f_pts[m]) / (f_pts[m+1] - f_pts[m]),
+                              (f_pts[m+2] - all_freqs[k]) / (f_pts[m+2] - f_pts[m+1])))
+    ``norm="slaney"`` multiplies column m by 2 / (f_pts[m+2] - f_pts[m]).  ``mel_scale`` "htk": mel(f) = 2595 log10(1 + f / 700);
+    "slaney": 3 f / 200 below 1000 Hz and 15 + 27 ln(f / 1000) / ln 6.4 from there; hz() is the inverse of each.
+    Argument errors are MifftError."""
+    import numpy as np
+    if norm is not None and norm != "slaney":
+        raise MifftError(ERR_UNSUPPORTED, f"norm must be None or \"slaney\", got {norm!r}")
+    if mel_scale not in ("htk", "slaney"):
+        raise MifftError(ERR_UNSUPPORTED, f"mel_scale must be \"htk\" or \"slaney\", got {mel_scale!r}")
+    n_freqs, n_mels, sample_rate = int(n_freqs), int(n_mels), int(sample_rate)
+    f_min, f_max = float(f_min), float(f_max)
+    if n_freqs < 2 or n_mels < 1 or sample_rate < 2:
+        raise MifftError(-2, f"n_freqs >= 2, n_mels >= 1 and sample_rate >= 2, got {n_freqs}, {n_mels}, {sample_rate}")
+    if not 0.0 <= f_min < f_max or f_max == float("inf"):
+        raise MifftError(-2, f"0 <= f_min < f_max, both finite, got {f_min}, {f_max}")
+    all_freqs = np.linspace(0.0, float(sample_rate // 2), n_freqs)
+    f_pts = _mel_to_hz(np.linspace(float(_mel(f_min, mel_scale)), float(_mel(f_max, mel_scale)), n_mels + 2), mel_scale)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - all_freqs[:, None]                       # (n_freqs, n_mels + 2)
+    down = -slopes[:, :-2] / f_diff[:-1]
+    up = slopes[:, 2:] / f_diff[1:]
+    fb = np.maximum(0.0, np.minimum(down, up))
+    if norm == "slaney":
+        fb = fb * (2.0 / (f_pts[2:] - f_pts[:-2]))[None, :]
+    return torch.from_numpy(np.ascontiguousarray(fb))
+
+
+def create_dct(n_mfcc: int, n_mels: int, norm="ortho") -> "torch.Tensor":
+    """The DCT-II matrix of torchaudio.functional.create_dct as a float64 (n_mels, n_mfcc) host tensor, the orientation
+    ``post=`` takes: D[m, q] = cos(pi / n_mels * (m + 0.5) * q), times 2 for ``norm=None``; for "ortho" column 0 times
+    1 / sqrt(2), then everything times sqrt(2 / n_mels).  ``y @ create_dct(Q, M, norm)`` is scipy.fft.dct(y, type=2,
+    norm=norm)[..., :Q]."""
+    import numpy as np
+    if norm is not None and norm != "ortho":
+        raise MifftError(ERR_UNSUPPORTED, f"norm must be None or \"ortho\", got {norm!r}")
+    n_mfcc, n_mels = int(n_mfcc), int(n_mels)
+    if n_mels < 1 or n_mfcc < 1:
+        raise MifftError(-2, f"n_mfcc >= 1 and n_mels >= 1, got {n_mfcc}, {n_mels}")
+    d = np.cos(np.pi / n_mels * (np.arange(n_mels, dtype=np.float64)[:, None] + 0.5) * np.arange(n_mfcc, dtype=np.float64)[None, :])
+    if norm is None:
+        d *= 2.0
+    else:
+        d[:, 0] *= 1.0 / np.sqrt(2.0)
+        d *= np.sqrt(2.0 / n_mels)
+    return torch.from_numpy(d)
+
+
+def mfcc(x: "torch.Tensor", sample_rate: int, n_mfcc: int = 40, *, n_fft: int = 400, hop_length: Optional[int] = None,
+         win_length: Optional[int] = None, window=None, n_mels: int = 128, f_min: float = 0.0, f_max: Optional[float] = None,
+         mel_norm=None, mel_scale: str = "htk", dct_norm="ortho", log="db", amin: float = 1e-10, eps: float = 0.0,
+         center: bool = True, pad_mode: str = "reflect") -> "torch.Tensor":
+    """Mel-frequency cepstral coefficients of a real ``x`` of shape (T,) or (..., T) in one kernel launch:
+    ``spectrogram(x, n_fft, ..., power=2, fb=melscale_fbanks(n_fft // 2 + 1, f_min, f_max, n_mels, sample_rate, mel_norm,
+    mel_scale), log=log, amin=amin, eps=eps, post=create_dct(n_mfcc, n_mels, dct_norm))``; ``f_max`` defaults to
+    sample_rate // 2, ``hop_length`` to n_fft // 4, ``window=None`` is rectangular (torchaudio's MFCC uses a Hann window: pass
+    one).  ``log=None`` skips the log stage.  torchaudio's and librosa's default ``top_db=80`` clamp is NOT applied: it needs
+    the maximum over a whole entry, which one pass over the frames does not have.  Needs n_mels <= n_fft // 2 - 1.
+    Returns (..., n_mfcc, F) as the same transposed view as ``spectrogram``.  Every argument error is a MifftError before any
+    device work."""
+    n_fft = int(n_fft)
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"mfcc with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    if int(n_mfcc) > int(n_mels):
+        raise MifftError(-2, f"n_mfcc ({n_mfcc}) cannot exceed n_mels ({n_mels})")
+    fb = melscale_fbanks(n_fft // 2 + 1, f_min, float(int(sample_rate) // 2) if f_max is None else f_max, n_mels, sample_rate,
+                         mel_norm, mel_scale)
+    if int(n_mels) > n_fft // 2 - 1:
+        raise MifftError(ERR_UNSUPPORTED, f"mfcc needs n_mels <= n_fft // 2 - 1 = {n_fft // 2 - 1}, got {n_mels}")
+    return spectrogram(x, n_fft, hop_length, win_length, window, center, pad_mode, False, 2.0, fb=fb, log=log, amin=amin,
+                       eps=eps, post=create_dct(n_mfcc, n_mels, dct_norm))
 
 
 def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None, window=None,

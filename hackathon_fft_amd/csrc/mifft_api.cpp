@@ -249,7 +249,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
             return rc == MIFFT_ERR_HIP ? rc : set_error(rc, why);
         };
         std::string why;
-        std::vector<double> window, fb;
+        std::vector<double> window, fb, post;
         std::vector<uint64_t> user;
         double gain = 1.0;
         int rc = fwd ? stft_check(p, why) : istft_check(p, bases_flat, bases_len, window, gain, user, why);
@@ -259,7 +259,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         p.prod = frames * n;  // (the rows the one pass transforms)
         p.prod_half = frames * (n / 2 + 1);
         if (fwd) {
-            rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, user, why);
+            rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, post, user, why);
             if (rc) return fail(rc, why);
         }
         if (user.empty()) user = plan_estimate_bases((uint64_t)n, /*gpu_target=*/true);
@@ -279,7 +279,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) p.num_cus = prop.multiProcessorCount;
         config_refresh();
-        rc = fwd ? build_stft(p, ordered[td], processed[td], window, fb, why)
+        rc = fwd ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
                  : build_istft(p, ordered[td], processed[td], window, gain, why);
         if (rc) return fail(rc, why);
         *out_plan = h;

@@ -174,7 +174,15 @@ struct Plan {
     // not set.  Filled by stft_unpack_bases.
     int spec_power = 0;
     int64_t spec_bands = 0;
-    int64_t stft_out_width() const { return spec_bands > 0 ? spec_bands : dims[1] / 2 + 1; }
+    // The tagged payload (MIFFT_STFT_EXT_TAG) adds two stages to that store: spec_log -- y = fma(spec_a, log2(max(v +
+    // spec_add, spec_amin)), spec_c), the four already rounded to the plan's float type -- and spec_post > 0, a dense
+    // (spec_bands, spec_post) matrix applied to the bands of every frame; its weights follow the band weights in the band
+    // table, spec_post_off elements behind their start (set by build_stft).
+    bool spec_log = false;
+    int64_t spec_post = 0;
+    double spec_add = 0.0, spec_amin = 0.0, spec_a = 0.0, spec_c = 0.0;
+    int64_t spec_post_off = 0;
+    int64_t stft_out_width() const { return spec_post > 0 ? spec_post : spec_bands > 0 ? spec_bands : dims[1] / 2 + 1; }
     // MIFFT_FLAG_ISTFT: dims = {T, F, n}; x is (batch, F, n / 2 + 1, 2), out (batch, T, 1) real: F frames of n samples every
     // stft_hop() overlap-added over istft_padded_len() samples, of which T from istft_trim() on are stored
     bool istft() const { return (flags & MIFFT_FLAG_ISTFT) != 0; }
@@ -309,13 +317,15 @@ int stft_check(const Plan& plan, std::string& why);
 // the window of such a plan from bases_flat / bases_len (2 n words: the binary64 bits of w[0 .. n-1], low word first; none:
 // rectangular, `window` left empty) and the user radices of the n-point transform (none: `radices` left empty).  With
 // MIFFT_FLAG_STFT_POWER also the power and the filterbank (row-major (n / 2 + 1, M); M = 0: `fb` left empty), which set
-// plan.spec_power and plan.spec_bands.
+// plan.spec_power and plan.spec_bands.  A payload with MIFFT_STFT_EXT_TAG in the power slot also carries the log stage and
+// the (M, Q) matrix `post` (row-major; Q = 0: left empty), which set plan.spec_log, spec_add .. spec_c and plan.spec_post.
 int stft_unpack_bases(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                      std::vector<double>& fb, std::vector<uint64_t>& radices, std::string& why);
+                      std::vector<double>& fb, std::vector<double>& post, std::vector<uint64_t>& radices, std::string& why);
 int build_stft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, const std::vector<double>& fb, std::string& why);
+               const std::vector<double>& window, const std::vector<double>& fb, const std::vector<double>& post,
+               std::string& why);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
-// count of ints, then the weights in the plan's float type
+// count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }
 // plans with MIFFT_FLAG_ISTFT (istft.cpp), in the same manner: istft_check needs no device and leaves the window (empty:
 // rectangular), the gain and the user radices in its outputs; it refuses a window whose squared overlap-add is zero

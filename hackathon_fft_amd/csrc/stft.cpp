@@ -10,6 +10,9 @@
 // product of that with a filterbank (TileCfg::FB), (batch, F, M, 1): `bases` then carries the window, the power and the
 // (n / 2 + 1, M) matrix, which is banded here -- per column the span from its first to its last non-zero row -- and lives in
 // the plan as one device table.
+//
+// A payload tagged with MIFFT_STFT_EXT_TAG adds a log stage (TileCfg::LOG) and a dense (M, Q) matrix after the bands
+// (TileCfg::POST) to the same launch: out is then (batch, F, Q, 1), and the matrix follows the band weights in that table.
 #include <cmath>
 #include <cstring>
 
@@ -121,16 +124,135 @@ static double word_pair(const uint32_t* w) {
     return v;
 }
 
+// a header value of the tagged payload that has to be a non-negative integer
+static bool header_count(double v, const char* field, int64_t& out, std::string& why) {
+    if (!std::isfinite(v) || v < 0 || v != std::floor(v) || v > 9007199254740992.0) {
+        why = std::string("the header value ") + field + " of a tagged MIFFT_FLAG_STFT_POWER payload is a non-negative integer, not " +
+              std::to_string(v);
+        return false;
+    }
+    out = (int64_t)v;
+    return true;
+}
+
+// the tagged payload: w | TAG | power | M | Q | log | add | amin | a | c | fb (K, M) | post (M, Q).  Everything but the
+// window, which the caller reads as it reads that of every payload.
+static int stft_unpack_tagged(Plan& p, const uint32_t* bases_flat, int64_t len0, std::vector<double>& fb, std::vector<double>& post,
+                              std::string& why) {
+    const int64_t n = p.dims[1], K = n / 2 + 1;
+    const bool f64 = p.out_dtype == MIFFT_F64;
+    auto bad_len = [&](const std::string& want) {
+        why = "bases_len[0] of a tagged MIFFT_FLAG_STFT_POWER payload is " + want + " words (the window, the tag, power, M, Q, log, "
+              "add, amin, a, c, an (n / 2 + 1, M) filterbank, an (M, Q) matrix), not " + std::to_string(len0);
+        return MIFFT_ERR_BAD_BASES;
+    };
+    if (len0 < 2 * (n + 9)) return bad_len("2 (n + 9 + K M + M Q) >= " + std::to_string(2 * (n + 9)));
+    const uint32_t* hd = bases_flat + 2 * n + 2;  // power, M, Q, log, add, amin, a, c
+    const double power = word_pair(hd);
+    int64_t M = 0, Q = 0, lg = 0;
+    if (!header_count(word_pair(hd + 2), "M", M, why) || !header_count(word_pair(hd + 4), "Q", Q, why) ||
+        !header_count(word_pair(hd + 6), "log", lg, why))
+        return MIFFT_ERR_BAD_BASES;
+    if (!(power == 1.0 || power == 2.0)) {
+        why = "the power of a plan with MIFFT_FLAG_STFT_POWER is 1 (magnitude) or 2 (power), not " + std::to_string(power);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (lg > 1) {
+        why = "the header value log of a tagged MIFFT_FLAG_STFT_POWER payload is 0 or 1, not " + std::to_string(lg);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (M > MIFFT_STFT_MAX_BANDS || Q > MIFFT_STFT_MAX_BANDS) {
+        why = std::string(M > MIFFT_STFT_MAX_BANDS ? "a filterbank of M = " : "a matrix post of Q = ") +
+              std::to_string(M > MIFFT_STFT_MAX_BANDS ? M : Q) + (M > MIFFT_STFT_MAX_BANDS ? " bands" : " columns") +
+              ": at most MIFFT_STFT_MAX_BANDS = " + std::to_string(MIFFT_STFT_MAX_BANDS);
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (len0 != 2 * (n + 9 + K * M + M * Q))
+        return bad_len("2 (n + 9 + K M + M Q) = " + std::to_string(2 * (n + 9 + K * M + M * Q)) + " (M = " + std::to_string(M) +
+                       ", Q = " + std::to_string(Q) + ")");
+    if (lg) {
+        const double add = word_pair(hd + 8), amin = word_pair(hd + 10), a = word_pair(hd + 12), c = word_pair(hd + 14);
+        auto round_t = [&](double v) { return f64 ? v : (double)(float)v; };
+        if (!std::isfinite(add) || add < 0) {
+            why = "add of the log stage is finite and not negative, not " + std::to_string(add);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (!(amin > 0) || !(f64 ? std::isnormal(amin) : std::isnormal((float)amin))) {
+            why = "amin of the log stage is positive and rounds to a normal number of the plan's float type, not " +
+                  std::to_string(amin);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (!std::isfinite(a) || a == 0) {
+            why = "a of the log stage is finite and not zero, not " + std::to_string(a);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (!std::isfinite(c)) {
+            why = "c of the log stage is finite, not " + std::to_string(c);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        p.spec_add = round_t(add);
+        p.spec_amin = round_t(amin);
+        p.spec_a = round_t(a);
+        p.spec_c = round_t(c);
+        if (!std::isfinite(p.spec_add) || !std::isfinite(p.spec_a) || p.spec_a == 0 || !std::isfinite(p.spec_c)) {
+            why = "add, a and c of the log stage stay finite, and a non-zero, when rounded to the plan's float type";
+            return MIFFT_ERR_BAD_BASES;
+        }
+    }
+    if (Q > 0 && M == 0) {
+        why = "Q = " + std::to_string(Q) + " with M = 0: the matrix post applies to the bands of a filterbank";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (Q > 0 && M > n / 2 - 1) {
+        why = "Q > 0 with M = " + std::to_string(M) + " bands on frames of " + std::to_string(n) +
+              " points: the bands of a frame wait in the free halves of its LDS row, M <= n / 2 - 1 = " + std::to_string(n / 2 - 1);
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    const uint32_t* body = hd + 16;
+    fb.resize((size_t)(K * M));
+    for (size_t i = 0; i < fb.size(); ++i) {
+        fb[i] = word_pair(body + 2 * i);
+        if (!std::isfinite(fb[i])) {
+            why = "filterbank weight (" + std::to_string(i / (size_t)M) + ", " + std::to_string(i % (size_t)M) + ") is not finite";
+            return MIFFT_ERR_BAD_BASES;
+        }
+    }
+    body += 2 * fb.size();
+    post.resize((size_t)(M * Q));
+    for (size_t i = 0; i < post.size(); ++i) {
+        post[i] = word_pair(body + 2 * i);
+        if (!std::isfinite(post[i])) {
+            why = "post weight (" + std::to_string(i / (size_t)Q) + ", " + std::to_string(i % (size_t)Q) + ") is not finite";
+            return MIFFT_ERR_BAD_BASES;
+        }
+    }
+    p.spec_power = (int)power;
+    p.spec_bands = M;
+    p.spec_post = Q;
+    p.spec_log = lg != 0;
+    return MIFFT_OK;
+}
+
 int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                      std::vector<double>& fb, std::vector<uint64_t>& radices, std::string& why) {
+                      std::vector<double>& fb, std::vector<double>& post, std::vector<uint64_t>& radices, std::string& why) {
     const int64_t n = p.dims[1], K = n / 2 + 1;
     const bool spec = (p.flags & MIFFT_FLAG_STFT_POWER) != 0;
     window.clear();
     fb.clear();
+    post.clear();
     radices.clear();
     p.spec_power = 0;
     p.spec_bands = 0;
-    if (spec) {  // the window written out, the power, and M columns of K weights: 2 n + 2 + 2 M K words
+    p.spec_post = 0;
+    p.spec_log = false;
+    p.spec_add = p.spec_amin = p.spec_a = p.spec_c = 0.0;
+    // the extension is chosen by one NaN in the power slot; every other payload means what it has always meant
+    const bool tagged = spec && bases_flat && bases_len && (int64_t)bases_len[0] >= 2 * n + 2 &&
+                        bases_flat[2 * n] == MIFFT_STFT_EXT_TAG_LO && bases_flat[2 * n + 1] == MIFFT_STFT_EXT_TAG_HI;
+    if (tagged) {
+        const int rc = stft_unpack_tagged(p, bases_flat, (int64_t)bases_len[0], fb, post, why);
+        if (rc) return rc;
+    } else if (spec) {  // the window written out, the power, and M columns of K weights: 2 n + 2 + 2 M K words
         const int64_t len0 = bases_len ? (int64_t)bases_len[0] : 0, rest = len0 - 2 * n - 2;
         if (!bases_flat || !bases_len || rest < 0 || rest % (2 * K) != 0) {
             why = "bases_len[0] of a plan with MIFFT_FLAG_STFT_POWER is 2 n + 2 + 2 M K = " + std::to_string(2 * n + 2) + " + " +
@@ -167,7 +289,7 @@ int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_
             window[(size_t)j] = v;
         }
     }
-    if (spec) {
+    if (spec && !tagged) {
         const double power = word_pair(bases_flat + 2 * n);
         if (!(power == 1.0 || power == 2.0)) {  // (NaN included)
             why = "the power of a plan with MIFFT_FLAG_STFT_POWER is 1 (magnitude) or 2 (power), not " + std::to_string(power);
@@ -203,7 +325,8 @@ static hipError_t upload_window_t(int64_t n, const std::vector<double>& window, 
 // between stay inside the span; a column of zeros has len 0), off = where its len weights start.  One device table: lo[M],
 // len[M], off[M] (int32, padded to an even count), then the weights, rounded once to T.
 template <typename T>
-static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>& fb, void** d_table) {
+static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>& fb, const std::vector<double>& post,
+                                 int64_t& post_off, void** d_table) {
     std::vector<int32_t> head((size_t)spec_table_ints(M), 0);
     std::vector<T> wt;
     for (int64_t m = 0; m < M; ++m) {
@@ -219,6 +342,8 @@ static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>
         head[(size_t)(2 * M + m)] = (int32_t)wt.size();  // (<= M K < 2^30: bases_len is an int32 of 2 M K words and more)
         for (int64_t j = 0; j < len; ++j) wt.push_back((T)fb[(size_t)((lo + j) * M + m)]);
     }
+    post_off = (int64_t)wt.size();  // the dense (M, Q) matrix of a POST configuration, behind the band weights
+    for (double v : post) wt.push_back((T)v);
     const size_t hb = head.size() * sizeof(int32_t), wb = wt.size() * sizeof(T);
     hipError_t e = hipMalloc(d_table, hb + (wb ? wb : sizeof(T)));
     if (e == hipSuccess) e = hipMemcpy(*d_table, head.data(), hb, hipMemcpyHostToDevice);
@@ -228,7 +353,8 @@ static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>
 
 // the one pass: dim 1 (n points) over the F frames of every batch entry
 int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, const std::vector<double>& fb, std::string& why) {
+               const std::vector<double>& window, const std::vector<double>& fb, const std::vector<double>& post,
+               std::string& why) {
     const int64_t n = p.dims[1];
     DimPass ps;
     ps.dim_index = 1;
@@ -246,8 +372,8 @@ int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     if (e == hipSuccess)
         e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(n, window, &ps.d_aux2) : upload_window_t<float>(n, window, &ps.d_aux2);
     if (e == hipSuccess && p.spec_bands > 0)
-        e = p.out_dtype == MIFFT_F64 ? upload_bands_t<double>(n / 2 + 1, p.spec_bands, fb, &ps.d_aux3)
-                                     : upload_bands_t<float>(n / 2 + 1, p.spec_bands, fb, &ps.d_aux3);
+        e = p.out_dtype == MIFFT_F64 ? upload_bands_t<double>(n / 2 + 1, p.spec_bands, fb, post, p.spec_post_off, &ps.d_aux3)
+                                     : upload_bands_t<float>(n / 2 + 1, p.spec_bands, fb, post, p.spec_post_off, &ps.d_aux3);
     p.passes.push_back(ps);
     if (e != hipSuccess) return hip_error(e, "STFT table upload");
     return MIFFT_OK;

@@ -127,6 +127,11 @@ MIFFT_DEV void gstore_real(T* p, T v) {
 MIFFT_DEV float sqrt_t(float v) { return __builtin_sqrtf(v); }
 MIFFT_DEV double sqrt_t(double v) { return __builtin_sqrt(v); }
 
+// the full-precision base-2 logarithm (log2f / log2 without a header, as above): the library routine, not v_log_f32 alone
+extern "C" __device__ double __ocml_log2_f64(double);
+MIFFT_DEV float log2_t(float v) { return __builtin_log2f(v); }
+MIFFT_DEV double log2_t(double v) { return __ocml_log2_f64(v); }
+
 template <class A, class B> struct same_t { static constexpr bool value = false; };
 template <class A> struct same_t<A, A> { static constexpr bool value = true; };
 
@@ -214,7 +219,21 @@ struct TileParams {
     const int* spec_len;
     const int* spec_off;
     int spec_bands;
+    // LOG configurations: y = fma(spec_a, log2(max(v + spec_add, spec_amin)), spec_c) on every value the SPEC / FB store
+    // would have written; the four are exact values of type T (spec_amin a normal one, so the logarithm sees no denormal).
+    // POST configurations (with FB): spec_post is a dense, row-major (spec_bands, spec_q) matrix of type T applied to the
+    // bands of every frame, spec_bands <= N - 1; the store writes spec_q reals per frame.
+    double spec_add, spec_amin, spec_a, spec_c;
+    const void* spec_post;
+    int spec_q;
 };
+
+// the log stage of a TileCfg::LOG store: fma(a, log2(max(v + add, amin)), c)
+template <typename T>
+MIFFT_DEV T spec_log(const TileParams& p, T v) {
+    const T s = v + (T)p.spec_add, lim = (T)p.spec_amin;
+    return fma_t((T)p.spec_a, log2_t(s < lim ? lim : s), (T)p.spec_c);  // (a NaN stays one, as through torch.clamp)
+}
 
 MIFFT_DEV long long tile_id(const TileParams& p, long long t) { return p.reverse ? p.n_tiles - 1 - t : t; }
 
@@ -301,7 +320,8 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FIRST_DIRECT_, bool LAST_DIRECT_, int TWMODE_, int MINW_ = 1, bool PREFETCH_ = false, int ROWPAD_ = 0,
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
-          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false>
+          int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
+          bool LOG_ = false, bool POST_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -513,6 +533,19 @@ struct TileCfg {
     static constexpr bool FB = FB_;
     static_assert(SPEC_ >= 0 && SPEC_ <= 2 && (SPEC_ == 0 || STFT_) && (!FB_ || SPEC_ != 0),
                   "SPEC: the magnitude / power store of an STFT tile; FB: its filterbank");
+    // LOG (with SPEC): every value v the store would write -- a bin without FB, a band with it -- becomes
+    // fma(a, log2(max(v + add, amin)), c) first (TileParams::spec_*; the library logarithm, one explicit fma).
+    // POST (with FB): a dense (M, Q) matrix follows the bands in the same launch, M <= N - 1.  The band loop stores
+    // nothing: y[m] goes to the .y of slot 1 + m of its row, which is dead -- P[k] lives in .x of slot k and P[N] in .y of
+    // slot 0, the other .y halves hold stale Z -- so no LDS is added.  The band loop of such a configuration reads only the
+    // 4- or 8-byte component it uses, since a neighbour may be writing the other half of the slot.  After a barrier one
+    // work item per (row c < nv, q < Q), q fastest, sums post[m * Q + q] * y[c][m] over ascending m, one fma per term from an
+    // exact zero, and stores out[(row0 + c) * Q + q]: adjacent lanes read adjacent q of one m from global memory (the
+    // matrix is a few KB, re-read from L1 / L2 by every tile as the band tables are) and the same y[m] from LDS, a
+    // broadcast.  The order of summation is fixed per frame.
+    static constexpr bool LOG = LOG_;
+    static constexpr bool POST = POST_;
+    static_assert((!LOG_ || SPEC_ != 0) && (!POST_ || FB_), "LOG: the log stage of a SPEC store; POST: the matrix after FB");
     static constexpr bool ISTFT = ISTFT_;
     static_assert(!ISTFT_ || (C2R_ && !LAST_DIRECT_ && DCT_ == 0 && !STFT_ && ROWPAD_ == 0),
                   "ISTFT: folded rows whose last pass stays in LDS for the overlap-add");
@@ -1937,6 +1970,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                             if (2 * k != C::N) lds[lds_index<C, C::NP - 1>(c, m)].x = pb;
                         }
                     } else {
+                        if constexpr (C::LOG) {
+                            pa = spec_log<T>(p, pa);
+                            pb = spec_log<T>(p, pb);
+                        }
                         T* row = (T*)p.out + (row0 + c) * (C::N + 1);
                         gstore_real<(C::NT & 2) != 0>(row + k, pa);
                         if (2 * k != C::N) gstore_real<(C::NT & 2) != 0>(row + C::N - k, pb);
@@ -1966,10 +2003,35 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     T acc = (T)0;
                     for (int j = 0; j < len; ++j) {
                         const int bin = lo + j;  // (<= N: bin N is the .y of slot 0)
-                        const V s = lds[lds_index<C, C::NP - 1>(c, bin == C::N ? 0 : bin)];
-                        acc = fma_t(wb[j], bin == C::N ? s.y : s.x, acc);
+                        if constexpr (C::POST) {  // the component alone: the other half of the slot may be written meanwhile
+                            const T* ldr = (const T*)lds;
+                            acc = fma_t(wb[j], bin == C::N ? ldr[2 * lds_index<C, C::NP - 1>(c, 0) + 1]
+                                                           : ldr[2 * lds_index<C, C::NP - 1>(c, bin)], acc);
+                        } else {
+                            const V s = lds[lds_index<C, C::NP - 1>(c, bin == C::N ? 0 : bin)];
+                            acc = fma_t(wb[j], bin == C::N ? s.y : s.x, acc);
+                        }
                     }
-                    gstore_real<(C::NT & 2) != 0>(orow + f, acc);
+                    if constexpr (C::LOG) acc = spec_log<T>(p, acc);
+                    if constexpr (C::POST)
+                        ((T*)lds)[2 * lds_index<C, C::NP - 1>(c, 1 + mb) + 1] = acc;  // (M <= N - 1: slots 1 .. N - 1)
+                    else
+                        gstore_real<(C::NT & 2) != 0>(orow + f, acc);
+                }
+                if constexpr (C::POST) {
+                    // y of the tile's frames lies in the .y halves: one work item per (row, column of post)
+                    __syncthreads();
+                    const int Q = p.spec_q;
+                    const T* pm = (const T*)p.spec_post;
+                    const T* ldr = (const T*)lds;
+                    T* zrow = (T*)p.out + row0 * Q;
+                    for (int f = tid; f < nv * Q; f += C::THREADS) {
+                        const int c = f / Q, q = f - c * Q;
+                        T z = (T)0;
+                        for (int mb = 0; mb < M; ++mb)
+                            z = fma_t(pm[mb * Q + q], ldr[2 * lds_index<C, C::NP - 1>(c, 1 + mb) + 1], z);
+                        gstore_real<(C::NT & 2) != 0>(zrow + f, z);
+                    }
                 }
             }
             __syncthreads();

@@ -308,16 +308,42 @@ typedef enum {
  * float type.  out[b, f, m] is summed over the kept rows in ascending k, one fused multiply-add per term from an exact zero,
  * so a frame's result is bit-identical for any batch, first / count and grid.  The cost of the filterbank is proportional to
  * the sum of the spans: a dense matrix is correct but slow (there is no matrix-core path; a mel filter spans a handful of
- * bins).  Weights may be of either sign.  No log / dB stage and no mel-filter generator: out of scope.
- * mifft_plan_out_bytes() is batch * F * (M ? M : K) elements; mifft_exec_batch(first, count) offsets out by first * F *
- * (M ? M : K) reals; mifft_plan_pass_geometry(1), mifft_plan_num_launches() (1), mifft_plan_scratch_bytes() (0) and
+ * bins).  Weights may be of either sign.  A log / dB stage and a dense matrix after the bands (MFCC) travel in the tagged
+ * payload below; the mel filterbank and the DCT matrix themselves are made by the caller (the Python package has generators).
+ * mifft_plan_out_bytes() is batch * F * W elements, W = Q ? Q : (M ? M : K) (Q: the tagged payload, else 0);
+ * mifft_exec_batch(first, count) offsets out by first * F * W reals; mifft_plan_pass_geometry(1), mifft_plan_num_launches() (1), mifft_plan_scratch_bytes() (0) and
  * mifft_plan_in_bytes() are the STFT plan's.
  * MIFFT_ERR_UNSUPPORTED, before any device work: the bit without MIFFT_FLAG_STFT (alone, or with MIFFT_FLAG_ISTFT); every
  * refusal of an STFT plan, MIFFT_JIT=0 included.  MIFFT_ERR_BAD_BASES: a bases_len[0] of any other length (the reason names
  * bases_len[0]; NULL bases included: the power has to be given), a power other than 1 or 2 (the reason names the power), a
- * window value, power or filterbank weight that is not finite.  MIFFT_ERR_TOO_LARGE: M > MIFFT_STFT_MAX_BANDS. */
+ * window value, power or filterbank weight that is not finite.  MIFFT_ERR_TOO_LARGE: M > MIFFT_STFT_MAX_BANDS.
+ *
+ * The tagged payload: two optional stages after the filterbank, in the same launch.  With v the value above (per band, or per
+ * bin when M = 0),
+ *       y[m] = fma(a, log2(max(v[m] + add, amin)), c)          (log = 1; y = v otherwise)
+ *       z[q] = sum_m post[m, q] y[m],  q < Q                   (Q > 0, which needs M > 0)
+ * and out is (batch, F, W, 1), W = Q ? Q : (M ? M : K).  log10(max(v, 1e-10)) is a = log10(2), c = 0, add = 0, amin = 1e-10;
+ * decibels are a = 10 log10(2); torchaudio's log(v + 1e-6) is add = 1e-6, a = ln 2.  bases_len[0] is then exactly
+ * 2 (n + 9 + K M + M Q) words, binary64 values as above, in this order:
+ *       w[0 .. n-1] | TAG | power | M | Q | log | add | amin | a | c | fb (K, M) row-major | post (M, Q) row-major
+ * TAG is the one NaN with the bits MIFFT_STFT_EXT_TAG_HI : MIFFT_STFT_EXT_TAG_LO, in the slot where the untagged payload has
+ * its power (no valid untagged payload has a NaN there; any other NaN is the untagged payload's refusal of its power).  M, Q
+ * and log are non-negative integers written as binary64, log 0 or 1; add, amin, a and c are read only when log = 1 and are
+ * rounded once to the plan's float type.  The logarithm is the full-precision one, not a native approximation.  post is dense,
+ * rounded once to the plan's float type, and z[q] is summed over ascending m, one fused multiply-add per term from an exact
+ * zero: a frame's result stays bit-identical for any batch, first / count and grid.  The bands of a frame wait for the matrix
+ * in the unused halves of the frame's row in LDS, hence M <= n / 2 - 1 when Q > 0; launches stay 1 and scratch 0 (kernel
+ * suffixes _lg and _pm after _fb).  A tagged payload with log = 0 and Q = 0 makes the plan the untagged payload makes.  There
+ * is no top_db and no max - 8 clamp (both need the maximum over a whole entry): apply them to the small output.
+ * Refusals of a tagged payload, before any device work, each reason naming its field.  MIFFT_ERR_BAD_BASES: bases_len[0] of
+ * any other length; M, Q or log not finite, negative or not integral; log above 1; power not 1 or 2; with log = 1 an add that
+ * is not finite or is negative, an amin that is not positive or does not round to a normal number of the plan's float type, an
+ * a that is not finite or is zero, a c that is not finite; a filterbank or post weight that is not finite.
+ * MIFFT_ERR_UNSUPPORTED: Q > 0 with M = 0, or with M > n / 2 - 1.  MIFFT_ERR_TOO_LARGE: M or Q > MIFFT_STFT_MAX_BANDS. */
 #define MIFFT_FLAG_STFT_POWER 0x8000u
 #define MIFFT_STFT_MAX_BANDS 32768
+#define MIFFT_STFT_EXT_TAG_LO 0x46465401u
+#define MIFFT_STFT_EXT_TAG_HI 0x7FF84D49u
 
 typedef struct mifft_plan mifft_plan;
 

@@ -162,6 +162,11 @@ static_assert(MIFFT_FLAG_STFT_POWER == 0x8000u &&
                                             MIFFT_FLAG_DCT_ND | MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ORTHO | MIFFT_FLAG_HALF_SPECTRUM |
                                             MIFFT_FLAG_FAITHFUL_STAGES)) == 0,
               "MIFFT_FLAG_STFT_POWER is its own bit");
+// The tag of the extended payload of such a plan (log stage, matrix after the bands): a quiet NaN in the power slot.
+static_assert(MIFFT_STFT_EXT_TAG_LO == 0x46465401u && MIFFT_STFT_EXT_TAG_HI == 0x7FF84D49u &&
+                  (MIFFT_STFT_EXT_TAG_HI & 0x7FF80000u) == 0x7FF80000u,
+              "MIFFT_STFT_EXT_TAG is the quiet NaN 0x7FF84D4946465401");
+constexpr uint64_t kStftExtTag = ((uint64_t)MIFFT_STFT_EXT_TAG_HI << 32) | MIFFT_STFT_EXT_TAG_LO;
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
