@@ -17,6 +17,7 @@ import collections
 import ctypes
 import enum
 import hashlib
+import math
 import threading
 from typing import Optional, Sequence
 
@@ -47,6 +48,9 @@ FLAG_STFT_POWER = 0x8000       # MIFFT_FLAG_STFT_POWER: beside FLAG_STFT, real |
 STFT_EXT_TAG_LO = 0x46465401   # MIFFT_STFT_EXT_TAG_LO / _HI: the NaN in the power slot that selects the extended payload of such
 STFT_EXT_TAG_HI = 0x7FF84D49   # a plan (log stage, matrix after the bands)
 STFT_MAX_BANDS = 32768         # MIFFT_STFT_MAX_BANDS
+DCT_TYPE4_TAG = 0x44435434     # MIFFT_DCT_TYPE4_TAG: the first ``bases`` word of a FLAG_DCT plan that is a DCT-IV
+MDCT_TAG_LO = 0x43544401       # MIFFT_MDCT_TAG_LO / _HI: the NaN behind the window of a FLAG_STFT plan that is an MDCT
+MDCT_TAG_HI = 0x7FF84D44
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -482,15 +486,24 @@ class Plan:
     ``inverse=True`` implied; ``stft_center`` None / False or True / "reflect" / "constant" (centred: n // 2 samples trimmed
     at both ends), ``stft_window`` as above, ``istft_gain`` a factor on the synthesis window that stays out of the envelope
     (MIFFT_FLAG_ISTFT in include/mifft.h, _check_istft_layout, plan_istft).  ``bases`` has three lists: two empty ones and
-    the radices of n (or an empty one)."""
+    the radices of n (or an empty one).
+    ``dct_type=4`` beside ``dct=True`` (no reference counterpart): the DCT-IV instead, both directions the same kernel with
+    another scale, in_dtype == out_dtype; the request travels as MIFFT_DCT_TYPE4_TAG in front of the radices of n // 2.
+    ``mdct`` = M > 0 (no reference counterpart): the MDCT of real signals, x (batch, T, 1) -> out (batch, F, M, 1),
+    F = mdct_frames(T, M) frames of 2 M samples every M; ``stft_window`` None (the sine window) or 2 M values, ``mdct_scale``
+    the factor on the cosine sum (MIFFT_MDCT_TAG in include/mifft.h, _check_mdct_layout, plan_mdct).  ``bases`` has two
+    lists, an empty one and the radices of M // 2 (or an empty one)."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
-                 stft_post=None):
+                 stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
-        stft = int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT)
+        mdct = int(mdct)
+        if dct_type not in (2, 4):
+            raise MifftError(ERR_UNSUPPORTED, f"dct_type must be 2 or 4, got {dct_type!r}")
+        stft = not mdct and (int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT))
         istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
         words = None
         if istft:  # (with any other mode as well: the library refuses the pair)
@@ -547,6 +560,16 @@ class Plan:
                 flags = int(flags) | FLAG_STFT_POWER
             flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(stft_hop) | _stft_center_flags(stft_center) |
                      (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0))
+        if mdct:  # (with any other mode as well: the library refuses the pair)
+            stft_dims = _check_mdct_layout(in_shape, out_shape, mdct)
+            if axes is not None:
+                raise MifftError(ERR_UNSUPPORTED, "an MDCT plan frames dim 0 and transforms dim 1: no axes")
+            w = mdct_window(mdct) if stft_window is None else _window_f64(stft_window, 2 * mdct)
+            words = window_words(w) + [MDCT_TAG_LO, MDCT_TAG_HI] + window_words(torch.tensor([float(mdct_scale)], dtype=torch.float64))
+            flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(mdct) | FLAG_STFT_CENTER_ZEROS | (FLAG_ISTFT if istft else 0) |
+                     (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
+                     (FLAG_STFT_POWER if stft_power is not None else 0))
+            stft, istft = True, False
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
         dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
@@ -561,6 +584,10 @@ class Plan:
         elif dct:  # (with half_spectrum as well: the library refuses the pair)
             dims = _check_dct_layout(in_shape, out_shape)
             flags = int(flags) | FLAG_DCT | _dct_norm_flags(norm) | (FLAG_HALF_SPECTRUM if half_spectrum else 0)
+            if dct_type == 4:  # (the tag, then the radices of n // 2; the tag alone: the default estimate)
+                if bases is not None and len(bases) != 1:
+                    raise MifftError(-7, "the bases list of a DCT plan has one entry, the radices of n // 2")
+                bases = [[DCT_TYPE4_TAG] + ([int(b) for b in bases[0]] if bases is not None else [])]
         elif half_spectrum:
             dims = _check_half_layout(in_shape, out_shape, bool(inverse))
             flags = int(flags) | FLAG_HALF_SPECTRUM
@@ -582,7 +609,9 @@ class Plan:
         self.dctn = dctn
         self.stft = stft
         self.istft = istft
-        self.spectrogram = stft and stft_power is not None
+        self.spectrogram = stft and stft_power is not None and not mdct
+        self.dct_type = int(dct_type) if dct and not dctn and not stft and not istft else 2
+        self.mdct = mdct
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
@@ -679,7 +708,8 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
              inverse: bool = False, runtime_twfs: bool = True, max_cluster_size: int = 8,
              _test: Optional[GPUTest] = None, faithful_stages: bool = False,
              ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False,
-             axes: Optional[Sequence[int]] = None, dct: bool = False, norm=None, dctn: bool = False) -> Plan:
+             axes: Optional[Sequence[int]] = None, dct: bool = False, norm=None, dctn: bool = False,
+             dct_type: int = 2) -> Plan:
     """GPU overload of plan_fft (fft/fft/fft.mojo:161-210).
 
     ``runtime_twfs`` and ``max_cluster_size`` are accepted for call-site compatibility
@@ -694,7 +724,8 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     are carried through untransformed (include/mifft.h, MIFFT_FLAG_KEEP_DIM).
     ``dct`` (no reference counterpart): DCT-II (``inverse``: its inverse) of the real rows of a (batch, n, 1) tensor into
     one of the same shape, ``norm`` None / "backward" / "ortho" as scipy.fft.dct (include/mifft.h, MIFFT_FLAG_DCT); ``bases``
-    then factor n // 2, the packed transform the plan runs.
+    then factor n // 2, the packed transform the plan runs.  ``dct_type=4`` beside ``dct``: the DCT-IV (scipy's type 4; its
+    own inverse up to the scale, in_dtype == out_dtype in both directions, MIFFT_DCT_TYPE4_TAG); the default is 2.
     ``dctn`` (no reference counterpart): the N-D DCT-II (``inverse``: its inverse) of a real (batch, d0.., 1) tensor into one of
     the same shape, over ``axes`` (None: every dim), ``norm`` as for ``dct`` (include/mifft.h, MIFFT_FLAG_DCT_ND).
     """
@@ -705,6 +736,8 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     elif dct:
         _check_dct_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout))
         _dct_norm_flags(norm)
+        if dct_type not in (2, 4):
+            raise MifftError(ERR_UNSUPPORTED, f"dct_type must be 2 or 4, got {dct_type!r}")
     elif half_spectrum:
         _check_half_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout), bool(inverse))
     _keep_flags(len(out_layout), axes)
@@ -713,7 +746,7 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     flags = FLAG_FAITHFUL_STAGES if (faithful_stages or _test is not None) else 0
     return Plan(in_dtype, out_dtype, in_layout, out_layout, bases=bases, inverse=inverse,
                 device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum, axes=axes,
-                dct=dct, norm=norm, dctn=dctn)
+                dct=dct, norm=norm, dctn=dctn, dct_type=dct_type if dct and not dctn else 2)
 
 
 def plan_stft(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, window=None, center=None,
@@ -911,7 +944,7 @@ _PLAN_CACHE_LOCK = threading.RLock()
 
 
 def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                 half_spectrum: bool = False, axes=None, dct_flags: int = 0) -> Plan:
+                 half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2) -> Plan:
     """Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
     costs a hipMalloc + copy per dimension, and its tables must outlive the kernels enqueued with it.
 
@@ -921,23 +954,26 @@ def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, fai
     two threads on their own streams) transforming the same shape never share a plan -- and is guarded by a lock."""
     with _PLAN_CACHE_LOCK:
         return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                                   half_spectrum, axes, dct_flags)
+                                   half_spectrum, axes, dct_flags, dct_type)
 
 
 def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                        half_spectrum: bool = False, axes=None, dct_flags: int = 0) -> Plan:
-    # dct_flags: FLAG_DCT or FLAG_DCT_ND (| FLAG_DCT_ORTHO) of the dct / idct / dctn / idctn wrappers' plans, 0 for every other
+                        half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2) -> Plan:
+    # dct_flags: FLAG_DCT or FLAG_DCT_ND (| FLAG_DCT_ORTHO) of the dct / idct / dctn / idctn wrappers' plans, 0 for every other;
+    # dct_type: 4 for the DCT-IV plans of dct / idct (the key of every other plan is what it has always been)
     key = (in_dtype, out_dtype, in_shape, out_shape,
            None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
            bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
            bool(half_spectrum), _keep_flags(len(out_shape), axes), int(dct_flags))
+    if dct_type != 2:
+        key += (int(dct_type),)
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         try:
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
                             faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
                             axes=axes, dct=bool(dct_flags & FLAG_DCT), dctn=bool(dct_flags & FLAG_DCT_ND),
-                            norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None)
+                            norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None, dct_type=dct_type)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
             # primes <= 97 otherwise, fft/fft/fft.mojo:49-104) rejects lengths with a larger prime factor.  The
@@ -1173,8 +1209,8 @@ def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtyp
 def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: bool) -> "torch.Tensor":
     """dct / idct: validation on the host, then one plan over the (batch, n, 1) view of ``x``"""
     name = "idct" if inverse else "dct"
-    if type != 2:
-        raise MifftError(ERR_UNSUPPORTED, f"{name}: only type 2 is supported, got type={type!r}")
+    if type not in (2, 4):
+        raise MifftError(ERR_UNSUPPORTED, f"{name}: only types 2 and 4 are supported, got type={type!r}")
     dct_flags = FLAG_DCT | _dct_norm_flags(norm)
     if x.is_complex():
         raise MifftError(-3, f"{name} expects a real tensor")
@@ -1201,13 +1237,14 @@ def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: 
         raise MifftError(-4, f"{name}: unsupported input dtype {x.dtype}")
     shape = (batch, n, 1)
     _check_dct_layout(shape, shape)
-    if inverse:
-        x = x.to(out_dtype)  # (the inverse reads the plan's own float type)
+    if inverse or type == 4:
+        x = x.to(out_dtype)  # (the inverse, and the DCT-IV in both directions, read the plan's own float type)
     xr = x.contiguous().reshape(shape)
     device = DeviceContext(xr.device.index if xr.is_cuda else None).device
     out = torch.empty(shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device, dct_flags=dct_flags)
+        plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device, dct_flags=dct_flags,
+                                   dct_type=int(type))
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical)
 
@@ -1216,15 +1253,19 @@ def dct(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: int
     """scipy.fft.dct(x, type=2, norm=norm) along the last dim of a real tensor of any rank >= 1 (an even length from 8 on):
     ``X[k] = 2 sum_j x[j] cos(pi k (2j+1) / 2n)``; ``norm="ortho"`` scales X[0] by sqrt(1/4n) and the other bins by sqrt(1/2n).
     The leading dims fold into the batch; the result has the shape of ``x`` and dtype ``out_dtype`` (default: that of a float32 /
-    float64 ``x``, else float64).  One kernel launch: n reals read once, n reals written once (MIFFT_FLAG_DCT).  Only
-    ``type=2``, and ``dim`` must be the innermost dim of size above 1 (MifftError -15 otherwise)."""
+    float64 ``x``, else float64).  One kernel launch: n reals read once, n reals written once (MIFFT_FLAG_DCT).
+    ``type=4`` is scipy's DCT-IV, ``X[k] = 2 sum_j x[j] cos(pi (2j+1)(2k+1) / 4n)``, ``norm="ortho"`` times sqrt(1/2n) (then
+    its own inverse): one n // 2-point complex transform between two twiddles, the same limits, one launch; its input is
+    converted to ``out_dtype`` first (MIFFT_DCT_TYPE4_TAG).  Only ``type=2`` and ``type=4``, and ``dim`` must be the innermost
+    dim of size above 1 (MifftError -15 otherwise)."""
     return _dct_rows(x, type, norm, out_dtype, dim, False)
 
 
 def idct(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: int = -1) -> "torch.Tensor":
     """scipy.fft.idct(x, type=2, norm=norm), the inverse of dct under the same ``norm``:
     ``x[j] = (X[0] + 2 sum_{k>=1} X[k] cos(pi k (2j+1) / 2n)) / 2n``.  Same layout, ``dim`` and dtype rules as dct; the input
-    is converted to ``out_dtype`` first."""
+    is converted to ``out_dtype`` first.  ``type=4``: dct(x, 4) / 2n (``norm="ortho"``: the orthonormal DCT-IV itself), the same
+    kernel as the forward with another scale."""
     return _dct_rows(x, type, norm, out_dtype, dim, True)
 
 
@@ -1282,6 +1323,189 @@ def idctn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=No
     """scipy.fft.idctn(x, type=2, norm=norm), the inverse of dctn under the same ``norm`` and ``dim``; the input is converted
     to ``out_dtype`` first."""
     return _dct_nd(x, type, norm, dim, out_dtype, True)
+
+
+def mdct_frames(length: int, n: int) -> int:
+    """Frames an MDCT of ``n`` coefficients per frame makes of ``length`` samples: ceil(length / n) + 1.  Frame f covers the
+    samples [(f - 1) n, (f + 1) n) with zeros outside [0, length), so every sample lies in two frames.  Pure host arithmetic."""
+    length, n = int(length), int(n)
+    if n < 1 or length < 1:
+        raise MifftError(-2, f"mdct_frames: length and n are positive, got {length} and {n}")
+    return (length + n - 1) // n + 1
+
+
+def mdct_window(n: int) -> "torch.Tensor":
+    """The sine window of an MDCT of ``n`` coefficients, sin(pi (j + 1/2) / 2n) for j < 2n, float64 on the host: it satisfies
+    w[j] ** 2 + w[j + n] ** 2 = 1 (perfect reconstruction through imdct)."""
+    n = int(n)
+    if n < 1:
+        raise MifftError(-2, f"mdct_window: n is positive, got {n}")
+    return torch.sin(math.pi * (torch.arange(2 * n, dtype=torch.float64) + 0.5) / (2 * n))
+
+
+def _mdct_fold_tables(n: int):
+    """The fold of a frame of 2n windowed samples y to the n values u whose DCT-IV is twice the MDCT: u = sa * y[ia] + sb * y[ib]
+    (u[i] = -y[3h-1-i] - y[3h+i] and u[h+i] = y[i] - y[n-1-i] for i < h = n // 2).  Returns (ia, sa, ib, sb), int64 / float64."""
+    h = n // 2
+    i = torch.arange(h, dtype=torch.int64)
+    ia = torch.cat([3 * h - 1 - i, i])
+    ib = torch.cat([3 * h + i, n - 1 - i])
+    one = torch.ones(h, dtype=torch.float64)
+    return ia, torch.cat([-one, one]), ib, torch.cat([-one, -one])
+
+
+def _mdct_unfold_tables(n: int):
+    """The unfold of v = DCT-IV(X) / 2 (n values) to the 2n samples of a frame, y[j] = sign[j] * v[idx[j]]:
+    y[i] = v[h+i], y[n-1-i] = -v[h+i], y[3h-1-i] = -v[i], y[3h+i] = -v[i] for i < h = n // 2.  Returns (idx, sign)."""
+    h = n // 2
+    i = torch.arange(h, dtype=torch.int64)
+    idx = torch.empty(2 * n, dtype=torch.int64)
+    sign = torch.empty(2 * n, dtype=torch.float64)
+    idx[i], sign[i] = h + i, 1.0
+    idx[n - 1 - i], sign[n - 1 - i] = h + i, -1.0
+    idx[3 * h - 1 - i], sign[3 * h - 1 - i] = i, -1.0
+    idx[3 * h + i], sign[3 * h + i] = i, -1.0
+    return idx, sign
+
+
+def _mdct_n(n, who: str) -> int:
+    n = int(n)
+    if n % 2 or n < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"{who} with an odd n or one below 8 ({n}) is not supported")
+    FLAG_STFT_HOP(n)
+    return n
+
+
+def _mdct_norm_scale(norm, n: int, who: str) -> float:
+    """the factor on the plain cosine sum: 1, or sqrt(2 / n) for ``norm="ortho"`` (the orthonormal DCT-IV of the folded frame)"""
+    if norm is None or norm == "backward":
+        return 1.0
+    if norm == "ortho":
+        return math.sqrt(2.0 / n)
+    raise MifftError(ERR_UNSUPPORTED, f"{who}: norm must be None, \"backward\" or \"ortho\", got {norm!r}")
+
+
+def _check_mdct_layout(in_shape: tuple, out_shape: tuple, n: int) -> tuple:
+    """Layouts of an MDCT plan (MIFFT_MDCT_TAG): x (batch, T, 1) real -> out (batch, F, n, 1) real with F = mdct_frames(T, n);
+    returns the dims (T, 2n)."""
+    if len(in_shape) != 3 or len(out_shape) != 4:
+        raise MifftError(-1, f"MDCT layouts are (batch, T, 1) -> (batch, F, n, 1), got {in_shape} -> {out_shape}")
+    if in_shape[-1] != 1 or out_shape[-1] != 1:
+        raise MifftError(-3, f"both sides of an MDCT plan have 1 component, got {in_shape[-1]} and {out_shape[-1]}")
+    if in_shape[0] != out_shape[0]:
+        raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
+    n = _mdct_n(n, "MDCT")
+    T = in_shape[1]
+    if T < 2:
+        raise MifftError(-2, f"signals of {T} samples: at least 2")
+    if out_shape[2] != n or out_shape[1] != mdct_frames(T, n):
+        raise MifftError(-2, f"{T} samples make {mdct_frames(T, n)} frames of {n} coefficients, out is {out_shape}")
+    return (T, 2 * n)
+
+
+def plan_mdct(dtype, batch: int, length: int, n: int, *, window=None, norm=None, ctx: Optional[DeviceContext] = None,
+              whole_batch: int = 0) -> Plan:
+    """Plan of the MDCT of ``batch`` real signals of ``length`` samples (no reference counterpart; MIFFT_MDCT_TAG in
+    include/mifft.h): ``n`` coefficients per frame of 2n samples, frames every n samples, multiplied by ``window`` (None: the
+    sine window mdct_window(n); else 2n values, taken by value when the plan is made).  ``in_shape`` (batch, length, 1),
+    ``out_shape`` (batch, mdct_frames(length, n), n, 1), both of ``dtype`` (float32 / float64); runs through
+    ``fft(out, x, plan=plan)``, ``first=`` / ``count=`` included: one kernel launch, no padded copy, no tensor of frames.
+    ``norm`` None / "backward" (the plain cosine sum) or "ortho" (times sqrt(2 / n)).  Every argument error is raised before
+    any device work."""
+    batch, length = int(batch), int(length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"an MDCT plan reads and writes float32 or float64, got {dtype}")
+    n = _mdct_n(n, "MDCT")
+    scale = _mdct_norm_scale(norm, n, "plan_mdct")
+    in_shape, out_shape = (batch, length, 1), (batch, mdct_frames(max(length, 1), n), n, 1)
+    _check_mdct_layout(in_shape, out_shape, n)
+    if window is not None:
+        window = _window_f64(window, 2 * n)
+    if ctx is None:
+        ctx = DeviceContext()
+    return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, mdct=n, mdct_scale=scale,
+                stft_window=window)
+
+
+def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -> "torch.Tensor":
+    """The MDCT of a real ``x`` of shape (T,) or (..., T) with ``n`` coefficients per frame (frames of 2n samples every n):
+    ``X[f, k] = sum_{j<2n} w[j] x~[(f - 1) n + j] cos(pi / n (j + 1/2 + n/2)(k + 1/2))``, x~ being x with zeros outside
+    [0, T).  Returns (..., F, n) contiguous, F = mdct_frames(T, n); the leading dims fold into the batch.  ``window=None`` is
+    the sine window; a tensor or sequence of 2n values is taken by value.  ``norm="ortho"`` multiplies by sqrt(2 / n) (the
+    orthonormal DCT-IV of the folded frame).  n is even, from 8 to 16384 (float64: 8192), n // 2 without a prime factor above
+    32.  Input that is not of ``out_dtype`` (default: that of a float32 / float64 ``x``, else float64) is converted first.
+    One kernel launch: the framing, the window and the fold of 2n samples to n happen in the load of a DCT-IV tile.  Plans are
+    cached per (shape, dtype, n, norm, device, stream) and the window's contents; loops should use ``plan_mdct``."""
+    if x.is_complex():
+        raise MifftError(-3, "mdct expects a real tensor")
+    if x.dim() < 1:
+        raise MifftError(-1, "mdct expects a tensor of rank 1 or more: (T,) or (..., T)")
+    n = _mdct_n(n, "mdct")
+    scale = _mdct_norm_scale(norm, n, "mdct")
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if out_dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"mdct: out_dtype must be float32 or float64, got {out_dtype}")
+    logical = tuple(x.shape)
+    T = logical[-1]
+    batch = 1
+    for m in logical[:-1]:
+        batch *= m
+    if T < 2:
+        raise MifftError(-2, f"mdct: signals of {T} samples: at least 2")
+    frames = mdct_frames(T, n)
+    in_shape, out_shape = (batch, T, 1), (batch, frames, n, 1)
+    w = None if window is None else _window_f64(window, 2 * n)
+    device = DeviceContext(x.device.index if x.is_cuda else None).device
+    if not x.is_cuda or x.device.index != device:
+        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    xr = x.to(out_dtype).contiguous().reshape(in_shape)
+    out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
+    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
+    with _PLAN_CACHE_LOCK:
+        key = ("mdct", out_dtype, in_shape, n, scale, digest, device, int(torch.cuda.current_stream(device).cuda_stream))
+        plan = _PLAN_CACHE.get(key)
+        if plan is None:
+            plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, mdct=n, mdct_scale=scale, stft_window=w)
+            _plan_cache_insert(key, plan)
+        else:
+            _PLAN_CACHE.move_to_end(key)
+        fft(out, xr, DeviceContext(device), plan=plan)
+    return out.reshape(logical[:-1] + (frames, n))
+
+
+def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = None) -> "torch.Tensor":
+    """The inverse of ``mdct`` under the same ``window`` and ``norm``: X of shape (..., F, n) real -> (..., length),
+    ``length`` defaulting to (F - 1) n.  A window with w[j] ** 2 + w[j + n] ** 2 = 1 (the default sine window, KBD, Vorbis)
+    reproduces the signal exactly (time-domain aliasing cancellation).
+    This is a COMPOSITION, not a fused kernel: one DCT-IV launch (``dct(X, type=4)``) plus torch -- a gather with a
+    precomputed index / sign table that unfolds the n values of a frame to its 2n samples, the product with the window
+    ((2 / n) w, or w under ``norm="ortho"``), two shifted adds of the half-frames into a (..., (F + 1) n) buffer (the hop
+    equals n, so no ``fold`` is needed) and the slice [n, n + length).  A fused IMDCT needs the inverse STFT's
+    overlap-adding store generalised to a row shorter than its frame and is not provided."""
+    if X.is_complex():
+        raise MifftError(-3, "imdct expects a real tensor")
+    if X.dim() < 2:
+        raise MifftError(-1, "imdct expects a tensor of rank 2 or more: (F, n) or (..., F, n)")
+    F, n = int(X.shape[-2]), _mdct_n(X.shape[-1], "imdct")
+    ortho = _mdct_norm_scale(norm, n, "imdct") != 1.0
+    if F < 2:
+        raise MifftError(-2, f"imdct: at least 2 frames, got {F}")
+    length = (F - 1) * n if length is None else int(length)
+    if not 1 <= length <= (F - 1) * n:
+        raise MifftError(-2, f"imdct: {F} frames of {n} coefficients cover 1 .. {(F - 1) * n} samples, length is {length}")
+    w = mdct_window(n) if window is None else _window_f64(window, 2 * n)
+    dt = X.dtype if X.dtype in _OUT_DTYPES else torch.float64
+    # v = DCT-IV(X) / 2 (ortho: the orthonormal DCT-IV itself), then y = (2 / n) w * unfold(v) (ortho: w * unfold(v))
+    v = dct(X.to(dt), type=4, norm="ortho" if ortho else None)
+    idx, sign = _mdct_unfold_tables(n)
+    gain = sign * w * (1.0 if ortho else 1.0 / n)  # (the 1 / 2 of v and the 2 / n of the synthesis in one table)
+    y = v.index_select(-1, idx.to(v.device)) * gain.to(device=v.device, dtype=dt)
+    out = torch.zeros(tuple(X.shape[:-2]) + ((F + 1) * n,), dtype=dt, device=v.device)
+    lead = tuple(X.shape[:-2])
+    out[..., :F * n] += y[..., :n].reshape(lead + (F * n,))
+    out[..., n:] += y[..., n:].reshape(lead + (F * n,))
+    return out[..., n:n + length].contiguous()
 
 
 def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None, window=None,

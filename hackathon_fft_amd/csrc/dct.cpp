@@ -4,6 +4,9 @@
 // tile whose load applies Makhoul's even / odd permutation on the LDS side and whose unpacking loop multiplies by the
 // quarter-sample twiddle W_4n^k and stores reals; the inverse is the mirror on a C2R tile (tile_kernel.h, TileCfg::DCT).  Both
 // sides of the plan are (batch, n, 1) real tensors, so every size-dependent choice sees batch * n real elements.
+//
+// A plan whose `bases` start with MIFFT_DCT_TYPE4_TAG (Plan::dct4) is a DCT-IV: a complex row tile of n / 2 points between the
+// twiddles p_m = e^(-i pi (8m+1) / 8n), the same kernel in both directions with another scale (TileCfg::DCT = 4).
 #include <cmath>
 
 #include "mifft_config.h"
@@ -33,6 +36,10 @@ int dct_check(const Plan& p, std::string& why) {
         why = "MIFFT_FLAG_DCT transforms the rows of a (batch, n, 1) tensor: ndim must be 1, not " + std::to_string(p.ndim);
         return MIFFT_ERR_UNSUPPORTED;
     }
+    if (p.dct4 && p.in_dtype != p.out_dtype) {
+        why = "a DCT-IV reads the plan's own float type in both directions (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
     if (p.inverse && p.in_dtype != p.out_dtype) {
         why = "an inverse DCT reads the plan's own float type (in_dtype == out_dtype)";
         return MIFFT_ERR_BAD_DTYPE;
@@ -47,6 +54,13 @@ int dct_check(const Plan& p, std::string& why) {
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
+    if (p.dct4) {
+        if (!dct4_rows_supported(p, n, w)) {
+            why = "DCT-IV of " + std::to_string(n) + " points: " + w;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+        return MIFFT_OK;
+    }
     if (!dct_rows_supported(p, n, w)) {
         why = "DCT of " + std::to_string(n) + " points: " + w;
         return MIFFT_ERR_UNSUPPORTED;
@@ -71,6 +85,53 @@ static hipError_t upload_quarter_table_t(int64_t n, void** d_table) {
 
 hipError_t upload_quarter_table(int out_dtype, int64_t n, void** d_table) {
     return out_dtype == MIFFT_F64 ? upload_quarter_table_t<double>(n, d_table) : upload_quarter_table_t<float>(n, d_table);
+}
+
+// p_m = e^(-i pi (8m+1) / 8n), m = 0 .. n / 2 - 1: the pre- and the post-twiddle of a DCT-IV of n points, evaluated in long
+// double and rounded once
+template <typename T>
+static hipError_t upload_dct4_table_t(int64_t n, void** d_table) {
+    const long double pi = 3.141592653589793238462643383279502884L;
+    std::vector<T> tab((size_t)(n / 2) * 2);
+    for (int64_t m = 0; m < n / 2; ++m) {
+        const long double th = -pi * (long double)(8 * m + 1) / (long double)(8 * n);
+        tab[2 * m] = (T)cosl(th);
+        tab[2 * m + 1] = (T)sinl(th);
+    }
+    hipError_t e = hipMalloc(d_table, tab.size() * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(*d_table, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
+hipError_t upload_dct4_table(int out_dtype, int64_t n, void** d_table) {
+    return out_dtype == MIFFT_F64 ? upload_dct4_table_t<double>(n, d_table) : upload_dct4_table_t<float>(n, d_table);
+}
+
+// the one scale of a DCT-IV: X = 2 sum, "ortho" times sqrt(1 / 2n) in both directions; the plain inverse divides by 2n
+static double dct4_scale(int64_t n, bool inverse, bool ortho) {
+    const long double dn = (long double)n;
+    return (double)(ortho ? 2.0L * sqrtl(1.0L / (2.0L * dn)) : inverse ? 1.0L / dn : 2.0L);
+}
+
+// the DCT-IV pass of n points over `outer` rows per batch entry: kernel, scale and tables; appended to plan.passes
+static int build_dct4_rows(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    const int64_t n = p.dims[0];
+    DimPass ps;
+    ps.dim_index = 0;
+    ps.N = n;
+    ps.inner = 1;
+    ps.outer = 1;
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    if (!select_jit_dct4_rows(p, ps, /*mdct=*/false, why)) return MIFFT_ERR_UNSUPPORTED;
+    ps.dct_s0 = ps.dct_s1 = dct4_scale(n, p.inverse != 0, (p.flags & MIFFT_FLAG_DCT_ORTHO) != 0);
+    // the passes run n / 2 points, forward in both directions
+    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, n, &ps.d_aux2);
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "DCT-IV table upload");
+    return MIFFT_OK;
 }
 
 // the scales of bin 0 and of the other bins.  Forward: X[k] = 2 Re(..), "ortho" times sqrt(1 / 4n) and sqrt(1 / 2n).
@@ -113,6 +174,7 @@ int build_dct_rows(Plan& p, int dim_index, int64_t outer, const std::vector<uint
 }
 
 int build_dct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    if (p.dct4) return build_dct4_rows(p, ordered, processed, why);
     return build_dct_rows(p, 0, 1, ordered, processed, why);
 }
 

@@ -35,6 +35,7 @@ size_t Plan::in_row_bytes() const {
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
+    if (stft() && mdct) return (size_t)(stft_frames() * mdct) * dtype_size(out_dtype);
     if (stft() && spec_power) return (size_t)(stft_frames() * stft_out_width()) * dtype_size(out_dtype);
     if (stft()) return (size_t)prod_half * out_elem_bytes();
     if (istft()) return (size_t)dims[0] * dtype_size(out_dtype);
@@ -252,13 +253,17 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         std::vector<double> window, fb, post;
         std::vector<uint64_t> user;
         double gain = 1.0;
-        int rc = fwd ? stft_check(p, why) : istft_check(p, bases_flat, bases_len, window, gain, user, why);
+        // (a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points)
+        const bool mdct = fwd && mdct_detect(ndim, dims, bases_flat, bases_len);
+        int rc = mdct  ? mdct_check(p, bases_flat, bases_len, window, user, why)
+                 : fwd ? stft_check(p, why)
+                       : istft_check(p, bases_flat, bases_len, window, gain, user, why);
         if (rc) return fail(rc, why);
         const int td = ndim - 1;  // the transformed dim
-        const int64_t n = dims[td], frames = fwd ? p.stft_frames() : dims[1];
-        p.prod = frames * n;  // (the rows the one pass transforms)
-        p.prod_half = frames * (n / 2 + 1);
-        if (fwd) {
+        const int64_t n = mdct ? dims[td] / 4 : dims[td], frames = fwd ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
+        p.prod = frames * (mdct ? p.mdct : n);  // (the rows the one pass transforms)
+        p.prod_half = mdct ? p.prod : frames * (n / 2 + 1);
+        if (fwd && !mdct) {
             rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, post, user, why);
             if (rc) return fail(rc, why);
         }
@@ -279,8 +284,9 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) p.num_cus = prop.multiProcessorCount;
         config_refresh();
-        rc = fwd ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
-                 : build_istft(p, ordered[td], processed[td], window, gain, why);
+        rc = mdct  ? build_mdct(p, ordered[td], processed[td], window, why)
+             : fwd ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
+                   : build_istft(p, ordered[td], processed[td], window, gain, why);
         if (rc) return fail(rc, why);
         *out_plan = h;
         return MIFFT_OK;
@@ -288,6 +294,11 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
     // ---- DCT plans (MIFFT_FLAG_DCT; dct.cpp): everything that can be refused without a device, before anything else ----
     if ((flags & MIFFT_FLAG_DCT_ORTHO) && !(flags & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ND)))
         return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND");
+    // (a MIFFT_FLAG_DCT plan whose first `bases` word is MIFFT_DCT_TYPE4_TAG is a DCT-IV; the radices of n / 2 follow the tag)
+    const bool dct4 = (flags & MIFFT_FLAG_DCT) && !(flags & MIFFT_FLAG_DCT_ND) && bases_flat && bases_len && bases_len[0] >= 1 &&
+                      bases_flat[0] == MIFFT_DCT_TYPE4_TAG;
+    if ((flags & MIFFT_FLAG_DCT_ND) && bases_flat && bases_len && bases_len[0] >= 1 && bases_flat[0] == MIFFT_DCT_TYPE4_TAG)
+        return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_DCT_TYPE4_TAG with MIFFT_FLAG_DCT_ND: the N-D DCT has no type 4");
     if (flags & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ND)) {  // (N-D plans, dctn.cpp: the same, and before the keep bits are looked at)
         Plan t;
         t.in_dtype = in_dtype;
@@ -301,6 +312,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         t.in_components = in_components;
         t.inverse = inverse ? 1 : 0;
         t.flags = flags;
+        t.dct4 = dct4;
         std::string why;
         const int rc = (flags & MIFFT_FLAG_DCT_ND) ? dctn_check(t, why) : dct_check(t, why);
         if (rc) return set_error(rc, why);
@@ -331,6 +343,7 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
     p.in_components = in_components;
     p.inverse = inverse ? 1 : 0;
     p.flags = flags;
+    p.dct4 = dct4;
     p.prod = 1;
     for (int i = 0; i < ndim; ++i) {
         p.dims[i] = dims[i];
@@ -350,13 +363,14 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
                 return set_error(MIFFT_ERR_NO_BASES, "negative bases_len");
             }
             for (int k = 0; k < bases_len[i]; ++k) user.push_back(*bp++);
+            if (dct4 && i == 0) user.erase(user.begin());  // (the tag; alone it selects the default estimate, below)
         } else {
             user = plan_estimate_bases((uint64_t)dims[i], /*gpu_target=*/true);
         }
         std::string err;
         // (a DCT plan runs, and reports, the stages of its packed n / 2-point transform: for its rows, the last dimension)
         const bool packed = p.dct() || (p.dct_nd() && i == ndim - 1);
-        if (packed && !bases_flat) user = plan_estimate_bases((uint64_t)dims[i] / 2, /*gpu_target=*/true);
+        if (packed && (!bases_flat || (dct4 && user.empty()))) user = plan_estimate_bases((uint64_t)dims[i] / 2, /*gpu_target=*/true);
         int rc = plan_ordered_bases((uint64_t)dims[i] / (packed ? 2 : 1), user, ordered[i], processed[i], err);
         if (rc) {
             delete h;

@@ -96,7 +96,11 @@ struct DimPass {
     // TileCfg::DCT of a packed-row pass (2: DCT-II on an r2c kernel, 3: its inverse on a c2r one) or of a paired-column pass
     // (neither r2c nor c2r; `inner` counts pairs of real columns): d_aux2 holds W_4N^k, k = 0 .. N / 2; the scales of bin 0
     // and of the other bins (TileParams::dct_s0 / dct_s1)
+    // 4 (DCT-IV): neither r2c nor c2r; the kernel runs N / 2 complex points over rows of N reals, d_twiddle is that forward
+    // table, d_aux2 holds p_m = e^(-i pi (8m+1) / 8N), m < N / 2, and dct_s1 the one scale.  mdct: the rows are the `outer`
+    // lapped frames of every batch entry (TileCfg::MDCT); d_aux3 holds the window, 2 N values of the plan's float type
     int dct = 0;
+    bool mdct = false;
     double dct_s0 = 1.0, dct_s1 = 1.0;
     // TileCfg::STFT of a packed-row pass: the rows are the `outer` frames of every batch entry (hop, length and centring are the
     // plan's); d_aux2 holds the window, N values of the plan's float type
@@ -168,7 +172,17 @@ struct Plan {
     bool stft() const { return (flags & MIFFT_FLAG_STFT) != 0; }
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
-    int64_t stft_frames() const { return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop(); }
+    int64_t stft_frames() const {
+        if (mdct) return (dims[0] + mdct - 1) / mdct + 1;
+        return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop();
+    }
+    // the payload of such a plan tagged with MIFFT_MDCT_TAG: an MDCT of mdct = M = dims[1] / 2 coefficients per frame.
+    // Frame f covers the samples [(f - 1) M, (f + 1) M) of its entry, F = ceil(T / M) + 1 frames; out is (batch, F, M, 1)
+    // real, mdct_scale times the cosine sum over the windowed frame.  0: not one.  Set by mdct_detect.
+    int64_t mdct = 0;
+    double mdct_scale = 1.0;
+    // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
+    bool dct4 = false;
     // MIFFT_FLAG_STFT_POWER on such a plan: out is real, (batch, F, n / 2 + 1, 1) of |X|^spec_power (1 or 2), or
     // (batch, F, spec_bands, 1) after a filterbank of spec_bands > 0 bands; stft_out_width() reals per frame.  0: the flag is
     // not set.  Filled by stft_unpack_bases.
@@ -292,6 +306,10 @@ int build_half_spectrum(Plan& plan, const std::vector<std::vector<uint32_t>>& or
 bool dct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_dct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 int dct_check(const Plan& plan, std::string& why);
+// DCT-IV rows (TileCfg::DCT = 4; compiled at run time only) and, with `mdct`, the lapped frames of an MDCT plan
+bool dct4_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_dct4_rows(const Plan& plan, DimPass& pass, bool mdct, std::string& why_not);
+hipError_t upload_dct4_table(int out_dtype, int64_t n, void** d_table);
 int build_dct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 // ... its pieces, shared with the N-D plans: the packed-row pass over dimension dim_index (`outer` rows per batch entry), the
 // scales of bin 0 and of the other bins, the table W_4n^k, k = 0 .. n / 2
@@ -324,6 +342,15 @@ int stft_unpack_bases(Plan& plan, const uint32_t* bases_flat, const int32_t* bas
 int build_stft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                const std::vector<double>& window, const std::vector<double>& fb, const std::vector<double>& post,
                std::string& why);
+// MDCT plans (the MIFFT_FLAG_STFT payload tagged with MIFFT_MDCT_TAG; stft.cpp).  mdct_detect: is bases_len[0] the tagged
+// length 2 dims[1] + 4 with the tag behind the window?  (Pure; it looks at nothing else.)  mdct_check: everything that can be
+// refused without a device, leaving the window, the scale (plan.mdct_scale) and the user radices of M / 2 in its outputs.
+// build_mdct: the one pass, a DCT-IV tile with the framing, folding load.
+bool mdct_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len);
+int mdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+               std::vector<uint64_t>& radices, std::string& why);
+int build_mdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+               const std::vector<double>& window, std::string& why);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }

@@ -321,6 +321,119 @@ static hipError_t upload_window_t(int64_t n, const std::vector<double>& window, 
     return e;
 }
 
+// ---- MDCT plans: the payload w[0 .. 2M-1] | MIFFT_MDCT_TAG | scale ------------------------------------------------------------
+bool mdct_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 2 || !dims || !bases_flat || !bases_len || dims[1] < 2 || dims[1] > (1 << 20)) return false;
+    const int64_t n = dims[1];
+    return (int64_t)bases_len[0] == 2 * n + 4 && bases_flat[2 * n] == MIFFT_MDCT_TAG_LO && bases_flat[2 * n + 1] == MIFFT_MDCT_TAG_HI;
+}
+
+int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+               std::vector<uint64_t>& radices, std::string& why) {
+    const struct {
+        uint32_t bits;
+        const char* what;
+    } other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: an MDCT has no magnitude or power store"},
+                 {MIFFT_FLAG_STFT_CENTER_REFLECT, "MIFFT_FLAG_STFT_CENTER_REFLECT: the frames of an MDCT see zeros beyond both ends"},
+                 {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no MDCT to be faithful to"},
+                 {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an MDCT has no half spectrum"},
+                 {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
+                 {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
+                 {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO: the norm of an MDCT travels as the scale of its payload"},
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an MDCT plan frames dim 0 and transforms dim 1"},
+                 {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
+    for (const auto& o : other)
+        if (p.flags & o.bits) {
+            why = std::string("an MDCT payload (MIFFT_MDCT_TAG) with ") + o.what;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+    if (!(p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS)) {
+        why = "an MDCT payload (MIFFT_MDCT_TAG) without a centre bit: MIFFT_FLAG_STFT_CENTER_ZEROS is required";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    const int64_t T = p.dims[0], n = p.dims[1], M = n / 2;
+    if (n % 2 != 0) {
+        why = "an MDCT frame has 2 M samples: dims[1] = " + std::to_string(n) + " is odd";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.stft_hop() != M) {
+        why = "the hop of an MDCT plan is M = dims[1] / 2 = " + std::to_string(M) + " (MIFFT_FLAG_STFT_HOP), not " +
+              std::to_string(p.stft_hop());
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.inverse) {
+        why = "the inverse MDCT is not routed (inverse must be 0)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 1) {
+        why = "an MDCT reads real signals (in_components = 1)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.in_dtype != p.out_dtype) {
+        why = "an MDCT reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    if (T >= (1ll << 31)) {
+        why = "signals of 2^31 samples or more (" + std::to_string(T) + "): the frames are addressed in 32 bits";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (M % 2 != 0 || M < 8) {
+        why = "MDCT with M = " + std::to_string(M) + " coefficients per frame: M is even and at least 8 (the limits of a DCT-IV row)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!dct4_rows_supported(p, M, w)) {
+        why = "MDCT with M = " + std::to_string(M) + " coefficients per frame: " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (bases_len[1] < 0) {
+        why = "negative bases_len";
+        return MIFFT_ERR_NO_BASES;
+    }
+    window.resize((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+        const double v = word_pair(bases_flat + 2 * j);
+        if (!std::isfinite(v)) {
+            why = "window value " + std::to_string(j) + " is not finite";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        window[(size_t)j] = v;
+    }
+    const double scale = word_pair(bases_flat + 2 * n + 2);
+    if (!std::isfinite(scale) || scale == 0.0) {
+        why = "the scale of an MDCT payload is finite and not zero, not " + std::to_string(scale);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    radices.clear();
+    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    p.mdct = M;
+    p.mdct_scale = scale;
+    return MIFFT_OK;
+}
+
+// the one pass: a DCT-IV of M points (dim 1) over the F frames of every batch entry, framed, windowed and folded by its load
+int build_mdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+               const std::vector<double>& window, std::string& why) {
+    const int64_t M = p.mdct;
+    DimPass ps;
+    ps.dim_index = 1;
+    ps.N = M;
+    ps.inner = 1;
+    ps.outer = p.stft_frames();
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    if (!select_jit_dct4_rows(p, ps, /*mdct=*/true, why)) return MIFFT_ERR_UNSUPPORTED;
+    ps.dct_s0 = ps.dct_s1 = p.mdct_scale;  // (X = DCT-IV(u) / 2: the factor 2 of the DCT-IV store is simply not applied)
+    hipError_t e = upload_twiddle_table(p.out_dtype, M / 2, false, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, M, &ps.d_aux2);
+    if (e == hipSuccess)
+        e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(2 * M, window, &ps.d_aux3) : upload_window_t<float>(2 * M, window, &ps.d_aux3);
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "MDCT table upload");
+    return MIFFT_OK;
+}
+
 // the (K, M) filterbank as bands: per column lo = its first non-zero row and len = its last non-zero row - lo + 1 (zeros in
 // between stay inside the span; a column of zeros has len 0), off = where its len weights start.  One device table: lo[M],
 // len[M], off[M] (int32, padded to an even count), then the weights, rounded once to T.

@@ -104,6 +104,13 @@ MIFFT_DEV cpx<T> gload_pair(const T* p) {
     const vec2u v = *(const vec2u*)p;
     return {v.x, v.y};
 }
+// ... and the store of two adjacent reals at such an address (the rows of a TileCfg::DCT = 4 store)
+template <typename T>
+MIFFT_DEV void gstore_pair(T* p, T a, T b) {
+    typedef T vec2u __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    const vec2u v = {a, b};
+    *(vec2u*)p = v;
+}
 template <bool NT, typename T>
 MIFFT_DEV void gstore(cpx<T>* p, cpx<T> v) {
     if constexpr (NT) {
@@ -198,7 +205,9 @@ struct TileParams {
     long long col_lim;
     // DCT configurations: W_(4n)^k = e^(-2 pi i k / 4n), k = 0 .. N (n = 2 N real points per row), and the scales of bin 0 and
     // of the other bins (the norm, the factor 2 of the forward, the 1 / 2n and the halves of the inverse): applied as the
-    // bins are stored (DCT = 2) or loaded (DCT = 3)
+    // bins are stored (DCT = 2) or loaded (DCT = 3).  DCT = 4: dct_tw holds p_m = e^(-i pi (8m+1) / 8n), m = 0 .. N - 1, the
+    // pre- and the post-twiddle alike, and dct_s1 the one scale of the store (dct_s0 is unused).  MDCT configurations reuse the
+    // STFT fields below: frames of 4 N samples every stft_hop = 2 N, stft_win their 4 N window values, stft_center = 2.
     const void* dct_tw;
     double dct_s0, dct_s1;
     // STFT configurations: logical row r of the launch is frame r % stft_frames of batch entry r / stft_frames, entries of
@@ -321,7 +330,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
-          bool LOG_ = false, bool POST_ = false>
+          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -461,7 +470,31 @@ struct TileCfg {
     // tile whose load forms V[k] = conj(W_4n^k) (X[k] - i X[n-k]) / 2 from four runs of reals before the fold, and whose
     // store reads x back from the slots of v.  n reals read once, n reals written once.
     static constexpr int DCT = DCT_;
-    static_assert(DCT_ == 0 || DCT_ == 2 || DCT_ == 3, "DCT: 0, 2 (DCT-II) or 3 (its inverse)");
+    static_assert(DCT_ == 0 || DCT_ == 2 || DCT_ == 3 || DCT_ == 4, "DCT: 0, 2 (DCT-II), 3 (its inverse) or 4 (DCT-IV)");
+    // DCT = 4: DCT-IV of real rows of n = 2 N points, X[k] = s / 2 * 2 sum_j x[j] cos(pi (2j+1)(2k+1) / 4n), as ONE N-point
+    // complex transform between two twiddles.  z_m = x[2m] + i x[n-1-2m], S = p . F(p . z) with p_m = e^(-i pi (8m+1) / 8n)
+    // (TileParams::dct_tw), X[2k] = s Re S_k and X[n-1-2k] = -s Im S_k.  A row tile that is neither R2C nor C2R: the load
+    // stages p . z in LDS, the passes are the forward complex row's and leave Z in LDS, the store multiplies by p again.
+    // Work item m < ceil(N / 2) of the load takes the adjacent pairs (x[2m], x[2m+1]) and (x[n-2-2m], x[n-1-2m]) -- one wave
+    // access ascending, one descending, both contiguous -- which are z_m = (x[2m], x[n-1-2m]) and z_(N-1-m) =
+    // (x[n-2-2m], x[2m+1]), and writes two whole LDS elements; the store is the mirror: from c_k = p_k Z_k and c_(N-1-k)
+    // the pairs (X[2k], X[2k+1]) = (s Re c_k, -s Im c_(N-1-k)) and (X[n-2-2k], X[n-1-2k]) = (s Re c_(N-1-k), -s Im c_k).
+    // The middle item of an odd N is its own partner.  The transform is its own inverse up to the scale s, so the plan's
+    // direction conjugates nothing (the host passes inverse = 0 and the forward tables).  n reals read once, n written once;
+    // the accesses are aligned to one element at least, as the DCT-II rows'.
+    static_assert(DCT_ != 4 || (!COLS_ && !R2C_ && !C2R_ && !FIRST_DIRECT_ && !LAST_DIRECT_ && !IN_REAL_ && !TSTORE_ && !FS1_ &&
+                                !HERM_ && !HS_ && !DMA_ && !ILV_ && same_t<IT_, T_>::value && R0_ <= 32 && ROWPAD_ >= 0),
+                  "DCT-IV: a complex row tile of the plan's own float type, staged in LDS by the twiddling load");
+    // MDCT (with DCT = 4): the rows are the lapped FRAMES of a signal.  Frame f of an entry of stft_len samples covers the
+    // samples [(f - 1) M, (f + 1) M), M = 2 N coefficients per frame, zeros outside [0, T) without a load; its 2 M windowed
+    // samples y are folded to u[i] = -y[3h-1-i] - y[3h+i], u[h+i] = y[i] - y[M-1-i] (i < h = M / 2) as they are loaded, and
+    // u takes the place of the DCT-IV row x.  The split of the tile's first row into (entry, frame) and the wrap into the
+    // following entries are the STFT load's.  A frame inside its entry forms its four values of u from four pair loads of
+    // the signal and of the window, two ascending and two descending; a frame that reaches beyond either end -- and the
+    // middle item of an odd h, whose pairs straddle a quarter boundary -- goes real by real with bounds tests.  The choice
+    // is per row, so a frame's result does not depend on batch, slab or grid.  The store is the DCT-IV store, rows of M reals.
+    static constexpr bool MDCT = MDCT_;
+    static_assert(!MDCT_ || DCT_ == 4, "MDCT: the framing, folding load of a DCT-IV tile");
     //
     // DCT on a COLUMN tile (N-D DCT plans, dctn.cpp): the dimension is n = N points at a stride of S reals, S even, and the
     // tile's complex element at stride S / 2 is a PAIR of adjacent real columns, u = x_a + i x_b.  2: the rows of the tile are
@@ -487,7 +520,7 @@ struct TileCfg {
 #ifdef MIFFT_DCT_PAIRS
     static constexpr bool DCT_QUADS = false;
 #else
-    static constexpr bool DCT_QUADS = DCT_ != 0 && !COLS_ && N_ % 2 == 0;
+    static constexpr bool DCT_QUADS = (DCT_ == 2 || DCT_ == 3) && !COLS_ && N_ % 2 == 0;
 #endif
     // STFT (torch.stft over real signals): an R2C tile whose rows are the overlapping FRAMES of a signal instead of the rows of
     // a tensor.  Only the load differs: row r = r0 + c of the launch is frame r % F of batch entry r / F, its packed element m
@@ -1745,6 +1778,63 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 }
             }
             __syncthreads();
+        } else if constexpr (C::DCT == 4) {
+            // item (c, m), m < ceil(N / 2): a = (x[2m], x[2m+1]) and b = (x[n-2-2m], x[n-1-2m]) of row c -- of the row as it
+            // lies in memory, or of the folded frame u (MDCT) -- become p_m z_m and p_(N-1-m) z_(N-1-m) in LDS
+            constexpr int H2 = (C::N + 1) / 2, NN = 2 * C::N;
+            const V* pw = (const V*)p.dct_tw;
+            const long long row0 = base / C::N;
+            // MDCT: (b, frame) of the tile's first row once, uniform; a row further on wraps into the entries that follow
+            long long b0 = 0;
+            int fr0 = 0;
+            if constexpr (C::MDCT) {
+                b0 = row0 / p.stft_frames;
+                fr0 = (int)(row0 - b0 * p.stft_frames);
+            }
+            for (int f = tid; f < nv * H2; f += C::THREADS) {
+                const int c = f / H2, m = f - c * H2;
+                V a, b;
+                if constexpr (C::MDCT) {
+                    constexpr int h = C::N;  // (a quarter of the frame: M = 2 h coefficients, 4 h samples)
+                    const int F = p.stft_frames, len = p.stft_len;
+                    int fr = fr0 + c, db = 0;
+                    if (fr >= F) {
+                        db = fr / F;
+                        fr -= db * F;
+                    }
+                    const T* xe = (const T*)p.in + (b0 + db) * (long long)len;
+                    const long long s0 = ((long long)fr - 1) * NN;  // the frame's first sample, in [-M, T)
+                    const T* win = (const T*)p.stft_win;
+                    if (s0 >= 0 && s0 + 2 * NN <= len && 2 * m + 1 < h) {
+                        const T* xs = xe + s0;
+                        const V d1 = gload_pair(xs + 3 * h - 2 - 2 * m), a1 = gload_pair(xs + 3 * h + 2 * m);
+                        const V d2 = gload_pair(xs + h - 2 - 2 * m), a2 = gload_pair(xs + h + 2 * m);
+                        const V wd1 = gload_pair(win + 3 * h - 2 - 2 * m), wa1 = gload_pair(win + 3 * h + 2 * m);
+                        const V wd2 = gload_pair(win + h - 2 - 2 * m), wa2 = gload_pair(win + h + 2 * m);
+                        a = {-(wd1.y * d1.y) - wa1.x * a1.x, -(wd1.x * d1.x) - wa1.y * a1.y};  // u[2m], u[2m+1]
+                        b = {wd2.x * d2.x - wa2.y * a2.y, wd2.y * d2.y - wa2.x * a2.x};        // u[M-2-2m], u[M-1-2m]
+                    } else {
+                        auto y = [&](int j) -> T {  // windowed sample j of the frame; zeros beyond the ends: no load at all
+                            const long long i = s0 + j;
+                            return (i < 0 || i > (long long)len - 1) ? (T)0 : win[j] * xe[i];
+                        };
+                        auto u = [&](int i) -> T {
+                            return i < h ? -y(3 * h - 1 - i) - y(3 * h + i) : y(i - h) - y(3 * h - 1 - i);
+                        };
+                        a = {u(2 * m), u(2 * m + 1)};
+                        b = {u(NN - 2 - 2 * m), u(NN - 1 - 2 * m)};
+                    }
+                } else {
+                    const T* row = (const T*)p.in + (row0 + c) * NN;
+                    a = gload_pair(row + 2 * m);
+                    b = gload_pair(row + NN - 2 - 2 * m);
+                }
+                const V w0 = pw[m], w1 = pw[C::N - 1 - m];
+                lds[lds_index<C, -1>(c, m)] = {w0.x * a.x - w0.y * b.y, w0.x * b.y + w0.y * a.x};
+                if (2 * m != C::N - 1)
+                    lds[lds_index<C, -1>(c, C::N - 1 - m)] = {w1.x * b.x - w1.y * a.y, w1.x * a.y + w1.y * b.x};
+            }
+            __syncthreads();
         } else if constexpr (C::STFT) {
             // (b, frame) of the tile's first row once, uniform; a row further on wraps into the entries that follow
             const long long r0 = base / C::N, b0 = r0 / p.stft_frames;
@@ -2094,6 +2184,24 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     const T x1 = ldr[2 * lds_index<C, C::NP - 1>(c, q >> 1) + (q & 1)];
                     gstore<(C::NT & 2) != 0>((V*)p.out + base + f, V{(j & 1) ? -x0 : x0, (q & 1) ? -x1 : x1});
                 }
+            }
+            __syncthreads();
+        } else if constexpr (C::DCT == 4) {
+            // Z = F(p . z) lies in LDS: item (c, k), k < ceil(N / 2), holds c_k = p_k Z_k and c_(N-1-k) and stores the pairs
+            // (X[2k], X[2k+1]) and (X[n-2-2k], X[n-1-2k]) of row c, one run ascending over the lanes and one descending
+            constexpr int H2 = (C::N + 1) / 2, NN = 2 * C::N;
+            const V* pw = (const V*)p.dct_tw;
+            const long long row0 = base / C::N;
+            const T s = (T)p.dct_s1;
+            for (int f = tid; f < nv * H2; f += C::THREADS) {
+                const int c = f / H2, k = f - c * H2;
+                const V z0 = lds[lds_index<C, C::NP - 1>(c, k)], z1 = lds[lds_index<C, C::NP - 1>(c, C::N - 1 - k)];
+                const V w0 = pw[k], w1 = pw[C::N - 1 - k];
+                const T re0 = w0.x * z0.x - w0.y * z0.y, im0 = w0.x * z0.y + w0.y * z0.x;
+                const T re1 = w1.x * z1.x - w1.y * z1.y, im1 = w1.x * z1.y + w1.y * z1.x;
+                T* row = (T*)p.out + (row0 + c) * NN;
+                gstore_pair(row + 2 * k, s * re0, -s * im1);
+                if (2 * k != C::N - 1) gstore_pair(row + NN - 2 - 2 * k, s * re1, -s * im0);
             }
             __syncthreads();
         } else if constexpr (!C::LAST_DIRECT) {

@@ -171,6 +171,24 @@ typedef enum {
  *     own float type); every other length is specialised at run time. */
 #define MIFFT_FLAG_DCT 4u
 #define MIFFT_FLAG_DCT_ORTHO 8u
+/* DCT-IV of real rows (scipy.fft.dct / idct of type 4; no reference counterpart): a MIFFT_FLAG_DCT plan, with or without
+ * MIFFT_FLAG_DCT_ORTHO, whose FIRST `bases` word is the tag MIFFT_DCT_TYPE4_TAG (no radix can equal it: radices multiply to at
+ * most 8192).  The optional radices of n / 2 follow the tag; a payload of the tag alone (bases_len[0] = 1) selects the default
+ * estimate for n / 2.  Without the tag nothing changes.  x and out are both REAL, (batch, n, 1), in_dtype == out_dtype in
+ * {F32, F64} in BOTH directions (MIFFT_ERR_BAD_DTYPE otherwise):
+ *   forward:   X[k] = 2 sum_j x[j] cos(pi (2j+1)(2k+1) / 4n)                                            = scipy dct(x, 4)
+ *   inverse:   the same sum over X, divided by 2n                                                        = scipy idct(X, 4)
+ * With MIFFT_FLAG_DCT_ORTHO both directions scale the sum by sqrt(1 / 2n): the orthonormal DCT-IV, which is its own inverse.
+ * One launch, no scratch: a complex row tile of N = n / 2 points (mifft_plan_stages(0) reports its stages) between two
+ * twiddles.  With z_m = x[2m] + i x[n-1-2m] and p_m = e^(-i pi (8m+1) / 8n), S = p . FFT_N(p . z) gives X[2k] = 2 Re S_k and
+ * X[n-1-2k] = -2 Im S_k; the load forms p . z from two pairs of adjacent reals per work item, the store writes two pairs.  The
+ * direction changes only the one scale the store applies: both directions run the same kernel,
+ * rows<n>[_f64]_dct4_<radices>_jit, compiled at run time only.  The table p (N complex values, evaluated in long double and
+ * rounded once) lives in the plan.  Sizes, slabs, whole_batch, mifft_plan_pass_geometry and the alignment of one element are
+ * those of a MIFFT_FLAG_DCT plan, and so is every refusal of one (ndim, odd n, n < 8, the packed configuration of n / 2,
+ * the excluded flags, in_components); in addition MIFFT_JIT=0 is MIFFT_ERR_UNSUPPORTED (no precompiled instances), and so is
+ * the tag as the first `bases` word of a MIFFT_FLAG_DCT_ND plan (the N-D DCT has no type 4). */
+#define MIFFT_DCT_TYPE4_TAG 0x44435434u
 /* N-D DCT-II / DCT-III (scipy.fft.dctn / idctn of type 2 over the transformed dims; no reference counterpart).  ndim = 1 .. 6,
  * in_components = 1 in both directions; x and out are both REAL tensors (batch, d0.., d{k-1}, 1) of one shape.  Every
  * transformed dim gets the 1-D transform of MIFFT_FLAG_DCT above (forward: any in_dtype when the last dim is transformed;
@@ -344,6 +362,35 @@ typedef enum {
 #define MIFFT_STFT_MAX_BANDS 32768
 #define MIFFT_STFT_EXT_TAG_LO 0x46465401u
 #define MIFFT_STFT_EXT_TAG_HI 0x7FF84D49u
+/* Modified discrete cosine transform (the critically sampled lapped transform of AAC / Vorbis / Opus; no reference
+ * counterpart): a MIFFT_FLAG_STFT plan whose window payload carries the tag MIFFT_MDCT_TAG.  M coefficients per frame of 2 M
+ * samples, frames every M samples:
+ *   flags = MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_CENTER_ZEROS | MIFFT_FLAG_STFT_HOP(M), dims = {T, 2 M}, inverse = 0,
+ *   in_components = 1, in_dtype == out_dtype in {F32, F64};
+ *       x (batch, T, 1)  ->  out (batch, F, M, 1),    F = (T + M - 1) / M + 1,
+ *       out[b, f, k] = scale * sum_{j < 2M} w[j] x~[b, (f - 1) M + j] cos(pi / M (j + 1/2 + M / 2)(k + 1/2)),
+ * x~ being x with zeros outside [0, T): every sample lies in two frames, so a window with w[j]^2 + w[j + M]^2 = 1 allows
+ * perfect reconstruction (time-domain aliasing cancellation) of all of [0, T).  scale = 1 is the plain MDCT, scale =
+ * sqrt(2 / M) the orthonormal DCT-IV of the folded frame.
+ *   - bases_len[0] is exactly 2 (2 M) + 4 words: w[0 .. 2M-1] | TAG | scale, binary64 values, low word first; TAG is the one
+ *     NaN with the bits MIFFT_MDCT_TAG_HI : MIFFT_MDCT_TAG_LO; scale is finite and not zero.  Host data, taken by value;
+ *   - bases_len[1] is 0 (the default estimate) or the radices of M / 2.
+ * ONE launch, no scratch, no padded copy and no tensor of frames: the DCT-IV tile above over rows of M reals, whose load
+ * frames the signal as the STFT load does, multiplies by the window and folds the 2 M samples y of a frame to M
+ * (u[i] = -y[3h-1-i] - y[3h+i], u[h+i] = y[i] - y[M-1-i], i < h = M / 2) as it loads them; out = (scale / 2) DCT-IV(u)
+ * (kernel rows<M>[_f64]_dct4_<radices>_mdct_jit, compiled at run time only).  Nothing outside [0, T) of an entry of the exec
+ * is read, and a frame's result is bit-identical for any batch, first / count and grid.
+ * mifft_plan_out_bytes() is batch * F * M elements; mifft_exec_batch(first, count) offsets x by first * T and out by
+ * first * F * M reals; mifft_plan_pass_geometry(1) counts rows of count * F frames; dim 1 reports the stages of M / 2 and the
+ * kernel; launches 1, scratch 0.  The STFT's untagged lengths 0 and 2 n keep their meaning, and every other length its refusal.
+ * Refused before any device work.  MIFFT_ERR_UNSUPPORTED: a hop other than M; MIFFT_FLAG_STFT_CENTER_REFLECT; no centre bit;
+ * MIFFT_FLAG_STFT_POWER; the other flags an STFT plan refuses; ndim != 2; inverse != 0; M outside the limits of a DCT-IV row
+ * (even, 8 .. 16384, F64 up to 8192, M / 2 without a prime factor above 32); MIFFT_JIT=0.  MIFFT_ERR_BAD_BASES: a window value
+ * or scale that is not finite, a scale of zero (or radices that do not multiply to M / 2).  MIFFT_ERR_BAD_DTYPE: in_dtype !=
+ * out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: T >= 2^31.  The inverse (IMDCT) is a DCT-IV
+ * plan followed by the unfolding and the overlap-add, which the Python package composes; a fused one is not routed. */
+#define MIFFT_MDCT_TAG_LO 0x43544401u
+#define MIFFT_MDCT_TAG_HI 0x7FF84D44u
 
 typedef struct mifft_plan mifft_plan;
 
