@@ -492,21 +492,37 @@ class Plan:
     ``mdct`` = M > 0 (no reference counterpart): the MDCT of real signals, x (batch, T, 1) -> out (batch, F, M, 1),
     F = mdct_frames(T, M) frames of 2 M samples every M; ``stft_window`` None (the sine window) or 2 M values, ``mdct_scale``
     the factor on the cosine sum (MIFFT_MDCT_TAG in include/mifft.h, _check_mdct_layout, plan_mdct).  ``bases`` has two
-    lists, an empty one and the radices of M // 2 (or an empty one)."""
+    lists, an empty one and the radices of M // 2 (or an empty one).
+    ``imdct`` = M > 0 (no reference counterpart): the inverse MDCT, x (batch, F, M, 1) -> out (batch, T, 1) real with
+    2 <= T <= (F - 1) M, ``inverse=True`` implied; ``stft_window`` as for ``mdct``, ``imdct_gain`` the factor on the synthesis
+    window (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan in include/mifft.h, _check_imdct_layout, plan_imdct).  ``bases`` has
+    three lists: two empty ones and the radices of M // 2 (or an empty one)."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
-                 stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0):
+                 stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
+                 imdct_gain: float = 1.0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
-        mdct = int(mdct)
+        mdct, imdct = int(mdct), int(imdct)
         if dct_type not in (2, 4):
             raise MifftError(ERR_UNSUPPORTED, f"dct_type must be 2 or 4, got {dct_type!r}")
         stft = not mdct and (int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT))
         istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
         words = None
-        if istft:  # (with any other mode as well: the library refuses the pair)
+        if imdct:  # (with any other mode as well: the library refuses the pair)
+            istft_dims = _check_imdct_layout(in_shape, out_shape, imdct)
+            if axes is not None:
+                raise MifftError(ERR_UNSUPPORTED, "an IMDCT plan transforms dim 2 and overlap-adds dim 1: no axes")
+            w = mdct_window(imdct) if stft_window is None else _window_f64(stft_window, 2 * imdct)
+            words = window_words(w) + [MDCT_TAG_LO, MDCT_TAG_HI] + window_words(torch.tensor([float(imdct_gain)], dtype=torch.float64))
+            inverse = True
+            flags = (int(flags) | FLAG_ISTFT | FLAG_STFT_HOP(imdct) | FLAG_STFT_CENTER_ZEROS |
+                     (FLAG_STFT if stft or mdct else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
+                     (FLAG_HALF_SPECTRUM if half_spectrum else 0))
+            istft, stft, mdct = True, False, 0
+        elif istft:  # (with any other mode as well: the library refuses the pair)
             if not int(istft_hop):
                 istft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
                 if stft_center is None:
@@ -612,6 +628,7 @@ class Plan:
         self.spectrogram = stft and stft_power is not None and not mdct
         self.dct_type = int(dct_type) if dct and not dctn and not stft and not istft else 2
         self.mdct = mdct
+        self.imdct = imdct
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
@@ -864,10 +881,15 @@ def istft_schedule(plan: Plan, count: Optional[int] = None) -> list:
     Tile t is tile t % tiles_per_entry of entry t // tiles_per_entry, tiles_per_entry = ceil(F / TILE) (the last tile of an
     entry is ragged); workgroup w owns the ascending run [first_tile, first_tile + run_tiles), lengths differing by one at
     most; a run that starts inside an entry at tile g first recomputes warmup_tiles = min(g, ceil((K - 1) / TILE)) tiles before
-    it with the stores suppressed, K = ceil(n_fft / hop) the frames that cover one sample."""
+    it with the stores suppressed, K = ceil(n_fft / hop) the frames that cover one sample.
+    An IMDCT plan (``plan_imdct``) walks the same runs over its tiles of ``pass_geometry(2)[0]`` frames; there the third value
+    counts FRAMES, not tiles: a run that starts inside an entry transforms one frame, the last of the tile before it, with
+    the stores suppressed (1), any other run none (0)."""
     if not getattr(plan, "istft", False):
         raise MifftError(ERR_UNSUPPORTED, "istft_schedule describes inverse STFT plans only")
     tile, _, n_tiles, grid = plan.pass_geometry(2, count)
+    if getattr(plan, "imdct", 0):
+        return _imdct_schedule(tile, n_tiles, grid, plan.in_shape[1])
     frames, n_fft = plan.in_shape[1], 2 * (plan.in_shape[2] - 1)
     hop = (plan.flags & FLAG_STFT_HOP_MASK) >> 16
     return _istft_schedule(tile, n_tiles, grid, frames, n_fft, hop)
@@ -882,6 +904,16 @@ def _istft_schedule(tile: int, n_tiles: int, grid: int, frames: int, n_fft: int,
     for w in range(grid):
         first = w * length + min(w, rem)
         runs.append((first, length + (1 if w < rem else 0), min(first % tpe, W)))
+    return runs
+
+
+def _imdct_schedule(tile: int, n_tiles: int, grid: int, frames: int) -> list:
+    tpe = -(-frames // tile)
+    length, rem = divmod(n_tiles, grid)
+    runs = []
+    for w in range(grid):
+        first = w * length + min(w, rem)
+        runs.append((first, length + (1 if w < rem else 0), 1 if first % tpe else 0))
     return runs
 
 
@@ -1474,30 +1506,65 @@ def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -
     return out.reshape(logical[:-1] + (frames, n))
 
 
-def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = None) -> "torch.Tensor":
-    """The inverse of ``mdct`` under the same ``window`` and ``norm``: X of shape (..., F, n) real -> (..., length),
-    ``length`` defaulting to (F - 1) n.  A window with w[j] ** 2 + w[j + n] ** 2 = 1 (the default sine window, KBD, Vorbis)
-    reproduces the signal exactly (time-domain aliasing cancellation).
-    This is a COMPOSITION, not a fused kernel: one DCT-IV launch (``dct(X, type=4)``) plus torch -- a gather with a
-    precomputed index / sign table that unfolds the n values of a frame to its 2n samples, the product with the window
-    ((2 / n) w, or w under ``norm="ortho"``), two shifted adds of the half-frames into a (..., (F + 1) n) buffer (the hop
-    equals n, so no ``fold`` is needed) and the slice [n, n + length).  A fused IMDCT needs the inverse STFT's
-    overlap-adding store generalised to a row shorter than its frame and is not provided."""
-    if X.is_complex():
-        raise MifftError(-3, "imdct expects a real tensor")
-    if X.dim() < 2:
-        raise MifftError(-1, "imdct expects a tensor of rank 2 or more: (F, n) or (..., F, n)")
-    F, n = int(X.shape[-2]), _mdct_n(X.shape[-1], "imdct")
-    ortho = _mdct_norm_scale(norm, n, "imdct") != 1.0
+def _imdct_norm_gain(norm, n: int, who: str) -> float:
+    """the factor on the windowed cosine sum of the synthesis: 2 / n, or sqrt(2 / n) for ``norm="ortho"``"""
+    return 2.0 / n if _mdct_norm_scale(norm, n, who) == 1.0 else math.sqrt(2.0 / n)
+
+
+def _check_imdct_layout(in_shape: tuple, out_shape: tuple, n: int) -> tuple:
+    """Layouts of an IMDCT plan (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan): x (batch, F, n, 1) real -> out (batch, T, 1) real
+    with F >= 2 and 2 <= T <= (F - 1) n; returns the dims (T, F, 2n)."""
+    if len(in_shape) != 4 or len(out_shape) != 3:
+        raise MifftError(-1, f"IMDCT layouts are (batch, F, n, 1) -> (batch, T, 1), got {in_shape} -> {out_shape}")
+    if in_shape[-1] != 1 or out_shape[-1] != 1:
+        raise MifftError(-3, f"both sides of an IMDCT plan have 1 component, got {in_shape[-1]} and {out_shape[-1]}")
+    if in_shape[0] != out_shape[0]:
+        raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
+    n = _mdct_n(n, "IMDCT")
+    F, T = in_shape[1], out_shape[1]
+    if in_shape[2] != n:
+        raise MifftError(-2, f"frames of {n} coefficients, x is {in_shape}")
     if F < 2:
-        raise MifftError(-2, f"imdct: at least 2 frames, got {F}")
-    length = (F - 1) * n if length is None else int(length)
-    if not 1 <= length <= (F - 1) * n:
-        raise MifftError(-2, f"imdct: {F} frames of {n} coefficients cover 1 .. {(F - 1) * n} samples, length is {length}")
-    w = mdct_window(n) if window is None else _window_f64(window, 2 * n)
-    dt = X.dtype if X.dtype in _OUT_DTYPES else torch.float64
+        raise MifftError(-2, f"an IMDCT needs at least 2 frames, got {F}")
+    if not 2 <= T <= (F - 1) * n:
+        raise MifftError(-2, f"{F} frames of {n} coefficients cover 2 .. {(F - 1) * n} samples, out is {out_shape}")
+    return (T, F, 2 * n)
+
+
+def plan_imdct(dtype, batch: int, frames: int, n: int, *, length: Optional[int] = None, window=None, norm=None,
+               ctx: Optional[DeviceContext] = None, whole_batch: int = 0) -> Plan:
+    """Plan of the inverse MDCT of ``batch`` entries of ``frames`` frames of ``n`` coefficients (no reference counterpart;
+    MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan in include/mifft.h): it inverts ``plan_mdct`` under the same ``window`` (None:
+    the sine window; else 2n values, taken by value) and ``norm``.  ``length``: output samples per entry, 2 .. (frames - 1) n,
+    the default.  ``in_shape`` (batch, frames, n, 1), ``out_shape`` (batch, length, 1), both of ``dtype`` (float32 / float64);
+    runs through ``fft(out, X, plan=plan)``, ``first=`` / ``count=`` included: one kernel launch -- the DCT-IV of every frame,
+    the unfold to 2n samples, the window and the overlap-add of the two half-frames that meet in every sample happen in the
+    store of a DCT-IV tile -- no tensor of frames, no memset; an entry's result is bit-identical for any batch and slab.
+    Every argument error is raised before any device work."""
+    batch, frames = int(batch), int(frames)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"an IMDCT plan reads and writes float32 or float64, got {dtype}")
+    n = _mdct_n(n, "IMDCT")
+    gain = _imdct_norm_gain(norm, n, "plan_imdct")
+    T = (frames - 1) * n if length is None else int(length)
+    in_shape, out_shape = (batch, frames, n, 1), (batch, T, 1)
+    _check_imdct_layout(in_shape, out_shape, n)
+    if window is not None:
+        window = _window_f64(window, 2 * n)
+    if ctx is None:
+        ctx = DeviceContext()
+    return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, whole_batch=whole_batch, imdct=n, imdct_gain=gain,
+                stft_window=window)
+
+
+def _imdct_composed(X: "torch.Tensor", w: "torch.Tensor", ortho: bool, length: int) -> "torch.Tensor":
+    """The IMDCT as one DCT-IV launch plus torch, X (..., F, n) of float32 / float64 -> (..., length): a gather with a
+    precomputed index / sign table that unfolds the n values of a frame to its 2n samples, the product with the window
+    ((2 / n) w, or w under ortho), two shifted adds of the half-frames into a (..., (F + 1) n) buffer and the slice
+    [n, n + length).  What ``imdct`` ran before the fused plan existed; it serves what that plan refuses."""
+    F, n, dt = int(X.shape[-2]), int(X.shape[-1]), X.dtype
     # v = DCT-IV(X) / 2 (ortho: the orthonormal DCT-IV itself), then y = (2 / n) w * unfold(v) (ortho: w * unfold(v))
-    v = dct(X.to(dt), type=4, norm="ortho" if ortho else None)
+    v = dct(X, type=4, norm="ortho" if ortho else None)
     idx, sign = _mdct_unfold_tables(n)
     gain = sign * w * (1.0 if ortho else 1.0 / n)  # (the 1 / 2 of v and the 2 / n of the synthesis in one table)
     y = v.index_select(-1, idx.to(v.device)) * gain.to(device=v.device, dtype=dt)
@@ -1506,6 +1573,60 @@ def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = 
     out[..., :F * n] += y[..., :n].reshape(lead + (F * n,))
     out[..., n:] += y[..., n:].reshape(lead + (F * n,))
     return out[..., n:n + length].contiguous()
+
+
+def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = None) -> "torch.Tensor":
+    """The inverse of ``mdct`` under the same ``window`` and ``norm``: X of shape (..., F, n) real -> (..., length),
+    ``length`` defaulting to (F - 1) n; the leading dims fold into the batch.  A window with w[j] ** 2 + w[j + n] ** 2 = 1
+    (the default sine window, KBD, Vorbis) reproduces the signal exactly (time-domain aliasing cancellation).
+    One kernel launch (``plan_imdct``): the DCT-IV of every frame, its unfold to 2n samples, the product with (2 / n) w
+    (sqrt(2 / n) w under ``norm="ortho"``) and the sum of the two half-frames that meet in every output sample happen in the
+    store of a DCT-IV tile; no tensor of frames and no zeroed buffer exist.  Input that is not float32 / float64 is converted
+    to float64 first.  Plans are cached per (shape, dtype, n, norm, length, device, stream) and the window's contents; loops
+    should use ``plan_imdct``.  Only what the fused plan refuses -- ``length == 1``, or a tile and carry beyond the CU's LDS
+    (no admissible n today) -- runs the earlier composition, one DCT-IV launch plus torch."""
+    if X.is_complex():
+        raise MifftError(-3, "imdct expects a real tensor")
+    if X.dim() < 2:
+        raise MifftError(-1, "imdct expects a tensor of rank 2 or more: (F, n) or (..., F, n)")
+    F, n = int(X.shape[-2]), _mdct_n(X.shape[-1], "imdct")
+    gain = _imdct_norm_gain(norm, n, "imdct")
+    if F < 2:
+        raise MifftError(-2, f"imdct: at least 2 frames, got {F}")
+    length = (F - 1) * n if length is None else int(length)
+    if not 1 <= length <= (F - 1) * n:
+        raise MifftError(-2, f"imdct: {F} frames of {n} coefficients cover 1 .. {(F - 1) * n} samples, length is {length}")
+    w = None if window is None else _window_f64(window, 2 * n)
+    dt = X.dtype if X.dtype in _OUT_DTYPES else torch.float64
+    device = DeviceContext(X.device.index if X.is_cuda else None).device
+    if not X.is_cuda or X.device.index != device:
+        raise MifftError(-10, f"X must live on HIP device {device}, got {X.device}")
+    ortho = gain != 2.0 / n
+    lead = tuple(X.shape[:-2])
+    if length == 1:
+        return _imdct_composed(X.to(dt), mdct_window(n) if w is None else w, ortho, length)
+    batch = 1
+    for m in lead:
+        batch *= m
+    in_shape, out_shape = (batch, F, n, 1), (batch, length, 1)
+    Xr = X.to(dt).contiguous().reshape(in_shape)
+    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
+    with _PLAN_CACHE_LOCK:
+        key = ("imdct", dt, in_shape, length, gain, digest, device, int(torch.cuda.current_stream(device).cuda_stream))
+        plan = _PLAN_CACHE.get(key)
+        if plan is None:
+            try:
+                plan = Plan(dt, dt, in_shape, out_shape, device=device, imdct=n, imdct_gain=gain, stft_window=w)
+            except MifftError as e:
+                if e.status != ERR_UNSUPPORTED or "LDS" not in str(e):
+                    raise
+                return _imdct_composed(X.to(dt), mdct_window(n) if w is None else w, ortho, length)
+            _plan_cache_insert(key, plan)
+        else:
+            _PLAN_CACHE.move_to_end(key)
+        out = torch.empty(out_shape, dtype=dt, device=Xr.device)
+        fft(out, Xr, DeviceContext(device), plan=plan)
+    return out.reshape(lead + (length,))
 
 
 def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_length: Optional[int] = None, window=None,

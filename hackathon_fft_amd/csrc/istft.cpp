@@ -7,6 +7,8 @@
 // travel through `bases` as host data; the plan keeps gain * w[j] / n with the sign of the kernel's conjugation (the 1 / n is
 // folded into this table: the pass's own scale is not applied) and 1 / sum w^2 at every padded sample as device tables of its
 // float type, both computed in binary64 and rounded once.
+//
+// The same flag with a window payload tagged MIFFT_MDCT_TAG is the inverse MDCT (imdct_check, build_imdct below).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -203,6 +205,146 @@ static hipError_t upload_tables_t(int64_t n, int64_t hop, int64_t F, const std::
     hipError_t e = upload_t<T>(ws, d_ws);
     if (e == hipSuccess) e = upload_t<T>(inv, d_env);
     return e;
+}
+
+// ---- IMDCT plans: the payload w[0 .. 2M-1] | MIFFT_MDCT_TAG | gain on a MIFFT_FLAG_ISTFT plan -------------------------------------
+// One launch, no scratch: the DCT-IV row kernel of M points with TileCfg::IMDCT set, whose store unfolds the M values of a frame
+// to its 2 M samples, multiplies by gain * w and adds the two half-frames that meet in every block of M output samples
+// (tile_kernel.h).  x is (batch, F, M, 1) real, out (batch, T, 1).  There is no envelope: time-domain aliasing cancellation
+// needs none, so there is no overlap-add condition to check either.
+bool imdct_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 3 || !bases_flat || !bases_len || bases_len[0] < 4) return false;
+    const int64_t l0 = bases_len[0];
+    return bases_flat[l0 - 4] == MIFFT_MDCT_TAG_LO && bases_flat[l0 - 3] == MIFFT_MDCT_TAG_HI;
+}
+
+int imdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
+                std::vector<uint64_t>& radices, std::string& why) {
+    window.clear();
+    radices.clear();
+    const char* who = "an IMDCT payload (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan)";
+    const struct {
+        uint32_t bits;
+        const char* what;
+    } other[] = {{MIFFT_FLAG_STFT_CENTER_REFLECT, "MIFFT_FLAG_STFT_CENTER_REFLECT: the frames of an MDCT see zeros beyond both ends"},
+                 {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no MDCT to be faithful to"},
+                 {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an MDCT has no half spectrum"},
+                 {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
+                 {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
+                 {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO: the norm of an IMDCT travels as the gain of its payload"},
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an IMDCT plan transforms dim 2 and overlap-adds dim 1"}};
+    for (const auto& o : other)
+        if (p.flags & o.bits) {
+            why = std::string(who) + " with " + o.what;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+    if (!(p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS)) {
+        why = std::string(who) + " without a centre bit: MIFFT_FLAG_STFT_CENTER_ZEROS is required";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (!p.inverse) {
+        why = std::string(who) + " with inverse = 0: the forward transform is the tagged MIFFT_FLAG_STFT plan";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    const int64_t T = p.dims[0], F = p.dims[1], n = p.dims[2], M = n / 2;
+    if (n % 2 != 0) {
+        why = "an MDCT frame has 2 M samples: dims[2] = " + std::to_string(n) + " is odd";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.stft_hop() != M) {
+        why = "the hop of an IMDCT plan is M = dims[2] / 2 = " + std::to_string(M) + " (MIFFT_FLAG_STFT_HOP), not " +
+              std::to_string(p.stft_hop());
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 1) {
+        why = "an IMDCT reads real coefficients (in_components = 1)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.in_dtype != p.out_dtype) {
+        why = "an IMDCT reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    if (M % 2 != 0 || M < 8) {
+        why = "IMDCT with M = " + std::to_string(M) + " coefficients per frame: M is even and at least 8 (the limits of a DCT-IV row)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!imdct_rows_supported(p, M, w)) {
+        why = "IMDCT with M = " + std::to_string(M) + " coefficients per frame: " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (F < 2) {
+        why = "an IMDCT needs at least two frames (dims[1] = " + std::to_string(F) + "): every output sample is the sum of two";
+        return MIFFT_ERR_BAD_DIM;
+    }
+    if (F > (1ll << 26)) {
+        why = "more than 2^26 frames per entry (dims[1] = " + std::to_string(F) + ")";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (T < 2 || T > (F - 1) * M) {
+        why = "T = dims[0] = " + std::to_string(T) + " output samples, but " + std::to_string(F) + " frames cover 2 .. " +
+              std::to_string((F - 1) * M) + " ((F - 1) M): a longer output is not zero-padded";
+        return MIFFT_ERR_BAD_DIM;
+    }
+    if (T >= (1ll << 31)) {
+        why = "outputs of 2^31 samples or more per entry (dims[0] = " + std::to_string(T) + "): the samples are addressed in 32 bits";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    const int64_t l0 = bases_len[0];
+    if (l0 != 2 * n + 4) {
+        why = "bases_len[0] of an IMDCT plan is exactly 2 (2 M) + 4 = " + std::to_string(2 * n + 4) +
+              " words (w[0 .. 2M-1] | TAG | gain), not " + std::to_string(l0);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (bases_len[1] != 0 || bases_len[2] < 0) {
+        why = "bases_len[1] of an IMDCT plan is 0 (dim 1 is overlap-added, not transformed) and bases_len[2] the radices of M / 2";
+        return bases_len[2] < 0 ? MIFFT_ERR_NO_BASES : MIFFT_ERR_BAD_BASES;
+    }
+    window.resize((size_t)n);
+    for (int64_t j = 0; j < n; ++j)
+        if (!read_f64(bases_flat + 2 * j, window[(size_t)j])) {
+            why = "window value " + std::to_string(j) + " is not finite";
+            return MIFFT_ERR_BAD_BASES;
+        }
+    if (!read_f64(bases_flat + 2 * n + 2, gain) || gain == 0.0) {
+        why = "the gain of an IMDCT payload is finite and not zero, not " + std::to_string(gain);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    for (int k = 0; k < bases_len[2]; ++k) radices.push_back(bases_flat[l0 + k]);
+    p.imdct = M;
+    return MIFFT_OK;
+}
+
+// the one pass: a DCT-IV of M points (dim 2) over the F frames of every batch entry, unfolded and overlap-added by its store
+int build_imdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+                const std::vector<double>& window, double gain, std::string& why) {
+    const int64_t M = p.imdct;
+    DimPass ps;
+    ps.dim_index = 2;
+    ps.N = M;
+    ps.inner = 1;
+    ps.outer = p.dims[1];
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    if (!select_jit_imdct_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    // (the sweep leaves the plain cosine sums: the whole scale is in the table below, and dct_s1 is not applied)
+    hipError_t e = upload_twiddle_table(p.out_dtype, M / 2, false, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, M, &ps.d_aux2);
+    if (e == hipSuccess) {  // ws[j] = gain * w[j], formed in binary64 and rounded once
+        if (p.out_dtype == MIFFT_F64) {
+            std::vector<double> ws((size_t)(2 * M));
+            for (int64_t j = 0; j < 2 * M; ++j) ws[(size_t)j] = gain * window[(size_t)j];
+            e = upload_t<double>(ws, &ps.d_aux3);
+        } else {
+            std::vector<float> ws((size_t)(2 * M));
+            for (int64_t j = 0; j < 2 * M; ++j) ws[(size_t)j] = (float)(gain * window[(size_t)j]);
+            e = upload_t<float>(ws, &ps.d_aux3);
+        }
+    }
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "IMDCT table upload");
+    return MIFFT_OK;
 }
 
 // the one pass: dim 2 (n points) over the F frames of every batch entry

@@ -255,14 +255,17 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         double gain = 1.0;
         // (a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points)
         const bool mdct = fwd && mdct_detect(ndim, dims, bases_flat, bases_len);
-        int rc = mdct  ? mdct_check(p, bases_flat, bases_len, window, user, why)
-                 : fwd ? stft_check(p, why)
-                       : istft_check(p, bases_flat, bases_len, window, gain, user, why);
+        // (the same tag on a MIFFT_FLAG_ISTFT plan: the inverse, frames of M = n / 2 coefficients overlap-added every M samples)
+        const bool imdct = !fwd && imdct_detect(ndim, bases_flat, bases_len);
+        int rc = mdct    ? mdct_check(p, bases_flat, bases_len, window, user, why)
+                 : imdct ? imdct_check(p, bases_flat, bases_len, window, gain, user, why)
+                 : fwd   ? stft_check(p, why)
+                         : istft_check(p, bases_flat, bases_len, window, gain, user, why);
         if (rc) return fail(rc, why);
         const int td = ndim - 1;  // the transformed dim
-        const int64_t n = mdct ? dims[td] / 4 : dims[td], frames = fwd ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
-        p.prod = frames * (mdct ? p.mdct : n);  // (the rows the one pass transforms)
-        p.prod_half = mdct ? p.prod : frames * (n / 2 + 1);
+        const int64_t n = mdct || imdct ? dims[td] / 4 : dims[td], frames = fwd ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
+        p.prod = frames * (mdct ? p.mdct : imdct ? p.imdct : n);  // (the rows the one pass transforms)
+        p.prod_half = mdct || imdct ? p.prod : frames * (n / 2 + 1);
         if (fwd && !mdct) {
             rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, post, user, why);
             if (rc) return fail(rc, why);
@@ -284,9 +287,10 @@ int mifft_plan_create_slab(mifft_plan** out_plan, int device, int in_dtype, int 
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) p.num_cus = prop.multiProcessorCount;
         config_refresh();
-        rc = mdct  ? build_mdct(p, ordered[td], processed[td], window, why)
-             : fwd ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
-                   : build_istft(p, ordered[td], processed[td], window, gain, why);
+        rc = mdct    ? build_mdct(p, ordered[td], processed[td], window, why)
+             : imdct ? build_imdct(p, ordered[td], processed[td], window, gain, why)
+             : fwd   ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
+                     : build_istft(p, ordered[td], processed[td], window, gain, why);
         if (rc) return fail(rc, why);
         *out_plan = h;
         return MIFFT_OK;

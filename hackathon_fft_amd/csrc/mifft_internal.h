@@ -101,6 +101,9 @@ struct DimPass {
     // lapped frames of every batch entry (TileCfg::MDCT); d_aux3 holds the window, 2 N values of the plan's float type
     int dct = 0;
     bool mdct = false;
+    // imdct: the rows are `outer` frames of N coefficients per batch entry, unfolded and overlap-added into dims[0] samples by
+    // the store (TileCfg::IMDCT); d_aux3 holds gain * w, 2 N values of the plan's float type; istft_min_run as below
+    bool imdct = false;
     double dct_s0 = 1.0, dct_s1 = 1.0;
     // TileCfg::STFT of a packed-row pass: the rows are the `outer` frames of every batch entry (hop, length and centring are the
     // plan's); d_aux2 holds the window, N values of the plan's float type
@@ -181,6 +184,9 @@ struct Plan {
     // real, mdct_scale times the cosine sum over the windowed frame.  0: not one.  Set by mdct_detect.
     int64_t mdct = 0;
     double mdct_scale = 1.0;
+    // a MIFFT_FLAG_ISTFT plan whose window payload is tagged with MIFFT_MDCT_TAG: the inverse MDCT of imdct = M = dims[2] / 2
+    // coefficients per frame, dims = {T, F, 2 M}; x is (batch, F, M, 1) real, out (batch, T, 1).  0: not one.  Set by imdct_check.
+    int64_t imdct = 0;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
     bool dct4 = false;
     // MIFFT_FLAG_STFT_POWER on such a plan: out is real, (batch, F, n / 2 + 1, 1) of |X|^spec_power (1 or 2), or
@@ -351,6 +357,16 @@ int mdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len,
                std::vector<uint64_t>& radices, std::string& why);
 int build_mdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                const std::vector<double>& window, std::string& why);
+// IMDCT plans (the MIFFT_FLAG_ISTFT payload tagged with MIFFT_MDCT_TAG; istft.cpp), in the same manner.  imdct_detect: does
+// the window payload end in TAG | gain?  (Pure; the length itself is imdct_check's business.)  select_jit_imdct_rows is the
+// DCT-IV kernel with TileCfg::IMDCT (run time only), imdct_rows_supported the same check without a device.
+bool imdct_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
+int imdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
+                std::vector<uint64_t>& radices, std::string& why);
+int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+                const std::vector<double>& window, double gain, std::string& why);
+bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }

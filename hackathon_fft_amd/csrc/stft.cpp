@@ -362,7 +362,7 @@ int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         return MIFFT_ERR_UNSUPPORTED;
     }
     if (p.inverse) {
-        why = "the inverse MDCT is not routed (inverse must be 0)";
+        why = "the inverse MDCT is not routed through MIFFT_FLAG_STFT (inverse must be 0): it is the same tag on a MIFFT_FLAG_ISTFT plan";
         return MIFFT_ERR_UNSUPPORTED;
     }
     if (p.in_components != 1) {

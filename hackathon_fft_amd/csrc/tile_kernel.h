@@ -330,7 +330,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
-          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false>
+          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -495,6 +495,21 @@ struct TileCfg {
     // is per row, so a frame's result does not depend on batch, slab or grid.  The store is the DCT-IV store, rows of M reals.
     static constexpr bool MDCT = MDCT_;
     static_assert(!MDCT_ || DCT_ == 4, "MDCT: the framing, folding load of a DCT-IV tile");
+    // IMDCT (with DCT = 4): the inverse.  The rows are TILE consecutive frames of M = 2 N coefficients of ONE batch entry (the
+    // tiles, the ascending runs and the ragged last tile of an entry are the ISTFT's); load and passes are the DCT-IV's.  The
+    // store first finishes the DCT-IV in place -- one sweep replaces Z_k by c_k = p_k Z_k, so that v[2k] = Re c_k and
+    // v[M-1-2k] = -Im c_k are the plain cosine sums of the frame -- and then has one work item per PAIR of output samples of
+    // the tile's blocks.  Block q of an entry is out[q M + i], i < M: acc = ws[M+i] y_q[M+i], out = fma(ws[i], y_(q+1)[i], acc),
+    // the term of the earlier frame first, with the unfold y[i] = v[h+i], y[M-1-i] = -v[h+i], y[3h-1-i] = -v[i],
+    // y[3h+i] = -v[i] (i < h = N) read straight from the slots of v: no frame of 2 M samples exists anywhere.  ws (stft_win,
+    // 2 M values) is gain * w; dct_s1 is not applied.  The second half of frame q is a function of v_q[0 .. h) alone: the last
+    // frame of a tile leaves those h reals in `carry` (behind the tables) AFTER every read of the previous carry, a barrier
+    // between them; the first tile of an entry reads none (frame 0 gives only its second half, to block 0) and the last one
+    // writes none.  A run that starts inside an entry at tile g first transforms ONE frame, g TILE - 1, with the stores
+    // suppressed, and takes its carry from it.  Every sample of [0, T) is written exactly once with a plain store (pairs; a
+    // tail of one real), from the same two products whatever the batch, slab, grid and run layout.
+    static constexpr bool IMDCT = IMDCT_;
+    static_assert(!IMDCT_ || (DCT_ == 4 && !MDCT_), "IMDCT: the unfolding, overlap-adding store of a DCT-IV tile");
     //
     // DCT on a COLUMN tile (N-D DCT plans, dctn.cpp): the dimension is n = N points at a stride of S reals, S even, and the
     // tile's complex element at stride S / 2 is a PAIR of adjacent real columns, u = x_a + i x_b.  2: the rows of the tile are
@@ -622,10 +637,13 @@ struct TileCfg {
     // ISTFT: the carry, 2 N - hop <= 2 N reals, where the Hermitian column would be (C2R excludes HERM)
     static constexpr int ISTFT_OFF = HERM_OFF;
     static constexpr int ISTFT_ELEMS = ISTFT_ ? N_ : 0;
+    // IMDCT: the carry, v[0 .. N) of a tile's last frame: N reals (DCT = 4 excludes HERM and ISTFT)
+    static constexpr int IMDCT_OFF = HERM_OFF;
+    static constexpr int IMDCT_ELEMS = IMDCT_ ? (N_ + 1) / 2 : 0;
     static_assert(!(HERM_ && DMA_), "HERM: no staging buffer");
     static constexpr size_t LDS_BYTES =
         DMA_ ? (size_t)(STAGE_OFF + STAGE_ELEMS) * 2 * sizeof(T_)
-             : (size_t)(DATA_ELEMS + TWL_TOTAL + CS_ELEMS + HERM_ELEMS + ISTFT_ELEMS) * 2 * sizeof(T_);
+             : (size_t)(DATA_ELEMS + TWL_TOTAL + CS_ELEMS + HERM_ELEMS + ISTFT_ELEMS + IMDCT_ELEMS) * 2 * sizeof(T_);
     static_assert(P(NP_) == N_, "radices must multiply to N");
     static_assert(LDS_BYTES <= 160 * 1024, "tile + twiddle table exceed the CU's 160 KiB of LDS");
 };
@@ -1538,9 +1556,17 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
         const long long K = (2 * C::N + p.stft_hop - 1) / p.stft_hop, W = (K - 1 + C::TILE - 1) / C::TILE;
         t = run_begin - (W < g ? W : g);
     }
+    if constexpr (C::IMDCT) {  // the ISTFT's runs; a run that starts inside an entry is preceded by ONE warm-up frame (position
+                               // run_begin - 1 of the walk), whose v[0 .. N) is the carry the first tile of the run needs
+        const long long len = p.n_tiles / gridDim.x, rem = p.n_tiles - len * gridDim.x, w = blockIdx.x;
+        run_begin = w * len + (w < rem ? w : rem);
+        t_end = run_begin + len + (w < rem ? 1 : 0);
+        t_step = 1;
+        t = run_begin - (run_begin % p.tiles_per_outer != 0 && run_begin < t_end ? 1 : 0);
+    }
     const long long t_first = t;
     // (runs: position t of the order is tile n_tiles - 1 - t, whatever p.reverse says; ISTFT: tile t)
-    auto tile_at = [&](long long pos) { return C::ISTFT ? pos : C::HERM_RUNS ? p.n_tiles - 1 - pos : tile_id(p, pos); };
+    auto tile_at = [&](long long pos) { return (C::ISTFT || C::IMDCT) ? pos : C::HERM_RUNS ? p.n_tiles - 1 - pos : tile_id(p, pos); };
     if constexpr (C::XCD_CHUNK) {
         if (gridDim.x >= 8) {  // (smaller grids: some XCD would own tiles but no workgroup)
             const long long x = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -1598,6 +1624,17 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             const long long b = tt / p.tiles_per_outer;
             const int f0 = (int)(tt - b * p.tiles_per_outer) * C::TILE;
             nv = p.stft_frames - f0 < C::TILE ? p.stft_frames - f0 : C::TILE;
+            base = (b * p.stft_frames + f0) * C::N;
+            obase = b;
+            fs_row = f0;
+        } else if constexpr (C::IMDCT) {  // as above; the warm-up position is the one frame before tile run_begin
+            const long long ta = t < run_begin ? run_begin : tt, b = ta / p.tiles_per_outer;
+            int f0 = (int)(ta - b * p.tiles_per_outer) * C::TILE;
+            nv = p.stft_frames - f0 < C::TILE ? p.stft_frames - f0 : C::TILE;
+            if (t < run_begin) {
+                f0 -= 1;
+                nv = 1;
+            }
             base = (b * p.stft_frames + f0) * C::N;
             obase = b;
             fs_row = f0;
@@ -2185,6 +2222,50 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     gstore<(C::NT & 2) != 0>((V*)p.out + base + f, V{(j & 1) ? -x0 : x0, (q & 1) ? -x1 : x1});
                 }
             }
+            __syncthreads();
+        } else if constexpr (C::IMDCT) {
+            // Z = F(p . z) lies in LDS.  Sweep: element k of every row becomes c_k = p_k Z_k, so slot a of v is the real part
+            // of element a / 2 (a even) or minus the imaginary part of element (M - 1 - a) / 2 (a odd)
+            constexpr int H = C::N, M = 2 * C::N;
+            const V* pw = (const V*)p.dct_tw;
+            for (int f = tid; f < nv * H; f += C::THREADS) {
+                const int c = f / H, k = f - c * H, at = lds_index<C, C::NP - 1>(c, k);
+                const V z = lds[at], w = pw[k];
+                lds[at] = {w.x * z.x - w.y * z.y, w.x * z.y + w.y * z.x};
+            }
+            __syncthreads();
+            const int f0 = fs_row, len = p.stft_len;
+            const bool last = f0 + nv >= p.stft_frames, warm = t < run_begin;
+            const T* ldr = (const T*)lds;
+            T* carry = (T*)(lds + C::IMDCT_OFF);
+            auto v_at = [&](int c, int a) -> T {
+                return (a & 1) ? -ldr[2 * lds_index<C, C::NP - 1>(c, (M - 1 - a) >> 1) + 1] : ldr[2 * lds_index<C, C::NP - 1>(c, a >> 1)];
+            };
+            if (!warm) {
+                // blocks f0 - 1 .. f0 + nv - 2 of the entry: the later frame of block f0 + c - 1 is row c, the earlier one row
+                // c - 1 or, for c = 0, the carry; frame 0 of an entry is nobody's later frame
+                const int c_lo = f0 == 0 ? 1 : 0;
+                const T* ws = (const T*)p.stft_win;
+                T* outb = (T*)p.out + obase * len;
+                auto sample = [&](int c, int i) -> T {
+                    const int a = i < H ? H - 1 - i : i - H;  // y_q[M + i] = -v_q[a]
+                    const T e = c == 0 ? carry[a] : v_at(c - 1, a);
+                    const T l = i < H ? v_at(c, H + i) : -v_at(c, 3 * H - 1 - i);  // y_(q+1)[i]
+                    return fma_t(ws[i], l, ws[M + i] * -e);
+                };
+                for (int f = tid; f < (nv - c_lo) * H; f += C::THREADS) {
+                    const int cc = f / H, i = 2 * (f - cc * H), c = cc + c_lo;
+                    const long long o = (long long)(f0 + c - 1) * M + i;
+                    if (o + 1 < len) {
+                        gstore_pair(outb + o, sample(c, i), sample(c, i + 1));
+                    } else if (o < len) {
+                        outb[o] = sample(c, i);
+                    }
+                }
+            }
+            __syncthreads();  // (uniform) every read of the previous carry before the next one is written
+            if (!last)
+                for (int a = tid; a < H; a += C::THREADS) carry[a] = v_at(nv - 1, a);
             __syncthreads();
         } else if constexpr (C::DCT == 4) {
             // Z = F(p . z) lies in LDS: item (c, k), k < ceil(N / 2), holds c_k = p_k Z_k and c_(N-1-k) and stores the pairs

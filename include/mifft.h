@@ -387,10 +387,47 @@ typedef enum {
  * MIFFT_FLAG_STFT_POWER; the other flags an STFT plan refuses; ndim != 2; inverse != 0; M outside the limits of a DCT-IV row
  * (even, 8 .. 16384, F64 up to 8192, M / 2 without a prime factor above 32); MIFFT_JIT=0.  MIFFT_ERR_BAD_BASES: a window value
  * or scale that is not finite, a scale of zero (or radices that do not multiply to M / 2).  MIFFT_ERR_BAD_DTYPE: in_dtype !=
- * out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: T >= 2^31.  The inverse (IMDCT) is a DCT-IV
- * plan followed by the unfolding and the overlap-add, which the Python package composes; a fused one is not routed. */
+ * out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: T >= 2^31.  The inverse (IMDCT) is the same
+ * tag on a MIFFT_FLAG_ISTFT plan, below. */
 #define MIFFT_MDCT_TAG_LO 0x43544401u
 #define MIFFT_MDCT_TAG_HI 0x7FF84D44u
+/* Inverse MDCT (IMDCT; no reference counterpart): a MIFFT_FLAG_ISTFT plan whose window payload carries the tag MIFFT_MDCT_TAG,
+ * mirroring the forward.  F frames of M coefficients per batch entry, overlap-added every M samples:
+ *   flags = MIFFT_FLAG_ISTFT | MIFFT_FLAG_STFT_CENTER_ZEROS | MIFFT_FLAG_STFT_HOP(M) (centred: the first M padded samples are
+ *   trimmed), ndim = 3, dims = {T, F, 2 M}, inverse = 1, in_components = 1, in_dtype == out_dtype in {F32, F64};
+ *       x (batch, F, M, 1)  ->  out (batch, T, 1),    F >= 2,  2 <= T <= (F - 1) M,
+ *       y_f[j] = g w[j] sum_{k < M} x[b, f, k] cos(pi / M (j + 1/2 + M / 2)(k + 1/2)),   j < 2 M,
+ *       out[b, q M + i] = y_q[M + i] + y_{q+1}[i],     0 <= q <= F - 2,  i < M,  q M + i < T.
+ * The first half of frame 0 and the second half of frame F - 1 are never used.  With g = 2 / M (g = sqrt(2 / M) against an
+ * MDCT of scale sqrt(2 / M)) and a window with w[j]^2 + w[j + M]^2 = 1 and w[j] = w[2M-1-j] the plan inverts the MDCT plan of
+ * the same window (time-domain aliasing cancellation).  There is no envelope to divide by, hence no overlap-add condition.
+ *   - bases_len[0] is exactly 2 (2 M) + 4 words: w[0 .. 2M-1] | TAG | g, binary64 values, low word first; g is finite and not
+ *     zero.  Host data, taken by value.  A payload of any length whose last four words are TAG | g is this request;
+ *   - bases_len[1] is 0;  bases_len[2] is 0 (the default estimate) or the radices of M / 2.
+ * Every untagged MIFFT_FLAG_ISTFT payload (0, 2 n, 2 n + 2 words) means what it meant, and every other length keeps its
+ * refusal naming bases_len[0].
+ * ONE launch, no scratch, no memset, no tensor of frames and no atomics: the DCT-IV tile above over TILE consecutive frames
+ * of one entry (kernel rows<M>[_f64]_dct4_<radices>_imdct_jit, compiled at run time only).  Its store finishes the DCT-IV in
+ * LDS (v = the plain cosine sums of a frame), reads the unfold y[i] = v[h+i], y[M-1-i] = -v[h+i], y[3h-1-i] = y[3h+i] = -v[i]
+ * (i < h = M / 2) straight from the slots of v, and forms every output sample from exactly two products,
+ * fma(ws[i], y_{q+1}[i], ws[M+i] y_q[M+i]) with ws = g w rounded once from binary64, the earlier frame first; the pass's
+ * own scale is not applied.  The second half of a tile's last frame travels to the workgroup's next tile as h reals in LDS.
+ * Workgroups own contiguous ascending runs of tiles exactly as for the inverse STFT (same grid formula); a run that starts
+ * inside an entry first transforms ONE frame, the last of the tile before it, with its stores suppressed.  Every sample of
+ * [0, T) of every entry of the exec is written exactly once with a plain store, nothing else is written, nothing outside the
+ * exec's entries of x is read, and an entry's result is bit-identical for any batch, first / count, whole_batch and grid.
+ * mifft_plan_num_launches() is 1, mifft_plan_scratch_bytes() 0; mifft_plan_in_bytes() / _out_bytes() are batch * F * M and
+ * batch * T elements; mifft_exec_batch(first, count) offsets x by first * F * M and out by first * T reals;
+ * mifft_plan_pass_geometry(2, count) reports {TILE, threads, count * ceil(F / TILE), grid}; dims 0 and 1 report no stages and
+ * "none", dim 2 the stages of M / 2 and the kernel.
+ * Refused before any device work, the reason in mifft_last_error().  MIFFT_ERR_UNSUPPORTED: a hop other than M; no centre bit,
+ * or MIFFT_FLAG_STFT_CENTER_REFLECT; inverse = 0; the other flags an inverse STFT plan refuses; M outside the limits of a
+ * DCT-IV row (even, 8 .. 16384, F64 up to 8192, M / 2 without a prime factor above 32); a tile and carry beyond the CU's LDS
+ * (the twiddle table moves to global memory first, from M = 16384 in F32 and 8192 in F64; no admissible M is refused today);
+ * MIFFT_JIT=0.  MIFFT_ERR_BAD_DIM: F < 2, T < 2 or T > (F - 1) M.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.
+ * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_BASES: a tagged bases_len[0] other than 2 (2 M) + 4, a non-zero
+ * bases_len[1], a window value or g that is not finite, g = 0 (or radices that do not multiply to M / 2).
+ * MIFFT_ERR_TOO_LARGE: F > 2^26 or T >= 2^31. */
 
 typedef struct mifft_plan mifft_plan;
 

@@ -169,8 +169,10 @@ static_assert(MIFFT_STFT_EXT_TAG_LO == 0x46465401u && MIFFT_STFT_EXT_TAG_HI == 0
 constexpr uint64_t kStftExtTag = ((uint64_t)MIFFT_STFT_EXT_TAG_HI << 32) | MIFFT_STFT_EXT_TAG_LO;
 // MIFFT_DCT_TYPE4_TAG as the first `bases` word of a MIFFT_FLAG_DCT plan: DCT-IV of real rows (no radix can equal the tag).
 // MIFFT_MDCT_TAG behind the 2 M window values of a MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_CENTER_ZEROS | MIFFT_FLAG_STFT_HOP(M)
-// plan with dims = {T, 2 M}: the MDCT, x (batch, T, 1) -> out (batch, F, M, 1) real (include/mifft.h).  Both are created
-// through mifft_plan_create itself, as the plans above.
+// plan with dims = {T, 2 M}: the MDCT, x (batch, T, 1) -> out (batch, F, M, 1) real (include/mifft.h).  The same tag behind
+// the window of a MIFFT_FLAG_ISTFT | MIFFT_FLAG_STFT_CENTER_ZEROS | MIFFT_FLAG_STFT_HOP(M) plan with dims = {T, F, 2 M} and
+// inverse = 1: the IMDCT, x (batch, F, M, 1) -> out (batch, T, 1).  All are created through mifft_plan_create itself, as the
+// plans above.
 static_assert(MIFFT_DCT_TYPE4_TAG == 0x44435434u && MIFFT_DCT_TYPE4_TAG > 16384u, "MIFFT_DCT_TYPE4_TAG is no radix");
 static_assert(MIFFT_MDCT_TAG_LO == 0x43544401u && MIFFT_MDCT_TAG_HI == 0x7FF84D44u &&
                   (MIFFT_MDCT_TAG_HI & 0x7FF80000u) == 0x7FF80000u &&
