@@ -1464,7 +1464,7 @@ def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -
     ``X[f, k] = sum_{j<2n} w[j] x~[(f - 1) n + j] cos(pi / n (j + 1/2 + n/2)(k + 1/2))``, x~ being x with zeros outside
     [0, T).  Returns (..., F, n) contiguous, F = mdct_frames(T, n); the leading dims fold into the batch.  ``window=None`` is
     the sine window; a tensor or sequence of 2n values is taken by value.  ``norm="ortho"`` multiplies by sqrt(2 / n) (the
-    orthonormal DCT-IV of the folded frame).  n is even, from 8 to 16384 (float64: 8192), n // 2 without a prime factor above
+    orthonormal DCT-IV of the folded frame).  n is even, from 8 to 16384 (float64: 12288), n // 2 without a prime factor above
     32.  Input that is not of ``out_dtype`` (default: that of a float32 / float64 ``x``, else float64) is converted first.
     One kernel launch: the framing, the window and the fold of 2n samples to n happen in the load of a DCT-IV tile.  Plans are
     cached per (shape, dtype, n, norm, device, stream) and the window's contents; loops should use ``plan_mdct``."""

@@ -121,8 +121,13 @@ typedef enum {
  * MIFFT_ERR_BAD_DTYPE.  MIFFT_ERR_UNSUPPORTED (with the reason) for:
  *   - an odd last dim, or one below 8;
  *   - MIFFT_FLAG_FAITHFUL_STAGES together with this flag (the reference has no half spectrum to be faithful to);
- *   - a last dim whose half d{k-1} / 2 has no packed configuration: a prime factor above 32, a last dim above 16384
- *     (F64: above 8192), a row tile beyond 96 KiB of LDS;
+ *   - a last dim n outside THE LIMITS OF THE PACKED ROWS, the one rule for every mode that runs on these kernels (this flag,
+ *     MIFFT_FLAG_DCT and its type 4, the last dim of MIFFT_FLAG_DCT_ND, MIFFT_FLAG_STFT with its spectrogram and MDCT forms,
+ *     MIFFT_FLAG_ISTFT with its IMDCT form): n is even, from 8 to 16384; its half n / 2 has no prime factor above 32; and
+ *     the row tile -- n / 2 complex elements of the plan's float type per row -- is at most 96 KiB of LDS.  Only a one-row
+ *     tile reaches that: F32 rows never do (16384 points are 64 KiB), F64 rows end at 12288 points (exactly 96 KiB; 12320,
+ *     the next length with a smooth half, is refused).  From about 10000 points an F64 row keeps its twiddle table in global
+ *     memory instead of LDS.  (MIFFT_FLAG_ISTFT alone is narrower in F64, for its carry: see there);
  *   - an outer dim above 4096 points (it would need the four-step routes), or one without a column kernel;
  *   - MIFFT_JIT=0 and a last dim without a precompiled packed-row kernel: precompiled for 128, 480, 1024, 1080 and 1920
  *     points (F32 and F64, input of the plan's own float type); every other length is specialised at run time. */
@@ -139,10 +144,11 @@ typedef enum {
  *   - a nonzero bases_len[d] for a kept dim: MIFFT_ERR_BAD_BASES;
  *   - MIFFT_FLAG_FAITHFUL_STAGES with any keep bit (the reference has no axes to be faithful to): MIFFT_ERR_UNSUPPORTED;
  *   - with MIFFT_FLAG_HALF_SPECTRUM, a kept last dim (numpy halves the last TRANSFORMED axis): MIFFT_ERR_UNSUPPORTED.
- * Routed: the innermost dim transformed up to the single-launch row limit (16384 points, F64 8192); any other transformed
- * dim up to 4096 points.  Anything else is MIFFT_ERR_UNSUPPORTED with a reason: masked plans have no four-step, plane,
- * Hermitian or half-store routes.  With MIFFT_FLAG_HALF_SPECTRUM the last dim is packed real rows as without a mask and
- * the other transformed dims are column passes over the half-spectrum tensor. */
+ * Routed: the innermost dim transformed up to the single-launch limit of a COMPLEX row (16384 points, F64 8192: 128 KiB; with
+ * MIFFT_FLAG_HALF_SPECTRUM the limits of the packed rows above instead); any other transformed dim up to 4096 points.
+ * Anything else is MIFFT_ERR_UNSUPPORTED with a reason: masked plans have no four-step, plane, Hermitian or half-store routes.
+ * With MIFFT_FLAG_HALF_SPECTRUM the last dim is packed real rows as without a mask and the other transformed dims are
+ * column passes over the half-spectrum tensor. */
 #define MIFFT_FLAG_KEEP_DIM(d) ((uint32_t)1u << (8 + (d)))
 #define MIFFT_FLAG_KEEP_MASK 0x3F00u
 
@@ -163,8 +169,8 @@ typedef enum {
  * MIFFT_ERR_UNSUPPORTED (with the reason), before any device work, for:
  *   - ndim != 1;
  *   - an odd n, or one below 8;
- *   - n / 2 without a packed configuration: a prime factor above 32, n above 16384 (F64: above 8192), a row tile beyond
- *     96 KiB of LDS;
+ *   - n outside the limits of the packed rows (MIFFT_FLAG_HALF_SPECTRUM above: n / 2 with a prime factor above 32, n above
+ *     16384, a row tile beyond 96 KiB of LDS, which ends F64 rows at 12288 points);
  *   - MIFFT_FLAG_DCT together with MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_FAITHFUL_STAGES or any keep bit;
  *   - MIFFT_FLAG_DCT_ORTHO without MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND;
  *   - MIFFT_JIT=0 and an n without a precompiled instance: precompiled for 1024 points (F32 and F64, input of the plan's
@@ -199,7 +205,7 @@ typedef enum {
  * plans run the same order): the first reads x and writes out, the others run in place on out.  No scratch
  * (mifft_plan_scratch_bytes is 0); mifft_plan_in_bytes / out_bytes are batch * d0 * .. * d{k-1} real elements.
  *   - a transformed LAST dim of n points runs the packed-row kernel of MIFFT_FLAG_DCT over the prod / n rows of every
- *     batch entry, with its limits (even, 8 .. 16384, F64 up to 8192, n / 2 without a prime factor above 32);
+ *     batch entry, with the limits of the packed rows (even, 8 .. 16384, F64 up to 12288, n / 2 without a prime factor above 32);
  *     mifft_plan_stages() reports the stages of its n / 2-point transform, `bases` factor n / 2;
  *     the kernel is rows<n>[_f64]_dct2_<radices> / ..._dct3_<radices>;
  *   - any other transformed dim of n points lies at a stride of S reals (S = the product of the dims after it), S even.  The
@@ -253,8 +259,8 @@ typedef enum {
  *   - MIFFT_FLAG_STFT with MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT, MIFFT_FLAG_DCT_ND,
  *     MIFFT_FLAG_DCT_ORTHO or a keep bit;
  *   - ndim != 2;  inverse != 0 (the inverse STFT is not routed through this bit: MIFFT_FLAG_ISTFT, below);
- *   - n outside the limits of the packed rows: odd, below 8, above 16384 (F64: 8192), n / 2 with a prime factor above 32, a
- *     row tile beyond 96 KiB of LDS;
+ *   - n outside the limits of the packed rows (MIFFT_FLAG_HALF_SPECTRUM above): odd, below 8, above 16384 (F64: 12288, the
+ *     row tile of 96 KiB), n / 2 with a prime factor above 32;
  *   - T < n without a centre bit;  n / 2 > T - 1 with MIFFT_FLAG_STFT_CENTER_REFLECT (one reflection must reach);
  *   - MIFFT_JIT=0 (no precompiled instances).
  * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_BAD_BASES: a
@@ -298,7 +304,11 @@ typedef enum {
  *   - MIFFT_FLAG_ISTFT with MIFFT_FLAG_STFT, MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT,
  *     MIFFT_FLAG_DCT_ND, MIFFT_FLAG_DCT_ORTHO or a keep bit;  inverse = 0;  ndim != 3;  both centre bits;
  *   - hop 0, or hop > n (gaps between the frames: the envelope would be zero there);
- *   - n outside the limits of the packed rows (as for MIFFT_FLAG_STFT), or a tile and carry beyond the CU's LDS;
+ *   - n outside the limits of the packed rows (as for MIFFT_FLAG_STFT), or a tile and carry beyond the CU's LDS: the carry of
+ *     n reals lies beside the row tile, and the two may fill the 160 KiB (the twiddle table moves to global memory first, from
+ *     about n = 13300 in F32 and 6650 in F64).  F32 always fits; in F64 tile and carry are n / 2 + n / 2 complex doubles, 160 KiB
+ *     exactly at n = 10240, the longest F64 frame (10290, the next length with a smooth half, is refused: the reason names the
+ *     "carry");
  *   - a window whose squared overlap-add falls below 1e-11 in absolute value at one of the samples t + c, 0 <= t < T
  *     (torch's own NOLA threshold and range): the reason names the "overlap-add" condition;
  *   - MIFFT_JIT=0 (no precompiled instances).
@@ -385,10 +395,10 @@ typedef enum {
  * kernel; launches 1, scratch 0.  The STFT's untagged lengths 0 and 2 n keep their meaning, and every other length its refusal.
  * Refused before any device work.  MIFFT_ERR_UNSUPPORTED: a hop other than M; MIFFT_FLAG_STFT_CENTER_REFLECT; no centre bit;
  * MIFFT_FLAG_STFT_POWER; the other flags an STFT plan refuses; ndim != 2; inverse != 0; M outside the limits of a DCT-IV row
- * (even, 8 .. 16384, F64 up to 8192, M / 2 without a prime factor above 32); MIFFT_JIT=0.  MIFFT_ERR_BAD_BASES: a window value
- * or scale that is not finite, a scale of zero (or radices that do not multiply to M / 2).  MIFFT_ERR_BAD_DTYPE: in_dtype !=
- * out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: T >= 2^31.  The inverse (IMDCT) is the same
- * tag on a MIFFT_FLAG_ISTFT plan, below. */
+ * (the limits of the packed rows: even, 8 .. 16384, F64 up to 12288, M / 2 without a prime factor above 32); MIFFT_JIT=0.
+ * MIFFT_ERR_BAD_BASES: a window value or scale that is not finite, a scale of zero (or radices that do not multiply to M / 2).
+ * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: T >= 2^31.
+ * The inverse (IMDCT) is the same tag on a MIFFT_FLAG_ISTFT plan, below. */
 #define MIFFT_MDCT_TAG_LO 0x43544401u
 #define MIFFT_MDCT_TAG_HI 0x7FF84D44u
 /* Inverse MDCT (IMDCT; no reference counterpart): a MIFFT_FLAG_ISTFT plan whose window payload carries the tag MIFFT_MDCT_TAG,
@@ -422,8 +432,9 @@ typedef enum {
  * "none", dim 2 the stages of M / 2 and the kernel.
  * Refused before any device work, the reason in mifft_last_error().  MIFFT_ERR_UNSUPPORTED: a hop other than M; no centre bit,
  * or MIFFT_FLAG_STFT_CENTER_REFLECT; inverse = 0; the other flags an inverse STFT plan refuses; M outside the limits of a
- * DCT-IV row (even, 8 .. 16384, F64 up to 8192, M / 2 without a prime factor above 32); a tile and carry beyond the CU's LDS
- * (the twiddle table moves to global memory first, from M = 16384 in F32 and 8192 in F64; no admissible M is refused today);
+ * DCT-IV row (the limits of the packed rows: even, 8 .. 16384, F64 up to 12288, M / 2 without a prime factor above 32); a tile
+ * and carry beyond the CU's LDS (the carry is M / 4 complex elements, half a one-row tile, so tile and carry are at most 144 KiB;
+ * the twiddle table moves to global memory first, from about M = 16000 in F32 and 8000 in F64; no admissible M is refused today);
  * MIFFT_JIT=0.  MIFFT_ERR_BAD_DIM: F < 2, T < 2 or T > (F - 1) M.  MIFFT_ERR_BAD_COMPONENTS: in_components != 1.
  * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_BASES: a tagged bases_len[0] other than 2 (2 M) + 4, a non-zero
  * bases_len[1], a window value or g that is not finite, g = 0 (or radices that do not multiply to M / 2).

@@ -80,7 +80,7 @@ def test_unrouted_masked_plans_are_unsupported_before_the_device():
     assert rc == UNSUPPORTED and "dimension 0" in why
     rc, why = _create([4, 32768], flags=KEEP(0))  # an innermost dim beyond one row launch
     assert rc == UNSUPPORTED and "dimension 1" in why
-    rc, why = _create([4, 16384], flags=KEEP(0), out_dtype=1, in_dtype=1)  # fp64 rows end at 8192
+    rc, why = _create([4, 16384], flags=KEEP(0), out_dtype=1, in_dtype=1)  # fp64 complex rows end at 8192 points (128 KiB)
     assert rc == UNSUPPORTED
     rc, why = _create([64, 32, 4], comps=1, flags=HALF | KEEP(2))  # half spectrum of a kept last dim
     assert rc == UNSUPPORTED and "last dimension kept" in why

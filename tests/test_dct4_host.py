@@ -110,7 +110,7 @@ def test_c_abi_refuses_before_looking_for_a_device(inverse):
             (dict(dims=[6]), UNSUPPORTED, "8 points"),
             (dict(dims=[2 * 37 * 4]), UNSUPPORTED, "packed"),
             (dict(dims=[32768]), UNSUPPORTED, "16384"),
-            (dict(dims=[16384], in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),  # fp64 rows end at 8192 points
+            (dict(dims=[16384], in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),  # fp64 rows end at 12288 points (a 96-KiB tile)
             (dict(dims=[1024], flags=DCT | 2), UNSUPPORTED, "HALF_SPECTRUM"),
             (dict(dims=[1024], flags=DCT | 1), UNSUPPORTED, "FAITHFUL"),
             (dict(dims=[1024], flags=DCT | (1 << 8)), UNSUPPORTED, "KEEP_DIM"),
@@ -131,7 +131,7 @@ def test_a_valid_request_gets_as_far_as_the_device(inverse):
         for flags in (DCT, DCT | ORTHO):
             rc, why = _create([n], inverse=inverse, flags=flags)
             assert rc == -10, (n, why)
-    rc, why = _create([8192], inverse=inverse, in_dtype=1, out_dtype=1)  # the longest fp64 row
+    rc, why = _create([8192], inverse=inverse, in_dtype=1, out_dtype=1)  # the longest fp64 power of two (the longest row: 12288)
     assert rc == -10, why
     rc, why = _create([1024], inverse=inverse, bases=(TAG, 16, 16, 2))  # the tag, then the radices of 512
     assert rc == -10, why

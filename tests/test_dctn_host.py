@@ -98,7 +98,7 @@ def test_a_valid_request_gets_as_far_as_the_device(inverse):
         assert rc == -10, (dims, flags, why)
     rc, why = _create([4096, 8, 16384], inverse=inverse, batch=1)  # the longest column and row
     assert rc == -10, why
-    rc, why = _create([2048, 8, 8192], inverse=inverse, in_dtype=1, out_dtype=1, batch=1)  # ... and the longest fp64 ones
+    rc, why = _create([2048, 8, 8192], inverse=inverse, in_dtype=1, out_dtype=1, batch=1)  # ... and long fp64 ones
     assert rc == -10, why
     rc, why = _create([4096, 64], inverse=inverse, in_dtype=1, out_dtype=1)  # (no fp64 column tile of 4096 points fits LDS)
     assert rc == UNSUPPORTED and "column configuration" in why, why

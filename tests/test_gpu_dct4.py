@@ -51,7 +51,7 @@ SHAPES = [((37, 8), True),      # N = 4
           ((21, 480), True),
           ((19, 1024), True),
           ((11, 686), True),    # N = 343
-          ((3, 8192), True),    # the longest fp64 row
+          ((3, 8192), True),    # the longest fp64 power of two
           ((2, 16384), False)]  # the longest row
 CASES = [(s, torch.float32) for s, _ in SHAPES] + [(s, torch.float64) for s, f64 in SHAPES if f64]
 

@@ -67,7 +67,7 @@ def _axes(x):
 # (shape incl. batch, fp64 too?) -- batches leave ragged row tiles and column tiles
 SHAPES_1D = [((37, 8), True), ((29, 16), False), ((33, 128), True), ((21, 480), True), ((19, 1024), True),
              ((13, 1080), False), ((5, 1920), True), ((11, 686), True),  # 686 = 2 * 7^3: odd packed length, hipRTC
-             ((3, 8192), True)]  # (the longest fp64 row)
+             ((3, 8192), True)]  # (the longest fp64 power of two)
 SHAPES_ND = [((3, 640, 480), True), ((2, 1920, 1080), False), ((3, 64, 64, 64), True), ((1, 128, 128, 128), False),
              ((1, 25, 160, 160, 48), False)]
 CASES = [(s, torch.float32) for s, _ in SHAPES_1D + SHAPES_ND] + \

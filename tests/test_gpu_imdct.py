@@ -159,7 +159,7 @@ def test_the_largest_length_that_plans():
     print(f"imdct n=16384: block rel L2 {err:.3e} {plan.kernel_name(2)} geometry={plan.pass_geometry(2)}")
     assert err <= REL_L2_TOL_F32
     plan.close()
-    with pytest.raises(mf.MifftError) as e:  # fp64 rows end at 8192 points
+    with pytest.raises(mf.MifftError) as e:  # fp64 rows end at 12288 points (a 96-KiB tile)
         mf.plan_imdct(torch.float64, B, F, n)
     assert e.value.status == -15
 

@@ -104,13 +104,19 @@ def test_without_runtime_specialisation_only_precompiled_lengths_are_routed():
             assert int(rc) in (0, -10), ln
 
 
-def test_fp64_rows_end_at_8192_points():
+def test_fp64_rows_end_at_12288_points():
     rc, why = _create([16384], comps=1, inverse=False, out_dtype=1, in_dtype=1)
     assert rc == UNSUPPORTED and "packed" in why
     rc, why = _create([16384], comps=1, inverse=False)  # fp32: the last supported length
     assert rc != UNSUPPORTED, why
     rc, why = _create([8192], comps=2, inverse=True, out_dtype=1, in_dtype=1)
     assert rc != UNSUPPORTED, why
+    # the rule: the n / 2-point row tile fits 96 KiB of LDS -- 12288 points in fp64; the next smooth half is 12320 / 2
+    for inverse in (False, True):
+        rc, why = _create([12288], comps=2 if inverse else 1, inverse=inverse, out_dtype=1, in_dtype=1)
+        assert rc != UNSUPPORTED, why
+        rc, why = _create([12320], comps=2 if inverse else 1, inverse=inverse, out_dtype=1, in_dtype=1)
+        assert rc == UNSUPPORTED and "packed" in why
 
 
 def test_the_flag_bit_alone_selects_the_half_spectrum_layouts():

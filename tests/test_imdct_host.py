@@ -135,7 +135,7 @@ def test_c_abi_refuses_before_looking_for_a_device():
             (dict(M=9), UNSUPPORTED, "M = 9"),                          # odd
             (dict(M=74), UNSUPPORTED, "packed"),                        # M / 2 = 37
             (dict(M=32768), UNSUPPORTED, "M = 32768"),
-            (dict(M=16384, in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),  # fp64 rows end at 8192 points
+            (dict(M=16384, in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),  # fp64 rows end at 12288 points (a 96-KiB tile)
             (dict(window=[1.0] * 7 + [inf] + [1.0] * 24), BAD_BASES, "window value 7"),
             (dict(window=[nan] + [1.0] * 31), BAD_BASES, "window value 0"),
             (dict(gain=inf), BAD_BASES, "gain"),

@@ -125,7 +125,7 @@ def test_c_abi_refuses_before_looking_for_a_device():
             (dict(M=9), UNSUPPORTED, "M = 9"),                        # odd
             (dict(M=74), UNSUPPORTED, "packed"),                      # M / 2 = 37
             (dict(M=32768), UNSUPPORTED, "M = 32768"),
-            (dict(M=16384, in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),  # fp64 rows end at 8192 points
+            (dict(M=16384, in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),  # fp64 rows end at 12288 points (a 96-KiB tile)
             (dict(scale=inf), -5, "scale"),
             (dict(scale=nan), -5, "scale"),
             (dict(scale=0.0), -5, "scale"),

@@ -88,7 +88,7 @@ def test_c_abi_refuses_before_looking_for_a_device():
             (dict(dims=[1000, 63]), UNSUPPORTED, "odd"),
             (dict(dims=[1000, 6]), UNSUPPORTED, "8 points"),
             (dict(dims=[40000, 32768]), UNSUPPORTED, "16384"),
-            (dict(dims=[40000, 16384], in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),      # fp64 rows end at 8192 points
+            (dict(dims=[40000, 16384], in_dtype=1, out_dtype=1), UNSUPPORTED, "packed"),      # fp64 rows end at 12288 points (a 96-KiB tile)
             (dict(dims=[1000, 2 * 37 * 4]), UNSUPPORTED, "prime factor above 32"),
             (dict(dims=[63, 64]), UNSUPPORTED, "T < n"),                                        # uncentred, shorter than a frame
             (dict(dims=[32, 64], flags=STFT | HOP(4) | REFLECT), UNSUPPORTED, "one reflection"),  # n / 2 = 32 > T - 1 = 31
