@@ -412,6 +412,12 @@ bool build_fourstep(Plan& plan, int dim_index, std::string& why_not);
 bool build_transposed_dim(Plan& plan, int dim_index, const std::vector<uint32_t>& radices,
                           const std::vector<uint32_t>& processed, std::string& why_not);
 hipError_t upload_twiddle_table(int out_dtype, int64_t N, bool inverse, void** d_table);
+// every other plan (schedule.cpp): the general route, one kernel per pass over every dimension chosen by its scheduler
+int build_general(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
+                  const std::vector<std::vector<uint32_t>>& processed, std::string& why);
+// Frees the device tables of every pass and the plan scratch (schedule.cpp).  No HIP call for a plan that owns nothing: it
+// also runs where no device was opened.
+void free_plan_device(Plan& plan);
 
 inline size_t dtype_size(int dt) {
     switch (dt) {
