@@ -49,6 +49,8 @@ STFT_EXT_TAG_LO = 0x46465401   # MIFFT_STFT_EXT_TAG_LO / _HI: the NaN in the pow
 STFT_EXT_TAG_HI = 0x7FF84D49   # a plan (log stage, matrix after the bands)
 STFT_MAX_BANDS = 32768         # MIFFT_STFT_MAX_BANDS
 DCT_TYPE4_TAG = 0x44435434     # MIFFT_DCT_TYPE4_TAG: the first ``bases`` word of a FLAG_DCT plan that is a DCT-IV
+DST_TAG = 0x44535432           # MIFFT_DST_TAG: the first ``bases`` word of a FLAG_DCT / FLAG_DCT_ND plan that is a DST-II
+DST_TYPE4_TAG = 0x44535434     # MIFFT_DST_TYPE4_TAG: the first ``bases`` word of a FLAG_DCT plan that is a DST-IV
 MDCT_TAG_LO = 0x43544401       # MIFFT_MDCT_TAG_LO / _HI: the NaN behind the window of a FLAG_STFT plan that is an MDCT
 MDCT_TAG_HI = 0x7FF84D44
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
@@ -489,6 +491,9 @@ class Plan:
     the radices of n (or an empty one).
     ``dct_type=4`` beside ``dct=True`` (no reference counterpart): the DCT-IV instead, both directions the same kernel with
     another scale, in_dtype == out_dtype; the request travels as MIFFT_DCT_TYPE4_TAG in front of the radices of n // 2.
+    ``dst=True`` beside ``dct=True`` or ``dctn=True`` (no reference counterpart): the sine transform of the same type on the
+    same passes (scipy's dst / idst of ``dct_type`` 2 or 4, dstn / idstn of type 2); the request travels as MIFFT_DST_TAG or
+    MIFFT_DST_TYPE4_TAG in front of the radices of the first list, and an empty list of such a plan is that dim's default.
     ``mdct`` = M > 0 (no reference counterpart): the MDCT of real signals, x (batch, T, 1) -> out (batch, F, M, 1),
     F = mdct_frames(T, M) frames of 2 M samples every M; ``stft_window`` None (the sine window) or 2 M values, ``mdct_scale``
     the factor on the cosine sum (MIFFT_MDCT_TAG in include/mifft.h, _check_mdct_layout, plan_mdct).  ``bases`` has two
@@ -503,7 +508,7 @@ class Plan:
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0):
+                 imdct_gain: float = 1.0, dst: bool = False):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct = int(mdct), int(imdct)
         if dct_type not in (2, 4):
@@ -589,6 +594,8 @@ class Plan:
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
         dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
+        if dst and not (dct or dctn):
+            raise MifftError(ERR_UNSUPPORTED, "dst=True selects the sine transform of a dct=True or dctn=True plan")
         if istft:
             dims = istft_dims
         elif stft:
@@ -597,13 +604,20 @@ class Plan:
             dims = _check_dctn_layout(in_shape, out_shape)
             flags = (int(flags) | FLAG_DCT_ND | _dct_norm_flags(norm) | (FLAG_DCT if dct else 0) |
                      (FLAG_HALF_SPECTRUM if half_spectrum else 0))
+            if dst:  # (the tag leads the first list; a type 4 travels as its own tag and the library refuses it)
+                if bases is not None and len(bases) != len(dims):
+                    raise MifftError(-7, "the bases list of an N-D DST plan has one entry per dim")
+                tag = DST_TYPE4_TAG if dct_type == 4 else DST_TAG
+                rest = [[int(b) for b in bs] for bs in bases] if bases is not None else [[] for _ in dims]
+                bases = [[tag] + rest[0]] + rest[1:]
         elif dct:  # (with half_spectrum as well: the library refuses the pair)
             dims = _check_dct_layout(in_shape, out_shape)
             flags = int(flags) | FLAG_DCT | _dct_norm_flags(norm) | (FLAG_HALF_SPECTRUM if half_spectrum else 0)
-            if dct_type == 4:  # (the tag, then the radices of n // 2; the tag alone: the default estimate)
+            if dct_type == 4 or dst:  # (the tag, then the radices of n // 2; the tag alone: the default estimate)
                 if bases is not None and len(bases) != 1:
                     raise MifftError(-7, "the bases list of a DCT plan has one entry, the radices of n // 2")
-                bases = [[DCT_TYPE4_TAG] + ([int(b) for b in bases[0]] if bases is not None else [])]
+                tag = (DST_TYPE4_TAG if dct_type == 4 else DST_TAG) if dst else DCT_TYPE4_TAG
+                bases = [[tag] + ([int(b) for b in bases[0]] if bases is not None else [])]
         elif half_spectrum:
             dims = _check_half_layout(in_shape, out_shape, bool(inverse))
             flags = int(flags) | FLAG_HALF_SPECTRUM
@@ -627,6 +641,7 @@ class Plan:
         self.istft = istft
         self.spectrogram = stft and stft_power is not None and not mdct
         self.dct_type = int(dct_type) if dct and not dctn and not stft and not istft else 2
+        self.dst = bool(dst) and (dct or dctn) and not stft and not istft
         self.mdct = mdct
         self.imdct = imdct
         self._ndim = len(dims)
@@ -726,7 +741,7 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
              _test: Optional[GPUTest] = None, faithful_stages: bool = False,
              ctx: Optional[DeviceContext] = None, whole_batch: int = 0, half_spectrum: bool = False,
              axes: Optional[Sequence[int]] = None, dct: bool = False, norm=None, dctn: bool = False,
-             dct_type: int = 2) -> Plan:
+             dct_type: int = 2, dst: bool = False) -> Plan:
     """GPU overload of plan_fft (fft/fft/fft.mojo:161-210).
 
     ``runtime_twfs`` and ``max_cluster_size`` are accepted for call-site compatibility
@@ -745,8 +760,13 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     own inverse up to the scale, in_dtype == out_dtype in both directions, MIFFT_DCT_TYPE4_TAG); the default is 2.
     ``dctn`` (no reference counterpart): the N-D DCT-II (``inverse``: its inverse) of a real (batch, d0.., 1) tensor into one of
     the same shape, over ``axes`` (None: every dim), ``norm`` as for ``dct`` (include/mifft.h, MIFFT_FLAG_DCT_ND).
+    ``dst`` beside ``dct`` or ``dctn`` (no reference counterpart): the sine transform instead, DST-II / its inverse or with
+    ``dct_type=4`` (``dct`` only) the DST-IV, as scipy.fft.dst / idst / dstn / idstn; layouts, ``bases``, ``norm`` and limits are
+    those of the cosine plan (include/mifft.h, MIFFT_DST_TAG / MIFFT_DST_TYPE4_TAG).
     """
     del runtime_twfs, max_cluster_size
+    if dst and not (dct or dctn):
+        raise MifftError(ERR_UNSUPPORTED, "dst=True selects the sine transform of a dct=True or dctn=True plan")
     if dctn:  # (layout errors before any device work)
         _check_dctn_layout(tuple(int(v) for v in in_layout), tuple(int(v) for v in out_layout))
         _dct_norm_flags(norm)
@@ -763,7 +783,8 @@ def plan_fft(in_dtype, out_dtype, in_layout: Sequence[int], out_layout: Sequence
     flags = FLAG_FAITHFUL_STAGES if (faithful_stages or _test is not None) else 0
     return Plan(in_dtype, out_dtype, in_layout, out_layout, bases=bases, inverse=inverse,
                 device=ctx.device, flags=flags, whole_batch=whole_batch, half_spectrum=half_spectrum, axes=axes,
-                dct=dct, norm=norm, dctn=dctn, dct_type=dct_type if dct and not dctn else 2)
+                dct=dct, norm=norm, dctn=dctn, dct_type=dct_type if (dct and not dctn) or (dst and dctn) else 2,
+                dst=dst)
 
 
 def plan_stft(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, window=None, center=None,
@@ -976,7 +997,7 @@ _PLAN_CACHE_LOCK = threading.RLock()
 
 
 def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                 half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2) -> Plan:
+                 half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2, dst: bool = False) -> Plan:
     """Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
     costs a hipMalloc + copy per dimension, and its tables must outlive the kernels enqueued with it.
 
@@ -986,26 +1007,30 @@ def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, fai
     two threads on their own streams) transforming the same shape never share a plan -- and is guarded by a lock."""
     with _PLAN_CACHE_LOCK:
         return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                                   half_spectrum, axes, dct_flags, dct_type)
+                                   half_spectrum, axes, dct_flags, dct_type, dst)
 
 
 def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                        half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2) -> Plan:
+                        half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2,
+                        dst: bool = False) -> Plan:
     # dct_flags: FLAG_DCT or FLAG_DCT_ND (| FLAG_DCT_ORTHO) of the dct / idct / dctn / idctn wrappers' plans, 0 for every other;
-    # dct_type: 4 for the DCT-IV plans of dct / idct (the key of every other plan is what it has always been)
+    # dct_type: 4 for the DCT-IV plans of dct / idct (the key of every other plan is what it has always been); dst: the sine
+    # twins of dst / idst / dstn / idstn, whose keys alone grow by a word
     key = (in_dtype, out_dtype, in_shape, out_shape,
            None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
            bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
            bool(half_spectrum), _keep_flags(len(out_shape), axes), int(dct_flags))
     if dct_type != 2:
         key += (int(dct_type),)
+    if dst:
+        key += ("dst",)
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         try:
             plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
                             faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
                             axes=axes, dct=bool(dct_flags & FLAG_DCT), dctn=bool(dct_flags & FLAG_DCT_ND),
-                            norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None, dct_type=dct_type)
+                            norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None, dct_type=dct_type, dst=dst)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
             # primes <= 97 otherwise, fft/fft/fft.mojo:49-104) rejects lengths with a larger prime factor.  The
@@ -1238,9 +1263,9 @@ def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtyp
     return out.reshape(logical[:-1] + (n,))
 
 
-def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: bool) -> "torch.Tensor":
-    """dct / idct: validation on the host, then one plan over the (batch, n, 1) view of ``x``"""
-    name = "idct" if inverse else "dct"
+def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: bool, kind: str = "dct") -> "torch.Tensor":
+    """dct / idct and, with ``kind="dst"``, dst / idst: validation on the host, then one plan over the (batch, n, 1) view of ``x``"""
+    name = ("i" if inverse else "") + kind
     if type not in (2, 4):
         raise MifftError(ERR_UNSUPPORTED, f"{name}: only types 2 and 4 are supported, got type={type!r}")
     dct_flags = FLAG_DCT | _dct_norm_flags(norm)
@@ -1276,7 +1301,7 @@ def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: 
     out = torch.empty(shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
         plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device, dct_flags=dct_flags,
-                                   dct_type=int(type))
+                                   dct_type=int(type), dst=kind == "dst")
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical)
 
@@ -1301,9 +1326,10 @@ def idct(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: in
     return _dct_rows(x, type, norm, out_dtype, dim, True)
 
 
-def _dct_nd(x: "torch.Tensor", type: int, norm, dim, out_dtype, inverse: bool) -> "torch.Tensor":
-    """dctn / idctn: validation on the host, then one plan over the reduced (batch, e0.., 1) view of ``x``"""
-    name = "idctn" if inverse else "dctn"
+def _dct_nd(x: "torch.Tensor", type: int, norm, dim, out_dtype, inverse: bool, kind: str = "dct") -> "torch.Tensor":
+    """dctn / idctn and, with ``kind="dst"``, dstn / idstn: validation on the host, then one plan over the reduced
+    (batch, e0.., 1) view of ``x``"""
+    name = ("i" if inverse else "") + kind + "n"
     if type != 2:
         raise MifftError(ERR_UNSUPPORTED, f"{name}: only type 2 is supported, got type={type!r}")
     dct_flags = FLAG_DCT_ND | _dct_norm_flags(norm)
@@ -1333,7 +1359,8 @@ def _dct_nd(x: "torch.Tensor", type: int, norm, dim, out_dtype, inverse: bool) -
     out = torch.empty(shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
         plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device,
-                                   axes=None if len(axes) == len(layout) - 1 else axes, dct_flags=dct_flags)
+                                   axes=None if len(axes) == len(layout) - 1 else axes, dct_flags=dct_flags,
+                                   dst=kind == "dst")
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical)
 
@@ -1355,6 +1382,36 @@ def idctn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=No
     """scipy.fft.idctn(x, type=2, norm=norm), the inverse of dctn under the same ``norm`` and ``dim``; the input is converted
     to ``out_dtype`` first."""
     return _dct_nd(x, type, norm, dim, out_dtype, True)
+
+
+def dst(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: int = -1) -> "torch.Tensor":
+    """scipy.fft.dst(x, type=2, norm=norm) along the last dim of a real tensor of any rank >= 1 (an even length from 8 on):
+    ``Y[k] = 2 sum_j x[j] sin(pi (k+1)(2j+1) / 2n)``; ``norm="ortho"`` scales the last bin Y[n-1] by sqrt(1/4n) and the other
+    bins by sqrt(1/2n).  ``type=4`` is scipy's DST-IV, ``Y[k] = 2 sum_j x[j] sin(pi (2j+1)(2k+1) / 4n)``, ``norm="ortho"`` times
+    sqrt(1/2n) (then its own inverse).  Each is the kernel of ``dct`` of that type with a sign in its load and the index
+    reversal in its store: one launch, n reals read once and written once, the layout, ``dim``, dtype rules and limits of
+    ``dct`` (MIFFT_DST_TAG, MIFFT_DST_TYPE4_TAG).  Only ``type=2`` and ``type=4`` (MifftError -15 otherwise)."""
+    return _dct_rows(x, type, norm, out_dtype, dim, False, "dst")
+
+
+def idst(x: "torch.Tensor", type: int = 2, norm=None, *, out_dtype=None, dim: int = -1) -> "torch.Tensor":
+    """scipy.fft.idst(x, type=2, norm=norm), the inverse of dst under the same ``norm`` (the DST-III divided by 2n); the rules
+    of idct.  ``type=4``: dst(x, 4) / 2n (``norm="ortho"``: the orthonormal DST-IV itself)."""
+    return _dct_rows(x, type, norm, out_dtype, dim, True, "dst")
+
+
+def dstn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=None) -> "torch.Tensor":
+    """scipy.fft.dstn(x, type=2, norm=norm) over the dims ``dim`` of a real tensor of rank >= 2: the DST-II of ``dst`` along
+    each of them, on the passes of ``dctn`` -- one launch per transformed dim, the same ``dim``, lengths, strides and dtype
+    rules (MIFFT_DST_TAG on a MIFFT_FLAG_DCT_ND plan).  Only ``type=2`` (MifftError -15 otherwise); a sine transform along one
+    dim with a cosine transform along another is two calls."""
+    return _dct_nd(x, type, norm, dim, out_dtype, False, "dst")
+
+
+def idstn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=None) -> "torch.Tensor":
+    """scipy.fft.idstn(x, type=2, norm=norm), the inverse of dstn under the same ``norm`` and ``dim``; the input is converted
+    to ``out_dtype`` first."""
+    return _dct_nd(x, type, norm, dim, out_dtype, True, "dst")
 
 
 def mdct_frames(length: int, n: int) -> int:

@@ -7,6 +7,9 @@
 //
 // A plan whose `bases` start with MIFFT_DCT_TYPE4_TAG (Plan::dct4) is a DCT-IV: a complex row tile of n / 2 points between the
 // twiddles p_m = e^(-i pi (8m+1) / 8n), the same kernel in both directions with another scale (TileCfg::DCT = 4).
+//
+// A plan tagged with MIFFT_DST_TAG or MIFFT_DST_TYPE4_TAG (Plan::dst) is the sine transform of the same type: the same pass,
+// tables and scales, and a kernel with TileCfg::DST set (kernels_jit.cpp takes the bit from the plan; compiled at run time only).
 #include <cmath>
 
 #include "mifft_config.h"

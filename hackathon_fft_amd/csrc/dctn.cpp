@@ -8,6 +8,8 @@
 //                    as complex elements at stride S / 2 is PAIRS of adjacent real columns, u = x_a + i x_b, and the in-place
 //                    column tile moves them coalesced.  TileCfg::DCT on a column configuration (tile_kernel.h) permutes,
 //                    transforms and separates (forward) or combines, transforms and un-permutes (inverse) such a pair.
+// A plan tagged with MIFFT_DST_TAG (Plan::dst) runs the DST-II / its inverse along every transformed dimension: the same
+// passes, tables and scales, every kernel with TileCfg::DST set (kernels_jit.cpp takes the bit from the plan).
 #include "mifft_config.h"
 #include "mifft_internal.h"
 

@@ -210,7 +210,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
 }
 
 // DCT plans (MIFFT_FLAG_DCT, dct.cpp; MIFFT_FLAG_DCT_ND, dctn.cpp) and kept dimensions (MIFFT_FLAG_KEEP_DIM; axes.cpp):
-// everything that can be refused without a device, the DCT checks before the keep bits are looked at.  Sets p.dct4.
+// everything that can be refused without a device, the DCT checks before the keep bits are looked at.  Sets p.dct4 and p.dst.
 int dct_and_keep_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len) {
     const uint32_t flags = p.flags;
     if ((flags & MIFFT_FLAG_DCT_ORTHO) && !(flags & (MIFFT_FLAG_DCT | MIFFT_FLAG_DCT_ND)))
@@ -219,7 +219,13 @@ int dct_and_keep_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases
     const bool tagged = bases_flat && bases_len && bases_len[0] >= 1 && bases_flat[0] == MIFFT_DCT_TYPE4_TAG;
     if ((flags & MIFFT_FLAG_DCT_ND) && tagged)
         return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_DCT_TYPE4_TAG with MIFFT_FLAG_DCT_ND: the N-D DCT has no type 4");
-    p.dct4 = (flags & MIFFT_FLAG_DCT) && tagged;
+    // (MIFFT_DST_TAG / MIFFT_DST_TYPE4_TAG in the same place: the sine transform of that type on the DCT plan's passes)
+    const uint32_t word0 = bases_flat && bases_len && bases_len[0] >= 1 ? bases_flat[0] : 0u;
+    const bool dst2 = word0 == MIFFT_DST_TAG, dst4 = word0 == MIFFT_DST_TYPE4_TAG;
+    if ((flags & MIFFT_FLAG_DCT_ND) && dst4)
+        return set_error(MIFFT_ERR_UNSUPPORTED, "MIFFT_DST_TYPE4_TAG with MIFFT_FLAG_DCT_ND: the N-D DST has no type 4");
+    p.dct4 = (flags & MIFFT_FLAG_DCT) && (tagged || dst4);
+    p.dst = ((flags & MIFFT_FLAG_DCT) && (dst2 || dst4)) || ((flags & MIFFT_FLAG_DCT_ND) && dst2);
     if (p.dct_any()) {
         std::string why;
         const int rc = p.dct_nd() ? dctn_check(p, why) : dct_check(p, why);
@@ -235,7 +241,7 @@ int dct_and_keep_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases
                          "MIFFT_FLAG_KEEP_DIM with MIFFT_FLAG_FAITHFUL_STAGES: the reference has no axes to be faithful to");
     if (bases_len)
         for (int i = 0; i < p.ndim; ++i)
-            if (p.kept(i) && bases_len[i] != 0)
+            if (p.kept(i) && bases_len[i] != (p.dst && i == 0 ? 1 : 0))  // (a kept dimension 0 still carries MIFFT_DST_TAG, alone)
                 return set_error(MIFFT_ERR_BAD_BASES, "dimension " + std::to_string(i) + " is kept: its bases_len must be 0");
     return MIFFT_OK;
 }
@@ -245,12 +251,15 @@ int plan_radices(const Plan& p, const uint32_t* bases_flat, const int32_t* bases
                  std::vector<std::vector<uint32_t>>& ordered, std::vector<std::vector<uint32_t>>& processed) {
     const uint32_t* bp = bases_flat;
     for (int i = 0; i < p.ndim; ++i) {
-        if (p.kept(i)) continue;  // (no stages: mifft_plan_stages() reports 0)
+        if (p.kept(i)) {  // (no stages: mifft_plan_stages() reports 0)
+            if (bases_flat && p.dst && i == 0) ++bp;  // (the tag)
+            continue;
+        }
         std::vector<uint64_t> user;
         if (bases_flat) {
             if (bases_len[i] < 0) return set_error(MIFFT_ERR_NO_BASES, "negative bases_len");
             for (int k = 0; k < bases_len[i]; ++k) user.push_back(*bp++);
-            if (p.dct4 && i == 0) user.erase(user.begin());  // (the tag; alone it selects the default estimate, below)
+            if ((p.dct4 || p.dst) && i == 0) user.erase(user.begin());  // (the tag; alone it selects the default estimate, below)
         } else {
             user = plan_estimate_bases((uint64_t)p.dims[i], /*gpu_target=*/true);
         }
@@ -258,6 +267,8 @@ int plan_radices(const Plan& p, const uint32_t* bases_flat, const int32_t* bases
         // (a DCT plan runs, and reports, the stages of its packed n / 2-point transform: for its rows, the last dimension)
         const bool packed = p.dct() || (p.dct_nd() && i == p.ndim - 1);
         if (packed && (!bases_flat || (p.dct4 && user.empty()))) user = plan_estimate_bases((uint64_t)p.dims[i] / 2, /*gpu_target=*/true);
+        // (a DST plan always has a `bases` argument, for its tag: an empty list there is the default of that dimension)
+        if (bases_flat && p.dst && user.empty()) user = plan_estimate_bases((uint64_t)p.dims[i] / (packed ? 2 : 1), /*gpu_target=*/true);
         const int rc = plan_ordered_bases((uint64_t)p.dims[i] / (packed ? 2 : 1), user, ordered[i], processed[i], err);
         if (rc) return set_error(rc, err);
     }

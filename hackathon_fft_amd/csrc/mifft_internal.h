@@ -101,6 +101,9 @@ struct DimPass {
     // lapped frames of every batch entry (TileCfg::MDCT); d_aux3 holds the window, 2 N values of the plan's float type
     int dct = 0;
     bool mdct = false;
+    // dst (with dct = 2 / 3 / 4, never with mdct / imdct): TileCfg::DST, the sine transform of that type on the same tile, tables
+    // and scales; part of the kernel's configuration and name (`dst2` / `dst3` / `dst4`)
+    bool dst = false;
     // imdct: the rows are `outer` frames of N coefficients per batch entry, unfolded and overlap-added into dims[0] samples by
     // the store (TileCfg::IMDCT); d_aux3 holds gain * w, 2 N values of the plan's float type; istft_min_run as below
     bool imdct = false;
@@ -189,6 +192,10 @@ struct Plan {
     int64_t imdct = 0;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
     bool dct4 = false;
+    // a MIFFT_FLAG_DCT / MIFFT_FLAG_DCT_ND plan whose `bases` start with MIFFT_DST_TAG (DST-II and its inverse, along every
+    // transformed dim) or, MIFFT_FLAG_DCT only, with MIFFT_DST_TYPE4_TAG (DST-IV; dct4 is set as well): every pass is the
+    // DCT plan's with DimPass::dst set
+    bool dst = false;
     // MIFFT_FLAG_STFT_POWER on such a plan: out is real, (batch, F, n / 2 + 1, 1) of |X|^spec_power (1 or 2), or
     // (batch, F, spec_bands, 1) after a filterbank of spec_bands > 0 bands; stft_out_width() reals per frame.  0: the flag is
     // not set.  Filled by stft_unpack_bases.

@@ -330,7 +330,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
-          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false>
+          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -527,6 +527,19 @@ struct TileCfg {
     static_assert(!(DCT_ != 0 && COLS_) || (!R2C_ && !C2R_ && !IN_REAL_ && !TSTORE_ && !FS1_ && !HERM_ && !HS_ && !DMA_ && !WSUB_ &&
                                             !ILV_ && same_t<IT_, T_>::value && R0_ <= 32 && R1_ <= 32),
                   "DCT on a column tile: a plain in-place tile of register butterflies over pairs of real columns");
+    // DST (with DCT = 2 / 3 / 4): the sine transform of the same type on the same tile.  With xs[j] = (-1)^j x[j], the DST-II is
+    // Y[k] = 2 sum_j x[j] sin(pi (k+1)(2j+1) / 2n) = DCT-II(xs)[n-1-k] and the DST-IV Y[k] = DCT-IV(xs)[n-1-k]: a sign where
+    // the samples are loaded (forward) or stored (inverse) and the index reversal where the bins are stored (forward) or
+    // loaded (inverse).  Passes, tables and scales are the DCT's; dct_s0 lands on the LAST bin.
+    //   rows, DCT = 2: the permuting load negates the odd samples (the quad's whole element z_(N-1-e)); the unpacking store
+    //     writes X[k] to n-1-k (descending), X[n-k] to k-1 (ascending), X[N-k] to N-1+k and X[N+k] to N-1-k: four runs still.
+    //   rows, DCT = 3: the four-run load reads X[j] from n-1-j; the store negates the odd samples as it reads the slots of v.
+    //   rows, DCT = 4: n is even, so x[n-1-2m] is an odd sample: z_m = x[2m] - i x[n-1-2m], and the store writes
+    //     out[2k] = -s Im c_k and out[n-1-2k] = s Re c_k.  No address changes.
+    //   columns, DCT = 2: row j of the pair takes (-1)^j as it is loaded, bin k is stored to row N-1-k.
+    //   columns, DCT = 3: bins k and N-k are read from rows N-1-k and k-1; the last pass negates what it stores to an odd row.
+    static constexpr bool DST = DST_;
+    static_assert(!DST_ || (DCT_ != 0 && !MDCT_ && !IMDCT_), "DST: the sign and the reversal on a plain DCT tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -974,6 +987,9 @@ MIFFT_DEV void load_pass0(const TileParams& p, cpx<typename C::T> (*v)[C::R(0)],
                     v[k][j].y = (T)0;
                 } else if constexpr (C::DCT == 2 && C::COLS) {  // the permuted row: no longer affine in j
                     v[k][j] = gload<(C::NT & 1) != 0>(gin + base + lane_off<C>(p, cc, dct_row_of<C>(b + j * NB)));
+                    if constexpr (C::DST) {  // (-1)^row: the odd rows are the elements of the second half of v
+                        if (b + j * NB >= (C::N + 1) / 2) v[k][j] = {-v[k][j].x, -v[k][j].y};
+                    }
                 } else {
                     v[k][j] = gload<(C::NT & 1) != 0>(gin + base + j * step + off);
                 }
@@ -1174,9 +1190,12 @@ MIFFT_DEV void pass_compute_scatter(const TileParams& p, cpx<typename C::T>* lds
                             y.x *= (T)p.scale;
                             y.y *= -(T)p.scale;
                         }
-                        if constexpr (C::DCT == 3 && C::COLS)  // element o0 + s P of v: its row of the column
+                        if constexpr (C::DCT == 3 && C::COLS) {  // element o0 + s P of v: its row of the column
+                            if constexpr (C::DST) {  // (an odd row: the second half of v)
+                                if (o0 + s * P >= (C::N + 1) / 2) y = {-y.x, -y.y};
+                            }
                             gstore<(C::NT & 2) != 0>(gout + base + lane_off<C>(p, c, dct_row_of<C>(o0 + s * P)), y);
-                        else if (!C::HS || o0 + s * P <= p.store_lim)
+                        } else if (!C::HS || o0 + s * P <= p.store_lim)
                             gstore<(C::NT & 2) != 0>(gout + base + s * step + off, y);
                     }
                 }
@@ -1693,8 +1712,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     // U[k] and U[N-k] (U[N] := 0), both runs over the lanes: Z[k] = conj(W^k) (s_k U[k] - i s U[N-k]) and
                     // Z[N-k] = i W^k (s U[N-k] - i s_k U[k]), W = W_4n^k; written conjugated (the passes run conj(F(conj Z)))
                     const V* gin = (const V*)p.in;
-                    const V a = gload<(C::NT & 1) != 0>(gin + gaddr<C>(p, base, cc, n));
-                    const V b = n ? gload<(C::NT & 1) != 0>(gin + gaddr<C>(p, base, cc, C::N - n)) : V{(T)0, (T)0};
+                    // (DST: bin j of the cosine transform lies in row N - 1 - j)
+                    const V a = gload<(C::NT & 1) != 0>(gin + gaddr<C>(p, base, cc, C::DST ? C::N - 1 - n : n));
+                    const V b = n ? gload<(C::NT & 1) != 0>(gin + gaddr<C>(p, base, cc, C::DST ? n - 1 : C::N - n)) : V{(T)0, (T)0};
                     const V w = ((const V*)p.dct_tw)[n];
                     const T s1 = (T)p.dct_s1, sk = n == 0 ? (T)p.dct_s0 : s1;
                     const T ar = sk * a.x, ai = sk * a.y, br = s1 * b.x, bi = s1 * b.y;
@@ -1711,6 +1731,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 else
                     x = gload<false>((const V*)p.in + gaddr<C>(p, base, cc, n));
                 if (p.inverse && C::CONJ_IN) x.y = -x.y;
+                if constexpr (C::DST) {  // (-1)^row on both columns of the pair
+                    if (n & 1) x = {-x.x, -x.y};
+                }
                 lds[lds_index<C, -1>(c, C::DCT == 2 ? dct_elem_of<C>(n) : n)] = x;
             }
             __syncthreads();
@@ -1738,11 +1761,13 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                         if constexpr (C::DCT == 3) {
                             // four runs of reals over the lanes: X[k] and X[N + k] ascending, X[n - k] and X[N - k] descending
                             // (k = 0: X[n] := 0, and X[N] twice)
+                            // (DST: X[j] lies at n - 1 - j -- descending, ascending, ascending, descending; k = 0: X[N] twice)
                             const T* row = (const T*)p.in + (row0 + c) * (2 * C::N);
-                            xk[j].x = gload_real<(C::NT & 1) != 0>(row + k);
-                            xk[j].y = k ? gload_real<(C::NT & 1) != 0>(row + (2 * C::N - k)) : (T)0;
-                            xm[j].x = gload_real<(C::NT & 1) != 0>(row + (C::N - k));
-                            xm[j].y = gload_real<(C::NT & 1) != 0>(row + (C::N + k));
+                            constexpr int NN = 2 * C::N;
+                            xk[j].x = gload_real<(C::NT & 1) != 0>(row + (C::DST ? NN - 1 - k : k));
+                            xk[j].y = k ? gload_real<(C::NT & 1) != 0>(row + (C::DST ? k - 1 : NN - k)) : (T)0;
+                            xm[j].x = gload_real<(C::NT & 1) != 0>(row + (C::DST ? C::N - 1 + k : C::N - k));
+                            xm[j].y = gload_real<(C::NT & 1) != 0>(row + (C::DST ? C::N - 1 - k : C::N + k));
                         } else {
                             const V* row = gin + (row0 + c) * p.half_pitch;
                             xk[j] = gload<(C::NT & 1) != 0>(row + k);
@@ -1799,7 +1824,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                         gload4<NTL>((const T*)p.in + 2 * base + 4 * (long long)f, x);
                     }
                     lds[lds_index<C, -1>(c, e)] = {x[0], x[2]};
-                    lds[lds_index<C, -1>(c, C::N - 1 - e)] = {x[3], x[1]};
+                    if constexpr (C::DST)  // the odd samples, negated: the whole element
+                        lds[lds_index<C, -1>(c, C::N - 1 - e)] = {-x[3], -x[1]};
+                    else
+                        lds[lds_index<C, -1>(c, C::N - 1 - e)] = {x[3], x[1]};
                 }
             } else {
                 T* ldr = (T*)lds;
@@ -1811,7 +1839,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     else
                         x = gload<NTL>((const V*)p.in + base + f);
                     ldr[2 * lds_index<C, -1>(c, j >> 1) + (j & 1)] = x.x;
-                    ldr[2 * lds_index<C, -1>(c, q >> 1) + (q & 1)] = x.y;
+                    ldr[2 * lds_index<C, -1>(c, q >> 1) + (q & 1)] = C::DST ? -x.y : x.y;  // (DST: the odd sample, negated)
                 }
             }
             __syncthreads();
@@ -1865,6 +1893,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     const T* row = (const T*)p.in + (row0 + c) * NN;
                     a = gload_pair(row + 2 * m);
                     b = gload_pair(row + NN - 2 - 2 * m);
+                    if constexpr (C::DST) {  // the odd samples x[2m+1] and x[n-1-2m], negated
+                        a.y = -a.y;
+                        b.y = -b.y;
+                    }
                 }
                 const V w0 = pw[m], w1 = pw[C::N - 1 - m];
                 lds[lds_index<C, -1>(c, m)] = {w0.x * a.x - w0.y * b.y, w0.x * b.y + w0.y * a.x};
@@ -2033,9 +2065,11 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                         const T bx = (T)0.5 * (zk.y + zm.y), by = (T)-0.5 * (zk.x - zm.x);
                         const V w = ((const V*)p.dct_tw)[n];
                         const T s1 = (T)p.dct_s1, sk = n == 0 ? (T)p.dct_s0 : s1;
-                        gstore<(C::NT & 2) != 0>(gout + gaddr<C>(p, base, c, n), V{sk * (w.x * ax - w.y * ay), sk * (w.x * bx - w.y * by)});
+                        // (DST: bin j of the cosine transform goes to row N - 1 - j)
+                        gstore<(C::NT & 2) != 0>(gout + gaddr<C>(p, base, c, C::DST ? C::N - 1 - n : n),
+                                                 V{sk * (w.x * ax - w.y * ay), sk * (w.x * bx - w.y * by)});
                         if (n != 0 && 2 * n != C::N)
-                            gstore<(C::NT & 2) != 0>(gout + gaddr<C>(p, base, c, C::N - n),
+                            gstore<(C::NT & 2) != 0>(gout + gaddr<C>(p, base, c, C::DST ? n - 1 : C::N - n),
                                                      V{-s1 * (w.x * ay + w.y * ax), -s1 * (w.x * by + w.y * bx)});
                     }
                     continue;
@@ -2073,12 +2107,15 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     const V* w4 = (const V*)p.dct_tw;
                     const V wa = w4[k], wb = w4[C::N - k];
                     const T s1 = (T)p.dct_s1, s0 = k == 0 ? (T)p.dct_s0 : s1;
+                    // DST: X[j] goes to n - 1 - j, so Y[n-1-k] = 2 Re t, Y[k-1] = -2 Im t, Y[N-1+k] = 2 Re u, Y[N-1-k] = -2 Im u:
+                    // the runs descending, ascending, ascending, descending
                     T* xrow = (T*)p.out + (row0 + c) * (2 * C::N);
-                    xrow[k] = s0 * (wa.x * a.x - wa.y * a.y);
-                    if (k) xrow[2 * C::N - k] = -s1 * (wa.x * a.y + wa.y * a.x);
+                    constexpr int NN = 2 * C::N;
+                    xrow[C::DST ? NN - 1 - k : k] = s0 * (wa.x * a.x - wa.y * a.y);
+                    if (k) xrow[C::DST ? k - 1 : NN - k] = -s1 * (wa.x * a.y + wa.y * a.x);
                     if (2 * k != C::N) {
-                        xrow[C::N - k] = s1 * (wb.x * b.x - wb.y * b.y);
-                        if (k) xrow[C::N + k] = -s1 * (wb.x * b.y + wb.y * b.x);
+                        xrow[C::DST ? C::N - 1 + k : C::N - k] = s1 * (wb.x * b.x - wb.y * b.y);
+                        if (k) xrow[C::DST ? C::N - 1 - k : C::N + k] = -s1 * (wb.x * b.y + wb.y * b.x);
                     }
                     continue;
                 }
@@ -2211,7 +2248,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 for (int f = tid; f < nv * H; f += C::THREADS) {
                     const int c = f / H, e = f - c * H;
                     const V a = lds[lds_index<C, C::NP - 1>(c, e)], b = lds[lds_index<C, C::NP - 1>(c, C::N - 1 - e)];
-                    gstore4<(C::NT & 2) != 0>((T*)p.out + 2 * base + 4 * (long long)f, a.x, -b.y, -a.y, b.x);
+                    if constexpr (C::DST)  // the odd samples x[4e+1] and x[4e+3], negated
+                        gstore4<(C::NT & 2) != 0>((T*)p.out + 2 * base + 4 * (long long)f, a.x, b.y, -a.y, -b.x);
+                    else
+                        gstore4<(C::NT & 2) != 0>((T*)p.out + 2 * base + 4 * (long long)f, a.x, -b.y, -a.y, b.x);
                 }
             } else {
                 const T* ldr = (const T*)lds;
@@ -2219,7 +2259,8 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     const int c = f / C::N, j = f - c * C::N, q = 2 * C::N - 1 - j;
                     const T x0 = ldr[2 * lds_index<C, C::NP - 1>(c, j >> 1) + (j & 1)];
                     const T x1 = ldr[2 * lds_index<C, C::NP - 1>(c, q >> 1) + (q & 1)];
-                    gstore<(C::NT & 2) != 0>((V*)p.out + base + f, V{(j & 1) ? -x0 : x0, (q & 1) ? -x1 : x1});
+                    // (DST: the odd sample x[2f+1], negated)
+                    gstore<(C::NT & 2) != 0>((V*)p.out + base + f, V{(j & 1) ? -x0 : x0, ((q & 1) != 0) != C::DST ? -x1 : x1});
                 }
             }
             __syncthreads();
@@ -2281,8 +2322,13 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 const T re0 = w0.x * z0.x - w0.y * z0.y, im0 = w0.x * z0.y + w0.y * z0.x;
                 const T re1 = w1.x * z1.x - w1.y * z1.y, im1 = w1.x * z1.y + w1.y * z1.x;
                 T* row = (T*)p.out + (row0 + c) * NN;
-                gstore_pair(row + 2 * k, s * re0, -s * im1);
-                if (2 * k != C::N - 1) gstore_pair(row + NN - 2 - 2 * k, s * re1, -s * im0);
+                if constexpr (C::DST) {  // out[2k] = -s Im c_k, out[n-1-2k] = s Re c_k: the same pairs, the roles exchanged
+                    gstore_pair(row + 2 * k, -s * im0, s * re1);
+                    if (2 * k != C::N - 1) gstore_pair(row + NN - 2 - 2 * k, -s * im1, s * re0);
+                } else {
+                    gstore_pair(row + 2 * k, s * re0, -s * im1);
+                    if (2 * k != C::N - 1) gstore_pair(row + NN - 2 - 2 * k, s * re1, -s * im0);
+                }
             }
             __syncthreads();
         } else if constexpr (!C::LAST_DIRECT) {

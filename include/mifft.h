@@ -195,6 +195,43 @@ typedef enum {
  * the excluded flags, in_components); in addition MIFFT_JIT=0 is MIFFT_ERR_UNSUPPORTED (no precompiled instances), and so is
  * the tag as the first `bases` word of a MIFFT_FLAG_DCT_ND plan (the N-D DCT has no type 4). */
 #define MIFFT_DCT_TYPE4_TAG 0x44435434u
+/* DST-II / DST-III and DST-IV (scipy.fft.dst / idst / dstn / idstn of types 2 and 4; no reference counterpart): the sine
+ * transforms ride on the DCT plans.  No flag and no entry point of their own: the request is a tag as the FIRST `bases` word,
+ * as MIFFT_DCT_TYPE4_TAG above (no radix can equal either tag).  With xs[j] = (-1)^j x[j] every DST is its DCT between a sign
+ * and an index reversal, DST(x)[k] = DCT(xs)[n-1-k]; both live in the load and the store the DCT tile already has, so the
+ * passes, the launch geometry, the tables and the scales are those of the DCT plan of the same shape.
+ * MIFFT_DST_TAG ("DST2") on a MIFFT_FLAG_DCT plan, x and out both REAL, (batch, n, 1):
+ *   forward (inverse = 0, any in_dtype):   Y[k] = 2 sum_j x[j] sin(pi (k+1)(2j+1) / 2n)             = scipy dst(x, 2)
+ *   inverse (inverse = 1, in_dtype == out_dtype in {F32, F64}):
+ *       x[j] = ((-1)^j Y[n-1] + 2 sum_{k<n-1} Y[k] sin(pi (k+1)(2j+1) / 2n)) / 2n                   = scipy idst(Y, 2)
+ * With MIFFT_FLAG_DCT_ORTHO the forward scales the LAST bin, Y[n-1], by sqrt(1/4n) and every other bin by sqrt(1/2n); the
+ * inverse is the transpose of that.  Forward: the permuting load negates the odd samples and the unpacking store writes
+ * Y[k-1] = -2 Im(W^k V[k]) and Y[n-1-k] = 2 Re(W^k V[k]), W = e^(-i pi / 2n): four contiguous runs of reals, as the DCT's.
+ * Inverse: the four-run load reads bin k of the cosine transform from n-1-k, the store negates the odd samples.  The kernel is
+ * rows<n>[_f64]_dst2_<radices>_jit or ..._dst3_<radices>_jit.
+ * MIFFT_DST_TAG on a MIFFT_FLAG_DCT_ND plan, as the first word of dimension 0's list (the only word there if dimension 0 is
+ * kept): the same transform along EVERY transformed dim (scipy dstn / idstn of type 2).  The last dim runs the row kernel
+ * above; another dim the paired-column tile cols<n>[_f64]_dst2_<radices>_jit / ..._dst3_..., whose load gives row j the sign
+ * (-1)^j and whose store writes bin k to row n-1-k (forward), or whose load reads bins k and n-k from rows n-1-k and k-1
+ * and whose store applies the sign of its row (inverse).  Odd column lengths and every stride of the N-D DCT are served.
+ * MIFFT_DST_TYPE4_TAG ("DST4") on a MIFFT_FLAG_DCT plan, in_dtype == out_dtype in {F32, F64} in BOTH directions:
+ *   forward:   Y[k] = 2 sum_j x[j] sin(pi (2j+1)(2k+1) / 4n)                                            = scipy dst(x, 4)
+ *   inverse:   the same sum over Y, divided by 2n                                                        = scipy idst(Y, 4)
+ * With MIFFT_FLAG_DCT_ORTHO both directions scale the sum by sqrt(1 / 2n): the orthonormal DST-IV, its own inverse.  On the
+ * DCT-IV tile no address changes: n is even, so the load forms z_m = x[2m] - i x[n-1-2m] and the store writes
+ * Y[2k] = -2 Im S_k and Y[n-1-2k] = 2 Re S_k.  The kernel is rows<n>[_f64]_dst4_<radices>_jit in both directions.
+ * The optional radices follow the tag in every list as on the DCT plan; a tag alone, and in a tagged payload every empty
+ * list of a transformed dim, selects the default estimate.  Without a tag nothing changes.  Sizes, slabs, whole_batch,
+ * mifft_plan_pass_geometry, the alignment of one element, the dtype rules and every refusal of the underlying DCT plan are
+ * that plan's, with its status codes.  In addition MIFFT_ERR_UNSUPPORTED for:
+ *   - MIFFT_JIT=0, for every DST plan: the kernels are compiled at run time only (the precompiled 1024-point DCT rows have no
+ *     sine twins);
+ *   - MIFFT_DST_TYPE4_TAG on a MIFFT_FLAG_DCT_ND plan (the N-D DST has no type 4).
+ * A tag on a plan without MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND is an ordinary, and wrong, radix (MIFFT_ERR_BAD_BASES).  Types 1
+ * and 3 as scipy's `type` argument, a type 4 over several dims, precompiled instances and sine along one dim with cosine
+ * along another in one plan are not provided. */
+#define MIFFT_DST_TAG 0x44535432u
+#define MIFFT_DST_TYPE4_TAG 0x44535434u
 /* N-D DCT-II / DCT-III (scipy.fft.dctn / idctn of type 2 over the transformed dims; no reference counterpart).  ndim = 1 .. 6,
  * in_components = 1 in both directions; x and out are both REAL tensors (batch, d0.., d{k-1}, 1) of one shape.  Every
  * transformed dim gets the 1-D transform of MIFFT_FLAG_DCT above (forward: any in_dtype when the last dim is transformed;

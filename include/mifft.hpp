@@ -178,7 +178,13 @@ static_assert(MIFFT_MDCT_TAG_LO == 0x43544401u && MIFFT_MDCT_TAG_HI == 0x7FF84D4
                   (MIFFT_MDCT_TAG_HI & 0x7FF80000u) == 0x7FF80000u &&
                   (MIFFT_MDCT_TAG_HI != MIFFT_STFT_EXT_TAG_HI || MIFFT_MDCT_TAG_LO != MIFFT_STFT_EXT_TAG_LO),
               "MIFFT_MDCT_TAG is the quiet NaN 0x7FF84D4443544401, distinct from MIFFT_STFT_EXT_TAG");
+// MIFFT_DST_TAG in the same place on a MIFFT_FLAG_DCT or MIFFT_FLAG_DCT_ND plan: DST-II (inverse: its inverse) of real rows, or
+// along every transformed dim; MIFFT_DST_TYPE4_TAG on a MIFFT_FLAG_DCT plan: DST-IV of real rows (include/mifft.h).
+static_assert(MIFFT_DST_TAG == 0x44535432u && MIFFT_DST_TYPE4_TAG == 0x44535434u && MIFFT_DST_TAG > 16384u,
+              "MIFFT_DST_TAG and MIFFT_DST_TYPE4_TAG are no radices");
 constexpr uint32_t kDctType4Tag = MIFFT_DCT_TYPE4_TAG;
+constexpr uint32_t kDstTag = MIFFT_DST_TAG;
+constexpr uint32_t kDstType4Tag = MIFFT_DST_TYPE4_TAG;
 constexpr uint64_t kMdctTag = ((uint64_t)MIFFT_MDCT_TAG_HI << 32) | MIFFT_MDCT_TAG_LO;
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
