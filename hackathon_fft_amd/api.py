@@ -53,6 +53,8 @@ DST_TAG = 0x44535432           # MIFFT_DST_TAG: the first ``bases`` word of a FL
 DST_TYPE4_TAG = 0x44535434     # MIFFT_DST_TYPE4_TAG: the first ``bases`` word of a FLAG_DCT plan that is a DST-IV
 MDCT_TAG_LO = 0x43544401       # MIFFT_MDCT_TAG_LO / _HI: the NaN behind the window of a FLAG_STFT plan that is an MDCT
 MDCT_TAG_HI = 0x7FF84D44
+CONV_TAG_LO = 0x4F4E5601       # MIFFT_CONV_TAG_LO / _HI: the NaN in front of the 8-word payload of a FLAG_STFT plan that is a
+CONV_TAG_HI = 0x7FF84D43       # fused FFT convolution (TAG | D | o | Lo | mode | the device address of the filter spectra)
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -501,19 +503,23 @@ class Plan:
     ``imdct`` = M > 0 (no reference counterpart): the inverse MDCT, x (batch, F, M, 1) -> out (batch, T, 1) real with
     2 <= T <= (F - 1) M, ``inverse=True`` implied; ``stft_window`` as for ``mdct``, ``imdct_gain`` the factor on the synthesis
     window (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan in include/mifft.h, _check_imdct_layout, plan_imdct).  ``bases`` has
-    three lists: two empty ones and the radices of M // 2 (or an empty one)."""
+    three lists: two empty ones and the radices of M // 2 (or an empty one).
+    ``conv`` = (n, D, o, Lo, mode, address) (no reference counterpart): the fused FFT convolution of real rows,
+    x (batch, L, 1) -> out (batch, Lo, 1), samples o .. o + Lo - 1 of irfft(rfft(x, n) * G[row % D], n) against the D filter
+    spectra at the device ``address`` (mode bit 0: their conjugates); the caller keeps that buffer alive (MIFFT_CONV_TAG in
+    include/mifft.h, plan_fftconv).  ``bases`` has two lists, an empty one and the radices of n (or an empty one)."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0, dst: bool = False):
+                 imdct_gain: float = 1.0, dst: bool = False, conv=None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct = int(mdct), int(imdct)
         if dct_type not in (2, 4):
             raise MifftError(ERR_UNSUPPORTED, f"dct_type must be 2 or 4, got {dct_type!r}")
-        stft = not mdct and (int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT))
+        stft = not mdct and conv is None and (int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT))
         istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
         words = None
         if imdct:  # (with any other mode as well: the library refuses the pair)
@@ -591,6 +597,23 @@ class Plan:
                      (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
                      (FLAG_STFT_POWER if stft_power is not None else 0))
             stft, istft = True, False
+        if conv is not None:  # (with any other mode as well: the library refuses the pair)
+            n_fft, D, o, Lo, mode, addr = (int(v) for v in conv)
+            if len(in_shape) != 3 or len(out_shape) != 3 or in_shape[-1] != 1 or out_shape[-1] != 1:
+                raise MifftError(-1, f"convolution layouts are (batch, L, 1) -> (batch, Lo, 1), got {in_shape} -> {out_shape}")
+            if in_shape[0] != out_shape[0] or out_shape[1] != Lo:
+                raise MifftError(-2, f"x {in_shape} against out {out_shape} with Lo = {Lo}")
+            if axes is not None:
+                raise MifftError(ERR_UNSUPPORTED, "a convolution plan extends dim 0 and transforms dim 1: no axes")
+            for v, what in ((D, "D"), (o, "o"), (Lo, "Lo"), (mode, "mode")):
+                if not 0 <= v < 1 << 32:
+                    raise MifftError(-5, f"{what} = {v} of a convolution plan does not fit an unsigned 32-bit word")
+            stft_dims = (in_shape[1], n_fft)
+            words = [CONV_TAG_LO, CONV_TAG_HI, D, o, Lo, mode, addr & 0xFFFFFFFF, (addr >> 32) & 0xFFFFFFFF]
+            flags = (int(flags) | FLAG_STFT | (FLAG_ISTFT if istft else 0) | (FLAG_DCT_ND if dctn else 0) |
+                     (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
+                     (FLAG_STFT_POWER if stft_power is not None else 0))
+            stft, istft, mdct = True, False, 0
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
         dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
@@ -644,6 +667,7 @@ class Plan:
         self.dst = bool(dst) and (dct or dctn) and not stft and not istft
         self.mdct = mdct
         self.imdct = imdct
+        self.conv = None if conv is None else tuple(int(v) for v in conv)
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
@@ -1561,6 +1585,193 @@ def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -
             _PLAN_CACHE.move_to_end(key)
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical[:-1] + (frames, n))
+
+
+# ---------------------------------------------------------------------------
+# fused FFT convolution of real rows
+# ---------------------------------------------------------------------------
+
+_FFTCONV_MAX = 16384
+_FFTCONV_MODES = ("causal", "full", "same", "valid")
+
+
+def _fftconv_ok(n: int) -> bool:
+    """an FFT length the packed rows accept: even, 8 .. 16384, n // 2 without a prime factor above 32"""
+    if n % 2 or n < 8 or n > _FFTCONV_MAX:
+        return False
+    h = n // 2
+    for p in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31):
+        while h % p == 0:
+            h //= p
+    return h == 1
+
+
+def _fftconv_accepted(n: int, dtype) -> bool:
+    """the library's own answer, from the checks it makes before it looks for a device (device -1 is none): the packed rows
+    of float64 refuse some sixty lengths below 12288 that those of float32 take (434 is the first)"""
+    code = _DTYPE_CODE[dtype]
+    h = ctypes.c_void_p()
+    flat = (ctypes.c_uint32 * 8)(CONV_TAG_LO, CONV_TAG_HI, 1, 0, 1, 0, 16, 0)
+    rc = _lib.lib().mifft_plan_create(ctypes.byref(h), -1, code, code, 2, (ctypes.c_int64 * 2)(2, n), 1, 1, 0, flat,
+                                      (ctypes.c_int32 * 2)(8, 0), FLAG_STFT)
+    return rc == -10
+
+
+def fftconv_length(m: int, dtype=torch.float32) -> int:
+    """The smallest FFT length n >= m that a fused convolution plan of ``dtype`` accepts (even, 8 .. 16384, n // 2 without a
+    prime factor above 32; float64 plans stop at 12288 and skip a few lengths more).  MifftError beyond the last one: longer
+    convolutions need overlap-save."""
+    m = int(m)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"fftconv_length: float32 or float64, got {dtype}")
+    n = max(m + (m & 1), 8)
+    while n <= _FFTCONV_MAX:
+        if _fftconv_ok(n) and _fftconv_accepted(n, dtype):
+            return n
+        n += 2
+    raise MifftError(ERR_UNSUPPORTED, f"fftconv_length({m}): no accepted FFT length up to {_FFTCONV_MAX}; longer convolutions "
+                                      "need overlap-save, which is out of scope")
+
+
+class ConvPlan(Plan):
+    """The plan of ``plan_fftconv``: a ``Plan`` that owns the tensor of filter spectra its kernel reads.
+    ``filter_spectrum`` is (channels, n // 2 + 1, 2) of the plan's dtype, zero-filled at first; its address is bound into
+    the plan and never changes, its contents may be rewritten between execs in stream order."""
+
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx):
+        self.ctx = ctx
+        self.channels, self.length, self.n = channels, length, n
+        self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
+        with torch.cuda.stream(ctx.stream):
+            self.filter_spectrum = torch.zeros((channels, n // 2 + 1, 2), dtype=dtype, device=f"cuda:{ctx.device}")
+        super().__init__(dtype, dtype, (batch * channels, length, 1), (batch * channels, out_length, 1), device=ctx.device,
+                         conv=(n, channels, offset, out_length, 1 if correlate else 0, self.filter_spectrum.data_ptr()))
+
+    def set_filter(self, k: "torch.Tensor") -> None:
+        """``k`` real, (channels, K) or (K,) (one filter for every channel), K <= n: writes rfft(k, n) into
+        ``filter_spectrum`` with the library's own one-sided rfftn, on the plan's stream."""
+        if k.is_complex() or k.dim() not in (1, 2):
+            raise MifftError(-3, f"set_filter expects a real (channels, K) or (K,) tensor, got {tuple(k.shape)} {k.dtype}")
+        if k.dim() == 2 and k.shape[0] != self.channels:
+            raise MifftError(-2, f"set_filter: {k.shape[0]} filters for {self.channels} channels")
+        K = int(k.shape[-1])
+        if K < 1 or K > self.n:
+            raise MifftError(-2, f"set_filter: a filter of K = {K} taps does not fit the FFT length n = {self.n} (1 <= K <= n)")
+        with torch.cuda.stream(self.ctx.stream):
+            kp = torch.zeros((self.channels, self.n), dtype=self.out_dtype, device=self.filter_spectrum.device)
+            kp[:, :K] = k.to(device=kp.device, dtype=self.out_dtype)
+            H = rfftn(kp, onesided=True)
+            self.filter_spectrum.copy_(torch.view_as_real(H))
+
+    def set_filter_spectrum(self, Hc: "torch.Tensor") -> None:
+        """copies a spectrum the caller already holds -- complex (channels, n // 2 + 1) or interleaved (.., 2), the
+        unnormalised rfft(k, n) -- into ``filter_spectrum``, on the plan's stream"""
+        Hr = torch.view_as_real(Hc) if Hc.is_complex() else Hc
+        if tuple(Hr.shape) != tuple(self.filter_spectrum.shape):
+            raise MifftError(-2, f"set_filter_spectrum expects {tuple(self.filter_spectrum.shape[:-1])} complex values, "
+                                 f"got {tuple(Hc.shape)} {Hc.dtype}")
+        with torch.cuda.stream(self.ctx.stream):
+            self.filter_spectrum.copy_(Hr.to(device=self.filter_spectrum.device, dtype=self.out_dtype))
+
+
+def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, offset: int = 0, out_length: Optional[int] = None,
+                 correlate: bool = False, ctx: Optional[DeviceContext] = None) -> ConvPlan:
+    """Plan of the fused FFT convolution (no reference counterpart; MIFFT_CONV_TAG in include/mifft.h) of ``batch * channels``
+    real rows of ``length`` samples, row-major (batch, channels, length), at the FFT length ``n`` (see fftconv_length):
+    ``y[r] = irfft(rfft(x[r], n) * G[r % channels], n)[offset : offset + out_length]`` in ONE kernel launch, G the plan's
+    ``filter_spectrum`` (``correlate``: its conjugate).  ``out_length`` defaults to ``length``.  ``in_shape``
+    (batch * channels, length, 1), ``out_shape`` (batch * channels, out_length, 1), both of ``dtype`` (float32 / float64);
+    runs through ``fft(out, x, plan=plan)``, ``first=`` / ``count=`` included.  ``n < length + K - 1`` gives the circular
+    result.  Every argument error is raised before any device work."""
+    batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
+    out_length = length if out_length is None else int(out_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"a convolution plan reads and writes float32 or float64, got {dtype}")
+    if batch < 1 or channels < 1:
+        raise MifftError(-8, f"plan_fftconv: batch = {batch} and channels = {channels} must be positive")
+    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
+        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
+                                          "n // 2 without a prime factor above 32): see fftconv_length")
+    if length < 2 or length > n:
+        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples at n = {n}: 2 <= length <= n")
+    if offset < 0 or out_length < 1 or offset + out_length > n:
+        raise MifftError(-5, f"plan_fftconv: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
+                             f"offset + out_length <= n = {n}")
+    if ctx is None:
+        ctx = DeviceContext()
+    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx)
+
+
+def _fftconv_window(mode: str, L: int, K: int) -> tuple:
+    """(offset, out_length) of scipy.signal.fftconvolve's crops of the full convolution of L and K samples"""
+    if mode == "causal":
+        return 0, L
+    if mode == "full":
+        return 0, L + K - 1
+    if mode == "same":
+        return (K - 1) // 2, L
+    return min(L, K) - 1, max(L, K) - min(L, K) + 1  # "valid"
+
+
+def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mode: str = "causal",
+            correlate: bool = False) -> "torch.Tensor":
+    """Convolution by FFT along the last dim of a real ``x`` of shape (..., D, L) with ``k`` of shape (D, K), one filter per
+    channel, or of shape (..., L) with a 1-D ``k``: one kernel launch per call (plus the transform of the filter).
+    ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one gives the circular result.
+    ``mode="causal"`` returns the first L samples (the Hyena / S4 convention); "full", "same" and "valid" are
+    scipy.signal.fftconvolve's crops.  ``correlate=True`` (with "causal" only) returns y[t] = sum_j k[j] x[t + j], the adjoint
+    of the causal convolution.  float32 / float64; other input is converted to float64.  Not differentiable: no autograd.
+    Plans are cached per (shape, dtype, n, mode, device, stream); the filter is transformed on every call, so loops over one
+    filter should use ``plan_fftconv``."""
+    if x.is_complex() or k.is_complex():
+        raise MifftError(-3, "fftconv expects real tensors (complex rows are out of scope)")
+    if mode not in _FFTCONV_MODES:
+        raise ValueError(f"fftconv: mode must be one of {_FFTCONV_MODES}, got {mode!r}")
+    if correlate and mode != "causal":
+        raise ValueError(f"fftconv: correlate=True goes with mode='causal' only, got {mode!r}")
+    if k.dim() not in (1, 2) or x.dim() < k.dim():
+        raise MifftError(-1, f"fftconv expects x (..., D, L) with k (D, K), or x (..., L) with k (K,), got {tuple(x.shape)} "
+                             f"and {tuple(k.shape)}")
+    logical = tuple(x.shape)
+    L, K = int(logical[-1]), int(k.shape[-1])
+    D = int(k.shape[0]) if k.dim() == 2 else 1
+    if k.dim() == 2 and logical[-2] != D:
+        raise MifftError(-2, f"fftconv: x has {logical[-2]} channels, k has {D} filters")
+    if L < 2 or K < 1:
+        raise MifftError(-2, f"fftconv: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
+    dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    n = fftconv_length(L + K - 1, dtype) if n is None else int(n)
+    if K > n:
+        raise MifftError(-2, f"fftconv: a filter of K = {K} taps does not fit the FFT length n = {n}")
+    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
+        raise MifftError(ERR_UNSUPPORTED, f"fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
+                                          "n // 2 without a prime factor above 32): see fftconv_length")
+    if L > n:
+        raise MifftError(ERR_UNSUPPORTED, f"fftconv: rows of {L} samples are longer than the FFT length n = {n}")
+    offset, out_length = _fftconv_window(mode, L, K)
+    rows = 1
+    for m in logical[:-1]:
+        rows *= m
+    if rows < 1:
+        raise MifftError(-8, f"fftconv: no rows in {logical}")
+    device = DeviceContext(x.device.index if x.is_cuda else None).device
+    if not x.is_cuda or x.device.index != device:
+        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    xr = x.to(dtype).contiguous().reshape(rows, L, 1)
+    out = torch.empty((rows, out_length, 1), dtype=dtype, device=xr.device)
+    with _PLAN_CACHE_LOCK:
+        key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
+               int(torch.cuda.current_stream(device).cuda_stream))
+        plan = _PLAN_CACHE.get(key)
+        if plan is None:
+            plan = plan_fftconv(dtype, rows // D, D, L, n, offset=offset, out_length=out_length, correlate=correlate,
+                                ctx=DeviceContext(device))
+            _plan_cache_insert(key, plan)
+        else:
+            _PLAN_CACHE.move_to_end(key)
+        plan.set_filter(k)
+        fft(out, xr, DeviceContext(device), plan=plan)
+    return out.reshape(logical[:-1] + (out_length,))
 
 
 def _imdct_norm_gain(norm, n: int, who: str) -> float:

@@ -1,0 +1,137 @@
+// conv.cpp -- the fused FFT convolution of real rows: the MIFFT_FLAG_STFT plans whose payload starts with MIFFT_CONV_TAG
+// (include/mifft.h).
+//
+// One launch, no scratch, no padded copy and no spectrum in memory: the packed real-row kernel of the FFT length n with
+// TileCfg::CONV set (tile_kernel.h).  Its load zero-extends a row of L samples to n, the passes run, one work item per pair of
+// bins multiplies the unpacked spectrum by the filter row's and folds the products back in LDS, the same passes run again as
+// the inverse, and the store writes the samples o .. o + Lo - 1.  x is (batch, L, 1) real, out (batch, Lo, 1) real.  The
+// filter spectra are the caller's device buffer, (D, n / 2 + 1) complex values of the plan's float type: the plan keeps the
+// address it was given and nothing else, so the caller may rewrite the contents between execs and must keep the buffer alive.
+#include "mifft_config.h"
+#include "mifft_internal.h"
+
+namespace mifft {
+
+// ---- the payload TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI ---------------------------------------------------------
+bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 2 || !bases_flat || !bases_len) return false;
+    return bases_len[0] == 8 && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
+}
+
+int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
+               std::string& why) {
+    const struct {
+        uint32_t bits;
+        const char* what;
+    } other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: a convolution has no magnitude or power store"},
+                 {MIFFT_FLAG_STFT_CENTER_REFLECT, "a centre bit (MIFFT_FLAG_STFT_CENTER_REFLECT): a convolution has no frames"},
+                 {MIFFT_FLAG_STFT_CENTER_ZEROS, "a centre bit (MIFFT_FLAG_STFT_CENTER_ZEROS): a convolution has no frames"},
+                 {MIFFT_FLAG_STFT_HOP_MASK, "a hop (MIFFT_FLAG_STFT_HOP): a convolution has no frames"},
+                 {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no convolution to be faithful to"},
+                 {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: the spectrum of a fused convolution is never stored"},
+                 {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
+                 {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
+                 {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: a convolution plan extends dim 0 and transforms dim 1"},
+                 {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
+    for (const auto& o : other)
+        if (p.flags & o.bits) {
+            why = std::string("a convolution payload (MIFFT_CONV_TAG) with ") + o.what;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+    if (p.inverse) {
+        why = "a convolution plan runs its own inverse: inverse must be 0";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 1) {
+        why = "a convolution reads real rows (in_components = 1)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.in_dtype != p.out_dtype) {
+        why = "a convolution reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    const int64_t L = p.dims[0], n = p.dims[1];
+    if (n % 2 != 0 || n < 8 || n > (1 << 14)) {
+        why = "convolution at an FFT length of " + std::to_string(n) +
+              ": the limits of the packed rows are an even length from 8 to 16384";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!conv_rows_supported(p, n, w)) {
+        why = "convolution at an FFT length of " + std::to_string(n) + ": " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (L > n) {
+        why = "rows of L = " + std::to_string(L) + " samples are longer than the FFT length n = " + std::to_string(n) +
+              " (L > n: rfft(x, n) would crop)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    const int64_t D = bases_flat[2], o = bases_flat[3], Lo = bases_flat[4];
+    const uint32_t mode = bases_flat[5];
+    const uint64_t addr = (uint64_t)bases_flat[6] | ((uint64_t)bases_flat[7] << 32);
+    if (Lo < 1 || o + Lo > n) {
+        why = "the output window o = " + std::to_string(o) + ", Lo = " + std::to_string(Lo) +
+              " of a convolution payload: Lo >= 1 and o + Lo <= n = " + std::to_string(n);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (D < 1) {
+        why = "D = 0 filter rows in a convolution payload: D >= 1";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (D > (1ll << 30)) {
+        why = "D = " + std::to_string(D) + " filter rows: at most 2^30";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (p.batch % D != 0) {
+        why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(D) + " filter rows";
+        return MIFFT_ERR_BAD_BATCH;
+    }
+    if (mode & ~1u) {
+        why = "the mode word of a convolution payload has bit 0 (correlate) alone, not " + std::to_string(mode);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (addr == 0) {
+        why = "the filter spectrum address H of a convolution payload is null";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (addr % (2 * dtype_size(p.out_dtype)) != 0) {
+        why = "the filter spectrum address H of a convolution payload is not aligned to one complex element (" +
+              std::to_string(2 * dtype_size(p.out_dtype)) + " bytes)";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (bases_len[1] < 0) {
+        why = "negative bases_len";
+        return MIFFT_ERR_NO_BASES;
+    }
+    radices.clear();
+    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    p.conv_D = D;
+    p.conv_o = o;
+    p.conv_Lo = Lo;
+    p.conv_mode = mode;
+    p.conv_h = (const void*)(uintptr_t)addr;
+    return MIFFT_OK;
+}
+
+// the one pass: dim 1 (n points) over the rows of the batch; the tables are the half-spectrum row pass's
+int build_conv(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    const int64_t n = p.dims[1];
+    DimPass ps;
+    ps.dim_index = 1;
+    ps.N = n;
+    ps.inner = 1;
+    ps.outer = 1;
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    ps.half_pitch = n / 2 + 1;
+    if (!select_jit_conv_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "convolution table upload");
+    return MIFFT_OK;
+}
+
+}  // namespace mifft

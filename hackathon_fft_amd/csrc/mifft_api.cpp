@@ -32,6 +32,7 @@ size_t Plan::in_row_bytes() const {
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
+    if (stft() && conv_D) return (size_t)conv_Lo * dtype_size(out_dtype);
     if (stft() && mdct) return (size_t)(stft_frames() * mdct) * dtype_size(out_dtype);
     if (stft() && spec_power) return (size_t)(stft_frames() * stft_out_width()) * dtype_size(out_dtype);
     if (stft()) return (size_t)prod_half * out_elem_bytes();
@@ -167,9 +168,9 @@ int open_device(Plan& p, std::optional<DeviceGuard>& guard) {
     return MIFFT_OK;
 }
 
-// STFT and inverse STFT plans (MIFFT_FLAG_STFT, stft.cpp; MIFFT_FLAG_ISTFT, istft.cpp) and the MDCT / IMDCT plans their
-// tagged payloads select: their own route to the end.  Everything that can be refused without a device first; `bases`
-// carries the window and the radices of the one transformed dim, the last.
+// STFT and inverse STFT plans (MIFFT_FLAG_STFT, stft.cpp; MIFFT_FLAG_ISTFT, istft.cpp) and the MDCT / IMDCT / fused
+// convolution plans (conv.cpp) their tagged payloads select: their own route to the end.  Everything that can be refused
+// without a device first; `bases` carries the window and the radices of the one transformed dim, the last.
 int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::optional<DeviceGuard>& guard) {
     const int ndim = p.ndim;
     const int64_t* dims = p.dims;
@@ -182,7 +183,10 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     const bool mdct = fwd && mdct_detect(ndim, dims, bases_flat, bases_len);
     // (the same tag on a MIFFT_FLAG_ISTFT plan: the inverse, frames of M = n / 2 coefficients overlap-added every M samples)
     const bool imdct = !fwd && imdct_detect(ndim, bases_flat, bases_len);
-    int rc = mdct    ? mdct_check(p, bases_flat, bases_len, window, user, why)
+    // (a payload that STARTS with MIFFT_CONV_TAG: the fused FFT convolution of rows of dims[0] samples at length dims[1])
+    const bool conv = fwd && conv_detect(ndim, bases_flat, bases_len);
+    int rc = conv    ? conv_check(p, bases_flat, bases_len, user, why)
+             : mdct  ? mdct_check(p, bases_flat, bases_len, window, user, why)
              : imdct ? imdct_check(p, bases_flat, bases_len, window, gain, user, why)
              : fwd   ? stft_check(p, why)
                      : istft_check(p, bases_flat, bases_len, window, gain, user, why);
@@ -191,7 +195,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     const int64_t n = mdct || imdct ? dims[td] / 4 : dims[td], frames = fwd ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
     p.prod = frames * (mdct ? p.mdct : imdct ? p.imdct : n);  // (the rows the one pass transforms)
     p.prod_half = mdct || imdct ? p.prod : frames * (n / 2 + 1);
-    if (fwd && !mdct) {
+    if (fwd && !mdct && !conv) {
         rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, post, user, why);
         if (rc) return fail(rc, why);
     }
@@ -202,7 +206,8 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     p.stage_radices = ordered;  // (the other dims are framed / overlap-added, not transformed: no stages)
     rc = open_device(p, guard);
     if (rc) return rc;
-    rc = mdct    ? build_mdct(p, ordered[td], processed[td], window, why)
+    rc = conv    ? build_conv(p, ordered[td], processed[td], why)
+         : mdct  ? build_mdct(p, ordered[td], processed[td], window, why)
          : imdct ? build_imdct(p, ordered[td], processed[td], window, gain, why)
          : fwd   ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
                  : build_istft(p, ordered[td], processed[td], window, gain, why);
@@ -444,6 +449,7 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     hipStream_t s = (hipStream_t)stream;
     char* sb = p.d_scratch ? (char*)p.d_scratch + (size_t)first * p.scratch_row_bytes() : nullptr;
     auto buf = [&](int which) -> char* { return which == 0 ? (char*)xb : which == 2 ? sb : ob; };
+    if (p.conv_D) return launch_jit_conv(p, p.passes[0], xb, ob, first, count, s);  // (the filter row of row i: (first + i) % D)
     for (const DimPass& ps : p.passes) {
         const void* src = ps.src_buf >= 0 ? buf(ps.src_buf) : (ps.first ? (const char*)xb : ob);
         void* dst = ps.dst_buf >= 0 ? buf(ps.dst_buf) : ob;

@@ -111,6 +111,9 @@ struct DimPass {
     // TileCfg::STFT of a packed-row pass: the rows are the `outer` frames of every batch entry (hop, length and centring are the
     // plan's); d_aux2 holds the window, N values of the plan's float type
     bool stft = false;
+    // TileCfg::CONV of a packed-row (r2c) pass: rows of dims[0] samples are convolved with the plan's filter spectra in the one
+    // launch (conv.cpp); d_twiddle and d_aux are the r2c tables, N is the FFT length
+    bool conv = false;
     // TileCfg::ISTFT of a C2R pass: `outer` frames per batch entry are overlap-added into dims[0] samples; d_aux2 holds the
     // synthesis table (N values), d_aux3 the reciprocal envelope (N + hop (outer - 1) values), both of the plan's float type
     bool istft = false;
@@ -179,6 +182,7 @@ struct Plan {
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
     int64_t stft_frames() const {
+        if (conv_D) return 1;  // (no frames, no hop: one row per batch entry)
         if (mdct) return (dims[0] + mdct - 1) / mdct + 1;
         return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop();
     }
@@ -190,6 +194,13 @@ struct Plan {
     // a MIFFT_FLAG_ISTFT plan whose window payload is tagged with MIFFT_MDCT_TAG: the inverse MDCT of imdct = M = dims[2] / 2
     // coefficients per frame, dims = {T, F, 2 M}; x is (batch, F, M, 1) real, out (batch, T, 1).  0: not one.  Set by imdct_check.
     int64_t imdct = 0;
+    // a MIFFT_FLAG_STFT plan whose payload starts with MIFFT_CONV_TAG: the fused FFT convolution, dims = {L, n}; x is
+    // (batch, L, 1) real, out (batch, conv_Lo, 1): the samples conv_o .. conv_o + conv_Lo - 1 of irfft(rfft(x, n) G, n), row r
+    // against row r % conv_D of the caller's device buffer conv_h (conv_D rows of n / 2 + 1 complex values; never copied, never
+    // freed); conv_mode bit 0: G = conj(H).  conv_D = 0: not one.  Set by conv_check.
+    int64_t conv_D = 0, conv_o = 0, conv_Lo = 0;
+    uint32_t conv_mode = 0;
+    const void* conv_h = nullptr;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
     bool dct4 = false;
     // a MIFFT_FLAG_DCT / MIFFT_FLAG_DCT_ND plan whose `bases` start with MIFFT_DST_TAG (DST-II and its inverse, along every
@@ -374,6 +385,19 @@ int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vec
                 const std::vector<double>& window, double gain, std::string& why);
 bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+// Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
+// bases_len[0] the tagged length 8 with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
+// be refused without a device, leaving the request in plan.conv_* and the user radices of n in `radices`.  build_conv: the
+// one pass.  select_jit_conv_rows is the packed-row kernel with TileCfg::CONV (kernels_jit.cpp; run time only),
+// conv_rows_supported the same check without a device; launch_jit_conv is its launch, which -- unlike a DimPass::launch --
+// knows the first row of the exec, for the filter row of every launch row.
+bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
+int conv_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
+int build_conv(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
+bool conv_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
+bool select_jit_conv_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void* out, int64_t first, int64_t count,
+                    hipStream_t stream);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }

@@ -235,6 +235,12 @@ struct TileParams {
     double spec_add, spec_amin, spec_a, spec_c;
     const void* spec_post;
     int spec_q;
+    // CONV configurations (an R2C tile that is neither STFT nor SPEC) reuse seven of the fields above, so that the layout of
+    // the kernel argument stays what every other kernel was built for: stft_len = L samples per input row, stft_hop = o and
+    // stft_frames = Lo (the samples o .. o + Lo - 1 of every result are stored, rows of Lo reals), stft_center = D filter
+    // rows, spec_wt = the filter spectra, D rows of N + 1 complex values of type T (the caller's buffer), spec_bands = the
+    // launch's first row modulo D (row r of the launch takes filter row (spec_bands + r) % D), spec_q bit 0 = correlate
+    // (multiply by the conjugate).  scale is 1 / 2N; inverse is 0.
 };
 
 // the log stage of a TileCfg::LOG store: fma(a, log2(max(v + add, amin)), c)
@@ -330,7 +336,8 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool IN_REAL_ = false, bool DMA_ = false, int NT_ = 0, bool TSTORE_ = false, typename IT_ = T_, bool WSUB_ = false,
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
-          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false>
+          bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
+          bool CONV_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -540,6 +547,24 @@ struct TileCfg {
     //   columns, DCT = 3: bins k and N-k are read from rows N-1-k and k-1; the last pass negates what it stores to an odd row.
     static constexpr bool DST = DST_;
     static_assert(!DST_ || (DCT_ != 0 && !MDCT_ && !IMDCT_), "DST: the sign and the reversal on a plain DCT tile");
+    // CONV (with R2C): y = irfft(rfft(x, 2N) . G, 2N)[o .. o + Lo) of real rows, the FFT convolution (or, with the conjugate of
+    // G, correlation) in ONE tile: load, passes, product, the same passes again, store.  The load packs a row of L <= 2N reals
+    // as the R2C rows are packed, with zeros from sample L on (pair loads inside the row, real by real at its end: L may be
+    // odd).  After the passes the work item of the pair (k, N - k) unpacks X[k] and X[N-k] as the R2C store does, multiplies
+    // them by G[d][k] and G[d][N-k] -- two runs over the lanes from global memory, d = the row's global index modulo D --
+    // folds the products with the C2R load's algebra (the imaginary parts of bins 0 and N dropped, as numpy's irfft drops
+    // them) and writes conj Z back to the two slots it read: it is their only reader.  A row tile's pass 0 gathers from the
+    // layout its last pass scatters to -- lds_index<C, -1> and lds_index<C, NP - 1> are both the unswizzled row -- so after
+    // one barrier run_pass runs a second time on the same tables and register twiddles and leaves conj(z) of the packed
+    // result; no second layout exists that another work item could still be reading.  The store scales by 1 / 2N, negates
+    // the odd samples' conjugation away and writes sample t of a row to out[r Lo + t - o] for o <= t < o + Lo only, each
+    // exactly once: a pair whose two samples are both wanted and whose address is aligned to two elements goes out as one
+    // access, every other wanted sample as one real.  x is read once, y written once; G is re-read by every row through
+    // L2 and the Infinity Cache.  No LDS beyond the R2C tile's.  A row's result depends on its own data and filter row alone.
+    static constexpr bool CONV = CONV_;
+    static_assert(!CONV_ || (R2C_ && !FIRST_DIRECT_ && DCT_ == 0 && !STFT_ && SPEC_ == 0 && NT_ == 0 && same_t<IT_, T_>::value &&
+                             R0_ <= 32 && R1_ <= 32),
+                  "CONV: packed real rows of the plan's own float type, staged in LDS by the zero-extending load");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -1904,6 +1929,21 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     lds[lds_index<C, -1>(c, C::N - 1 - m)] = {w1.x * b.x - w1.y * a.y, w1.x * a.y + w1.y * b.x};
             }
             __syncthreads();
+        } else if constexpr (C::CONV) {
+            // packed element m of row c: the reals 2 m and 2 m + 1 of a row of L samples, zeros from sample L on
+            const int L = p.stft_len;
+            const T* x0 = (const T*)p.in + (base / C::N) * L;
+            for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                const int c = f / C::N, m = f - c * C::N;
+                const T* xr = x0 + (long long)c * L;
+                V x = {(T)0, (T)0};
+                if (2 * m + 1 < L)
+                    x = gload_pair(xr + 2 * m);
+                else if (2 * m < L)
+                    x.x = xr[2 * m];
+                lds[lds_index<C, -1>(c, m)] = x;
+            }
+            __syncthreads();
         } else if constexpr (C::STFT) {
             // (b, frame) of the tile's first row once, uniform; a row further on wraps into the entries that follow
             const long long r0 = base / C::N, b0 = r0 / p.stft_frames;
@@ -2081,6 +2121,78 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                         y.y *= -(T)p.scale;
                     }
                     gout[gaddr<C>(p, base, c, n)] = y;
+                }
+            }
+            __syncthreads();
+        } else if constexpr (C::CONV) {
+            // Z = F(z) of the packed rows lies in LDS.  One work item per pair (k, N - k), k = 0 .. N / 2, a fixed number per
+            // thread in groups of G whose filter loads are all issued before the first product (as the C2R load's)
+            const V* w = (const V*)p.r2c_tw;
+            constexpr int PAIRS = C::N / 2 + 1;
+            constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS, G = IT < 4 ? IT : 4;
+            const long long row0 = base / C::N;
+            const unsigned D = (unsigned)p.stft_center;
+            const unsigned d0 = (unsigned)(((long long)p.spec_bands + row0) % (long long)D);  // (uniform; d0 + c < 2^31)
+            const V* hs = (const V*)p.spec_wt;
+            const T cj = (p.spec_q & 1) ? (T)-1 : (T)1;
+#pragma unroll 1
+            for (int i0 = 0; i0 < IT; i0 += G) {
+                V ga[G], gb[G];
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    const int f = tid + (i0 + j) * C::THREADS;
+                    if ((IT % G == 0 || i0 + j < IT) && f < nv * PAIRS) {
+                        const int c = f / PAIRS, k = f - c * PAIRS;
+                        const V* hr = hs + (long long)((d0 + (unsigned)c) % D) * (C::N + 1);
+                        ga[j] = hr[k];
+                        gb[j] = hr[C::N - k];  // (k = 0: bin N, the last of the row)
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    const int f = tid + (i0 + j) * C::THREADS;
+                    if ((IT % G == 0 || i0 + j < IT) && f < nv * PAIRS) {
+                        const int c = f / PAIRS, k = f - c * PAIRS, m = k ? C::N - k : 0;
+                        const int ik = lds_index<C, C::NP - 1>(c, k), im = lds_index<C, C::NP - 1>(c, m);
+                        const V zk = lds[ik], zm = lds[im];
+                        // X[k] and X[N-k], as the R2C store unpacks them
+                        const T ex = (T)0.5 * (zk.x + zm.x), ey = (T)0.5 * (zk.y - zm.y);
+                        const T ox = (T)0.5 * (zk.y + zm.y), oy = (T)-0.5 * (zk.x - zm.x);
+                        const V wk = w[k];
+                        const T tx = wk.x * ox - wk.y * oy, ty = wk.x * oy + wk.y * ox;
+                        const V xa = {ex + tx, ey + ty}, xb = {ex - tx, ty - ey};
+                        // times G (conjugated: correlation)
+                        const V ha = {ga[j].x, cj * ga[j].y}, hb = {gb[j].x, cj * gb[j].y};
+                        V a = cmul(xa, ha), b = cmul(xb, hb);
+                        if (k == 0) a.y = b.y = (T)0;
+                        // the C2R fold: Z[k] = E + i O, Z[N-k] = conj(E) + i conj(O), E = a + conj b, O = (a - conj b) conj(W^k);
+                        // written conjugated, so that the forward passes run the inverse as conj(F(conj Z))
+                        const T fx = a.x + b.x, fy = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
+                        const T px = dx * wk.x + dy * wk.y, py = dy * wk.x - dx * wk.y;
+                        lds[ik] = {fx - py, -(fy + px)};
+                        if (k != 0 && 2 * k != C::N) lds[im] = {fx + py, fy - px};
+                    }
+                }
+            }
+            __syncthreads();
+            // (pass 0 gathers at lds_index<C, -1>, where the last pass left its results: see TileCfg::CONV)
+            run_pass<C, 0>(p, lds, twr, cur, base, nv, tid, obase, fs_row, drain, slice);
+            // conj(z) of the packed result, unscaled: sample 2 j is the real part of element j, sample 2 j + 1 minus its
+            // imaginary part.  Samples o .. o + Lo - 1 go to a row of Lo reals.
+            const int o = p.stft_hop, Lo = p.stft_frames;
+            const T s = (T)p.scale;
+            T* out0 = (T*)p.out + row0 * Lo;
+            for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                const int c = f / C::N, j = f - c * C::N, t = 2 * j - o;
+                if (t + 1 < 0 || t >= Lo) continue;
+                const V v = lds[lds_index<C, C::NP - 1>(c, j)];
+                const T y0 = v.x * s, y1 = -(v.y * s);
+                T* q = out0 + (long long)c * Lo + t;
+                if (t >= 0 && t + 1 < Lo && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                    gstore<false>((V*)q, V{y0, y1});
+                } else {
+                    if (t >= 0) q[0] = y0;
+                    if (t + 1 < Lo) q[1] = y1;
                 }
             }
             __syncthreads();

@@ -476,6 +476,42 @@ typedef enum {
  * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_BASES: a tagged bases_len[0] other than 2 (2 M) + 4, a non-zero
  * bases_len[1], a window value or g that is not finite, g = 0 (or radices that do not multiply to M / 2).
  * MIFFT_ERR_TOO_LARGE: F > 2^26 or T >= 2^31. */
+/* Fused FFT convolution of real rows (numpy: irfft(rfft(x, n) * G, n)[..., o : o + Lo]; no reference counterpart): a
+ * MIFFT_FLAG_STFT plan -- that bit ALONE, no hop, no centre bit -- whose payload starts with the tag MIFFT_CONV_TAG.
+ *   flags = MIFFT_FLAG_STFT, ndim = 2, dims = {L, n}, inverse = 0, in_components = 1, in_dtype == out_dtype in {F32, F64};
+ *       x (batch, L, 1)  ->  out (batch, Lo, 1),      batch = B * D rows, row r filtered by row r % D of H,
+ *       out[r, t] = irfft( rfft(x[r], n) * G[r % D], n )[o + t],   t < Lo,    G = H, or conj(H) with mode bit 0 (correlation).
+ * rfft zero-pads the row from sample L to n (L <= n; L may be odd), the inverse's 1 / n is included, and H is the UNNORMALISED
+ * rfft of the filter: D rows of n / 2 + 1 complex values of the plan's float type.  n < L + K - 1 gives the circular result.
+ * The imaginary parts of the products at bins 0 and n / 2 are ignored, as numpy's irfft ignores them.
+ *   - bases_len[0] is exactly 8 words of 32 bits:  TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI.  The two tag words are
+ *     the halves of a NaN that no window value can have (window values are finite), in the place of w[0]; D, o, Lo and mode
+ *     are plain unsigned words (mode: bit 0 = correlate, every other bit 0); H_HI : H_LO is the 64-bit DEVICE address of H.
+ *     No other payload of a MIFFT_FLAG_STFT plan has length 8 with these first two words; every other payload means what it
+ *     meant and keeps its refusals;
+ *   - bases_len[1] is 0 (the default estimate) or radices of n, as for an STFT plan.
+ * H is the CALLER's buffer, bound when the plan is created: the plan stores the address and never copies or frees it.  It
+ * must stay allocated as long as the plan lives; its contents may be rewritten between execs, in stream order with them.
+ * ONE launch, no scratch, no padded copy, no spectrum in memory: the packed-row R2C tile of n / 2 complex points with
+ * TileCfg::CONV (kernel rows<n>[_f64]_r2c_<radices>_conv_jit, compiled at run time only).  Its load packs and zero-extends
+ * the row; after the passes one work item per pair of bins (k, n / 2 - k) unpacks X[k] and X[n/2 - k] in LDS, multiplies them by
+ * the two filter bins read from global memory, folds the products back and leaves them where it read them; the same passes
+ * run again on the same tables (inverse = conj(F(conj .))), and the store writes only the samples o .. o + Lo - 1, each exactly
+ * once, in pairs where the address is aligned to two elements and real by real elsewhere.  Nothing outside the exec's rows
+ * is read or written; a row's result is bit-identical for any batch, first / count, whole_batch and grid.
+ * mifft_plan_num_launches() is 1, mifft_plan_scratch_bytes() 0; mifft_plan_in_bytes() / _out_bytes() are batch * L and
+ * batch * Lo elements; mifft_exec_batch(first, count) offsets x by first * L and out by first * Lo reals and takes the filter
+ * row of launch row i as (first + i) % D; mifft_plan_pass_geometry(1, count) counts rows of count; dim 0 reports no stages and
+ * "none", dim 1 the stages and the kernel, as an STFT plan.
+ * Refused before any device work, the reason in mifft_last_error().  MIFFT_ERR_UNSUPPORTED: n outside the limits of the packed
+ * rows (even, 8 .. 16384, F64 up to 12288, n / 2 without a prime factor above 32); L > n; ndim != 2; inverse != 0; a hop, a
+ * centre bit, MIFFT_FLAG_STFT_POWER, MIFFT_FLAG_ISTFT, MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT,
+ * MIFFT_FLAG_DCT_ND, MIFFT_FLAG_DCT_ORTHO or a keep bit; MIFFT_JIT=0.  MIFFT_ERR_BAD_BASES: Lo < 1 or o + Lo > n; D < 1; a
+ * mode word with a bit other than bit 0; a null H address or one not aligned to one complex element (or radices that do not
+ * multiply to n).  MIFFT_ERR_BAD_BATCH: batch not a multiple of D.  MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.
+ * MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: D > 2^30. */
+#define MIFFT_CONV_TAG_LO 0x4F4E5601u
+#define MIFFT_CONV_TAG_HI 0x7FF84D43u
 
 typedef struct mifft_plan mifft_plan;
 

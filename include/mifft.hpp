@@ -186,6 +186,14 @@ constexpr uint32_t kDctType4Tag = MIFFT_DCT_TYPE4_TAG;
 constexpr uint32_t kDstTag = MIFFT_DST_TAG;
 constexpr uint32_t kDstType4Tag = MIFFT_DST_TYPE4_TAG;
 constexpr uint64_t kMdctTag = ((uint64_t)MIFFT_MDCT_TAG_HI << 32) | MIFFT_MDCT_TAG_LO;
+// MIFFT_CONV_TAG as the FIRST two words of the 8-word payload of a plain MIFFT_FLAG_STFT plan with dims = {L, n}: the fused FFT
+// convolution of real rows, x (batch, L, 1) -> out (batch, Lo, 1), against the caller's device buffer of filter spectra
+// (TAG | D | o | Lo | mode | address; include/mifft.h).  Created through mifft_plan_create itself.
+static_assert(MIFFT_CONV_TAG_LO == 0x4F4E5601u && MIFFT_CONV_TAG_HI == 0x7FF84D43u &&
+                  (MIFFT_CONV_TAG_HI & 0x7FF80000u) == 0x7FF80000u && MIFFT_CONV_TAG_HI != MIFFT_MDCT_TAG_HI &&
+                  MIFFT_CONV_TAG_HI != MIFFT_STFT_EXT_TAG_HI,
+              "MIFFT_CONV_TAG is the quiet NaN 0x7FF84D434F4E5601, distinct from the other payload tags");
+constexpr uint64_t kConvTag = ((uint64_t)MIFFT_CONV_TAG_HI << 32) | MIFFT_CONV_TAG_LO;
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
