@@ -19,6 +19,7 @@ import enum
 import hashlib
 import math
 import threading
+from fractions import Fraction
 from typing import Optional, Sequence
 
 import torch
@@ -507,7 +508,10 @@ class Plan:
     ``conv`` = (n, D, o, Lo, mode, address) (no reference counterpart): the fused FFT convolution of real rows,
     x (batch, L, 1) -> out (batch, Lo, 1), samples o .. o + Lo - 1 of irfft(rfft(x, n) * G[row % D], n) against the D filter
     spectra at the device ``address`` (mode bit 0: their conjugates); the caller keeps that buffer alive (MIFFT_CONV_TAG in
-    include/mifft.h, plan_fftconv).  ``bases`` has two lists, an empty one and the radices of n (or an empty one)."""
+    include/mifft.h, plan_fftconv).  ``bases`` has two lists, an empty one and the radices of n (or an empty one).
+    Nine values, (n, D, c, S, mode, address, F, s0, Lo), are the overlap-save form (the 12-word payload): x (batch, T, 1) with
+    T possibly beyond n, F blocks of n samples per row, block f from sample s0 + f S on, of whose circular result the S
+    samples from c on are stored at f S of the row's Lo output samples."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
@@ -598,18 +602,29 @@ class Plan:
                      (FLAG_STFT_POWER if stft_power is not None else 0))
             stft, istft = True, False
         if conv is not None:  # (with any other mode as well: the library refuses the pair)
-            n_fft, D, o, Lo, mode, addr = (int(v) for v in conv)
+            conv = tuple(int(v) for v in conv)
+            ols = len(conv) == 9  # (overlap-save: n, D, c, S, mode, address, F, s0, Lo; the 12-word payload)
+            if len(conv) not in (6, 9):
+                raise MifftError(-5, f"conv = (n, D, o, Lo, mode, address) or (n, D, c, S, mode, address, F, s0, Lo), got {len(conv)} values")
+            n_fft, D, o, Lo, mode, addr = conv[:6]
+            step = Lo
+            if ols:
+                blocks, start, Lo = conv[6:]
             if len(in_shape) != 3 or len(out_shape) != 3 or in_shape[-1] != 1 or out_shape[-1] != 1:
                 raise MifftError(-1, f"convolution layouts are (batch, L, 1) -> (batch, Lo, 1), got {in_shape} -> {out_shape}")
             if in_shape[0] != out_shape[0] or out_shape[1] != Lo:
                 raise MifftError(-2, f"x {in_shape} against out {out_shape} with Lo = {Lo}")
             if axes is not None:
                 raise MifftError(ERR_UNSUPPORTED, "a convolution plan extends dim 0 and transforms dim 1: no axes")
-            for v, what in ((D, "D"), (o, "o"), (Lo, "Lo"), (mode, "mode")):
+            for v, what in ((D, "D"), (o, "o"), (Lo, "Lo"), (mode, "mode")) + (((step, "S"), (blocks, "F")) if ols else ()):
                 if not 0 <= v < 1 << 32:
                     raise MifftError(-5, f"{what} = {v} of a convolution plan does not fit an unsigned 32-bit word")
             stft_dims = (in_shape[1], n_fft)
-            words = [CONV_TAG_LO, CONV_TAG_HI, D, o, Lo, mode, addr & 0xFFFFFFFF, (addr >> 32) & 0xFFFFFFFF]
+            words = [CONV_TAG_LO, CONV_TAG_HI, D, o, step, mode, addr & 0xFFFFFFFF, (addr >> 32) & 0xFFFFFFFF]
+            if ols:
+                if not -(1 << 31) <= start < 1 << 31:
+                    raise MifftError(-5, f"s0 = {start} of a convolution plan does not fit a signed 32-bit word")
+                words += [blocks, start & 0xFFFFFFFF, Lo, 0]
             flags = (int(flags) | FLAG_STFT | (FLAG_ISTFT if istft else 0) | (FLAG_DCT_ND if dctn else 0) |
                      (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
                      (FLAG_STFT_POWER if stft_power is not None else 0))
@@ -1620,7 +1635,7 @@ def _fftconv_accepted(n: int, dtype) -> bool:
 def fftconv_length(m: int, dtype=torch.float32) -> int:
     """The smallest FFT length n >= m that a fused convolution plan of ``dtype`` accepts (even, 8 .. 16384, n // 2 without a
     prime factor above 32; float64 plans stop at 12288 and skip a few lengths more).  MifftError beyond the last one: longer
-    convolutions need overlap-save."""
+    convolutions run as overlap-save blocks (fftconv_block, plan_fftconv(taps=))."""
     m = int(m)
     if dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"fftconv_length: float32 or float64, got {dtype}")
@@ -1630,22 +1645,63 @@ def fftconv_length(m: int, dtype=torch.float32) -> int:
             return n
         n += 2
     raise MifftError(ERR_UNSUPPORTED, f"fftconv_length({m}): no accepted FFT length up to {_FFTCONV_MAX}; longer convolutions "
-                                      "need overlap-save, which is out of scope")
+                                      "run as overlap-save blocks (fftconv_block, plan_fftconv(taps=), fftconv(block=))")
+
+
+# the measured time per block sample of the overlap-save kernel at every block length, in hundredths of the cheapest
+# (profiles/r17_fftconv_long.txt, the sweep at 33 taps)
+_FFTCONV_BLOCK_COST = {
+    torch.float32: {256: 100, 512: 136, 1024: 148, 2048: 154, 4096: 133, 8192: 179, 16384: 166},
+    torch.float64: {256: 100, 512: 109, 1024: 117, 2048: 133, 4096: 163, 8192: 200},
+}
+
+
+def fftconv_block(K: int, dtype=torch.float32) -> int:
+    """The FFT length of the overlap-save blocks ``fftconv`` picks for a filter of ``K`` taps: among the powers of two from 256
+    to 16384 (float64: 8192) with n >= 2 (K - 1), the one with the least w(n) n / (n - K + 1) -- the block samples transformed
+    per stored sample, times w(n), the measured time per block sample of the kernel of that length (_FFTCONV_BLOCK_COST;
+    DESIGN.md 3.4n) --, the smaller on a tie.  MifftError when there is none (K > 8193, float64 4097): a filter longer than half a block needs
+    partitioned convolution, which is out of scope."""
+    K = int(K)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"fftconv_block: float32 or float64, got {dtype}")
+    if K < 1:
+        raise MifftError(-2, f"fftconv_block: a filter of K = {K} taps (at least 1)")
+    best, best_cost = None, None
+    for n, w in sorted(_FFTCONV_BLOCK_COST[dtype].items()):
+        if n >= 2 * (K - 1):
+            cost = Fraction(w * n, n - K + 1)  # (exact: a tie is a tie)
+            if best is None or cost < best_cost:
+                best, best_cost = n, cost
+    if best is None:
+        raise MifftError(ERR_UNSUPPORTED, f"fftconv_block({K}): no block of up to {8192 if dtype == torch.float64 else _FFTCONV_MAX} "
+                                          "points holds two filter lengths; filters longer than half a block need partitioned "
+                                          "convolution, which is out of scope")
+    return best
 
 
 class ConvPlan(Plan):
     """The plan of ``plan_fftconv``: a ``Plan`` that owns the tensor of filter spectra its kernel reads.
     ``filter_spectrum`` is (channels, n // 2 + 1, 2) of the plan's dtype, zero-filled at first; its address is bound into
-    the plan and never changes, its contents may be rewritten between execs in stream order."""
+    the plan and never changes, its contents may be rewritten between execs in stream order.
+    An overlap-save plan (``plan_fftconv(taps=K)``) has ``taps`` = K, ``step`` = n - K + 1 samples stored per block and
+    ``blocks`` per row; a single-block plan has ``taps`` and ``step`` None and one block."""
 
-    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx):
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None):
         self.ctx = ctx
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
+        self.taps, self.step, self.blocks = taps, None, 1
         with torch.cuda.stream(ctx.stream):
             self.filter_spectrum = torch.zeros((channels, n // 2 + 1, 2), dtype=dtype, device=f"cuda:{ctx.device}")
+        mode, addr = 1 if correlate else 0, self.filter_spectrum.data_ptr()
+        if taps is None:
+            conv = (n, channels, offset, out_length, mode, addr)
+        else:
+            c, self.step, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
+            conv = (n, channels, c, self.step, mode, addr, self.blocks, s0, out_length)
         super().__init__(dtype, dtype, (batch * channels, length, 1), (batch * channels, out_length, 1), device=ctx.device,
-                         conv=(n, channels, offset, out_length, 1 if correlate else 0, self.filter_spectrum.data_ptr()))
+                         conv=conv)
 
     def set_filter(self, k: "torch.Tensor") -> None:
         """``k`` real, (channels, K) or (K,) (one filter for every channel), K <= n: writes rfft(k, n) into
@@ -1657,6 +1713,9 @@ class ConvPlan(Plan):
         K = int(k.shape[-1])
         if K < 1 or K > self.n:
             raise MifftError(-2, f"set_filter: a filter of K = {K} taps does not fit the FFT length n = {self.n} (1 <= K <= n)")
+        if self.taps is not None and K > self.taps:
+            raise MifftError(-2, f"set_filter: a filter of K = {K} taps on an overlap-save plan of taps = {self.taps}: the blocks "
+                                 "would wrap around")
         with torch.cuda.stream(self.ctx.stream):
             kp = torch.zeros((self.channels, self.n), dtype=self.out_dtype, device=self.filter_spectrum.device)
             kp[:, :K] = k.to(device=kp.device, dtype=self.out_dtype)
@@ -1674,15 +1733,27 @@ class ConvPlan(Plan):
             self.filter_spectrum.copy_(Hr.to(device=self.filter_spectrum.device, dtype=self.out_dtype))
 
 
-def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, offset: int = 0, out_length: Optional[int] = None,
-                 correlate: bool = False, ctx: Optional[DeviceContext] = None) -> ConvPlan:
+def _fftconv_ols_geometry(n: int, K: int, offset: int, out_length: int, correlate: bool) -> tuple:
+    """(c, S, s0, F) of an overlap-save plan: S = n - K + 1 samples per block are free of wrap-around, from c = K - 1 on
+    (correlation: from 0 on); block 0 starts c samples before the first wanted one"""
+    S = n - K + 1
+    c = 0 if correlate else K - 1
+    return c, S, offset - c, -(-out_length // S)
+
+
+def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
+                 out_length: Optional[int] = None, correlate: bool = False, ctx: Optional[DeviceContext] = None) -> ConvPlan:
     """Plan of the fused FFT convolution (no reference counterpart; MIFFT_CONV_TAG in include/mifft.h) of ``batch * channels``
     real rows of ``length`` samples, row-major (batch, channels, length), at the FFT length ``n`` (see fftconv_length):
     ``y[r] = irfft(rfft(x[r], n) * G[r % channels], n)[offset : offset + out_length]`` in ONE kernel launch, G the plan's
     ``filter_spectrum`` (``correlate``: its conjugate).  ``out_length`` defaults to ``length``.  ``in_shape``
     (batch * channels, length, 1), ``out_shape`` (batch * channels, out_length, 1), both of ``dtype`` (float32 / float64);
     runs through ``fft(out, x, plan=plan)``, ``first=`` / ``count=`` included.  ``n < length + K - 1`` gives the circular
-    result.  Every argument error is raised before any device work."""
+    result.  Every argument error is raised before any device work.
+    ``taps=K`` makes it an overlap-save plan at the block length ``n``, still one launch: filters of up to K taps,
+    1 <= K <= n - 1, on rows of any ``length`` >= 2; every block of n samples stores its n - K + 1 samples that no wrap-around
+    touched.  ``offset`` / ``out_length`` are then coordinates in the full linear convolution of length + K - 1 samples
+    (``correlate``: in y[t] = sum_j k[j] x[t + j], t < length), wholly inside it."""
     batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
     out_length = length if out_length is None else int(out_length)
     if dtype not in _OUT_DTYPES:
@@ -1692,6 +1763,20 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, offse
     if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
         raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
                                           "n // 2 without a prime factor above 32): see fftconv_length")
+    if taps is not None:
+        taps = int(taps)
+        if taps < 1 or taps > n - 1:
+            raise MifftError(-2, f"plan_fftconv: taps = {taps} at the block length n = {n}: 1 <= taps <= n - 1")
+        if length < 2 or length > 1 << 30:
+            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples: 2 <= length <= 2^30")
+        full = length if correlate else length + taps - 1
+        if offset < 0 or out_length < 1 or offset + out_length > full:
+            raise MifftError(-5, f"plan_fftconv: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
+                                 f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
+                                 f"{length} samples with {taps} taps)")
+        if ctx is None:
+            ctx = DeviceContext()
+        return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps)
     if length < 2 or length > n:
         raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples at n = {n}: 2 <= length <= n")
     if offset < 0 or out_length < 1 or offset + out_length > n:
@@ -1714,7 +1799,7 @@ def _fftconv_window(mode: str, L: int, K: int) -> tuple:
 
 
 def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mode: str = "causal",
-            correlate: bool = False) -> "torch.Tensor":
+            correlate: bool = False, block: Optional[int] = None) -> "torch.Tensor":
     """Convolution by FFT along the last dim of a real ``x`` of shape (..., D, L) with ``k`` of shape (D, K), one filter per
     channel, or of shape (..., L) with a 1-D ``k``: one kernel launch per call (plus the transform of the filter).
     ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one gives the circular result.
@@ -1722,7 +1807,10 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     scipy.signal.fftconvolve's crops.  ``correlate=True`` (with "causal" only) returns y[t] = sum_j k[j] x[t + j], the adjoint
     of the causal convolution.  float32 / float64; other input is converted to float64.  Not differentiable: no autograd.
     Plans are cached per (shape, dtype, n, mode, device, stream); the filter is transformed on every call, so loops over one
-    filter should use ``plan_fftconv``."""
+    filter should use ``plan_fftconv``.
+    Rows too long for one FFT (L + K - 1 beyond fftconv_length's last length) run as overlap-save blocks of
+    fftconv_block(K) points, in the same single launch; ``block=`` forces that path at the given FFT length for any L (it
+    excludes ``n``), K <= block - 1."""
     if x.is_complex() or k.is_complex():
         raise MifftError(-3, "fftconv expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -1740,13 +1828,28 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     if L < 2 or K < 1:
         raise MifftError(-2, f"fftconv: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
     dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-    n = fftconv_length(L + K - 1, dtype) if n is None else int(n)
+    if block is not None and n is not None:
+        raise ValueError("fftconv: n is the FFT length of the single-block path, block that of the overlap-save path: not both")
+    taps = None
+    if block is not None:
+        n, taps = int(block), K
+    elif n is None:
+        try:
+            n = fftconv_length(L + K - 1, dtype)
+        except MifftError as e:
+            if e.status != ERR_UNSUPPORTED:
+                raise
+            n, taps = fftconv_block(K, dtype), K
+    else:
+        n = int(n)
+    if taps is not None and K > n - 1:
+        raise MifftError(-2, f"fftconv: a filter of K = {K} taps does not fit overlap-save blocks of {n} points (K <= block - 1)")
     if K > n:
         raise MifftError(-2, f"fftconv: a filter of K = {K} taps does not fit the FFT length n = {n}")
     if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
         raise MifftError(ERR_UNSUPPORTED, f"fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
                                           "n // 2 without a prime factor above 32): see fftconv_length")
-    if L > n:
+    if taps is None and L > n:
         raise MifftError(ERR_UNSUPPORTED, f"fftconv: rows of {L} samples are longer than the FFT length n = {n}")
     offset, out_length = _fftconv_window(mode, L, K)
     rows = 1
@@ -1761,11 +1864,11 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     out = torch.empty((rows, out_length, 1), dtype=dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
         key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-               int(torch.cuda.current_stream(device).cuda_stream))
+               int(torch.cuda.current_stream(device).cuda_stream), taps)
         plan = _PLAN_CACHE.get(key)
         if plan is None:
-            plan = plan_fftconv(dtype, rows // D, D, L, n, offset=offset, out_length=out_length, correlate=correlate,
-                                ctx=DeviceContext(device))
+            plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length,
+                                correlate=correlate, ctx=DeviceContext(device))
             _plan_cache_insert(key, plan)
         else:
             _PLAN_CACHE.move_to_end(key)

@@ -7,15 +7,20 @@
 // the inverse, and the store writes the samples o .. o + Lo - 1.  x is (batch, L, 1) real, out (batch, Lo, 1) real.  The
 // filter spectra are the caller's device buffer, (D, n / 2 + 1) complex values of the plan's float type: the plan keeps the
 // address it was given and nothing else, so the caller may rewrite the contents between execs and must keep the buffer alive.
+//
+// The 12-word payload is overlap-save on the same tile (TileCfg::OLS): signal rows of T samples, T possibly far beyond n, are
+// convolved as F blocks of n samples every S, one launch row each; block f stores the S samples from c on of its circular
+// result, every output sample exactly once.  Still one launch and no scratch: a plan exec covers count * F block rows.
 #include "mifft_config.h"
 #include "mifft_internal.h"
 
 namespace mifft {
 
-// ---- the payload TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI ---------------------------------------------------------
+// ---- the payload TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI, or, overlap-save, ---------------------------------------
+// ---- TAG_LO | TAG_HI | D | c | S | mode | H_LO | H_HI | F | s0 | Lo | 0 ------------------------------------------------------
 bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
     if (ndim != 2 || !bases_flat || !bases_len) return false;
-    return bases_len[0] == 8 && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
+    return (bases_len[0] == 8 || bases_len[0] == 12) && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
 }
 
 int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
@@ -62,7 +67,12 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "convolution at an FFT length of " + std::to_string(n) + ": " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
-    if (L > n) {
+    const bool ols = bases_len[0] == 12;  // (overlap-save: rows of T = L samples in blocks of n)
+    if (ols && (L < 2 || L > (1ll << 30))) {
+        why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save convolution payload: 2 <= T <= 2^30";
+        return L < 2 ? MIFFT_ERR_BAD_DIM : MIFFT_ERR_TOO_LARGE;
+    }
+    if (!ols && L > n) {
         why = "rows of L = " + std::to_string(L) + " samples are longer than the FFT length n = " + std::to_string(n) +
               " (L > n: rfft(x, n) would crop)";
         return MIFFT_ERR_UNSUPPORTED;
@@ -70,7 +80,13 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
     const int64_t D = bases_flat[2], o = bases_flat[3], Lo = bases_flat[4];
     const uint32_t mode = bases_flat[5];
     const uint64_t addr = (uint64_t)bases_flat[6] | ((uint64_t)bases_flat[7] << 32);
-    if (Lo < 1 || o + Lo > n) {
+    if (ols) {  // (words 3 and 4 are c and S; Lo is word 10)
+        if (Lo < 1 || o + Lo > n) {
+            why = "the stored part c = " + std::to_string(o) + ", S = " + std::to_string(Lo) +
+                  " of every block of an overlap-save convolution payload: S >= 1 and c + S <= n = " + std::to_string(n);
+            return MIFFT_ERR_BAD_BASES;
+        }
+    } else if (Lo < 1 || o + Lo > n) {
         why = "the output window o = " + std::to_string(o) + ", Lo = " + std::to_string(Lo) +
               " of a convolution payload: Lo >= 1 and o + Lo <= n = " + std::to_string(n);
         return MIFFT_ERR_BAD_BASES;
@@ -100,6 +116,33 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
               std::to_string(2 * dtype_size(p.out_dtype)) + " bytes)";
         return MIFFT_ERR_BAD_BASES;
     }
+    int64_t F = 1, s0 = 0, S = 0, rowLo = Lo;
+    if (ols) {
+        S = Lo;
+        F = bases_flat[8];
+        s0 = (int32_t)bases_flat[9];
+        rowLo = bases_flat[10];
+        if (F < 1 || rowLo < 1) {
+            why = "F = " + std::to_string(F) + " blocks and Lo = " + std::to_string(rowLo) +
+                  " output samples per row in an overlap-save convolution payload: F >= 1 and Lo >= 1";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (rowLo <= (F - 1) * S || rowLo > F * S) {
+            why = "Lo = " + std::to_string(rowLo) + " output samples per row against F = " + std::to_string(F) + " blocks of S = " +
+                  std::to_string(S) + ": (F - 1) S < Lo <= F S (the last block stores at least one sample)";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (s0 <= -n || s0 + (F - 1) * S >= L) {
+            why = "block start s0 = " + std::to_string(s0) + " with F = " + std::to_string(F) + " blocks every S = " +
+                  std::to_string(S) + " samples: a block reads no sample of its row (-n < s0 and s0 + (F - 1) S < T = " +
+                  std::to_string(L) + ")";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (bases_flat[11] != 0) {
+            why = "the reserved word 11 of an overlap-save convolution payload must be 0, not " + std::to_string(bases_flat[11]);
+            return MIFFT_ERR_BAD_BASES;
+        }
+    }
     if (bases_len[1] < 0) {
         why = "negative bases_len";
         return MIFFT_ERR_NO_BASES;
@@ -108,7 +151,10 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
     for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
     p.conv_D = D;
     p.conv_o = o;
-    p.conv_Lo = Lo;
+    p.conv_Lo = rowLo;
+    p.conv_S = S;
+    p.conv_F = F;
+    p.conv_s0 = s0;
     p.conv_mode = mode;
     p.conv_h = (const void*)(uintptr_t)addr;
     return MIFFT_OK;
@@ -121,7 +167,7 @@ int build_conv(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     ps.dim_index = 1;
     ps.N = n;
     ps.inner = 1;
-    ps.outer = 1;
+    ps.outer = p.conv_F;  // (overlap-save: the block rows of one signal row; else 1)
     ps.radices = ordered;
     ps.processed = processed;
     ps.first = true;

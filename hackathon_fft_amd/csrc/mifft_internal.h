@@ -182,7 +182,7 @@ struct Plan {
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
     int64_t stft_frames() const {
-        if (conv_D) return 1;  // (no frames, no hop: one row per batch entry)
+        if (conv_D) return conv_F;  // (no frames, no hop: one row per batch entry, or the blocks of an overlap-save row)
         if (mdct) return (dims[0] + mdct - 1) / mdct + 1;
         return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop();
     }
@@ -198,7 +198,11 @@ struct Plan {
     // (batch, L, 1) real, out (batch, conv_Lo, 1): the samples conv_o .. conv_o + conv_Lo - 1 of irfft(rfft(x, n) G, n), row r
     // against row r % conv_D of the caller's device buffer conv_h (conv_D rows of n / 2 + 1 complex values; never copied, never
     // freed); conv_mode bit 0: G = conj(H).  conv_D = 0: not one.  Set by conv_check.
+    // The 12-word payload (overlap-save, conv_S > 0): dims = {T, n}, x is (batch, T, 1); every row is conv_F blocks of n
+    // samples, block f from sample conv_s0 + f conv_S on (zeros outside the row), of whose circular result the conv_S samples
+    // from conv_o (= c) on are stored at f conv_S of the row's conv_Lo output samples.  conv_S = 0, conv_F = 1: single block.
     int64_t conv_D = 0, conv_o = 0, conv_Lo = 0;
+    int64_t conv_S = 0, conv_F = 1, conv_s0 = 0;
     uint32_t conv_mode = 0;
     const void* conv_h = nullptr;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
@@ -386,7 +390,7 @@ int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vec
 bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
-// bases_len[0] the tagged length 8 with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
+// bases_len[0] a tagged length (8, or 12: overlap-save) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
 // be refused without a device, leaving the request in plan.conv_* and the user radices of n in `radices`.  build_conv: the
 // one pass.  select_jit_conv_rows is the packed-row kernel with TileCfg::CONV (kernels_jit.cpp; run time only),
 // conv_rows_supported the same check without a device; launch_jit_conv is its launch, which -- unlike a DimPass::launch --

@@ -241,6 +241,13 @@ struct TileParams {
     // rows, spec_wt = the filter spectra, D rows of N + 1 complex values of type T (the caller's buffer), spec_bands = the
     // launch's first row modulo D (row r of the launch takes filter row (spec_bands + r) % D), spec_q bit 0 = correlate
     // (multiply by the conjugate).  scale is 1 / 2N; inverse is 0.
+    // OLS configurations (CONV's overlap-save twin) keep that mapping with stft_len = T samples per signal row (T may exceed
+    // 2N), stft_hop = c (the first sample of every block's circular result that is stored) and stft_frames = Lo (output
+    // samples per signal row), and add the three fields below: launch row r is block r % ols_blocks of signal r / ols_blocks;
+    // block f loads the 2N samples from ols_start + f * ols_step on (zeros outside [0, T)) and stores the samples
+    // c .. c + ols_step - 1 of its result to out[f * ols_step ..] of its signal's row, up to Lo.  spec_bands counts signals,
+    // not launch rows: signal b of the launch takes filter row (spec_bands + b) % D.
+    int ols_step, ols_blocks, ols_start;
 };
 
 // the log stage of a TileCfg::LOG store: fma(a, log2(max(v + add, amin)), c)
@@ -337,7 +344,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
-          bool CONV_ = false>
+          bool CONV_ = false, bool OLS_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -565,6 +572,16 @@ struct TileCfg {
     static_assert(!CONV_ || (R2C_ && !FIRST_DIRECT_ && DCT_ == 0 && !STFT_ && SPEC_ == 0 && NT_ == 0 && same_t<IT_, T_>::value &&
                              R0_ <= 32 && R1_ <= 32),
                   "CONV: packed real rows of the plan's own float type, staged in LDS by the zero-extending load");
+    // OLS (with CONV): overlap-save.  A signal row of T samples is convolved as F blocks of 2N samples, each one launch row
+    // and one CONV tile row: block f loads the samples s0 + f S .. s0 + f S + 2N - 1 of its signal (zeros outside the row,
+    // never loaded; one pair load where both samples lie inside, as aligned as the block's start), and of its circular result
+    // stores the S samples from c on -- those no wrap-around touched, by the caller's choice of c and S -- to out[f S ..] of
+    // the signal's row of Lo samples, the last block up to Lo.  Every output sample is written exactly once by exactly one
+    // block: no overlap-add, no carry between tiles, no scratch.  Tiles may straddle signals: (signal, block) of the tile's
+    // first row is computed once, uniformly, and wrapped per row as the STFT load wraps its frames.  The filter row follows
+    // the signal, not the launch row.  The passes, the product and the fold are CONV's.
+    static constexpr bool OLS = OLS_;
+    static_assert(!OLS_ || CONV_, "OLS: the overlap-save twin of a CONV tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -1929,6 +1946,32 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     lds[lds_index<C, -1>(c, C::N - 1 - m)] = {w1.x * b.x - w1.y * a.y, w1.x * a.y + w1.y * b.x};
             }
             __syncthreads();
+        } else if constexpr (C::OLS) {
+            // (signal, block) of the tile's first row once, uniform; a row further on wraps into the signals that follow.
+            // Packed element m of block fr: the samples st + 2 m and st + 2 m + 1 of its signal, st = s0 + fr S
+            const int F = p.ols_blocks, S = p.ols_step, len = p.stft_len;
+            const long long r0 = base / C::N, b0 = r0 / F;
+            const int fr0 = (int)(r0 - b0 * F);
+            const T* x0 = (const T*)p.in + b0 * len;
+            for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                const int c = f / C::N, m = f - c * C::N;
+                int fr = fr0 + c, db = 0;
+                if (fr >= F) {
+                    db = fr / F;
+                    fr -= db * F;
+                }
+                const T* xe = x0 + (long long)db * len;
+                const int i = p.ols_start + fr * S + 2 * m;  // (-2N < s0 + fr S < T <= 2^30: 32 bits hold it)
+                V x = {(T)0, (T)0};
+                if (i >= 0 && i + 1 < len) {
+                    x = gload_pair(xe + i);
+                } else {  // (zeros beyond the ends: no load at all)
+                    if (i >= 0 && i < len) x.x = xe[i];
+                    if (i + 1 >= 0 && i + 1 < len) x.y = xe[i + 1];
+                }
+                lds[lds_index<C, -1>(c, m)] = x;
+            }
+            __syncthreads();
         } else if constexpr (C::CONV) {
             // packed element m of row c: the reals 2 m and 2 m + 1 of a row of L samples, zeros from sample L on
             const int L = p.stft_len;
@@ -2132,7 +2175,11 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS, G = IT < 4 ? IT : 4;
             const long long row0 = base / C::N;
             const unsigned D = (unsigned)p.stft_center;
-            const unsigned d0 = (unsigned)(((long long)p.spec_bands + row0) % (long long)D);  // (uniform; d0 + c < 2^31)
+            // OLS: the filter row follows the signal row0 / F, and row c of the tile lies (ofr0 + c) / F signals further on
+            const unsigned OF = C::OLS ? (unsigned)p.ols_blocks : 1u;
+            const long long sig0 = C::OLS ? row0 / (long long)OF : row0;
+            const unsigned ofr0 = C::OLS ? (unsigned)(row0 - sig0 * (long long)OF) : 0u;
+            const unsigned d0 = (unsigned)(((long long)p.spec_bands + sig0) % (long long)D);  // (uniform; d0 + c < 2^31)
             const V* hs = (const V*)p.spec_wt;
             const T cj = (p.spec_q & 1) ? (T)-1 : (T)1;
 #pragma unroll 1
@@ -2143,7 +2190,8 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     const int f = tid + (i0 + j) * C::THREADS;
                     if ((IT % G == 0 || i0 + j < IT) && f < nv * PAIRS) {
                         const int c = f / PAIRS, k = f - c * PAIRS;
-                        const V* hr = hs + (long long)((d0 + (unsigned)c) % D) * (C::N + 1);
+                        const unsigned dc = C::OLS ? (ofr0 + (unsigned)c) / OF : (unsigned)c;
+                        const V* hr = hs + (long long)((d0 + dc) % D) * (C::N + 1);
                         ga[j] = hr[k];
                         gb[j] = hr[C::N - k];  // (k = 0: bin N, the last of the row)
                     }
@@ -2181,18 +2229,45 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             // imaginary part.  Samples o .. o + Lo - 1 go to a row of Lo reals.
             const int o = p.stft_hop, Lo = p.stft_frames;
             const T s = (T)p.scale;
-            T* out0 = (T*)p.out + row0 * Lo;
-            for (int f = tid; f < nv * C::N; f += C::THREADS) {
-                const int c = f / C::N, j = f - c * C::N, t = 2 * j - o;
-                if (t + 1 < 0 || t >= Lo) continue;
-                const V v = lds[lds_index<C, C::NP - 1>(c, j)];
-                const T y0 = v.x * s, y1 = -(v.y * s);
-                T* q = out0 + (long long)c * Lo + t;
-                if (t >= 0 && t + 1 < Lo && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
-                    gstore<false>((V*)q, V{y0, y1});
-                } else {
-                    if (t >= 0) q[0] = y0;
-                    if (t + 1 < Lo) q[1] = y1;
+            if constexpr (C::OLS) {
+                // sample i of block fr goes to out[b Lo + fr S + i - c] for c <= i < c + S and fr S + i - c < Lo only
+                const int F = p.ols_blocks, S = p.ols_step;
+                T* out0 = (T*)p.out + sig0 * Lo;
+                for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                    const int c = f / C::N, j = f - c * C::N, u = 2 * j - o;
+                    if (u + 1 < 0 || u >= S) continue;
+                    int fr = (int)ofr0 + c, db = 0;
+                    if (fr >= F) {
+                        db = fr / F;
+                        fr -= db * F;
+                    }
+                    const int t = fr * S + u;  // (< Lo + 2N: 32 bits hold it)
+                    const bool w0 = u >= 0 && t < Lo, w1 = u + 1 < S && t + 1 < Lo;
+                    if (!w0 && !w1) continue;
+                    const V v = lds[lds_index<C, C::NP - 1>(c, j)];
+                    const T y0 = v.x * s, y1 = -(v.y * s);
+                    T* q = out0 + (long long)db * Lo + t;
+                    if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                        gstore<false>((V*)q, V{y0, y1});
+                    } else {
+                        if (w0) q[0] = y0;
+                        if (w1) q[1] = y1;
+                    }
+                }
+            } else {
+                T* out0 = (T*)p.out + row0 * Lo;
+                for (int f = tid; f < nv * C::N; f += C::THREADS) {
+                    const int c = f / C::N, j = f - c * C::N, t = 2 * j - o;
+                    if (t + 1 < 0 || t >= Lo) continue;
+                    const V v = lds[lds_index<C, C::NP - 1>(c, j)];
+                    const T y0 = v.x * s, y1 = -(v.y * s);
+                    T* q = out0 + (long long)c * Lo + t;
+                    if (t >= 0 && t + 1 < Lo && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                        gstore<false>((V*)q, V{y0, y1});
+                    } else {
+                        if (t >= 0) q[0] = y0;
+                        if (t + 1 < Lo) q[1] = y1;
+                    }
                 }
             }
             __syncthreads();

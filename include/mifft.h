@@ -509,7 +509,40 @@ typedef enum {
  * MIFFT_FLAG_DCT_ND, MIFFT_FLAG_DCT_ORTHO or a keep bit; MIFFT_JIT=0.  MIFFT_ERR_BAD_BASES: Lo < 1 or o + Lo > n; D < 1; a
  * mode word with a bit other than bit 0; a null H address or one not aligned to one complex element (or radices that do not
  * multiply to n).  MIFFT_ERR_BAD_BATCH: batch not a multiple of D.  MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.
- * MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: D > 2^30. */
+ * MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: D > 2^30.
+ *
+ * Overlap-save: the same tag in front of exactly 12 words convolves signal rows of ANY length T (dims = {T, n}; T may exceed
+ * n) as F blocks of n samples per row, still in ONE launch with no scratch: x (batch, T, 1) -> out (batch, Lo, 1).
+ *     word  0, 1   MIFFT_CONV_TAG_LO, MIFFT_CONV_TAG_HI
+ *     word  2      D, the filter rows; signal row r takes filter row r % D
+ *     word  3      c, the first sample of every block's circular result that is stored
+ *     word  4      S, the samples stored per block, which is also the step between blocks
+ *     word  5      mode; bit 0 = correlate (multiply by the conjugate), every other bit 0
+ *     word  6, 7   H_LO, H_HI: the device address of the filter spectra, D rows of n / 2 + 1 complex values, as above
+ *     word  8      F, the blocks per signal row
+ *     word  9      s0 as a two's-complement int32: the index in x of block 0's first sample; it may be negative
+ *     word 10      Lo, the output samples per signal row
+ *     word 11      reserved, 0
+ * For signal row r and block f < F:
+ *     blk[i] = x[r][s0 + f S + i], 0 <= i < n, zeros outside [0, T) (never loaded);
+ *     y = irfft( rfft(blk) * G[r % D], n );
+ *     out[r][f S + j] = y[c + j]   for 0 <= j < S and f S + j < Lo.
+ * Every output sample is written exactly once, by exactly one block; nothing is added, carried between blocks or zeroed
+ * first.  THE CALLER'S CONTRACT: the library does not know the filter length K.  That the stored samples are free of the
+ * circular wrap-around -- c >= K - 1 and S <= n - c for a convolution; c = 0 and S <= n - K + 1 for a correlation -- is the
+ * caller's business: a payload that breaks it is run as written and returns wrapped samples.  The full linear convolution
+ * from sample `a` on is c = K - 1, S = n - K + 1, s0 = a - c, F = ceil(Lo / S) (mf.plan_fftconv(taps=K) derives exactly these).
+ * The kernel is the CONV tile with TileCfg::OLS (rows<n>[_f64]_r2c_<radices>_conv_ols_jit, run time only): launch row
+ * first * F + i is block i % F of signal i / F, its load starts S samples after the block before it (one pair load where both
+ * samples lie inside the row, as aligned as x + s0 + f S happens to be), and its store keeps the S samples from c on.
+ * mifft_exec_batch's first / count stay in units of SIGNAL rows: x is offset by first * T, out by first * Lo reals, the launch
+ * covers count * F block rows (mifft_plan_pass_geometry counts those), and signal row first + i takes filter row
+ * (first + i) % D.  A sample's result depends on its own block alone: bit-identical for any batch, first / count and grid.
+ * The 8-word payload means exactly what it meant (L > n and mode = 2 are refused there as before).
+ * Refused before any device work: everything above that still applies (flags, inverse, components, dtypes, the limits of n,
+ * D, batch % D, mode, H); MIFFT_ERR_BAD_BASES: S < 1 or c + S > n; F < 1 or Lo < 1; Lo outside ((F - 1) S, F S]; s0 <= -n or
+ * s0 + (F - 1) S >= T (a block that reads no sample of its row); word 11 non-zero.  MIFFT_ERR_TOO_LARGE: T > 2^30
+ * (MIFFT_ERR_BAD_DIM: T < 2). */
 #define MIFFT_CONV_TAG_LO 0x4F4E5601u
 #define MIFFT_CONV_TAG_HI 0x7FF84D43u
 

@@ -186,6 +186,9 @@ constexpr uint32_t kDctType4Tag = MIFFT_DCT_TYPE4_TAG;
 constexpr uint32_t kDstTag = MIFFT_DST_TAG;
 constexpr uint32_t kDstType4Tag = MIFFT_DST_TYPE4_TAG;
 constexpr uint64_t kMdctTag = ((uint64_t)MIFFT_MDCT_TAG_HI << 32) | MIFFT_MDCT_TAG_LO;
+// (In front of 12 words -- TAG | D | c | S | mode | H | F | s0 | Lo | 0 -- it is the overlap-save form for rows of any length T:
+// F blocks of n samples every S per row, of which the S samples from c on are stored; that c and S keep the stored samples free
+// of wrap-around, c >= K - 1 and c + S <= n for K taps, is the caller's contract.  mifft.h has the table.)
 // MIFFT_CONV_TAG as the FIRST two words of the 8-word payload of a plain MIFFT_FLAG_STFT plan with dims = {L, n}: the fused FFT
 // convolution of real rows, x (batch, L, 1) -> out (batch, Lo, 1), against the caller's device buffer of filter spectra
 // (TAG | D | o | Lo | mode | address; include/mifft.h).  Created through mifft_plan_create itself.
