@@ -56,7 +56,14 @@ MDCT_TAG_LO = 0x43544401       # MIFFT_MDCT_TAG_LO / _HI: the NaN behind the win
 MDCT_TAG_HI = 0x7FF84D44
 CONV_TAG_LO = 0x4F4E5601       # MIFFT_CONV_TAG_LO / _HI: the NaN in front of the 8-word payload of a FLAG_STFT plan that is a
 CONV_TAG_HI = 0x7FF84D43       # fused FFT convolution (TAG | D | o | Lo | mode | the device address of the filter spectra)
+GATED_ARGS_MAGIC = 0x314147544646494D  # MIFFT_GATED_ARGS_MAGIC ("MIFFTGA1")
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
+
+
+class GatedArgs(ctypes.Structure):
+    """mifft_gated_args: what the exec of a gated convolution plan takes, by host address, in the place of x"""
+    _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("pregate", ctypes.c_void_p),
+                ("postgate", ctypes.c_void_p)]
 
 
 def FLAG_KEEP_DIM(d: int) -> int:
@@ -511,14 +518,16 @@ class Plan:
     include/mifft.h, plan_fftconv).  ``bases`` has two lists, an empty one and the radices of n (or an empty one).
     Nine values, (n, D, c, S, mode, address, F, s0, Lo), are the overlap-save form (the 12-word payload): x (batch, T, 1) with
     T possibly beyond n, F blocks of n samples per row, block f from sample s0 + f S on, of whose circular result the S
-    samples from c on are stored at f S of the row's Lo output samples."""
+    samples from c on are stored at f S of the row's Lo output samples.
+    ``conv_gates`` = 1, 2 or 3 beside either form: the 16-word payload, bit 0 a pregate of x's shape multiplied into the load,
+    bit 1 a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run)."""
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0, dst: bool = False, conv=None):
+                 imdct_gain: float = 1.0, dst: bool = False, conv=None, conv_gates: int = 0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct = int(mdct), int(imdct)
         if dct_type not in (2, 4):
@@ -625,6 +634,10 @@ class Plan:
                 if not -(1 << 31) <= start < 1 << 31:
                     raise MifftError(-5, f"s0 = {start} of a convolution plan does not fit a signed 32-bit word")
                 words += [blocks, start & 0xFFFFFFFF, Lo, 0]
+            if conv_gates:  # (the 16-word payload: word 8 is F, 0 for the single block; word 11 the gates)
+                if conv_gates not in (1, 2, 3):
+                    raise MifftError(-5, f"conv_gates = {conv_gates}: bit 0 the pregate, bit 1 the postgate (1, 2 or 3)")
+                words = (words + [0, 0, 0])[:11] + [int(conv_gates), 0, 0, 0, 0]
             flags = (int(flags) | FLAG_STFT | (FLAG_ISTFT if istft else 0) | (FLAG_DCT_ND if dctn else 0) |
                      (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
                      (FLAG_STFT_POWER if stft_power is not None else 0))
@@ -683,6 +696,7 @@ class Plan:
         self.mdct = mdct
         self.imdct = imdct
         self.conv = None if conv is None else tuple(int(v) for v in conv)
+        self.conv_gates = int(conv_gates) if conv is not None else 0
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
@@ -994,6 +1008,9 @@ def fft(output: "torch.Tensor", x: "torch.Tensor", ctx: Optional[DeviceContext] 
     batch range) is written.  ``first``/``count`` select a slab of the leading dimension
     (used by the batch-sharded multi-GPU host); default is the whole batch.
     """
+    if getattr(plan, "conv_gates", 0):
+        raise MifftError(ERR_UNSUPPORTED, "a gated convolution plan takes its gates with every exec: "
+                                          "plan.run(out, x, pregate=, postgate=) instead of fft(out, x, plan=plan)")
     if ctx is None:
         ctx = DeviceContext(plan.device)
     _check_tensor(x, plan.in_shape, plan.in_dtype, plan.device, "x")
@@ -1685,13 +1702,17 @@ class ConvPlan(Plan):
     ``filter_spectrum`` is (channels, n // 2 + 1, 2) of the plan's dtype, zero-filled at first; its address is bound into
     the plan and never changes, its contents may be rewritten between execs in stream order.
     An overlap-save plan (``plan_fftconv(taps=K)``) has ``taps`` = K, ``step`` = n - K + 1 samples stored per block and
-    ``blocks`` per row; a single-block plan has ``taps`` and ``step`` None and one block."""
+    ``blocks`` per row; a single-block plan has ``taps`` and ``step`` None and one block.
+    A gated plan (``plan_fftconv(pregate=True)`` and / or ``postgate=True``) has ``pregate`` / ``postgate`` True and runs
+    through ``run``, which takes the gate tensors of that exec; ``fft(out, x, plan=plan)`` refuses it."""
 
-    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None):
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, pregate=False,
+                 postgate=False):
         self.ctx = ctx
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         self.taps, self.step, self.blocks = taps, None, 1
+        self.pregate, self.postgate = bool(pregate), bool(postgate)
         with torch.cuda.stream(ctx.stream):
             self.filter_spectrum = torch.zeros((channels, n // 2 + 1, 2), dtype=dtype, device=f"cuda:{ctx.device}")
         mode, addr = 1 if correlate else 0, self.filter_spectrum.data_ptr()
@@ -1701,7 +1722,34 @@ class ConvPlan(Plan):
             c, self.step, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
             conv = (n, channels, c, self.step, mode, addr, self.blocks, s0, out_length)
         super().__init__(dtype, dtype, (batch * channels, length, 1), (batch * channels, out_length, 1), device=ctx.device,
-                         conv=conv)
+                         conv=conv, conv_gates=(1 if self.pregate else 0) | (2 if self.postgate else 0))
+
+    def run(self, out: "torch.Tensor", x: "torch.Tensor", *, pregate: Optional["torch.Tensor"] = None,
+            postgate: Optional["torch.Tensor"] = None, first: Optional[int] = None, count: Optional[int] = None) -> None:
+        """The exec of a gated plan, enqueued on the plan's stream: ``out[r] = postgate[r] * conv(pregate[r] * x[r])`` for the
+        signal rows ``first`` .. ``first + count - 1`` (default: all).  ``pregate`` has ``in_shape``, ``postgate`` ``out_shape``,
+        both of the plan's dtype, contiguous, on its device; each is given exactly where the plan has it.  All four tensors
+        are the WHOLE batch's: the library offsets them by ``first`` rows.  A gate may alias ``x``, not ``out``; none is written."""
+        if not self.conv_gates:
+            raise MifftError(ERR_UNSUPPORTED, "run() is the exec of a gated plan (plan_fftconv(pregate=True) / postgate=True); "
+                                              "this plan runs through fft(out, x, plan=plan)")
+        for t, want, what in ((pregate, self.pregate, "pregate"), (postgate, self.postgate, "postgate")):
+            if want and t is None:
+                raise MifftError(-12, f"the plan has a {what}: run(..., {what}=) is missing")
+            if not want and t is not None:
+                raise MifftError(ERR_UNSUPPORTED, f"the plan has no {what}: plan_fftconv(..., {what}=True) makes one that has")
+        _check_tensor(x, self.in_shape, self.in_dtype, self.device, "x")
+        _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
+        if pregate is not None:
+            _check_tensor(pregate, self.in_shape, self.in_dtype, self.device, "pregate")
+        if postgate is not None:
+            _check_tensor(postgate, self.out_shape, self.out_dtype, self.device, "postgate")
+        first = 0 if first is None else int(first)
+        count = self.out_shape[0] - first if count is None else int(count)
+        args = GatedArgs(GATED_ARGS_MAGIC, x.data_ptr(), pregate.data_ptr() if pregate is not None else None,
+                         postgate.data_ptr() if postgate is not None else None)
+        check(_lib.lib().mifft_exec_batch(self._h, ctypes.addressof(args), out.data_ptr(), first, count,
+                                          self.ctx.stream.cuda_stream))
 
     def set_filter(self, k: "torch.Tensor") -> None:
         """``k`` real, (channels, K) or (K,) (one filter for every channel), K <= n: writes rfft(k, n) into
@@ -1721,6 +1769,17 @@ class ConvPlan(Plan):
             kp[:, :K] = k.to(device=kp.device, dtype=self.out_dtype)
             H = rfftn(kp, onesided=True)
             self.filter_spectrum.copy_(torch.view_as_real(H))
+
+    def add_skip(self, d) -> None:
+        """adds the skip term ``d`` -- a float, or a real (channels,) tensor -- to every bin of ``filter_spectrum``, on the
+        plan's stream: conv(x, h) + d x = conv(x, h') with h'[0] = h[0] + d, whose spectrum is H + d (d is real, so the same
+        holds for the conjugate a correlation multiplies by).  Call it after ``set_filter``, which overwrites the spectrum."""
+        with torch.cuda.stream(self.ctx.stream):
+            if isinstance(d, torch.Tensor):
+                if d.is_complex() or tuple(d.shape) != (self.channels,):
+                    raise MifftError(-2, f"add_skip expects a float or a real ({self.channels},) tensor, got {tuple(d.shape)} {d.dtype}")
+                d = d.to(device=self.filter_spectrum.device, dtype=self.out_dtype).reshape(self.channels, 1)
+            self.filter_spectrum[:, :, 0] += d
 
     def set_filter_spectrum(self, Hc: "torch.Tensor") -> None:
         """copies a spectrum the caller already holds -- complex (channels, n // 2 + 1) or interleaved (.., 2), the
@@ -1742,7 +1801,8 @@ def _fftconv_ols_geometry(n: int, K: int, offset: int, out_length: int, correlat
 
 
 def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
-                 out_length: Optional[int] = None, correlate: bool = False, ctx: Optional[DeviceContext] = None) -> ConvPlan:
+                 out_length: Optional[int] = None, correlate: bool = False, ctx: Optional[DeviceContext] = None,
+                 pregate: bool = False, postgate: bool = False) -> ConvPlan:
     """Plan of the fused FFT convolution (no reference counterpart; MIFFT_CONV_TAG in include/mifft.h) of ``batch * channels``
     real rows of ``length`` samples, row-major (batch, channels, length), at the FFT length ``n`` (see fftconv_length):
     ``y[r] = irfft(rfft(x[r], n) * G[r % channels], n)[offset : offset + out_length]`` in ONE kernel launch, G the plan's
@@ -1753,7 +1813,11 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     ``taps=K`` makes it an overlap-save plan at the block length ``n``, still one launch: filters of up to K taps,
     1 <= K <= n - 1, on rows of any ``length`` >= 2; every block of n samples stores its n - K + 1 samples that no wrap-around
     touched.  ``offset`` / ``out_length`` are then coordinates in the full linear convolution of length + K - 1 samples
-    (``correlate``: in y[t] = sum_j k[j] x[t + j], t < length), wholly inside it."""
+    (``correlate``: in y[t] = sum_j k[j] x[t + j], t < length), wholly inside it.
+    ``pregate`` / ``postgate`` = True make it a gated plan (the 16-word payload), of either kind:
+    ``y[r] = b[r] * conv(a[r] * x[r])`` with a tensor ``a`` of ``in_shape`` and / or ``b`` of ``out_shape`` given with every
+    exec, multiplied into the kernel's load and store -- still one launch, no intermediate.  Such a plan runs through
+    ``plan.run(out, x, pregate=a, postgate=b)``.  A skip term d * (a * x) is d added to every bin of ``filter_spectrum``."""
     batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
     out_length = length if out_length is None else int(out_length)
     if dtype not in _OUT_DTYPES:
@@ -1776,7 +1840,8 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
                                  f"{length} samples with {taps} taps)")
         if ctx is None:
             ctx = DeviceContext()
-        return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps)
+        return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, pregate=pregate,
+                        postgate=postgate)
     if length < 2 or length > n:
         raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples at n = {n}: 2 <= length <= n")
     if offset < 0 or out_length < 1 or offset + out_length > n:
@@ -1784,7 +1849,7 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
                              f"offset + out_length <= n = {n}")
     if ctx is None:
         ctx = DeviceContext()
-    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx)
+    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, pregate=pregate, postgate=postgate)
 
 
 def _fftconv_window(mode: str, L: int, K: int) -> tuple:
@@ -1799,7 +1864,8 @@ def _fftconv_window(mode: str, L: int, K: int) -> tuple:
 
 
 def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mode: str = "causal",
-            correlate: bool = False, block: Optional[int] = None) -> "torch.Tensor":
+            correlate: bool = False, block: Optional[int] = None, pregate: Optional["torch.Tensor"] = None,
+            postgate: Optional["torch.Tensor"] = None, skip=None) -> "torch.Tensor":
     """Convolution by FFT along the last dim of a real ``x`` of shape (..., D, L) with ``k`` of shape (D, K), one filter per
     channel, or of shape (..., L) with a 1-D ``k``: one kernel launch per call (plus the transform of the filter).
     ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one gives the circular result.
@@ -1810,7 +1876,12 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     filter should use ``plan_fftconv``.
     Rows too long for one FFT (L + K - 1 beyond fftconv_length's last length) run as overlap-save blocks of
     fftconv_block(K) points, in the same single launch; ``block=`` forces that path at the given FFT length for any L (it
-    excludes ``n``), K <= block - 1."""
+    excludes ``n``), K <= block - 1.
+    ``pregate`` / ``postgate`` / ``skip`` make it the gated filter stage of Hyena / H3 / S4 models in the same launch:
+    ``postgate * (conv(pregate * x, k) + skip * (pregate * x))``.  ``pregate`` has exactly ``x``'s shape, ``postgate`` exactly
+    the result's (ValueError otherwise: nothing is broadcast, a gate broadcast and then copied would cost what the fusion
+    saves); both live on ``x``'s device and are converted to the working dtype as ``x`` is.  ``skip`` is a float or a real (D,)
+    tensor, one value per channel, added to every bin of the filter spectrum (the term costs no kernel work)."""
     if x.is_complex() or k.is_complex():
         raise MifftError(-3, "fftconv expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -1857,23 +1928,48 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         rows *= m
     if rows < 1:
         raise MifftError(-8, f"fftconv: no rows in {logical}")
+    for g, shape, what, of in ((pregate, logical, "pregate", "x"), (postgate, logical[:-1] + (out_length,), "postgate", "the result")):
+        if g is None:
+            continue
+        if g.is_complex():
+            raise MifftError(-3, f"fftconv: {what} must be real")
+        if tuple(g.shape) != shape:
+            raise ValueError(f"fftconv: {what} is {tuple(g.shape)}, {of} is {shape}: a gate has exactly that shape (nothing is "
+                             "broadcast: a gate broadcast and then copied would cost what the fusion saves)")
+        if g.device != x.device:
+            raise MifftError(-10, f"fftconv: {what} lives on {g.device}, x on {x.device}")
+    if skip is not None:
+        if isinstance(skip, torch.Tensor):
+            if skip.is_complex() or tuple(skip.shape) != (D,):
+                raise ValueError(f"fftconv: skip is a float or a real tensor of shape ({D},), one value per channel, got "
+                                 f"{tuple(skip.shape)} {skip.dtype}")
+        else:
+            skip = float(skip)
     device = DeviceContext(x.device.index if x.is_cuda else None).device
     if not x.is_cuda or x.device.index != device:
         raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
     xr = x.to(dtype).contiguous().reshape(rows, L, 1)
     out = torch.empty((rows, out_length, 1), dtype=dtype, device=xr.device)
+    gates = (1 if pregate is not None else 0) | (2 if postgate is not None else 0)
     with _PLAN_CACHE_LOCK:
         key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-               int(torch.cuda.current_stream(device).cuda_stream), taps)
+               int(torch.cuda.current_stream(device).cuda_stream), taps, gates)
         plan = _PLAN_CACHE.get(key)
         if plan is None:
             plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length,
-                                correlate=correlate, ctx=DeviceContext(device))
+                                correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2))
             _plan_cache_insert(key, plan)
         else:
             _PLAN_CACHE.move_to_end(key)
         plan.set_filter(k)
-        fft(out, xr, DeviceContext(device), plan=plan)
+        if skip is not None:
+            plan.add_skip(skip)
+        if gates:
+            a = pregate.to(dtype).contiguous().reshape(rows, L, 1) if pregate is not None else None
+            b = postgate.to(dtype).contiguous().reshape(rows, out_length, 1) if postgate is not None else None
+            plan.run(out, xr, pregate=a, postgate=b)
+        else:
+            fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical[:-1] + (out_length,))
 
 

@@ -11,16 +11,21 @@
 // The 12-word payload is overlap-save on the same tile (TileCfg::OLS): signal rows of T samples, T possibly far beyond n, are
 // convolved as F blocks of n samples every S, one launch row each; block f stores the S samples from c on of its circular
 // result, every output sample exactly once.  Still one launch and no scratch: a plan exec covers count * F block rows.
+//
+// The 16-word payload is either of the two with elementwise gates fused into the tile's load and store (TileCfg::GATE):
+// y = b . conv(a . x), a of x's shape, b of out's.  The plan knows only WHICH gates there are; the tensors are arguments of
+// every exec (mifft_gated_args through mifft_exec_batch: mifft_api.cpp).
 #include "mifft_config.h"
 #include "mifft_internal.h"
 
 namespace mifft {
 
 // ---- the payload TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI, or, overlap-save, ---------------------------------------
-// ---- TAG_LO | TAG_HI | D | c | S | mode | H_LO | H_HI | F | s0 | Lo | 0 ------------------------------------------------------
+// ---- TAG_LO | TAG_HI | D | c | S | mode | H_LO | H_HI | F | s0 | Lo | 0, or, gated, ------------------------------------------
+// ---- the eight words | F (0: single block) | s0 | Lo | gates | 0 | 0 | 0 | 0 ------------------------------------------------
 bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
     if (ndim != 2 || !bases_flat || !bases_len) return false;
-    return (bases_len[0] == 8 || bases_len[0] == 12) && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
+    return (bases_len[0] == 8 || bases_len[0] == 12 || bases_len[0] == 16) && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
 }
 
 int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
@@ -67,7 +72,8 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "convolution at an FFT length of " + std::to_string(n) + ": " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
-    const bool ols = bases_len[0] == 12;  // (overlap-save: rows of T = L samples in blocks of n)
+    const bool gated = bases_len[0] == 16;  // (word 8 says which of the two forms it is: F = 0 the single block)
+    const bool ols = bases_len[0] == 12 || (gated && bases_flat[8] != 0);  // (overlap-save: rows of T = L samples in blocks of n)
     if (ols && (L < 2 || L > (1ll << 30))) {
         why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save convolution payload: 2 <= T <= 2^30";
         return L < 2 ? MIFFT_ERR_BAD_DIM : MIFFT_ERR_TOO_LARGE;
@@ -138,10 +144,28 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
                   std::to_string(L) + ")";
             return MIFFT_ERR_BAD_BASES;
         }
-        if (bases_flat[11] != 0) {
+        if (!gated && bases_flat[11] != 0) {
             why = "the reserved word 11 of an overlap-save convolution payload must be 0, not " + std::to_string(bases_flat[11]);
             return MIFFT_ERR_BAD_BASES;
         }
+    }
+    if (gated) {
+        if (!ols && (bases_flat[9] != 0 || bases_flat[10] != 0)) {
+            why = "words 9 and 10 (s0 = " + std::to_string(bases_flat[9]) + ", Lo = " + std::to_string(bases_flat[10]) +
+                  ") of a gated convolution payload with F = 0 (a single block: o and Lo are words 3 and 4) must be 0";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (bases_flat[11] < 1 || bases_flat[11] > 3) {
+            why = "the gates word 11 of a gated convolution payload has bit 0 (pregate) and bit 1 (postgate), at least one of them, not " +
+                  std::to_string(bases_flat[11]);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        for (int w = 12; w < 16; ++w)
+            if (bases_flat[w] != 0) {
+                why = "the reserved word " + std::to_string(w) + " of a gated convolution payload must be 0, not " +
+                      std::to_string(bases_flat[w]);
+                return MIFFT_ERR_BAD_BASES;
+            }
     }
     if (bases_len[1] < 0) {
         why = "negative bases_len";
@@ -156,6 +180,7 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
     p.conv_F = F;
     p.conv_s0 = s0;
     p.conv_mode = mode;
+    p.conv_gates = gated ? bases_flat[11] : 0u;
     p.conv_h = (const void*)(uintptr_t)addr;
     return MIFFT_OK;
 }

@@ -106,6 +106,33 @@ struct DeviceGuard {
     }
 };
 
+// The exec of a gated convolution plan (conv.cpp; Plan::conv_gates): the `x` of mifft_exec / mifft_exec_batch is the HOST
+// address of a mifft_gated_args, which names x and the gates of this exec.  Refused without a launch: a device address (the
+// signal itself, as an ungated plan takes it) or a block without the magic word, MIFFT_ERR_UNSUPPORTED; a gate the plan has
+// and the block lacks, MIFFT_ERR_NULL; a gate the plan did not ask for, MIFFT_ERR_UNSUPPORTED.  On success `x` is the signal.
+static int unpack_gated_args(const Plan& p, const void*& x, const void*& pregate, const void*& postgate) {
+    static const char* kHow =
+        "the exec of a gated convolution plan takes the host address of a mifft_gated_args (magic, x, pregate, postgate) in "
+        "the place of x: include/mifft.h";
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, x) != hipSuccess)
+        (void)hipGetLastError();  // (memory the runtime has never seen: host memory)
+    else if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray)
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("x is a device address: ") + kHow);
+    const mifft_gated_args* g = (const mifft_gated_args*)x;
+    if (g->magic != MIFFT_GATED_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + kHow);
+    if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_gated_args.x is NULL");
+    const bool want_a = p.conv_gates & 1u, want_b = p.conv_gates & 2u;
+    if (want_a && !g->pregate) return set_error(MIFFT_ERR_NULL, "the plan has a pregate (gates bit 0): mifft_gated_args.pregate is NULL");
+    if (want_b && !g->postgate) return set_error(MIFFT_ERR_NULL, "the plan has a postgate (gates bit 1): mifft_gated_args.postgate is NULL");
+    if (!want_a && g->pregate) return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_gated_args.pregate is set, but the plan has no pregate (gates bit 0)");
+    if (!want_b && g->postgate) return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_gated_args.postgate is set, but the plan has no postgate (gates bit 1)");
+    x = g->x;
+    pregate = g->pregate;
+    postgate = g->postgate;
+    return MIFFT_OK;
+}
+
 static int device_count_quiet() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {
@@ -438,18 +465,30 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
         return set_error(MIFFT_ERR_BAD_BATCH, "batch range out of bounds");
     if (count == 0) return MIFFT_OK;
     if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
+    const void *pregate = nullptr, *postgate = nullptr;
+    if (p.conv_gates) {  // (a gated convolution: `x` is the HOST address of the exec's mifft_gated_args)
+        const int rc = unpack_gated_args(p, x, pregate, postgate);  // (x: now the signal itself)
+        if (rc) return rc;
+    }
     const size_t in_row = p.in_row_bytes(), out_row = p.out_row_bytes();
     const char* xb = (const char*)x + (size_t)first * in_row;
     char* ob = (char*)out + (size_t)first * out_row;
     // out-of-place contract (reference: first stage reads x, all writes go elsewhere)
     if (xb < ob + (size_t)count * out_row && ob < xb + (size_t)count * in_row)
         return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
+    // (the gates of the exec's rows: the pregate is offset like x, the postgate like out; either may alias x, neither out)
+    const char* ab = pregate ? (const char*)pregate + (size_t)first * in_row : nullptr;
+    const char* bb = postgate ? (const char*)postgate + (size_t)first * out_row : nullptr;
+    if (ab && ab < ob + (size_t)count * out_row && ob < ab + (size_t)count * in_row)
+        return set_error(MIFFT_ERR_ALIAS, "the pregate and out must not overlap");
+    if (bb && bb < ob + (size_t)count * out_row && ob < bb + (size_t)count * out_row)
+        return set_error(MIFFT_ERR_ALIAS, "the postgate and out must not overlap");
     DeviceGuard guard(p.device);
     MIFFT_HIP_TRY(guard.err);
     hipStream_t s = (hipStream_t)stream;
     char* sb = p.d_scratch ? (char*)p.d_scratch + (size_t)first * p.scratch_row_bytes() : nullptr;
     auto buf = [&](int which) -> char* { return which == 0 ? (char*)xb : which == 2 ? sb : ob; };
-    if (p.conv_D) return launch_jit_conv(p, p.passes[0], xb, ob, first, count, s);  // (the filter row of row i: (first + i) % D)
+    if (p.conv_D) return launch_jit_conv(p, p.passes[0], xb, ob, ab, bb, first, count, s);  // (the filter row of row i: (first + i) % D)
     for (const DimPass& ps : p.passes) {
         const void* src = ps.src_buf >= 0 ? buf(ps.src_buf) : (ps.first ? (const char*)xb : ob);
         void* dst = ps.dst_buf >= 0 ? buf(ps.dst_buf) : ob;

@@ -205,6 +205,10 @@ struct Plan {
     int64_t conv_S = 0, conv_F = 1, conv_s0 = 0;
     uint32_t conv_mode = 0;
     const void* conv_h = nullptr;
+    // The 16-word payload (gated): conv_gates bit 0 the pregate (a tensor of x's shape that multiplies x as it is loaded), bit 1
+    // the postgate (one of out's shape that multiplies the result as it is stored); the tensors are arguments of every exec
+    // (mifft_gated_args), never plan state.  Its word 8 is F: 0 the single block (conv_S = 0), >= 1 overlap-save.  0: ungated.
+    uint32_t conv_gates = 0;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
     bool dct4 = false;
     // a MIFFT_FLAG_DCT / MIFFT_FLAG_DCT_ND plan whose `bases` start with MIFFT_DST_TAG (DST-II and its inverse, along every
@@ -390,18 +394,19 @@ int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vec
 bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
-// bases_len[0] a tagged length (8, or 12: overlap-save) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
+// bases_len[0] a tagged length (8, 12: overlap-save, or 16: gated) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
 // be refused without a device, leaving the request in plan.conv_* and the user radices of n in `radices`.  build_conv: the
 // one pass.  select_jit_conv_rows is the packed-row kernel with TileCfg::CONV (kernels_jit.cpp; run time only),
 // conv_rows_supported the same check without a device; launch_jit_conv is its launch, which -- unlike a DimPass::launch --
-// knows the first row of the exec, for the filter row of every launch row.
+// knows the first row of the exec, for the filter row of every launch row, and takes the exec's two gates (null where the plan
+// has none), offset to the exec's first signal row as `in` and `out` are.
 bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
 int conv_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
 int build_conv(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 bool conv_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_conv_rows(const Plan& plan, DimPass& pass, std::string& why_not);
-int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void* out, int64_t first, int64_t count,
-                    hipStream_t stream);
+int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void* out, const void* pregate,
+                    const void* postgate, int64_t first, int64_t count, hipStream_t stream);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }

@@ -248,6 +248,12 @@ struct TileParams {
     // c .. c + ols_step - 1 of its result to out[f * ols_step ..] of its signal's row, up to Lo.  spec_bands counts signals,
     // not launch rows: signal b of the launch takes filter row (spec_bands + b) % D.
     int ols_step, ols_blocks, ols_start;
+    // GATE configurations (CONV / OLS with elementwise gates; the arguments of one exec, not plan state): gate_in has the
+    // shape of `in` (rows of stft_len reals) and multiplies every sample as it is loaded, gate_out the shape of `out` (rows of
+    // stft_frames reals) and multiplies every sample as it is stored.  Both point, as `in` and `out` do, at the exec's first
+    // signal row; null where the configuration has no such gate.
+    const void* gate_in;
+    const void* gate_out;
 };
 
 // the log stage of a TileCfg::LOG store: fma(a, log2(max(v + add, amin)), c)
@@ -344,7 +350,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
-          bool CONV_ = false, bool OLS_ = false>
+          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -582,6 +588,15 @@ struct TileCfg {
     // the signal, not the launch row.  The passes, the product and the fold are CONV's.
     static constexpr bool OLS = OLS_;
     static_assert(!OLS_ || CONV_, "OLS: the overlap-save twin of a CONV tile");
+    // GATE (with CONV): bit 0 the pregate, y = conv(a . x): every sample the load reads is multiplied by the element of
+    // TileParams::gate_in at the same (signal row, sample) before it goes to LDS -- one multiply in T; a position the load
+    // zero-extends reads no gate.  Bit 1 the postgate, y = b . conv(x): the finished sample v * scale (signed as ever) is
+    // multiplied by the element of TileParams::gate_out at the same (signal row, sample) immediately before the store -- a
+    // multiplication of its own, never folded into the scale, so that the result equals the ungated kernel's on a . x, times
+    // b, bit for bit.  A gate is read in pairs (gload_pair: aligned to one element) exactly where x is read, or the result
+    // stored, in pairs, and real by real elsewhere; the gate load stands beside the access it accompanies, issued with it.
+    static constexpr int GATE = GATE_;
+    static_assert(GATE_ >= 0 && GATE_ <= 3 && (GATE_ == 0 || CONV_), "GATE: the pregate (1) and postgate (2) of a CONV tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -1953,6 +1968,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             const long long r0 = base / C::N, b0 = r0 / F;
             const int fr0 = (int)(r0 - b0 * F);
             const T* x0 = (const T*)p.in + b0 * len;
+            const T* g0 = (C::GATE & 1) ? (const T*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
             for (int f = tid; f < nv * C::N; f += C::THREADS) {
                 const int c = f / C::N, m = f - c * C::N;
                 int fr = fr0 + c, db = 0;
@@ -1961,13 +1977,24 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     fr -= db * F;
                 }
                 const T* xe = x0 + (long long)db * len;
+                const T* ge = g0 + (long long)db * len;
                 const int i = p.ols_start + fr * S + 2 * m;  // (-2N < s0 + fr S < T <= 2^30: 32 bits hold it)
                 V x = {(T)0, (T)0};
                 if (i >= 0 && i + 1 < len) {
                     x = gload_pair(xe + i);
-                } else {  // (zeros beyond the ends: no load at all)
-                    if (i >= 0 && i < len) x.x = xe[i];
-                    if (i + 1 >= 0 && i + 1 < len) x.y = xe[i + 1];
+                    if constexpr (C::GATE & 1) {
+                        const V g = gload_pair(ge + i);
+                        x = {g.x * x.x, g.y * x.y};
+                    }
+                } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
+                    if (i >= 0 && i < len) {
+                        x.x = xe[i];
+                        if constexpr (C::GATE & 1) x.x = ge[i] * x.x;
+                    }
+                    if (i + 1 >= 0 && i + 1 < len) {
+                        x.y = xe[i + 1];
+                        if constexpr (C::GATE & 1) x.y = ge[i + 1] * x.y;
+                    }
                 }
                 lds[lds_index<C, -1>(c, m)] = x;
             }
@@ -1976,14 +2003,22 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             // packed element m of row c: the reals 2 m and 2 m + 1 of a row of L samples, zeros from sample L on
             const int L = p.stft_len;
             const T* x0 = (const T*)p.in + (base / C::N) * L;
+            const T* g0 = (C::GATE & 1) ? (const T*)p.gate_in + (base / C::N) * L : x0;  // (else unused)
             for (int f = tid; f < nv * C::N; f += C::THREADS) {
                 const int c = f / C::N, m = f - c * C::N;
                 const T* xr = x0 + (long long)c * L;
+                const T* gr = g0 + (long long)c * L;
                 V x = {(T)0, (T)0};
-                if (2 * m + 1 < L)
+                if (2 * m + 1 < L) {
                     x = gload_pair(xr + 2 * m);
-                else if (2 * m < L)
+                    if constexpr (C::GATE & 1) {
+                        const V g = gload_pair(gr + 2 * m);
+                        x = {g.x * x.x, g.y * x.y};
+                    }
+                } else if (2 * m < L) {
                     x.x = xr[2 * m];
+                    if constexpr (C::GATE & 1) x.x = gr[2 * m] * x.x;
+                }
                 lds[lds_index<C, -1>(c, m)] = x;
             }
             __syncthreads();
@@ -2233,6 +2268,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                 // sample i of block fr goes to out[b Lo + fr S + i - c] for c <= i < c + S and fr S + i - c < Lo only
                 const int F = p.ols_blocks, S = p.ols_step;
                 T* out0 = (T*)p.out + sig0 * Lo;
+                const T* b0 = (C::GATE & 2) ? (const T*)p.gate_out + sig0 * Lo : out0;  // (else unused)
                 for (int f = tid; f < nv * C::N; f += C::THREADS) {
                     const int c = f / C::N, j = f - c * C::N, u = 2 * j - o;
                     if (u + 1 < 0 || u >= S) continue;
@@ -2245,28 +2281,51 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     const bool w0 = u >= 0 && t < Lo, w1 = u + 1 < S && t + 1 < Lo;
                     if (!w0 && !w1) continue;
                     const V v = lds[lds_index<C, C::NP - 1>(c, j)];
-                    const T y0 = v.x * s, y1 = -(v.y * s);
+                    T y0 = v.x * s, y1 = -(v.y * s);
                     T* q = out0 + (long long)db * Lo + t;
+                    const T* bq = b0 + (long long)db * Lo + t;
                     if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                        if constexpr (C::GATE & 2) {
+                            const V g = gload_pair(bq);
+                            y0 = g.x * y0, y1 = g.y * y1;
+                        }
                         gstore<false>((V*)q, V{y0, y1});
                     } else {
-                        if (w0) q[0] = y0;
-                        if (w1) q[1] = y1;
+                        if (w0) {
+                            if constexpr (C::GATE & 2) y0 = bq[0] * y0;
+                            q[0] = y0;
+                        }
+                        if (w1) {
+                            if constexpr (C::GATE & 2) y1 = bq[1] * y1;
+                            q[1] = y1;
+                        }
                     }
                 }
             } else {
                 T* out0 = (T*)p.out + row0 * Lo;
+                const T* b0 = (C::GATE & 2) ? (const T*)p.gate_out + row0 * Lo : out0;  // (else unused)
                 for (int f = tid; f < nv * C::N; f += C::THREADS) {
                     const int c = f / C::N, j = f - c * C::N, t = 2 * j - o;
                     if (t + 1 < 0 || t >= Lo) continue;
                     const V v = lds[lds_index<C, C::NP - 1>(c, j)];
-                    const T y0 = v.x * s, y1 = -(v.y * s);
+                    T y0 = v.x * s, y1 = -(v.y * s);
                     T* q = out0 + (long long)c * Lo + t;
+                    const T* bq = b0 + (long long)c * Lo + t;
                     if (t >= 0 && t + 1 < Lo && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                        if constexpr (C::GATE & 2) {
+                            const V g = gload_pair(bq);
+                            y0 = g.x * y0, y1 = g.y * y1;
+                        }
                         gstore<false>((V*)q, V{y0, y1});
                     } else {
-                        if (t >= 0) q[0] = y0;
-                        if (t + 1 < Lo) q[1] = y1;
+                        if (t >= 0) {
+                            if constexpr (C::GATE & 2) y0 = bq[0] * y0;
+                            q[0] = y0;
+                        }
+                        if (t + 1 < Lo) {
+                            if constexpr (C::GATE & 2) y1 = bq[1] * y1;
+                            q[1] = y1;
+                        }
                     }
                 }
             }

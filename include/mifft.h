@@ -542,9 +542,58 @@ typedef enum {
  * Refused before any device work: everything above that still applies (flags, inverse, components, dtypes, the limits of n,
  * D, batch % D, mode, H); MIFFT_ERR_BAD_BASES: S < 1 or c + S > n; F < 1 or Lo < 1; Lo outside ((F - 1) S, F S]; s0 <= -n or
  * s0 + (F - 1) S >= T (a block that reads no sample of its row); word 11 non-zero.  MIFFT_ERR_TOO_LARGE: T > 2^30
- * (MIFFT_ERR_BAD_DIM: T < 2). */
+ * (MIFFT_ERR_BAD_DIM: T < 2).
+ *
+ * Gates: the same tag in front of exactly 16 words fuses two elementwise gates into either form, still ONE launch, no scratch
+ * and no intermediate tensor -- the filter stage of Hyena / H3 / S4 models, y = b . conv(a . x):
+ *     xg[r][i] = a[r][i] * x[r][i]                                            (pregate:  a has x's shape and dtype)
+ *     out[r][t] = b[r][t] * irfft( rfft(xg[r], n) * G[r % D], n )[o + t]       (postgate: b has out's shape and dtype)
+ *     word  0 .. 7  as the 8-word payload: tag, D, o (or c), Lo (or S), mode, H_LO, H_HI
+ *     word  8       F.  0: a single block -- words 3 and 4 are o and Lo, words 9 and 10 must be 0, L <= n.
+ *                   >= 1: overlap-save -- words 3, 4, 9 and 10 are c, S, s0 and Lo as in the 12-word payload
+ *     word  9, 10   s0, Lo (overlap-save)
+ *     word 11       gates: bit 0 the pregate, bit 1 the postgate; 1, 2 or 3 (0 and every other bit are refused)
+ *     word 12 .. 15 reserved, 0
+ * (A skip term d * xg needs no gate: conv(xg, h) + d xg = conv(xg, h') with h'[0] = h[0] + d, which is H + d on every bin of
+ * the filter spectrum -- real d, so under the conjugate of a correlation as well.  The caller adds it to H.)
+ * The order of operations is part of the contract.  The pregate is ONE multiplication of the loaded sample by its gate, in the
+ * plan's float type, before the value reaches LDS; a position the load zero-extends (beyond L; outside [0, T) in
+ * overlap-save) reads no gate.  The postgate is ONE multiplication of the finished sample (v * 1/n, signed as in the ungated
+ * kernel) by its gate immediately before the store, never folded into the scale.  So the result equals, bit for bit, what
+ * the ungated plan of the same shape makes of the rounded products a * x, multiplied by b; gates of ones change nothing.
+ * A gate element is addressed by signal row and sample, as x and out are: every output sample is still written exactly once
+ * by one block, and a row's result is bit-identical for any batch, first / count, whole_batch and grid.  A gate is read in
+ * pairs exactly where x is read, or the result stored, in pairs (an address aligned to ONE element suffices), real by real
+ * elsewhere; each element of a gate that belongs to a loaded sample or a stored one is read once, and no other.
+ * The kernel is the CONV / OLS tile with TileCfg::GATE = the gates word: rows<n>[_f64]_r2c_<radices>_conv[_ols]_g<1|2|3>_jit, run
+ * time only.  The ungated payloads select exactly the kernels they selected.
+ * THE EXEC.  Gates are activations -- new tensors on every call -- so they are arguments of the exec, not plan state bound by
+ * address as H is.  The exec of a gated plan is mifft_exec / mifft_exec_batch / mifft_time_exec with the HOST address of a
+ * mifft_gated_args (below) in the place of x:
+ *     mifft_gated_args g = { MIFFT_GATED_ARGS_MAGIC, x, pregate, postgate };   mifft_exec_batch(plan, &g, out, first, count, stream);
+ * The block is read before the call returns and may live on the stack.  first / count are signal rows as ever: x and the
+ * pregate are offset by first * L (or T) reals, out and the postgate by first * Lo.  A gate pointer is non-null exactly where
+ * the plan's bit is set: MIFFT_ERR_NULL for a missing gate (or a null x), MIFFT_ERR_UNSUPPORTED for a gate the plan did not ask
+ * for.  A gate may alias x; one that overlaps the exec's part of out is MIFFT_ERR_ALIAS.  A gated plan given the device address
+ * of the signal itself, as an ungated plan takes it, or a block without the magic word, is refused with
+ * MIFFT_ERR_UNSUPPORTED and a message that names mifft_gated_args; nothing is launched in any of these cases.  (The block
+ * travels through the existing entry points: the library's set of exported functions does not change.)
+ * mifft_plan_num_launches() is 1, mifft_plan_scratch_bytes() 0; mifft_plan_in_bytes() / _out_bytes() stay the sizes of x and out,
+ * which are also the sizes of the pregate and the postgate.
+ * Refused before any device work: every check of the 8-word payload (F = 0; L > n among them) or of the 12-word one (F >= 1)
+ * with its status; MIFFT_ERR_BAD_BASES: a gates word of 0 or above 3; a non-zero word 12 .. 15; F = 0 with a non-zero word 9
+ * or 10.  The tag in front of 13, 14 or 15 words is no convolution payload.  MIFFT_JIT=0 refuses the plan as it does the
+ * ungated ones. */
 #define MIFFT_CONV_TAG_LO 0x4F4E5601u
 #define MIFFT_CONV_TAG_HI 0x7FF84D43u
+/* the argument block of a gated convolution exec (above); the magic word is "MIFFTGA1" */
+#define MIFFT_GATED_ARGS_MAGIC 0x314147544646494Dull
+typedef struct mifft_gated_args {
+    uint64_t magic;       /* MIFFT_GATED_ARGS_MAGIC */
+    const void* x;        /* (batch, L, 1) reals on the plan's device */
+    const void* pregate;  /* x's shape and dtype, or NULL where the plan has no pregate */
+    const void* postgate; /* out's shape and dtype, or NULL where the plan has no postgate */
+} mifft_gated_args;
 
 typedef struct mifft_plan mifft_plan;
 

@@ -197,6 +197,11 @@ static_assert(MIFFT_CONV_TAG_LO == 0x4F4E5601u && MIFFT_CONV_TAG_HI == 0x7FF84D4
                   MIFFT_CONV_TAG_HI != MIFFT_STFT_EXT_TAG_HI,
               "MIFFT_CONV_TAG is the quiet NaN 0x7FF84D434F4E5601, distinct from the other payload tags");
 constexpr uint64_t kConvTag = ((uint64_t)MIFFT_CONV_TAG_HI << 32) | MIFFT_CONV_TAG_LO;
+// (In front of 16 words -- the eight | F (0: single block) | s0 | Lo | gates | 0 0 0 0 -- either form with an elementwise pregate
+// (bit 0, x's shape) and postgate (bit 1, out's shape) fused into the tile's load and store.  The gates are arguments of every
+// exec: mifft_exec_batch takes the host address of a mifft_gated_args {MIFFT_GATED_ARGS_MAGIC, x, pregate, postgate} as its x.)
+static_assert(MIFFT_GATED_ARGS_MAGIC == 0x314147544646494Dull && sizeof(mifft_gated_args) == 8 + 3 * sizeof(void*),
+              "mifft_gated_args is the magic word \"MIFFTGA1\" and three pointers");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
