@@ -57,6 +57,9 @@ MDCT_TAG_HI = 0x7FF84D44
 CONV_TAG_LO = 0x4F4E5601       # MIFFT_CONV_TAG_LO / _HI: the NaN in front of the 8-word payload of a FLAG_STFT plan that is a
 CONV_TAG_HI = 0x7FF84D43       # fused FFT convolution (TAG | D | o | Lo | mode | the device address of the filter spectra)
 GATED_ARGS_MAGIC = 0x314147544646494D  # MIFFT_GATED_ARGS_MAGIC ("MIFFTGA1")
+CONV_GRAD_TAG_LO = 0x44524701  # MIFFT_CONV_GRAD_TAG_LO / _HI: the NaN in front of the 16-word payload of a FLAG_STFT plan that is the
+CONV_GRAD_TAG_HI = 0x7FF84D47  # filter gradient of a fused convolution (TAG | D | c | S | mode | F | s0 | Lo | P | 0 x 6)
+CONV_GRAD_ARGS_MAGIC = 0x314757544646494D  # MIFFT_CONV_GRAD_ARGS_MAGIC ("MIFFTWG1")
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -64,6 +67,11 @@ class GatedArgs(ctypes.Structure):
     """mifft_gated_args: what the exec of a gated convolution plan takes, by host address, in the place of x"""
     _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("pregate", ctypes.c_void_p),
                 ("postgate", ctypes.c_void_p)]
+
+
+class ConvGradArgs(ctypes.Structure):
+    """mifft_conv_grad_args: what the exec of a filter-gradient plan takes, by host address, in the place of x"""
+    _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("gy", ctypes.c_void_p)]
 
 
 def FLAG_KEEP_DIM(d: int) -> int:
@@ -1817,7 +1825,9 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     ``pregate`` / ``postgate`` = True make it a gated plan (the 16-word payload), of either kind:
     ``y[r] = b[r] * conv(a[r] * x[r])`` with a tensor ``a`` of ``in_shape`` and / or ``b`` of ``out_shape`` given with every
     exec, multiplied into the kernel's load and store -- still one launch, no intermediate.  Such a plan runs through
-    ``plan.run(out, x, pregate=a, postgate=b)``.  A skip term d * (a * x) is d added to every bin of ``filter_spectrum``."""
+    ``plan.run(out, x, pregate=a, postgate=b)``.  A skip term d * (a * x) is d added to every bin of ``filter_spectrum``.
+    The plan-level API carries no autograd; ``plan_fftconv_grad`` of the same arguments is the plan of its filter gradient,
+    and the opposite-``correlate`` plan on rows of ``out_length`` samples its input gradient (what ``fftconv`` does)."""
     batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
     out_length = length if out_length is None else int(out_length)
     if dtype not in _OUT_DTYPES:
@@ -1852,6 +1862,36 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, pregate=pregate, postgate=postgate)
 
 
+def _fftconv_pick(who: str, L: int, K: int, dtype, n: Optional[int], block: Optional[int]) -> tuple:
+    """(n, taps) of ``fftconv``'s two paths for rows of L samples and K taps: the single block at the FFT length n (taps None),
+    or overlap-save blocks of n points (taps = K) -- forced by ``block``, or chosen when L + K - 1 is beyond the last single
+    length.  Every refusal of the pair (n, block) is raised here, for ``fftconv`` and for what mirrors its choice."""
+    if block is not None and n is not None:
+        raise ValueError(f"{who}: n is the FFT length of the single-block path, block that of the overlap-save path: not both")
+    taps = None
+    if block is not None:
+        n, taps = int(block), K
+    elif n is None:
+        try:
+            n = fftconv_length(L + K - 1, dtype)
+        except MifftError as e:
+            if e.status != ERR_UNSUPPORTED:
+                raise
+            n, taps = fftconv_block(K, dtype), K
+    else:
+        n = int(n)
+    if taps is not None and K > n - 1:
+        raise MifftError(-2, f"{who}: a filter of K = {K} taps does not fit overlap-save blocks of {n} points (K <= block - 1)")
+    if K > n:
+        raise MifftError(-2, f"{who}: a filter of K = {K} taps does not fit the FFT length n = {n}")
+    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
+                                          "n // 2 without a prime factor above 32): see fftconv_length")
+    if taps is None and L > n:
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {L} samples are longer than the FFT length n = {n}")
+    return n, taps
+
+
 def _fftconv_window(mode: str, L: int, K: int) -> tuple:
     """(offset, out_length) of scipy.signal.fftconvolve's crops of the full convolution of L and K samples"""
     if mode == "causal":
@@ -1871,7 +1911,16 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one gives the circular result.
     ``mode="causal"`` returns the first L samples (the Hyena / S4 convention); "full", "same" and "valid" are
     scipy.signal.fftconvolve's crops.  ``correlate=True`` (with "causal" only) returns y[t] = sum_j k[j] x[t + j], the adjoint
-    of the causal convolution.  float32 / float64; other input is converted to float64.  Not differentiable: no autograd.
+    of the causal convolution.  float32 / float64; other input is converted to float64.
+    Differentiable, first order: when grad mode is on and ``x``, ``k``, ``pregate``, ``postgate`` or a tensor ``skip`` requires
+    grad, the call goes through a torch.autograd.Function whose forward is this same code (the same kernels, the same bits)
+    and whose backward computes only the gradients asked for: the gradient of ``x`` and ``pregate`` by ONE launch of the
+    opposite-``correlate`` plan on the incoming gradient (``postgate`` fused into its load; ``pregate`` into its store when
+    only ``x`` wants a gradient), the gradient of ``k`` and ``skip`` by the fused filter-gradient kernel
+    (``fftconv_filter_grad``; with gates its two inputs are torch products), the gradient of ``postgate`` from one forward
+    launch recomputed without it.  Modes "same" and "valid" first zero-embed the incoming gradient into the window of the
+    full result with one torch pad and then take the route of "full".  No double backward, no torch.compile / functorch
+    rules.  Otherwise the result carries no grad_fn and the call is what it has always been.
     Plans are cached per (shape, dtype, n, mode, device, stream); the filter is transformed on every call, so loops over one
     filter should use ``plan_fftconv``.
     Rows too long for one FFT (L + K - 1 beyond fftconv_length's last length) run as overlap-save blocks of
@@ -1899,29 +1948,7 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     if L < 2 or K < 1:
         raise MifftError(-2, f"fftconv: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
     dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-    if block is not None and n is not None:
-        raise ValueError("fftconv: n is the FFT length of the single-block path, block that of the overlap-save path: not both")
-    taps = None
-    if block is not None:
-        n, taps = int(block), K
-    elif n is None:
-        try:
-            n = fftconv_length(L + K - 1, dtype)
-        except MifftError as e:
-            if e.status != ERR_UNSUPPORTED:
-                raise
-            n, taps = fftconv_block(K, dtype), K
-    else:
-        n = int(n)
-    if taps is not None and K > n - 1:
-        raise MifftError(-2, f"fftconv: a filter of K = {K} taps does not fit overlap-save blocks of {n} points (K <= block - 1)")
-    if K > n:
-        raise MifftError(-2, f"fftconv: a filter of K = {K} taps does not fit the FFT length n = {n}")
-    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
-        raise MifftError(ERR_UNSUPPORTED, f"fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
-                                          "n // 2 without a prime factor above 32): see fftconv_length")
-    if taps is None and L > n:
-        raise MifftError(ERR_UNSUPPORTED, f"fftconv: rows of {L} samples are longer than the FFT length n = {n}")
+    n, taps = _fftconv_pick("fftconv", L, K, dtype, n, block)
     offset, out_length = _fftconv_window(mode, L, K)
     rows = 1
     for m in logical[:-1]:
@@ -1948,6 +1975,11 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     device = DeviceContext(x.device.index if x.is_cuda else None).device
     if not x.is_cuda or x.device.index != device:
         raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, k, pregate, postgate, skip)):
+        # (the forward of the Function runs with grad mode off: it comes back here and takes the lines below)
+        skip_t = skip if isinstance(skip, torch.Tensor) else None
+        return _FFTConvFunction.apply(x, k, pregate, postgate, skip_t, None if skip_t is not None else skip,
+                                      (n, taps, mode, bool(correlate)))
     xr = x.to(dtype).contiguous().reshape(rows, L, 1)
     out = torch.empty((rows, out_length, 1), dtype=dtype, device=xr.device)
     gates = (1 if pregate is not None else 0) | (2 if postgate is not None else 0)
@@ -1971,6 +2003,273 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         else:
             fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical[:-1] + (out_length,))
+
+
+class ConvGradPlan(Plan):
+    """The plan of ``plan_fftconv_grad``: the filter gradient of the ``plan_fftconv`` plan of the same arguments, one launch
+    of ``channels * partials`` persistent workgroups (MIFFT_CONV_GRAD_TAG in include/mifft.h).  ``partials`` partial sums
+    per channel (the library's choice unless given), ``blocks`` per row and ``step`` samples per block as on ``ConvPlan``
+    (a single block: 1 and None).  ``in_shape`` (batch * channels, length, 1) is x's, ``grad_shape``
+    (batch * channels, out_length, 1) the incoming gradient's, ``out_shape`` (partials, channels, n // 2 + 1, 2)."""
+
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, partials=None):
+        self.ctx = ctx
+        self.channels, self.length, self.n = channels, length, n
+        self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
+        self.taps, self.step, self.blocks = taps, None, 1
+        c, S, s0 = offset, out_length, 0
+        if taps is not None:
+            c, S, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
+            self.step = S
+        rows = batch * channels
+        words = [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, channels, c, S, 1 if correlate else 0, self.blocks, s0 & 0xFFFFFFFF,
+                 out_length, 0 if partials is None else int(partials)] + [0] * 6
+        self.in_dtype = self.out_dtype = dtype
+        self.in_shape, self.grad_shape = (rows, length, 1), (rows, out_length, 1)
+        self.inverse, self.device, self.flags, self.axes, self.whole_batch = False, int(ctx.device), FLAG_STFT, None, 0
+        self.half_spectrum = self.dct = self.dctn = self.istft = self.spectrogram = self.dst = False
+        self.stft, self.dct_type, self.mdct, self.imdct, self.conv, self.conv_gates = True, 2, 0, 0, None, 0
+        self._ndim = 2
+        h = ctypes.c_void_p()
+        check(_lib.lib().mifft_plan_create_slab(ctypes.byref(h), self.device, _DTYPE_CODE[dtype], _DTYPE_CODE[dtype], 2,
+                                                (ctypes.c_int64 * 2)(length, n), rows, 1, 0, (ctypes.c_uint32 * 16)(*words),
+                                                (ctypes.c_int32 * 2)(16, 0), FLAG_STFT, 0))
+        self._h = h
+        self.partials = self.pass_geometry(1)[3] // channels
+        self.out_shape = (self.partials, channels, n // 2 + 1, 2)
+
+    def pass_geometry(self, dim: int, count: Optional[int] = None) -> tuple:
+        """(tile, threads, n_tiles, grid): pairs per step of a workgroup, threads, the steps of all workgroups, and
+        ``channels * partials`` workgroups; workgroup (d, p) walks ceil(its pairs / tile) steps"""
+        return super().pass_geometry(dim, self.in_shape[0] if count is None else count)
+
+    def run(self, out: "torch.Tensor", x: "torch.Tensor", gy: "torch.Tensor") -> None:
+        """fills ``out`` of ``out_shape`` with the unscaled partial spectra sum conj(rfft(x-block)) rfft(gy-block), enqueued on
+        the plan's stream; ``x`` of ``in_shape`` and ``gy`` of ``grad_shape``, the plan's dtype, contiguous; neither is written"""
+        _check_tensor(x, self.in_shape, self.in_dtype, self.device, "x")
+        _check_tensor(gy, self.grad_shape, self.in_dtype, self.device, "gy")
+        _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
+        args = ConvGradArgs(CONV_GRAD_ARGS_MAGIC, x.data_ptr(), gy.data_ptr())
+        check(_lib.lib().mifft_exec_batch(self._h, ctypes.addressof(args), out.data_ptr(), 0, self.in_shape[0],
+                                          self.ctx.stream.cuda_stream))
+
+    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int) -> "torch.Tensor":
+        """the real (channels, K) gradient of the filter: ``run``, the sum of the partials, the library's own irfftn, the
+        first K lags (lag 0 is also the gradient of a skip term)"""
+        K = int(K)
+        if K < 1 or K > self.n or (self.taps is not None and K > self.taps):
+            raise MifftError(-2, f"filter_grad: K = {K} taps at n = {self.n}" +
+                                 (f" on an overlap-save plan of taps = {self.taps}" if self.taps is not None else "") +
+                                 ": 1 <= K <= " + str(self.n if self.taps is None else self.taps))
+        out = torch.empty(self.out_shape, dtype=self.out_dtype, device=x.device)
+        self.run(out, x, gy)
+        with torch.cuda.stream(self.ctx.stream):
+            A = out[0] if self.partials == 1 else out.sum(0)
+            return irfftn(A, self.n)[:, :K]
+
+
+def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
+                      out_length: Optional[int] = None, correlate: bool = False, partials: Optional[int] = None,
+                      ctx: Optional[DeviceContext] = None) -> ConvGradPlan:
+    """Plan of the fused filter gradient (no reference counterpart) of the ``plan_fftconv`` plan of the same arguments:
+    ``gk[d, j] = sum over b and t of gy[b, d, t] * u[b, d, o + t - j]`` (``correlate``: ``o + t + j``), computed as
+    ``irfft(sum_b conj(rfft(u[b, d], n)) * rfft(gy[b, d] put at o, n), n)[:K]`` in ONE launch that reads ``u`` and ``gy`` once
+    each and writes ``channels * partials`` rows of n // 2 + 1 bins -- the exact adjoint of what the forward plan computes,
+    circular where that is, block by block on an overlap-save plan (``taps=K``).  ``partials`` workgroups share a channel's
+    sum (default: enough that channels * partials fills the device; capped by the (row, block) pairs of a channel); the
+    order of every sum is fixed by the plan, so two runs give the same bits.  Gates are not fused: ``u`` = pregate * x and
+    ``gy`` = postgate * (the incoming gradient) are the caller's.  Every argument error is raised before any device work."""
+    batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
+    out_length = length if out_length is None else int(out_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"a filter-gradient plan reads and writes float32 or float64, got {dtype}")
+    if batch < 1 or channels < 1:
+        raise MifftError(-8, f"plan_fftconv_grad: batch = {batch} and channels = {channels} must be positive")
+    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
+        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to "
+                                          "12288, n // 2 without a prime factor above 32): see fftconv_length")
+    blocks = 1
+    if taps is not None:
+        taps = int(taps)
+        if taps < 1 or taps > n - 1:
+            raise MifftError(-2, f"plan_fftconv_grad: taps = {taps} at the block length n = {n}: 1 <= taps <= n - 1")
+        if length < 2 or length > 1 << 30:
+            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: rows of {length} samples: 2 <= length <= 2^30")
+        full = length if correlate else length + taps - 1
+        if offset < 0 or out_length < 1 or offset + out_length > full:
+            raise MifftError(-5, f"plan_fftconv_grad: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
+                                 f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
+                                 f"{length} samples with {taps} taps)")
+        blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)[3]
+    else:
+        if length < 2 or length > n:
+            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: rows of {length} samples at n = {n}: 2 <= length <= n")
+        if offset < 0 or out_length < 1 or offset + out_length > n:
+            raise MifftError(-5, f"plan_fftconv_grad: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
+                                 f"offset + out_length <= n = {n}")
+    if partials is not None:
+        partials = int(partials)
+        if partials < 1 or partials > 65535:
+            raise MifftError(-5, f"plan_fftconv_grad: partials = {partials}: 1 .. 65535")
+        partials = min(partials, batch * blocks)  # (capped by the pairs of a channel)
+    if ctx is None:
+        ctx = DeviceContext()
+    return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, partials=partials)
+
+
+def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device) -> ConvGradPlan:
+    """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK)"""
+    key = ("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
+           int(torch.cuda.current_stream(device).cuda_stream), taps)
+    plan = _PLAN_CACHE.get(key)
+    if plan is None:
+        plan = plan_fftconv_grad(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length,
+                                 correlate=correlate, ctx=DeviceContext(device))
+        _plan_cache_insert(key, plan)
+    else:
+        _PLAN_CACHE.move_to_end(key)
+    return plan
+
+
+def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Optional[int] = None, mode: str = "causal",
+                        correlate: bool = False, block: Optional[int] = None) -> "torch.Tensor":
+    """The gradient of ``sum(gy * fftconv(x, k, n=n, mode=mode, correlate=correlate, block=block))`` with respect to a filter
+    ``k`` of ``K`` taps, by the fused filter-gradient kernel in one launch (plus a sum of partials and one irfftn, both on
+    ``channels`` rows): ``x`` (..., D, L) and ``gy`` of the result's shape (..., D, Lo) give (D, K); a 1-D ``x`` (L,) with
+    ``gy`` (Lo,) gives (K,), the gradient of a 1-D filter.  (A 1-D filter shared by rows (..., L): reshape to (-1, 1, L) and take
+    row 0.)  The choice of ``n`` / overlap-save mirrors ``fftconv``'s for the same arguments, so this is the gradient of THAT
+    call, circular where it is.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s."""
+    if x.is_complex() or gy.is_complex():
+        raise MifftError(-3, "fftconv_filter_grad expects real tensors (complex rows are out of scope)")
+    if mode not in _FFTCONV_MODES:
+        raise ValueError(f"fftconv_filter_grad: mode must be one of {_FFTCONV_MODES}, got {mode!r}")
+    if correlate and mode != "causal":
+        raise ValueError(f"fftconv_filter_grad: correlate=True goes with mode='causal' only, got {mode!r}")
+    if x.dim() < 1 or x.dim() != gy.dim():
+        raise MifftError(-1, f"fftconv_filter_grad expects x (..., D, L) with gy (..., D, Lo), or x (L,) with gy (Lo,), got "
+                             f"{tuple(x.shape)} and {tuple(gy.shape)}")
+    logical = tuple(x.shape)
+    L, K = int(logical[-1]), int(K)
+    D = int(logical[-2]) if x.dim() >= 2 else 1
+    if L < 2 or K < 1:
+        raise MifftError(-2, f"fftconv_filter_grad: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
+    dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    n, taps = _fftconv_pick("fftconv_filter_grad", L, K, dtype, n, block)
+    offset, out_length = _fftconv_window(mode, L, K)
+    if tuple(gy.shape) != logical[:-1] + (out_length,):
+        raise ValueError(f"fftconv_filter_grad: gy is {tuple(gy.shape)}, the result of that fftconv call is "
+                         f"{logical[:-1] + (out_length,)}")
+    rows = 1
+    for m in logical[:-1]:
+        rows *= m
+    if rows < 1:
+        raise MifftError(-8, f"fftconv_filter_grad: no rows in {logical}")
+    device = DeviceContext(x.device.index if x.is_cuda else None).device
+    if not x.is_cuda or x.device.index != device:
+        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    if gy.device != x.device:
+        raise MifftError(-10, f"fftconv_filter_grad: gy lives on {gy.device}, x on {x.device}")
+    xr = x.detach().to(dtype).contiguous().reshape(rows, L, 1)
+    gr = gy.detach().to(dtype).contiguous().reshape(rows, out_length, 1)
+    with _PLAN_CACHE_LOCK:
+        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device)
+        gk = plan.filter_grad(xr, gr, K)
+    return gk if x.dim() >= 2 else gk.reshape(K)
+
+
+class _FFTConvFunction(torch.autograd.Function):
+    """``fftconv`` with a backward (first order).  forward: the plain call, grad mode off.  backward, with u = a x,
+    gv = b gy and G = rfft(k, n) + d: gu = the adjoint convolution of gv (one launch of the opposite-correlate plan),
+    gx = a gu, ga = x gu, gb = gy v with v recomputed without the postgate, gk and gd from the fused filter gradient of
+    (u, gv).  The filter spectra of the cached plans are rewritten from the saved k and skip by every launch here: a second
+    layer of the same shape may have overwritten them since the forward."""
+
+    @staticmethod
+    def forward(ctx, x, k, pregate, postgate, skip_t, skip_f, cfg):
+        n, taps, mode, correlate = cfg
+        ctx.cfg, ctx.skip_f = cfg, skip_f
+        ctx.save_for_backward(x, k, pregate, postgate, skip_t)
+        return fftconv(x, k, mode=mode, correlate=correlate, pregate=pregate, postgate=postgate,
+                       skip=skip_t if skip_t is not None else skip_f,
+                       **({"block": n} if taps is not None else {"n": n}))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, k, a, b, skip_t = ctx.saved_tensors
+        n, taps, mode, correlate = ctx.cfg
+        skip = skip_t.detach() if skip_t is not None else ctx.skip_f
+        need_x, need_k, need_a, need_b, need_d = ctx.needs_input_grad[:5]
+        logical = tuple(x.shape)
+        L, K = int(logical[-1]), int(k.shape[-1])
+        D = int(k.shape[0]) if k.dim() == 2 else 1
+        dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+        o, Lo = _fftconv_window(mode, L, K)
+        rows = x.numel() // L
+        device = x.device.index
+        sel = {"block": n} if taps is not None else {"n": n}
+        gyr = gy.to(dtype).contiguous().reshape(rows, Lo)  # (sum().backward() hands in an expanded tensor)
+        xr = x.to(dtype).contiguous().reshape(rows, L)
+        ar = None if a is None else a.to(dtype).contiguous().reshape(rows, L)
+        br = None if b is None else b.to(dtype).contiguous().reshape(rows, Lo)
+        gx = gk = ga = gb = gd = None
+        gv = None
+        if need_k or need_d or (o > 0 and (need_x or need_a)):
+            gv = gyr if br is None else br * gyr
+        if need_x or need_a:
+            # gu: the adjoint of u -> crop(conv(u, k') , o, Lo), one launch of the existing kernels on the gradient put at o
+            fuse_a = ar is not None and need_x and not need_a
+            if o > 0:
+                src, pre = torch.nn.functional.pad(gv, (o, 0)), None
+            else:
+                src, pre = gyr, br
+            if src.shape[-1] < 2:
+                src = torch.nn.functional.pad(src, (0, 1))
+                pre = None if pre is None else torch.nn.functional.pad(pre, (0, 1))
+            Lin = int(src.shape[-1])
+            gates = (1 if pre is not None else 0) | (2 if fuse_a else 0)
+            out = torch.empty((rows, L, 1), dtype=dtype, device=x.device)
+            with _PLAN_CACHE_LOCK:
+                key = ("fftconv", dtype, rows, D, Lin, n, 0, L, not correlate, device,
+                       int(torch.cuda.current_stream(device).cuda_stream), taps, gates)
+                plan = _PLAN_CACHE.get(key)
+                if plan is None:
+                    plan = plan_fftconv(dtype, rows // D, D, Lin, n, taps=taps, offset=0, out_length=L, correlate=not correlate,
+                                        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2))
+                    _plan_cache_insert(key, plan)
+                else:
+                    _PLAN_CACHE.move_to_end(key)
+                plan.set_filter(k.detach())
+                if skip is not None:
+                    plan.add_skip(skip)
+                if gates:
+                    plan.run(out, src.reshape(rows, Lin, 1), pregate=None if pre is None else pre.reshape(rows, Lin, 1),
+                             postgate=ar.reshape(rows, L, 1) if fuse_a else None)
+                else:
+                    fft(out, src.reshape(rows, Lin, 1), DeviceContext(device), plan=plan)
+            gu = out.reshape(rows, L)
+            if ar is None or fuse_a:
+                gx = gu
+            else:
+                gx = ar * gu if need_x else None
+                ga = xr * gu
+            if not need_x:
+                gx = None
+        if need_b:  # gb = gy v, v = conv(u, k) + d u recomputed by one forward launch without the postgate
+            v = fftconv(x.detach(), k.detach(), mode=mode, correlate=correlate, pregate=None if a is None else a.detach(),
+                        skip=skip, **sel)
+            gb = gyr * v.reshape(rows, Lo)
+        if need_k or need_d:
+            u = xr if ar is None else ar * xr
+            with _PLAN_CACHE_LOCK:
+                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device)
+                g = gplan.filter_grad(u.reshape(rows, L, 1), gv.reshape(rows, Lo, 1), K)
+            if need_k:
+                gk = g.reshape(k.shape).to(k.dtype)
+            if need_d:
+                gd = g[:, 0].to(skip_t.dtype)
+        back = lambda g, t: None if g is None else g.reshape(t.shape).to(t.dtype)
+        return back(gx, x), gk, back(ga, a) if need_a else None, back(gb, b) if need_b else None, gd, None, None
 
 
 def _imdct_norm_gain(norm, n: int, who: str) -> float:

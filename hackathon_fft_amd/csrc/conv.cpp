@@ -15,6 +15,8 @@
 // The 16-word payload is either of the two with elementwise gates fused into the tile's load and store (TileCfg::GATE):
 // y = b . conv(a . x), a of x's shape, b of out's.  The plan knows only WHICH gates there are; the tensors are arguments of
 // every exec (mifft_gated_args through mifft_exec_batch: mifft_api.cpp).
+#include <algorithm>
+
 #include "mifft_config.h"
 #include "mifft_internal.h"
 
@@ -28,8 +30,8 @@ bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len)
     return (bases_len[0] == 8 || bases_len[0] == 12 || bases_len[0] == 16) && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
 }
 
-int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
-               std::string& why) {
+// what the convolution payloads share: the flag, direction, dtype and component checks and the limits of n
+static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
     const struct {
         uint32_t bits;
         const char* what;
@@ -46,7 +48,7 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
                  {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
     for (const auto& o : other)
         if (p.flags & o.bits) {
-            why = std::string("a convolution payload (MIFFT_CONV_TAG) with ") + o.what;
+            why = std::string("a convolution payload (") + tag + ") with " + o.what;
             return MIFFT_ERR_UNSUPPORTED;
         }
     if (p.inverse) {
@@ -61,7 +63,7 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "a convolution reads the plan's own float type (in_dtype == out_dtype)";
         return MIFFT_ERR_BAD_DTYPE;
     }
-    const int64_t L = p.dims[0], n = p.dims[1];
+    const int64_t n = p.dims[1];
     if (n % 2 != 0 || n < 8 || n > (1 << 14)) {
         why = "convolution at an FFT length of " + std::to_string(n) +
               ": the limits of the packed rows are an even length from 8 to 16384";
@@ -72,6 +74,13 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "convolution at an FFT length of " + std::to_string(n) + ": " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
+    return MIFFT_OK;
+}
+
+int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
+               std::string& why) {
+    if (const int rc = conv_header_check(p, "MIFFT_CONV_TAG", why)) return rc;
+    const int64_t L = p.dims[0], n = p.dims[1];
     const bool gated = bases_len[0] == 16;  // (word 8 says which of the two forms it is: F = 0 the single block)
     const bool ols = bases_len[0] == 12 || (gated && bases_flat[8] != 0);  // (overlap-save: rows of T = L samples in blocks of n)
     if (ols && (L < 2 || L > (1ll << 30))) {
@@ -202,6 +211,111 @@ int build_conv(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
     p.passes.push_back(ps);
     if (e != hipSuccess) return hip_error(e, "convolution table upload");
+    return MIFFT_OK;
+}
+
+// ---- the filter gradient: TAG_LO | TAG_HI | D | c | S | mode | F | s0 | Lo | P | 0 x 6 (MIFFT_CONV_GRAD_TAG, include/mifft.h) ----
+bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 2 || !bases_flat || !bases_len) return false;
+    return bases_len[0] == 16 && bases_flat[0] == MIFFT_CONV_GRAD_TAG_LO && bases_flat[1] == MIFFT_CONV_GRAD_TAG_HI;
+}
+
+int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
+                    std::string& why) {
+    if (const int rc = conv_header_check(p, "MIFFT_CONV_GRAD_TAG", why)) return rc;
+    const int64_t L = p.dims[0], n = p.dims[1];
+    const int64_t D = bases_flat[2], c = bases_flat[3], S = bases_flat[4], F = bases_flat[6], s0 = (int32_t)bases_flat[7];
+    const int64_t Lo = bases_flat[8], P = bases_flat[9];
+    const uint32_t mode = bases_flat[5];
+    // (one block that holds the whole row is CONV's geometry; everything else, a single block of a longer row included, OLS's)
+    const bool single = F == 1 && s0 == 0 && S == Lo && L <= n;
+    if (!single && (L < 2 || L > (1ll << 30))) {
+        why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save filter-gradient payload: 2 <= T <= 2^30";
+        return L < 2 ? MIFFT_ERR_BAD_DIM : MIFFT_ERR_TOO_LARGE;
+    }
+    if (S < 1 || c + S > n) {
+        why = "the stored part c = " + std::to_string(c) + ", S = " + std::to_string(S) +
+              " of every block of a filter-gradient payload: S >= 1 and c + S <= n = " + std::to_string(n);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (D < 1) {
+        why = "D = 0 filter rows in a filter-gradient payload: D >= 1";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (D > (1ll << 30)) {
+        why = "D = " + std::to_string(D) + " filter rows: at most 2^30";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (p.batch % D != 0) {
+        why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(D) + " filter rows";
+        return MIFFT_ERR_BAD_BATCH;
+    }
+    if (mode & ~1u) {
+        why = "the mode word of a filter-gradient payload has bit 0 (the forward correlated) alone, not " + std::to_string(mode);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (F < 1 || Lo < 1 || Lo > (1ll << 30)) {
+        why = "F = " + std::to_string(F) + " blocks and Lo = " + std::to_string(Lo) +
+              " samples per row of gy in a filter-gradient payload: F >= 1 and 1 <= Lo <= 2^30";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (Lo <= (F - 1) * S || Lo > F * S) {
+        why = "Lo = " + std::to_string(Lo) + " samples per row of gy against F = " + std::to_string(F) + " blocks of S = " +
+              std::to_string(S) + ": (F - 1) S < Lo <= F S (the last block stored at least one sample)";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (s0 <= -n || s0 + (F - 1) * S >= L) {
+        why = "block start s0 = " + std::to_string(s0) + " with F = " + std::to_string(F) + " blocks every S = " +
+              std::to_string(S) + " samples: a block reads no sample of its row (-n < s0 and s0 + (F - 1) S < T = " +
+              std::to_string(L) + ")";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    const int64_t pairs = p.batch / D * F;  // (of one channel)
+    if (P > 65535 || P > pairs) {
+        why = "P = " + std::to_string(P) + " partial sums per channel in a filter-gradient payload: at most 65535 and at most the " +
+              std::to_string(pairs) + " (row, block) pairs of a channel (0: the library's choice)";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    for (int w = 10; w < 16; ++w)
+        if (bases_flat[w] != 0) {
+            why = "the reserved word " + std::to_string(w) + " of a filter-gradient payload must be 0, not " +
+                  std::to_string(bases_flat[w]);
+            return MIFFT_ERR_BAD_BASES;
+        }
+    if (bases_len[1] < 0) {
+        why = "negative bases_len";
+        return MIFFT_ERR_NO_BASES;
+    }
+    radices.clear();
+    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    p.conv_grad = true;
+    p.conv_D = D;
+    p.conv_o = c;
+    p.conv_Lo = Lo;
+    p.conv_S = single ? 0 : S;
+    p.conv_F = F;
+    p.conv_s0 = s0;
+    p.conv_mode = mode;
+    p.conv_P = P;
+    return MIFFT_OK;
+}
+
+// P of a built pass when the payload left it to the library: D P workgroups fill the device (as many as the persistent
+// grid of a row pass would have), every slice keeps at least one full step of TILE pairs, at most 65535
+static int64_t conv_grad_partials(const Plan& p, const DimPass& ps) {
+    long long per_cu = (160 * 1024) / (long long)(ps.lds_bytes ? ps.lds_bytes : 1);
+    per_cu = std::min<long long>(per_cu, 2048 / ps.threads);
+    per_cu = std::max<long long>(1, std::min<long long>(per_cu, 16));
+    const int64_t want = (int64_t)p.num_cus * per_cu, pairs = p.batch / p.conv_D * p.conv_F;
+    const int64_t P = (want + p.conv_D - 1) / p.conv_D;
+    return std::max<int64_t>(1, std::min<int64_t>({P, pairs / ps.tile, (int64_t)65535}));
+}
+
+// the one pass, as build_conv's; then P
+int build_conv_grad(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    const int rc = build_conv(p, ordered, processed, why);
+    if (rc) return rc;
+    if (p.conv_P == 0) p.conv_P = conv_grad_partials(p, p.passes[0]);
     return MIFFT_OK;
 }
 

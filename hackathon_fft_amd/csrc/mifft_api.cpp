@@ -32,6 +32,7 @@ size_t Plan::in_row_bytes() const {
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
+    if (stft() && conv_grad) return 0;  // (the result is no row per batch entry: mifft_plan_out_bytes)
     if (stft() && conv_D) return (size_t)conv_Lo * dtype_size(out_dtype);
     if (stft() && mdct) return (size_t)(stft_frames() * mdct) * dtype_size(out_dtype);
     if (stft() && spec_power) return (size_t)(stft_frames() * stft_out_width()) * dtype_size(out_dtype);
@@ -133,6 +134,47 @@ static int unpack_gated_args(const Plan& p, const void*& x, const void*& pregate
     return MIFFT_OK;
 }
 
+// The exec of a filter-gradient plan (conv.cpp; Plan::conv_grad): `x` is the HOST address of a mifft_conv_grad_args, refused
+// without a launch as above.  On success `x` and `gy` are the two inputs.
+static int unpack_conv_grad_args(const void*& x, const void*& gy) {
+    static const char* kHow =
+        "the exec of a filter-gradient plan takes the host address of a mifft_conv_grad_args (magic, x, gy) in the place of "
+        "x: include/mifft.h";
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, x) != hipSuccess)
+        (void)hipGetLastError();  // (memory the runtime has never seen: host memory)
+    else if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray)
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("x is a device address: ") + kHow);
+    const mifft_conv_grad_args* g = (const mifft_conv_grad_args*)x;
+    if (g->magic != MIFFT_CONV_GRAD_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + kHow);
+    if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.x is NULL");
+    if (!g->gy) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.gy is NULL");
+    gy = g->gy;
+    x = g->x;
+    return MIFFT_OK;
+}
+
+// the bytes of a filter-gradient plan's result: (P D, n / 2 + 1) complex values
+static size_t conv_grad_out_bytes(const Plan& p) {
+    return (size_t)(p.conv_P * p.conv_D) * (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
+}
+
+static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first, int64_t count, void* stream) {
+    if (first != 0 || count != p.batch)
+        return set_error(MIFFT_ERR_BAD_BATCH, "the exec of a filter-gradient plan covers the whole batch (first = 0, count = batch): "
+                                              "a slab would be a partial sum");
+    const void* gy = nullptr;
+    if (const int rc = unpack_conv_grad_args(x, gy)) return rc;
+    const char *xb = (const char*)x, *gb = (const char*)gy, *ob = (const char*)out;
+    const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv_Lo * dtype_size(p.out_dtype),
+                 on = conv_grad_out_bytes(p);
+    if (xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
+    if (gb < ob + on && ob < gb + gn) return set_error(MIFFT_ERR_ALIAS, "gy and out must not overlap");
+    DeviceGuard guard(p.device);
+    MIFFT_HIP_TRY(guard.err);
+    return launch_jit_conv_grad(p, p.passes[0], x, gy, out, (hipStream_t)stream);
+}
+
 static int device_count_quiet() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {
@@ -212,7 +254,10 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     const bool imdct = !fwd && imdct_detect(ndim, bases_flat, bases_len);
     // (a payload that STARTS with MIFFT_CONV_TAG: the fused FFT convolution of rows of dims[0] samples at length dims[1])
     const bool conv = fwd && conv_detect(ndim, bases_flat, bases_len);
-    int rc = conv    ? conv_check(p, bases_flat, bases_len, user, why)
+    // (or with MIFFT_CONV_GRAD_TAG: the filter gradient of such a convolution)
+    const bool wgrad = fwd && conv_grad_detect(ndim, bases_flat, bases_len);
+    int rc = wgrad   ? conv_grad_check(p, bases_flat, bases_len, user, why)
+             : conv  ? conv_check(p, bases_flat, bases_len, user, why)
              : mdct  ? mdct_check(p, bases_flat, bases_len, window, user, why)
              : imdct ? imdct_check(p, bases_flat, bases_len, window, gain, user, why)
              : fwd   ? stft_check(p, why)
@@ -222,7 +267,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     const int64_t n = mdct || imdct ? dims[td] / 4 : dims[td], frames = fwd ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
     p.prod = frames * (mdct ? p.mdct : imdct ? p.imdct : n);  // (the rows the one pass transforms)
     p.prod_half = mdct || imdct ? p.prod : frames * (n / 2 + 1);
-    if (fwd && !mdct && !conv) {
+    if (fwd && !mdct && !conv && !wgrad) {
         rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, post, user, why);
         if (rc) return fail(rc, why);
     }
@@ -233,7 +278,8 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     p.stage_radices = ordered;  // (the other dims are framed / overlap-added, not transformed: no stages)
     rc = open_device(p, guard);
     if (rc) return rc;
-    rc = conv    ? build_conv(p, ordered[td], processed[td], why)
+    rc = wgrad   ? build_conv_grad(p, ordered[td], processed[td], why)
+         : conv  ? build_conv(p, ordered[td], processed[td], why)
          : mdct  ? build_mdct(p, ordered[td], processed[td], window, why)
          : imdct ? build_imdct(p, ordered[td], processed[td], window, gain, why)
          : fwd   ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
@@ -463,6 +509,10 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     const Plan& p = plan->p;
     if (first < 0 || count < 0 || first + count > p.batch)
         return set_error(MIFFT_ERR_BAD_BATCH, "batch range out of bounds");
+    if (p.conv_grad) {  // (`x`: the HOST address of the exec's mifft_conv_grad_args; the whole batch or nothing)
+        if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
+        return exec_conv_grad(p, x, out, first, count, stream);
+    }
     if (count == 0) return MIFFT_OK;
     if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
     const void *pregate = nullptr, *postgate = nullptr;
@@ -560,6 +610,7 @@ size_t mifft_plan_in_bytes(const mifft_plan* plan) {
 }
 
 size_t mifft_plan_out_bytes(const mifft_plan* plan) {
+    if (plan && plan->p.conv_grad) return conv_grad_out_bytes(plan->p);
     return plan ? (size_t)plan->p.batch * plan->p.out_row_bytes() : 0;
 }
 

@@ -114,6 +114,8 @@ struct DimPass {
     // TileCfg::CONV of a packed-row (r2c) pass: rows of dims[0] samples are convolved with the plan's filter spectra in the one
     // launch (conv.cpp); d_twiddle and d_aux are the r2c tables, N is the FFT length
     bool conv = false;
+    // TileCfg::WGRAD beside it: the pass is the filter gradient of that convolution (conv.cpp), launched by launch_jit_conv_grad
+    bool wgrad = false;
     // TileCfg::ISTFT of a C2R pass: `outer` frames per batch entry are overlap-added into dims[0] samples; d_aux2 holds the
     // synthesis table (N values), d_aux3 the reciprocal envelope (N + hop (outer - 1) values), both of the plan's float type
     bool istft = false;
@@ -209,6 +211,11 @@ struct Plan {
     // the postgate (one of out's shape that multiplies the result as it is stored); the tensors are arguments of every exec
     // (mifft_gated_args), never plan state.  Its word 8 is F: 0 the single block (conv_S = 0), >= 1 overlap-save.  0: ungated.
     uint32_t conv_gates = 0;
+    // The MIFFT_CONV_GRAD_TAG payload: the plan computes the filter gradient of the convolution the fields above describe
+    // (conv_h unused) as conv_P partial sums per channel: x and gy (mifft_conv_grad_args) -> (conv_P conv_D, n / 2 + 1)
+    // complex values, unscaled.  A single block has conv_S = 0, conv_F = 1, conv_s0 = 0 as in the forward plan.
+    bool conv_grad = false;
+    int64_t conv_P = 0;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
     bool dct4 = false;
     // a MIFFT_FLAG_DCT / MIFFT_FLAG_DCT_ND plan whose `bases` start with MIFFT_DST_TAG (DST-II and its inverse, along every
@@ -407,6 +414,12 @@ bool conv_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_conv_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void* out, const void* pregate,
                     const void* postgate, int64_t first, int64_t count, hipStream_t stream);
+// The filter-gradient plans (MIFFT_CONV_GRAD_TAG): the same trio and the launch of the whole batch; build_conv_grad picks P where the payload says 0
+// for a built pass (pure arithmetic on its tile and the device's size).
+bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
+int conv_grad_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
+int build_conv_grad(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
+int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, const void* gy, void* out, hipStream_t stream);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }

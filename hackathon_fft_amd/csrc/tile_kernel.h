@@ -248,6 +248,10 @@ struct TileParams {
     // c .. c + ols_step - 1 of its result to out[f * ols_step ..] of its signal's row, up to Lo.  spec_bands counts signals,
     // not launch rows: signal b of the launch takes filter row (spec_bands + b) % D.
     int ols_step, ols_blocks, ols_start;
+    // WGRAD configurations (the filter gradient of CONV / OLS) keep CONV's mapping and always carry the three ols_* fields
+    // (a single block: ols_blocks = 1, ols_start = 0, ols_step = Lo); `in` is x, gate_in is gy (rows of stft_frames = Lo
+    // reals), n_rows the pairs of ONE channel, B F, and spec_bands the partials P: workgroup w is slice w % P of channel
+    // w / P and stores row (w % P) D + w / P of `out`, (P D) rows of N + 1 complex values.
     // GATE configurations (CONV / OLS with elementwise gates; the arguments of one exec, not plan state): gate_in has the
     // shape of `in` (rows of stft_len reals) and multiplies every sample as it is loaded, gate_out the shape of `out` (rows of
     // stft_frames reals) and multiplies every sample as it is stored.  Both point, as `in` and `out` do, at the exec's first
@@ -350,7 +354,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
-          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0>
+          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -597,6 +601,20 @@ struct TileCfg {
     // stored, in pairs, and real by real elsewhere; the gate load stands beside the access it accompanies, issued with it.
     static constexpr int GATE = GATE_;
     static_assert(GATE_ >= 0 && GATE_ <= 3 && (GATE_ == 0 || CONV_), "GATE: the pregate (1) and postgate (2) of a CONV tile");
+    // WGRAD (with CONV, ungated): the filter gradient of the convolution, gk[d][j] = sum over the rows r of channel d and the
+    // samples t of gy[r][t] x[r][t - j], as the sum over PAIRS (signal row r, block f) of conj(U) G, U and G the half spectra
+    // of the u-block the forward block loaded (CONV's / OLS's load) and of the g-block -- the part of gy the forward block
+    // stored, put back where the block had it: gb[i] = gy[r][f S + i - c] for c <= i < c + S, f S + i - c < Lo, zero elsewhere.
+    // The exact adjoint of the forward block, circular where that is.  A grid of D P persistent workgroups, workgroup
+    // (d, s) walking slice s of the B F pairs of channel d -- contiguous, ascending, lengths differing by one at most -- TILE
+    // pairs at a time: load the u-blocks, passes, every work item unpacks the bin pairs (k, N - k) it owns into registers,
+    // barrier, the g-blocks into the same LDS, passes, unpack, multiply by the conjugates of the held values and add into
+    // register accumulators per (tile row, bin pair).  At the end the TILE rows are summed in ascending order through the
+    // tile's own LDS and row (s D + d) of N + 1 bins is stored, unscaled, once (conjugated when the forward correlated).
+    // x and gy are read once each; no spectrum of a row reaches memory, no scratch, no atomics; the order of every sum is
+    // fixed by the plan, so the result is bit-identical from run to run.  wgrad_walk below; the main tile loop is not run.
+    static constexpr bool WGRAD = WGRAD_;
+    static_assert(!WGRAD_ || (CONV_ && GATE_ == 0), "WGRAD: the filter-gradient twin of an ungated CONV / OLS tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -1558,6 +1576,145 @@ MIFFT_DEV void run_pass(const TileParams& p, cpx<typename C::T>* lds, const cpx<
     }
 }
 
+// The walk of a TileCfg::WGRAD workgroup (see there): the whole kernel body behind the table set-up.
+template <class C>
+MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx<typename C::T>* twr, const int tid_entry) {
+    using T = typename C::T;
+    using V = cpx<T>;
+    constexpr int PAIRS = C::N / 2 + 1;
+    constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
+    const int D = p.stft_center, P = p.spec_bands;
+    const int d = (int)blockIdx.x / P, sl = (int)blockIdx.x - d * P;
+    // slice sl of the channel's pairs: a contiguous ascending range
+    const long long Q = p.n_rows, len = Q / P, rem = Q - len * P;
+    long long q = sl * len + (sl < rem ? sl : rem);
+    const long long q_end = q + len + (sl < rem ? 1 : 0);
+    const int F = C::OLS ? p.ols_blocks : 1, S = p.ols_step, s0 = C::OLS ? p.ols_start : 0;
+    const int c0 = p.stft_hop, Lo = p.stft_frames, L = p.stft_len;
+    const T* x = (const T*)p.in;
+    const T* gy = (const T*)p.gate_in;
+    const V* w = (const V*)p.r2c_tw;
+    V acc_a[IT], acc_b[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) acc_a[i] = acc_b[i] = {(T)0, (T)0};
+    V cur[1][C::R(0)];
+    int tid = tid_entry;
+    // X[k] and X[N-k] of the row the item owns, as the R2C store unpacks them (zeros past the last item)
+    auto unpack = [&](int i, V& xa, V& xb) {
+        const int f = tid + i * C::THREADS;
+        xa = xb = {(T)0, (T)0};
+        if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
+            const int c = f / PAIRS, k = f - c * PAIRS, m = k ? C::N - k : 0;
+            const V zk = lds[lds_index<C, C::NP - 1>(c, k)], zm = lds[lds_index<C, C::NP - 1>(c, m)];
+            const T ex = (T)0.5 * (zk.x + zm.x), ey = (T)0.5 * (zk.y - zm.y);
+            const T ox = (T)0.5 * (zk.y + zm.y), oy = (T)-0.5 * (zk.x - zm.x);
+            const V wk = w[k];
+            const T tx = wk.x * ox - wk.y * oy, ty = wk.x * oy + wk.y * ox;
+            xa = {ex + tx, ey + ty};
+            xb = {ex - tx, ty - ey};
+        }
+    };
+    for (; q < q_end; q += C::TILE) {
+        const int nv = q_end - q < C::TILE ? (int)(q_end - q) : C::TILE;
+        tid = tid_entry;  // (opaque once per step, as in tile_kernel: the offsets derived from it are not kept live across steps)
+#ifndef MIFFT_NO_OPAQUE_TID
+        if constexpr (C::OPAQUE_TID) asm volatile("" : "+v"(tid));
+#endif
+        // (signal of the channel, block) of the tile's first pair once, uniform; a pair further on wraps into the next signals
+        const long long b0 = q / F;
+        const int fr0 = (int)(q - b0 * F);
+        // u-blocks: packed element m of pair c holds the samples s0 + fr S + 2 m and + 1 of its row, zeros outside [0, L)
+        for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
+            const int c = f / C::N, m = f - c * C::N;
+            V v = {(T)0, (T)0};
+            if (c < nv) {
+                int fr = fr0 + c, db = 0;
+                if (fr >= F) {
+                    db = fr / F;
+                    fr -= db * F;
+                }
+                const T* xe = x + ((b0 + db) * D + d) * (long long)L;
+                const int i = s0 + fr * S + 2 * m;
+                if (i >= 0 && i + 1 < L) {
+                    v = gload_pair(xe + i);
+                } else {
+                    if (i >= 0 && i < L) v.x = xe[i];
+                    if (i + 1 >= 0 && i + 1 < L) v.y = xe[i + 1];
+                }
+            }
+            lds[lds_index<C, -1>(c, m)] = v;
+        }
+        __syncthreads();
+        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        V ua[IT], ub[IT];
+#pragma unroll
+        for (int i = 0; i < IT; ++i) unpack(i, ua[i], ub[i]);
+        __syncthreads();
+        // g-blocks: sample i of the block is gy[row][fr S + i - c] for c <= i < c + S and fr S + i - c < Lo, zero elsewhere
+        for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
+            const int c = f / C::N, m = f - c * C::N;
+            V v = {(T)0, (T)0};
+            if (c < nv) {
+                int fr = fr0 + c, db = 0;
+                if (fr >= F) {
+                    db = fr / F;
+                    fr -= db * F;
+                }
+                const int u = 2 * m - c0, t = fr * S + u;
+                const bool w0 = u >= 0 && u < S && t < Lo, w1 = u + 1 >= 0 && u + 1 < S && t + 1 < Lo;
+                const T* ge = gy + ((b0 + db) * D + d) * (long long)Lo;
+                if (w0 && w1) {
+                    v = gload_pair(ge + t);
+                } else {
+                    if (w0) v.x = ge[t];
+                    if (w1) v.y = ge[t + 1];
+                }
+            }
+            lds[lds_index<C, -1>(c, m)] = v;
+        }
+        __syncthreads();
+        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            V ga, gb;
+            unpack(i, ga, gb);
+            // conj(U) G
+            acc_a[i].x += ua[i].x * ga.x + ua[i].y * ga.y;
+            acc_a[i].y += ua[i].x * ga.y - ua[i].y * ga.x;
+            acc_b[i].x += ub[i].x * gb.x + ub[i].y * gb.y;
+            acc_b[i].y += ub[i].x * gb.y - ub[i].y * gb.x;
+        }
+        __syncthreads();
+    }
+    // the TILE rows in ascending order, through the tile's LDS: first the bins k, then the bins N - k
+    V* out = (V*)p.out + ((long long)sl * D + d) * (C::N + 1);
+    const T cj = (p.spec_q & 1) ? (T)-1 : (T)1;
+    static_assert(C::TILE * PAIRS <= C::DATA_ELEMS, "WGRAD: one accumulator per (row, bin pair) fits the tile");
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            const int f = tid + i * C::THREADS;
+            if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) lds[f] = half ? acc_b[i] : acc_a[i];
+        }
+        __syncthreads();
+        for (int k = tid; k < PAIRS; k += C::THREADS) {
+            V s = lds[k];
+            for (int c = 1; c < C::TILE; ++c) {
+                const V a = lds[c * PAIRS + k];
+                s.x += a.x;
+                s.y += a.y;
+            }
+            s.y *= cj;
+            if (half == 0)
+                out[k] = s;
+            else if (2 * k != C::N)
+                out[C::N - k] = s;  // (k = 0: bin N)
+        }
+        __syncthreads();
+    }
+}
+
 template <class C>
 __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TileParams p) {
     using T = typename C::T;
@@ -1611,6 +1768,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
     }
 
     MIFFT_STAMP(C, -1);
+    if constexpr (C::WGRAD) {  // (the filter gradient walks pairs of blocks, not tiles of rows: its own loop)
+        wgrad_walk<C>(p, lds, twr, tid0);
+        return;
+    }
     V pre[C::PREFETCH ? C::IPT(0) : 1][C::R(0)];
     // this workgroup's tiles: t, t + t_step, ... < t_end
     long long t = blockIdx.x, t_end = p.n_tiles, t_step = gridDim.x;

@@ -595,6 +595,56 @@ typedef struct mifft_gated_args {
     const void* postgate; /* out's shape and dtype, or NULL where the plan has no postgate */
 } mifft_gated_args;
 
+/*
+ * THE FILTER GRADIENT of such a convolution (no reference counterpart): a MIFFT_FLAG_STFT plan -- that bit alone, as above --
+ * whose 16-word payload starts with MIFFT_CONV_GRAD_TAG.  dims = {L, n} (overlap-save: {T, n}), batch signal rows as in the
+ * forward plan.  With u = the rows the forward plan read (x, or a . x) and gv = the gradient of what it stored (gy, or
+ * b . gy), the plan computes
+ *     A[p][d][k] = sum over the pairs (row r, block f) of channel d (r % D == d) in slice p of  conj(U[k]) G[k],   0 <= k <= n / 2,
+ * U = rfft(u-block, n) of the n samples s0 + f S .. of row r that the forward block loaded (zeros outside the row), G =
+ * rfft(g-block, n) of the part of gv the forward block stored, put back where the block had it: g-block[i] =
+ * gv[r][f S + i - c] for c <= i < c + S with f S + i - c < Lo, zero elsewhere.  Unscaled; with mode bit 0 (the forward
+ * correlated) the conjugate is stored, so that irfft(sum_p A[p][d], n)[0 .. K) is the gradient of filter row d in both
+ * cases -- the exact adjoint of the forward blocks, circular where they are -- and its lag 0 the gradient of a skip term.
+ *     word  0, 1   MIFFT_CONV_GRAD_TAG_LO, MIFFT_CONV_GRAD_TAG_HI
+ *     word  2      D >= 1 filter rows, batch % D == 0
+ *     word  3      c: the first stored sample of every block (a single block: the forward plan's o)
+ *     word  4      S: the samples stored per block (a single block: Lo), S >= 1, c + S <= n
+ *     word  5      mode: bit 0, the forward plan correlated
+ *     word  6      F >= 1 blocks per row, (F - 1) S < Lo <= F S
+ *     word  7      s0: the first sample of block 0 (signed), -n < s0 and s0 + (F - 1) S < L
+ *     word  8      Lo >= 1: samples per row of gv
+ *     word  9      P: partial sums per channel, 1 <= P <= min(65535, batch / D * F); 0: the library picks it, so that D P
+ *                  workgroups fill the device when D alone does not
+ *     word 10 .. 15 reserved, 0
+ * A single block is F = 1, s0 = 0, S = Lo, c = o with L <= n; anything else runs the overlap-save geometry (2 <= T <= 2^30).
+ * x is (batch, L, 1) real, gv (batch, Lo, 1) real, out (P D, n / 2 + 1, 2), all of the plan's float type (in_dtype ==
+ * out_dtype, in_components = 1, inverse = 0).  ONE launch of D P persistent workgroups, no scratch, no atomics: workgroup
+ * (d, p) walks a contiguous, ascending slice of the batch / D * F pairs of channel d (lengths differ by one at most), keeps
+ * its sums in registers and stores row p D + d once.  x and gv are read once each; the sum of a channel runs in an order
+ * the plan fixes (shape and P), so two execs give the same bits.  The kernel is TileCfg::WGRAD on the CONV / OLS tile:
+ * rows<n>[_f64]_r2c_<radices>_wgrad[_ols]_jit, run time only (MIFFT_JIT=0 refuses the plan).
+ * THE EXEC takes the HOST address of a mifft_conv_grad_args in the place of x, as a gated plan takes its block:
+ *     mifft_conv_grad_args g = { MIFFT_CONV_GRAD_ARGS_MAGIC, x, gv };   mifft_exec(plan, &g, out, stream);
+ * and covers the whole batch: first != 0 or count != batch is MIFFT_ERR_BAD_BATCH (a slab would be a partial sum).  A
+ * device address or a block without the magic word is MIFFT_ERR_UNSUPPORTED, a null member MIFFT_ERR_NULL, x or gv
+ * overlapping out MIFFT_ERR_ALIAS; nothing is launched in any of these cases.  mifft_plan_pass_geometry(plan, 1, batch, g)
+ * answers {tile (pairs per step), threads, steps of all workgroups, grid = D P}: P is grid / D.  mifft_plan_out_bytes() is
+ * the size of the (P D, n / 2 + 1, 2) result.
+ * Refused before any device work, with the forward plan's statuses: the flag, direction, dtype and component checks, the
+ * limits of n (even, 8 .. 16384, float64 to 12288, n / 2 without a prime factor above 32), D and batch % D; MIFFT_ERR_BAD_BASES for the geometry rules above, a mode word beyond bit 0, P beyond its range or a non-zero
+ * reserved word.  The 8-, 12- and 16-word MIFFT_CONV_TAG payloads are what they were.
+ */
+#define MIFFT_CONV_GRAD_TAG_LO 0x44524701u
+#define MIFFT_CONV_GRAD_TAG_HI 0x7FF84D47u
+/* the argument block of a filter-gradient exec (above); the magic word is "MIFFTWG1" */
+#define MIFFT_CONV_GRAD_ARGS_MAGIC 0x314757544646494Dull
+typedef struct mifft_conv_grad_args {
+    uint64_t magic;  /* MIFFT_CONV_GRAD_ARGS_MAGIC */
+    const void* x;   /* (batch, L, 1) reals on the plan's device: what the forward plan read */
+    const void* gy;  /* (batch, Lo, 1) reals: the gradient of what it stored */
+} mifft_conv_grad_args;
+
 typedef struct mifft_plan mifft_plan;
 
 /*

@@ -202,6 +202,17 @@ constexpr uint64_t kConvTag = ((uint64_t)MIFFT_CONV_TAG_HI << 32) | MIFFT_CONV_T
 // exec: mifft_exec_batch takes the host address of a mifft_gated_args {MIFFT_GATED_ARGS_MAGIC, x, pregate, postgate} as its x.)
 static_assert(MIFFT_GATED_ARGS_MAGIC == 0x314147544646494Dull && sizeof(mifft_gated_args) == 8 + 3 * sizeof(void*),
               "mifft_gated_args is the magic word \"MIFFTGA1\" and three pointers");
+// MIFFT_CONV_GRAD_TAG in front of 16 words -- TAG | D | c | S | mode | F | s0 | Lo | P | 0 x 6 -- on the same kind of plan: the
+// filter gradient of such a convolution, x (batch, L, 1) and gy (batch, Lo, 1) -> out (P D, n / 2 + 1, 2), unscaled partial
+// sums of conj(U) G per channel.  The exec takes the host address of a mifft_conv_grad_args {MIFFT_CONV_GRAD_ARGS_MAGIC, x, gy}
+// as its x and covers the whole batch (include/mifft.h).
+static_assert(MIFFT_CONV_GRAD_TAG_LO == 0x44524701u && MIFFT_CONV_GRAD_TAG_HI == 0x7FF84D47u &&
+                  (MIFFT_CONV_GRAD_TAG_HI & 0x7FF80000u) == 0x7FF80000u && MIFFT_CONV_GRAD_TAG_HI != MIFFT_CONV_TAG_HI &&
+                  MIFFT_CONV_GRAD_TAG_HI != MIFFT_MDCT_TAG_HI && MIFFT_CONV_GRAD_TAG_HI != MIFFT_STFT_EXT_TAG_HI,
+              "MIFFT_CONV_GRAD_TAG is the quiet NaN 0x7FF84D4744524701, distinct from the other payload tags");
+constexpr uint64_t kConvGradTag = ((uint64_t)MIFFT_CONV_GRAD_TAG_HI << 32) | MIFFT_CONV_GRAD_TAG_LO;
+static_assert(MIFFT_CONV_GRAD_ARGS_MAGIC == 0x314757544646494Dull && sizeof(mifft_conv_grad_args) == 8 + 2 * sizeof(void*),
+              "mifft_conv_grad_args is the magic word \"MIFFTWG1\" and two pointers");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
