@@ -527,6 +527,7 @@ class Plan:
     Nine values, (n, D, c, S, mode, address, F, s0, Lo), are the overlap-save form (the 12-word payload): x (batch, T, 1) with
     T possibly beyond n, F blocks of n samples per row, block f from sample s0 + f S on, of whose circular result the S
     samples from c on are stored at f S of the row's Lo output samples.
+    ``conv`` with Q and P behind the nine values: partitioned overlap-save, the 20-word payload (plan_fftconv(partition=)).
     ``conv_gates`` = 1, 2 or 3 beside either form: the 16-word payload, bit 0 a pregate of x's shape multiplied into the load,
     bit 1 a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run)."""
 
@@ -620,13 +621,15 @@ class Plan:
             stft, istft = True, False
         if conv is not None:  # (with any other mode as well: the library refuses the pair)
             conv = tuple(int(v) for v in conv)
-            ols = len(conv) == 9  # (overlap-save: n, D, c, S, mode, address, F, s0, Lo; the 12-word payload)
-            if len(conv) not in (6, 9):
-                raise MifftError(-5, f"conv = (n, D, o, Lo, mode, address) or (n, D, c, S, mode, address, F, s0, Lo), got {len(conv)} values")
+            part = len(conv) == 11  # (partitioned overlap-save: the nine values, then Q and P; the 20-word payload)
+            ols = len(conv) == 9 or part  # (overlap-save: n, D, c, S, mode, address, F, s0, Lo; the 12-word payload)
+            if len(conv) not in (6, 9, 11):
+                raise MifftError(-5, "conv = (n, D, o, Lo, mode, address), (n, D, c, S, mode, address, F, s0, Lo) or the latter with "
+                                     f"Q and P behind it, got {len(conv)} values")
             n_fft, D, o, Lo, mode, addr = conv[:6]
             step = Lo
             if ols:
-                blocks, start, Lo = conv[6:]
+                blocks, start, Lo = conv[6:9]
             if len(in_shape) != 3 or len(out_shape) != 3 or in_shape[-1] != 1 or out_shape[-1] != 1:
                 raise MifftError(-1, f"convolution layouts are (batch, L, 1) -> (batch, Lo, 1), got {in_shape} -> {out_shape}")
             if in_shape[0] != out_shape[0] or out_shape[1] != Lo:
@@ -646,6 +649,11 @@ class Plan:
                 if conv_gates not in (1, 2, 3):
                     raise MifftError(-5, f"conv_gates = {conv_gates}: bit 0 the pregate, bit 1 the postgate (1, 2 or 3)")
                 words = (words + [0, 0, 0])[:11] + [int(conv_gates), 0, 0, 0, 0]
+            if part:  # (words 16 and 17 behind the 16 of the gated form, whose gates word 11 may be 0 here)
+                for v, what in ((conv[9], "Q"), (conv[10], "P")):
+                    if not 0 <= v < 1 << 32:
+                        raise MifftError(-5, f"{what} = {v} of a convolution plan does not fit an unsigned 32-bit word")
+                words = (words + [0] * 4)[:16] + [conv[9], conv[10], 0, 0]
             flags = (int(flags) | FLAG_STFT | (FLAG_ISTFT if istft else 0) | (FLAG_DCT_ND if dctn else 0) |
                      (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
                      (FLAG_STFT_POWER if stft_power is not None else 0))
@@ -1686,7 +1694,7 @@ def fftconv_block(K: int, dtype=torch.float32) -> int:
     to 16384 (float64: 8192) with n >= 2 (K - 1), the one with the least w(n) n / (n - K + 1) -- the block samples transformed
     per stored sample, times w(n), the measured time per block sample of the kernel of that length (_FFTCONV_BLOCK_COST;
     DESIGN.md 3.4n) --, the smaller on a tie.  MifftError when there is none (K > 8193, float64 4097): a filter longer than half a block needs
-    partitioned convolution, which is out of scope."""
+    partitioned convolution (``partition=``; fftconv_partition)."""
     K = int(K)
     if dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"fftconv_block: float32 or float64, got {dtype}")
@@ -1701,8 +1709,28 @@ def fftconv_block(K: int, dtype=torch.float32) -> int:
     if best is None:
         raise MifftError(ERR_UNSUPPORTED, f"fftconv_block({K}): no block of up to {8192 if dtype == torch.float64 else _FFTCONV_MAX} "
                                           "points holds two filter lengths; filters longer than half a block need partitioned "
-                                          "convolution, which is out of scope")
+                                          "convolution: fftconv(..., partition=\"auto\") or plan_fftconv(..., taps=K, partition=Q) "
+                                          "(see fftconv_partition)")
     return best
+
+
+def fftconv_partition(K: int, dtype=torch.float32) -> tuple:
+    """(n, Q) of the partitioned convolution ``fftconv(partition="auto")`` picks for a filter of ``K`` taps that no
+    overlap-save block holds: ``n`` the largest power-of-two block of ``dtype`` (16384; float64 8192) and ``Q = n // 2 + 1`` taps
+    per partition, so that every block of n samples stores S = n - Q + 1 = n // 2 samples and the filter has
+    P = ceil(K / Q) partitions -- the fewest transforms per stored sample among the pairs (n, Q).  The rule
+    does not look at K; MifftError for K < 1, for more than 2^30 taps after rounding up to whole partitions, or for another
+    dtype."""
+    K = int(K)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"fftconv_partition: float32 or float64, got {dtype}")
+    if K < 1:
+        raise MifftError(-2, f"fftconv_partition: a filter of K = {K} taps (at least 1)")
+    n = 8192 if dtype == torch.float64 else _FFTCONV_MAX
+    Q = n // 2 + 1
+    if -(-K // Q) * Q > 1 << 30:
+        raise MifftError(ERR_UNSUPPORTED, f"fftconv_partition({K}): more than 2^30 taps in whole partitions of {Q}")
+    return n, Q
 
 
 class ConvPlan(Plan):
@@ -1712,20 +1740,30 @@ class ConvPlan(Plan):
     An overlap-save plan (``plan_fftconv(taps=K)``) has ``taps`` = K, ``step`` = n - K + 1 samples stored per block and
     ``blocks`` per row; a single-block plan has ``taps`` and ``step`` None and one block.
     A gated plan (``plan_fftconv(pregate=True)`` and / or ``postgate=True``) has ``pregate`` / ``postgate`` True and runs
-    through ``run``, which takes the gate tensors of that exec; ``fft(out, x, plan=plan)`` refuses it."""
+    through ``run``, which takes the gate tensors of that exec; ``fft(out, x, plan=plan)`` refuses it.
+    A partitioned plan (``plan_fftconv(taps=K, partition=Q)``) has ``partition`` = Q taps per partition, ``partitions`` =
+    ceil(K / Q), ``step`` = n - Q + 1 and a ``filter_spectrum`` of (channels, partitions, n // 2 + 1, 2): partition p holds
+    rfft(k[p Q : (p + 1) Q], n).  ``partition`` is None and ``partitions`` 1 on every other plan."""
 
     def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, pregate=False,
-                 postgate=False):
+                 postgate=False, partition=None):
         self.ctx = ctx
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         self.taps, self.step, self.blocks = taps, None, 1
+        self.partition, self.partitions = partition, 1
         self.pregate, self.postgate = bool(pregate), bool(postgate)
+        if partition is not None:
+            self.partitions = -(-taps // partition)
         with torch.cuda.stream(ctx.stream):
-            self.filter_spectrum = torch.zeros((channels, n // 2 + 1, 2), dtype=dtype, device=f"cuda:{ctx.device}")
+            shape = (channels, n // 2 + 1, 2) if partition is None else (channels, self.partitions, n // 2 + 1, 2)
+            self.filter_spectrum = torch.zeros(shape, dtype=dtype, device=f"cuda:{ctx.device}")
         mode, addr = 1 if correlate else 0, self.filter_spectrum.data_ptr()
         if taps is None:
             conv = (n, channels, offset, out_length, mode, addr)
+        elif partition is not None:
+            c, self.step, s0, self.blocks, P = _fftconv_part_geometry(n, partition, taps, offset, out_length, correlate)
+            conv = (n, channels, c, self.step, mode, addr, self.blocks, s0, out_length, partition, P)
         else:
             c, self.step, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
             conv = (n, channels, c, self.step, mode, addr, self.blocks, s0, out_length)
@@ -1767,6 +1805,18 @@ class ConvPlan(Plan):
         if k.dim() == 2 and k.shape[0] != self.channels:
             raise MifftError(-2, f"set_filter: {k.shape[0]} filters for {self.channels} channels")
         K = int(k.shape[-1])
+        if self.partition is not None:  # (P spectra per channel: partition p is rfft(k[p Q : (p + 1) Q], n), the last zero-filled)
+            P, Q = self.partitions, self.partition
+            if K < 1 or K > self.taps:
+                raise MifftError(-2, f"set_filter: a filter of K = {K} taps on a partitioned plan of taps = {self.taps} (1 <= K <= taps)")
+            with torch.cuda.stream(self.ctx.stream):
+                kq = torch.zeros((self.channels, P * Q), dtype=self.out_dtype, device=self.filter_spectrum.device)
+                kq[:, :K] = k.to(device=kq.device, dtype=self.out_dtype)
+                kp = torch.zeros((self.channels * P, self.n), dtype=self.out_dtype, device=kq.device)
+                kp[:, :Q] = kq.reshape(self.channels * P, Q)
+                H = rfftn(kp, onesided=True)
+                self.filter_spectrum.copy_(torch.view_as_real(H).reshape(self.filter_spectrum.shape))
+            return
         if K < 1 or K > self.n:
             raise MifftError(-2, f"set_filter: a filter of K = {K} taps does not fit the FFT length n = {self.n} (1 <= K <= n)")
         if self.taps is not None and K > self.taps:
@@ -1781,17 +1831,22 @@ class ConvPlan(Plan):
     def add_skip(self, d) -> None:
         """adds the skip term ``d`` -- a float, or a real (channels,) tensor -- to every bin of ``filter_spectrum``, on the
         plan's stream: conv(x, h) + d x = conv(x, h') with h'[0] = h[0] + d, whose spectrum is H + d (d is real, so the same
-        holds for the conjugate a correlation multiplies by).  Call it after ``set_filter``, which overwrites the spectrum."""
+        holds for the conjugate a correlation multiplies by).  Call it after ``set_filter``, which overwrites the spectrum.
+        On a partitioned plan d goes to partition 0 alone, which holds tap 0."""
         with torch.cuda.stream(self.ctx.stream):
             if isinstance(d, torch.Tensor):
                 if d.is_complex() or tuple(d.shape) != (self.channels,):
                     raise MifftError(-2, f"add_skip expects a float or a real ({self.channels},) tensor, got {tuple(d.shape)} {d.dtype}")
                 d = d.to(device=self.filter_spectrum.device, dtype=self.out_dtype).reshape(self.channels, 1)
-            self.filter_spectrum[:, :, 0] += d
+            if self.partition is not None:
+                self.filter_spectrum[:, 0, :, 0] += d
+            else:
+                self.filter_spectrum[:, :, 0] += d
 
     def set_filter_spectrum(self, Hc: "torch.Tensor") -> None:
         """copies a spectrum the caller already holds -- complex (channels, n // 2 + 1) or interleaved (.., 2), the
-        unnormalised rfft(k, n) -- into ``filter_spectrum``, on the plan's stream"""
+        unnormalised rfft(k, n); on a partitioned plan (channels, partitions, n // 2 + 1), one spectrum per partition -- into
+        ``filter_spectrum``, on the plan's stream"""
         Hr = torch.view_as_real(Hc) if Hc.is_complex() else Hc
         if tuple(Hr.shape) != tuple(self.filter_spectrum.shape):
             raise MifftError(-2, f"set_filter_spectrum expects {tuple(self.filter_spectrum.shape[:-1])} complex values, "
@@ -1808,9 +1863,34 @@ def _fftconv_ols_geometry(n: int, K: int, offset: int, out_length: int, correlat
     return c, S, offset - c, -(-out_length // S)
 
 
+def _fftconv_part_geometry(n: int, Q: int, K: int, offset: int, out_length: int, correlate: bool) -> tuple:
+    """(c, S, s0, F, P) of a partitioned plan: P = ceil(K / Q) partitions of Q taps; the overlap-save geometry of a filter of Q
+    taps -- S = n - Q + 1 samples per block free of wrap-around, from c = Q - 1 on (correlation: from 0 on)"""
+    return _fftconv_ols_geometry(n, Q, offset, out_length, correlate) + (-(-K // Q),)
+
+
+def _fftconv_part_check(who: str, n: int, taps, partition, length: int, offset: int, out_length: int, correlate: bool) -> tuple:
+    """the argument checks of a partitioned plan (``taps`` = K, ``partition`` = Q), before any device work: (K, Q)"""
+    if taps is None:
+        raise MifftError(-2, f"{who}: partition = {partition} goes with taps = K, the length of the filter")
+    K, Q = int(taps), int(partition)
+    if Q < 1 or Q > n - 1:
+        raise MifftError(-2, f"{who}: partition = {Q} taps per partition at the block length n = {n}: 1 <= partition <= n - 1")
+    if K < 1 or -(-K // Q) * Q > 1 << 30:
+        raise MifftError(-2, f"{who}: taps = {K} in partitions of {Q}: 1 <= taps, and at most 2^30 taps in whole partitions")
+    if length < 2 or length > 1 << 30:
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {length} samples: 2 <= length <= 2^30")
+    full = length if correlate else length + K - 1
+    if offset < 0 or out_length < 1 or offset + out_length > full or out_length > 1 << 30:
+        raise MifftError(-5, f"{who}: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length <= 2^30, "
+                             f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
+                             f"{length} samples with {K} taps)")
+    return K, Q
+
+
 def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
                  out_length: Optional[int] = None, correlate: bool = False, ctx: Optional[DeviceContext] = None,
-                 pregate: bool = False, postgate: bool = False) -> ConvPlan:
+                 pregate: bool = False, postgate: bool = False, partition: Optional[int] = None) -> ConvPlan:
     """Plan of the fused FFT convolution (no reference counterpart; MIFFT_CONV_TAG in include/mifft.h) of ``batch * channels``
     real rows of ``length`` samples, row-major (batch, channels, length), at the FFT length ``n`` (see fftconv_length):
     ``y[r] = irfft(rfft(x[r], n) * G[r % channels], n)[offset : offset + out_length]`` in ONE kernel launch, G the plan's
@@ -1826,6 +1906,10 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     ``y[r] = b[r] * conv(a[r] * x[r])`` with a tensor ``a`` of ``in_shape`` and / or ``b`` of ``out_shape`` given with every
     exec, multiplied into the kernel's load and store -- still one launch, no intermediate.  Such a plan runs through
     ``plan.run(out, x, pregate=a, postgate=b)``.  A skip term d * (a * x) is d added to every bin of ``filter_spectrum``.
+    ``partition=Q`` (with ``taps=K``) makes it a partitioned plan (the 20-word payload), for filters longer than half a block:
+    ``taps`` may then be any K >= 1, 1 <= Q <= n - 1; the filter is cut into ceil(K / Q) partitions of Q taps, every block of n
+    samples stores n - Q + 1, and the kernel transforms one shifted input block per live partition for every block it stores
+    -- still one launch and no intermediate, but the work grows with K / Q.  Gates as above (``run``); without them ``fft``.
     The plan-level API carries no autograd; ``plan_fftconv_grad`` of the same arguments is the plan of its filter gradient,
     and the opposite-``correlate`` plan on rows of ``out_length`` samples its input gradient (what ``fftconv`` does)."""
     batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
@@ -1837,6 +1921,12 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
         raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
                                           "n // 2 without a prime factor above 32): see fftconv_length")
+    if partition is not None:
+        taps, partition = _fftconv_part_check("plan_fftconv", n, taps, partition, length, offset, out_length, correlate)
+        if ctx is None:
+            ctx = DeviceContext()
+        return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, pregate=pregate,
+                        postgate=postgate, partition=partition)
     if taps is not None:
         taps = int(taps)
         if taps < 1 or taps > n - 1:
@@ -1892,6 +1982,35 @@ def _fftconv_pick(who: str, L: int, K: int, dtype, n: Optional[int], block: Opti
     return n, taps
 
 
+def _fftconv_pick_part(who: str, L: int, K: int, dtype, n: Optional[int], block: Optional[int], partition) -> tuple:
+    """(n, taps, Q): ``_fftconv_pick`` when ``partition`` is None (Q None: today's paths and refusals); an integer Q forces
+    the partitioned path at ``block`` (default: the largest power-of-two block of the dtype); "auto" takes the existing path
+    whenever there is one and fftconv_partition(K) otherwise.  ``partition`` excludes ``n``."""
+    if partition is None:
+        return _fftconv_pick(who, L, K, dtype, n, block) + (None,)
+    if n is not None:
+        raise ValueError(f"{who}: n is the FFT length of the single-block path, partition belongs to the blocks of the "
+                         "partitioned path (block=): not both")
+    if isinstance(partition, str):
+        if partition != "auto":
+            raise ValueError(f"{who}: partition is None, a number of taps per partition or \"auto\", got {partition!r}")
+        try:
+            return _fftconv_pick(who, L, K, dtype, None, block) + (None,)
+        except MifftError as e:
+            if e.status != ERR_UNSUPPORTED or block is not None or K <= (4097 if dtype == torch.float64 else 8193):
+                raise  # (a refusal of the arguments, not the want of a block that holds two filter lengths)
+        n, Q = fftconv_partition(K, dtype)
+    else:
+        Q = int(partition)
+        n = int(block) if block is not None else (8192 if dtype == torch.float64 else _FFTCONV_MAX)
+    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: block = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
+                                          "n // 2 without a prime factor above 32): see fftconv_length")
+    if Q < 1 or Q > n - 1:
+        raise MifftError(-2, f"{who}: partition = {Q} taps per partition does not fit blocks of {n} points (1 <= partition <= block - 1)")
+    return n, K, Q
+
+
 def _fftconv_window(mode: str, L: int, K: int) -> tuple:
     """(offset, out_length) of scipy.signal.fftconvolve's crops of the full convolution of L and K samples"""
     if mode == "causal":
@@ -1905,7 +2024,7 @@ def _fftconv_window(mode: str, L: int, K: int) -> tuple:
 
 def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mode: str = "causal",
             correlate: bool = False, block: Optional[int] = None, pregate: Optional["torch.Tensor"] = None,
-            postgate: Optional["torch.Tensor"] = None, skip=None) -> "torch.Tensor":
+            postgate: Optional["torch.Tensor"] = None, skip=None, partition=None) -> "torch.Tensor":
     """Convolution by FFT along the last dim of a real ``x`` of shape (..., D, L) with ``k`` of shape (D, K), one filter per
     channel, or of shape (..., L) with a 1-D ``k``: one kernel launch per call (plus the transform of the filter).
     ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one gives the circular result.
@@ -1926,6 +2045,12 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     Rows too long for one FFT (L + K - 1 beyond fftconv_length's last length) run as overlap-save blocks of
     fftconv_block(K) points, in the same single launch; ``block=`` forces that path at the given FFT length for any L (it
     excludes ``n``), K <= block - 1.
+    ``partition=`` opens the partitioned path for filters longer than half a block (K > 8193; float64 4097), the Hyena-style
+    K = L beyond one FFT: an integer Q cuts the filter into ceil(K / Q) partitions of Q taps at ``block=`` (default: the largest
+    power-of-two block, 16384 / float64 8192), 1 <= Q <= block - 1, for any K; "auto" takes the paths above whenever they
+    exist (the same bits) and fftconv_partition(K) otherwise.  One launch, no intermediate; the work grows with K / Q
+    (DESIGN.md 3.4q).  It excludes ``n``; None refuses such filters as ever.  Gates, skip and autograd as on the other paths
+    (the filter gradient: one launch of the overlap-save filter-gradient plan per partition).
     ``pregate`` / ``postgate`` / ``skip`` make it the gated filter stage of Hyena / H3 / S4 models in the same launch:
     ``postgate * (conv(pregate * x, k) + skip * (pregate * x))``.  ``pregate`` has exactly ``x``'s shape, ``postgate`` exactly
     the result's (ValueError otherwise: nothing is broadcast, a gate broadcast and then copied would cost what the fusion
@@ -1948,7 +2073,7 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     if L < 2 or K < 1:
         raise MifftError(-2, f"fftconv: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
     dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-    n, taps = _fftconv_pick("fftconv", L, K, dtype, n, block)
+    n, taps, Q = _fftconv_pick_part("fftconv", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
     rows = 1
     for m in logical[:-1]:
@@ -1979,16 +2104,16 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         # (the forward of the Function runs with grad mode off: it comes back here and takes the lines below)
         skip_t = skip if isinstance(skip, torch.Tensor) else None
         return _FFTConvFunction.apply(x, k, pregate, postgate, skip_t, None if skip_t is not None else skip,
-                                      (n, taps, mode, bool(correlate)))
+                                      (n, taps, mode, bool(correlate), Q))
     xr = x.to(dtype).contiguous().reshape(rows, L, 1)
     out = torch.empty((rows, out_length, 1), dtype=dtype, device=xr.device)
     gates = (1 if pregate is not None else 0) | (2 if postgate is not None else 0)
     with _PLAN_CACHE_LOCK:
         key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-               int(torch.cuda.current_stream(device).cuda_stream), taps, gates)
+               int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q)
         plan = _PLAN_CACHE.get(key)
         if plan is None:
-            plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length,
+            plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
                                 correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2))
             _plan_cache_insert(key, plan)
         else:
@@ -2068,14 +2193,95 @@ class ConvGradPlan(Plan):
             return irfftn(A, self.n)[:, :K]
 
 
+class PartConvGradPlan:
+    """The plan of ``plan_fftconv_grad(partition=Q)``: the filter gradient of the partitioned ``plan_fftconv`` plan of the same
+    arguments, COMPOSED of one overlap-save filter-gradient plan (``ConvGradPlan``, taps = Q at the same block length) per
+    partition -- ``partitions`` launches, not one.  Taps p Q .. (p + 1) Q - 1 of the gradient are the gradient of a filter of Q
+    taps against the same rows with the window moved by p Q samples: ``gk[p Q + j] = sum_t gy[t] u[o - p Q + t - j]``
+    (correlation: ``u[o + p Q + t + j]``), which is the existing plan on a contiguous slice of ``u`` (correlation) or of ``gy``
+    (where o - p Q is negative), cropped to the samples that can meet.  ``plans[p]`` is None where none can: those taps are
+    exact zeros.  Every sub-plan sums in an order fixed by its own shape, so two runs give the same bits."""
+
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition, partials=None):
+        self.ctx, self.dtype = ctx, dtype
+        self.channels, self.length, self.n = channels, length, n
+        self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
+        self.taps, self.partition, self.partitions = taps, partition, -(-taps // partition)
+        self.step = n - partition + 1
+        rows = batch * channels
+        self.in_shape, self.grad_shape = (rows, length, 1), (rows, out_length, 1)
+        self.device = int(ctx.device)
+        self.slices = [_fftconv_part_grad_slice(length, partition, offset, out_length, correlate, p) for p in range(self.partitions)]
+        self.plans = [None if sl is None else
+                      plan_fftconv_grad(dtype, batch, channels, max(sl[1] - sl[0], 2), n, taps=partition, offset=sl[4],
+                                        out_length=sl[3] - sl[2], correlate=correlate, partials=partials, ctx=ctx)
+                      for sl in self.slices]
+
+    @property
+    def num_launches(self) -> int:
+        return sum(pl.num_launches for pl in self.plans if pl is not None)
+
+    @property
+    def scratch_bytes(self) -> int:
+        return sum(pl.scratch_bytes for pl in self.plans if pl is not None)
+
+    def close(self) -> None:
+        for pl in self.plans:
+            if pl is not None:
+                pl.close()
+
+    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int) -> "torch.Tensor":
+        """the real (channels, K) gradient of the filter, K <= taps: ``ConvGradPlan.filter_grad`` of every partition on its
+        slices of ``x`` of ``in_shape`` and ``gy`` of ``grad_shape`` (copied where they are no whole rows), concatenated"""
+        K = int(K)
+        if K < 1 or K > self.taps:
+            raise MifftError(-2, f"filter_grad: K = {K} taps on a partitioned plan of taps = {self.taps}: 1 <= K <= {self.taps}")
+        _check_tensor(x, self.in_shape, self.dtype, self.device, "x")
+        _check_tensor(gy, self.grad_shape, self.dtype, self.device, "gy")
+        Q, parts = self.partition, []
+        with torch.cuda.stream(self.ctx.stream):
+            for p in range(-(-K // Q)):
+                Kp = min(Q, K - p * Q)
+                sl, plan = self.slices[p], self.plans[p]
+                if plan is None:
+                    parts.append(torch.zeros((self.channels, Kp), dtype=self.dtype, device=x.device))
+                    continue
+                u0, u1, g0, g1, _ = sl
+                us, gs = x[:, u0:u1], gy[:, g0:g1]
+                if u1 - u0 < 2:  # (rows of at least two samples: a zero behind the one)
+                    us = torch.nn.functional.pad(us, (0, 0, 0, 2 - (u1 - u0)))
+                parts.append(plan.filter_grad(us.contiguous(), gs.contiguous(), Kp))
+            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+def _fftconv_part_grad_slice(L: int, Q: int, o: int, Lo: int, correlate: bool, p: int):
+    """(u0, u1, g0, g1, offset) of partition p of the composed filter gradient: the overlap-save filter-gradient plan of Q taps
+    and that offset on u[u0:u1] and gy[g0:g1] gives the taps p Q .. of the filter gradient; None when no sample of gy meets a
+    sample of u (the taps are zero)."""
+    if correlate:  # gk[p Q + j] = sum_t gy[t] u[p Q + o + t + j]: u from p Q on, gy as far as it reaches into it
+        u0, u1 = p * Q, L
+        g1 = min(Lo, u1 - u0 - o)
+        return None if u1 - u0 < 1 or g1 < 1 else (u0, u1, 0, g1, o)
+    off = o - p * Q  # gk[p Q + j] = sum_t gy[t] u[off + t - j]
+    if off >= 0:
+        g1 = min(Lo, L + Q - 1 - off)
+        return None if g1 < 1 else (0, L, 0, g1, off)
+    g0 = -off  # (earlier samples of gy meet u before its first sample); gy' = gy[g0:] at offset 0, u as far as gy' reaches
+    if g0 >= Lo:
+        return None
+    g1 = min(Lo, g0 + L + Q - 1)
+    return (0, min(L, g1 - g0), g0, g1, 0)
+
+
 def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
                       out_length: Optional[int] = None, correlate: bool = False, partials: Optional[int] = None,
-                      ctx: Optional[DeviceContext] = None) -> ConvGradPlan:
+                      ctx: Optional[DeviceContext] = None, partition: Optional[int] = None):
     """Plan of the fused filter gradient (no reference counterpart) of the ``plan_fftconv`` plan of the same arguments:
     ``gk[d, j] = sum over b and t of gy[b, d, t] * u[b, d, o + t - j]`` (``correlate``: ``o + t + j``), computed as
     ``irfft(sum_b conj(rfft(u[b, d], n)) * rfft(gy[b, d] put at o, n), n)[:K]`` in ONE launch that reads ``u`` and ``gy`` once
     each and writes ``channels * partials`` rows of n // 2 + 1 bins -- the exact adjoint of what the forward plan computes,
-    circular where that is, block by block on an overlap-save plan (``taps=K``).  ``partials`` workgroups share a channel's
+    circular where that is, block by block on an overlap-save plan (``taps=K``).  ``partition=Q`` (with ``taps=K``, any K >= 1)
+    gives the gradient of the partitioned plan as a ``PartConvGradPlan``: one such launch per partition.  ``partials`` workgroups share a channel's
     sum (default: enough that channels * partials fills the device; capped by the (row, block) pairs of a channel); the
     order of every sum is fixed by the plan, so two runs give the same bits.  Gates are not fused: ``u`` = pregate * x and
     ``gy`` = postgate * (the incoming gradient) are the caller's.  Every argument error is raised before any device work."""
@@ -2088,6 +2294,14 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
     if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
         raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to "
                                           "12288, n // 2 without a prime factor above 32): see fftconv_length")
+    if partition is not None:  # (the composed gradient of a partitioned plan: PartConvGradPlan)
+        taps, partition = _fftconv_part_check("plan_fftconv_grad", n, taps, partition, length, offset, out_length, correlate)
+        if partials is not None and not 1 <= int(partials) <= 65535:
+            raise MifftError(-5, f"plan_fftconv_grad: partials = {partials}: 1 .. 65535")
+        if ctx is None:
+            ctx = DeviceContext()
+        return PartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition,
+                                partials=partials)
     blocks = 1
     if taps is not None:
         taps = int(taps)
@@ -2117,13 +2331,13 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
     return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, partials=partials)
 
 
-def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device) -> ConvGradPlan:
+def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None):
     """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK)"""
     key = ("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-           int(torch.cuda.current_stream(device).cuda_stream), taps)
+           int(torch.cuda.current_stream(device).cuda_stream), taps, Q)
     plan = _PLAN_CACHE.get(key)
     if plan is None:
-        plan = plan_fftconv_grad(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length,
+        plan = plan_fftconv_grad(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
                                  correlate=correlate, ctx=DeviceContext(device))
         _plan_cache_insert(key, plan)
     else:
@@ -2132,13 +2346,14 @@ def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate
 
 
 def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Optional[int] = None, mode: str = "causal",
-                        correlate: bool = False, block: Optional[int] = None) -> "torch.Tensor":
+                        correlate: bool = False, block: Optional[int] = None, partition=None) -> "torch.Tensor":
     """The gradient of ``sum(gy * fftconv(x, k, n=n, mode=mode, correlate=correlate, block=block))`` with respect to a filter
     ``k`` of ``K`` taps, by the fused filter-gradient kernel in one launch (plus a sum of partials and one irfftn, both on
     ``channels`` rows): ``x`` (..., D, L) and ``gy`` of the result's shape (..., D, Lo) give (D, K); a 1-D ``x`` (L,) with
     ``gy`` (Lo,) gives (K,), the gradient of a 1-D filter.  (A 1-D filter shared by rows (..., L): reshape to (-1, 1, L) and take
     row 0.)  The choice of ``n`` / overlap-save mirrors ``fftconv``'s for the same arguments, so this is the gradient of THAT
-    call, circular where it is.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s."""
+    call, circular where it is.  With ``partition=`` (as ``fftconv``'s) it is the gradient of the partitioned call: one launch
+    per partition.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s."""
     if x.is_complex() or gy.is_complex():
         raise MifftError(-3, "fftconv_filter_grad expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -2154,7 +2369,7 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     if L < 2 or K < 1:
         raise MifftError(-2, f"fftconv_filter_grad: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
     dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-    n, taps = _fftconv_pick("fftconv_filter_grad", L, K, dtype, n, block)
+    n, taps, Q = _fftconv_pick_part("fftconv_filter_grad", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
     if tuple(gy.shape) != logical[:-1] + (out_length,):
         raise ValueError(f"fftconv_filter_grad: gy is {tuple(gy.shape)}, the result of that fftconv call is "
@@ -2172,7 +2387,7 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     xr = x.detach().to(dtype).contiguous().reshape(rows, L, 1)
     gr = gy.detach().to(dtype).contiguous().reshape(rows, out_length, 1)
     with _PLAN_CACHE_LOCK:
-        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device)
+        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q)
         gk = plan.filter_grad(xr, gr, K)
     return gk if x.dim() >= 2 else gk.reshape(K)
 
@@ -2186,18 +2401,18 @@ class _FFTConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, k, pregate, postgate, skip_t, skip_f, cfg):
-        n, taps, mode, correlate = cfg
+        n, taps, mode, correlate, Q = cfg
         ctx.cfg, ctx.skip_f = cfg, skip_f
         ctx.save_for_backward(x, k, pregate, postgate, skip_t)
         return fftconv(x, k, mode=mode, correlate=correlate, pregate=pregate, postgate=postgate,
                        skip=skip_t if skip_t is not None else skip_f,
-                       **({"block": n} if taps is not None else {"n": n}))
+                       **({"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, k, a, b, skip_t = ctx.saved_tensors
-        n, taps, mode, correlate = ctx.cfg
+        n, taps, mode, correlate, Q = ctx.cfg
         skip = skip_t.detach() if skip_t is not None else ctx.skip_f
         need_x, need_k, need_a, need_b, need_d = ctx.needs_input_grad[:5]
         logical = tuple(x.shape)
@@ -2207,7 +2422,7 @@ class _FFTConvFunction(torch.autograd.Function):
         o, Lo = _fftconv_window(mode, L, K)
         rows = x.numel() // L
         device = x.device.index
-        sel = {"block": n} if taps is not None else {"n": n}
+        sel = {"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}
         gyr = gy.to(dtype).contiguous().reshape(rows, Lo)  # (sum().backward() hands in an expanded tensor)
         xr = x.to(dtype).contiguous().reshape(rows, L)
         ar = None if a is None else a.to(dtype).contiguous().reshape(rows, L)
@@ -2231,11 +2446,11 @@ class _FFTConvFunction(torch.autograd.Function):
             out = torch.empty((rows, L, 1), dtype=dtype, device=x.device)
             with _PLAN_CACHE_LOCK:
                 key = ("fftconv", dtype, rows, D, Lin, n, 0, L, not correlate, device,
-                       int(torch.cuda.current_stream(device).cuda_stream), taps, gates)
+                       int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q)
                 plan = _PLAN_CACHE.get(key)
                 if plan is None:
                     plan = plan_fftconv(dtype, rows // D, D, Lin, n, taps=taps, offset=0, out_length=L, correlate=not correlate,
-                                        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2))
+                                        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2), partition=Q)
                     _plan_cache_insert(key, plan)
                 else:
                     _PLAN_CACHE.move_to_end(key)
@@ -2262,7 +2477,7 @@ class _FFTConvFunction(torch.autograd.Function):
         if need_k or need_d:
             u = xr if ar is None else ar * xr
             with _PLAN_CACHE_LOCK:
-                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device)
+                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q)
                 g = gplan.filter_grad(u.reshape(rows, L, 1), gv.reshape(rows, Lo, 1), K)
             if need_k:
                 gk = g.reshape(k.shape).to(k.dtype)

@@ -15,6 +15,10 @@
 // The 16-word payload is either of the two with elementwise gates fused into the tile's load and store (TileCfg::GATE):
 // y = b . conv(a . x), a of x's shape, b of out's.  The plan knows only WHICH gates there are; the tensors are arguments of
 // every exec (mifft_gated_args through mifft_exec_batch: mifft_api.cpp).
+//
+// The 20-word payload is partitioned overlap-save (TileCfg::PART), for filters longer than half a block: the filter is P
+// partitions of Q taps, H holds (D, P, n / 2 + 1) complex values, and every stored block sums the products of P shifted input
+// blocks with the P spectra in registers before the one inverse.  Gated or not (word 11); one launch, no scratch.
 #include <algorithm>
 
 #include "mifft_config.h"
@@ -24,10 +28,11 @@ namespace mifft {
 
 // ---- the payload TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI, or, overlap-save, ---------------------------------------
 // ---- TAG_LO | TAG_HI | D | c | S | mode | H_LO | H_HI | F | s0 | Lo | 0, or, gated, ------------------------------------------
-// ---- the eight words | F (0: single block) | s0 | Lo | gates | 0 | 0 | 0 | 0 ------------------------------------------------
+// ---- the eight words | F (0: single block) | s0 | Lo | gates | 0 | 0 | 0 | 0, or, partitioned, -------------------------------
+// ---- the eight words | F | s0 | Lo | gates (0: none) | 0 | 0 | 0 | 0 | Q | P | 0 | 0 -----------------------------------------
 bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
     if (ndim != 2 || !bases_flat || !bases_len) return false;
-    return (bases_len[0] == 8 || bases_len[0] == 12 || bases_len[0] == 16) && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
+    return (bases_len[0] == 8 || bases_len[0] == 12 || bases_len[0] == 16 || bases_len[0] == 20) && bases_flat[0] == MIFFT_CONV_TAG_LO && bases_flat[1] == MIFFT_CONV_TAG_HI;
 }
 
 // what the convolution payloads share: the flag, direction, dtype and component checks and the limits of n
@@ -81,8 +86,9 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
                std::string& why) {
     if (const int rc = conv_header_check(p, "MIFFT_CONV_TAG", why)) return rc;
     const int64_t L = p.dims[0], n = p.dims[1];
-    const bool gated = bases_len[0] == 16;  // (word 8 says which of the two forms it is: F = 0 the single block)
-    const bool ols = bases_len[0] == 12 || (gated && bases_flat[8] != 0);  // (overlap-save: rows of T = L samples in blocks of n)
+    const bool part = bases_len[0] == 20;  // (partitioned overlap-save: always blocks, F >= 1; word 11 = 0: no gates)
+    const bool gated = bases_len[0] == 16 || (part && bases_flat[11] != 0);  // (16 words: word 8 says which form it is, F = 0 the single block)
+    const bool ols = bases_len[0] == 12 || part || (gated && bases_flat[8] != 0);  // (overlap-save: rows of T = L samples in blocks of n)
     if (ols && (L < 2 || L > (1ll << 30))) {
         why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save convolution payload: 2 <= T <= 2^30";
         return L < 2 ? MIFFT_ERR_BAD_DIM : MIFFT_ERR_TOO_LARGE;
@@ -147,10 +153,15 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
                   std::to_string(S) + ": (F - 1) S < Lo <= F S (the last block stores at least one sample)";
             return MIFFT_ERR_BAD_BASES;
         }
-        if (s0 <= -n || s0 + (F - 1) * S >= L) {
+        // (partitioned: a block without a live partition stores zeros, so this rule does not apply; Lo is bounded instead)
+        if (!part && (s0 <= -n || s0 + (F - 1) * S >= L)) {
             why = "block start s0 = " + std::to_string(s0) + " with F = " + std::to_string(F) + " blocks every S = " +
                   std::to_string(S) + " samples: a block reads no sample of its row (-n < s0 and s0 + (F - 1) S < T = " +
                   std::to_string(L) + ")";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (part && rowLo > (1ll << 30)) {
+            why = "Lo = " + std::to_string(rowLo) + " output samples per row in a partitioned convolution payload: at most 2^30";
             return MIFFT_ERR_BAD_BASES;
         }
         if (!gated && bases_flat[11] != 0) {
@@ -176,6 +187,32 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
                 return MIFFT_ERR_BAD_BASES;
             }
     }
+    int64_t Q = 0, parts = 0;
+    if (part) {
+        Q = bases_flat[16];
+        parts = bases_flat[17];
+        if (Q < 1 || Q > n - 1) {
+            why = "Q = " + std::to_string(Q) + " taps per partition in a partitioned convolution payload: 1 <= Q <= n - 1 = " +
+                  std::to_string(n - 1);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (S > n - Q + 1) {
+            why = "S = " + std::to_string(S) + " samples stored per block against Q = " + std::to_string(Q) +
+                  " taps per partition: S <= n - Q + 1 = " + std::to_string(n - Q + 1) + " (the rest wraps around)";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (parts < 1 || parts * Q > (1ll << 30)) {
+            why = "P = " + std::to_string(parts) + " partitions of Q = " + std::to_string(Q) +
+                  " taps in a partitioned convolution payload: P >= 1 and P Q <= 2^30";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        for (int w = 12; w < 20; ++w)
+            if (w != 16 && w != 17 && bases_flat[w] != 0) {
+                why = "the reserved word " + std::to_string(w) + " of a partitioned convolution payload must be 0, not " +
+                      std::to_string(bases_flat[w]);
+                return MIFFT_ERR_BAD_BASES;
+            }
+    }
     if (bases_len[1] < 0) {
         why = "negative bases_len";
         return MIFFT_ERR_NO_BASES;
@@ -185,6 +222,8 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
     p.conv_D = D;
     p.conv_o = o;
     p.conv_Lo = rowLo;
+    p.conv_Q = Q;
+    p.conv_parts = parts;
     p.conv_S = S;
     p.conv_F = F;
     p.conv_s0 = s0;

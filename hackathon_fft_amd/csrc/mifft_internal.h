@@ -211,6 +211,10 @@ struct Plan {
     // the postgate (one of out's shape that multiplies the result as it is stored); the tensors are arguments of every exec
     // (mifft_gated_args), never plan state.  Its word 8 is F: 0 the single block (conv_S = 0), >= 1 overlap-save.  0: ungated.
     uint32_t conv_gates = 0;
+    // The 20-word payload (partitioned overlap-save, conv_Q > 0): the filter is conv_parts partitions of conv_Q taps, conv_h
+    // (conv_D, conv_parts, n / 2 + 1) complex values; block f of a row sums, over the partitions p, the block of n samples
+    // from conv_s0 + f conv_S - p conv_Q on (correlation: + p conv_Q) times spectrum (d, p).  conv_gates as above, or 0.
+    int64_t conv_Q = 0, conv_parts = 0;
     // The MIFFT_CONV_GRAD_TAG payload: the plan computes the filter gradient of the convolution the fields above describe
     // (conv_h unused) as conv_P partial sums per channel: x and gy (mifft_conv_grad_args) -> (conv_P conv_D, n / 2 + 1)
     // complex values, unscaled.  A single block has conv_S = 0, conv_F = 1, conv_s0 = 0 as in the forward plan.
@@ -401,7 +405,7 @@ int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vec
 bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
-// bases_len[0] a tagged length (8, 12: overlap-save, or 16: gated) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
+// bases_len[0] a tagged length (8, 12: overlap-save, 16: gated, or 20: partitioned) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
 // be refused without a device, leaving the request in plan.conv_* and the user radices of n in `radices`.  build_conv: the
 // one pass.  select_jit_conv_rows is the packed-row kernel with TileCfg::CONV (kernels_jit.cpp; run time only),
 // conv_rows_supported the same check without a device; launch_jit_conv is its launch, which -- unlike a DimPass::launch --

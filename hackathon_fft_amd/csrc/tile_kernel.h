@@ -252,6 +252,8 @@ struct TileParams {
     // (a single block: ols_blocks = 1, ols_start = 0, ols_step = Lo); `in` is x, gate_in is gy (rows of stft_frames = Lo
     // reals), n_rows the pairs of ONE channel, B F, and spec_bands the partials P: workgroup w is slice w % P of channel
     // w / P and stores row (w % P) D + w / P of `out`, (P D) rows of N + 1 complex values.
+    // PART configurations (partitioned overlap-save) keep OLS's mapping and reuse two fields no row tile reads: herm_d0 = Q
+    // taps per partition and herm_d1 = P partitions; spec_wt is (D, P, N + 1) complex values.
     // GATE configurations (CONV / OLS with elementwise gates; the arguments of one exec, not plan state): gate_in has the
     // shape of `in` (rows of stft_len reals) and multiplies every sample as it is loaded, gate_out the shape of `out` (rows of
     // stft_frames reals) and multiplies every sample as it is stored.  Both point, as `in` and `out` do, at the exec's first
@@ -354,7 +356,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
-          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false>
+          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false, bool PART_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -615,6 +617,20 @@ struct TileCfg {
     // fixed by the plan, so the result is bit-identical from run to run.  wgrad_walk below; the main tile loop is not run.
     static constexpr bool WGRAD = WGRAD_;
     static_assert(!WGRAD_ || (CONV_ && GATE_ == 0), "WGRAD: the filter-gradient twin of an ungated CONV / OLS tile");
+    // PART (with CONV and OLS, any GATE): uniformly partitioned overlap-save, for filters longer than half a block.  The filter
+    // is P partitions of Q taps with one spectrum each, H[d][p]; output block f of a signal is the sum over p of the spectrum of
+    // the n samples from s0 + f S - p Q on (correlation: + p Q) times H[d][p] (its conjugate), folded and inverted ONCE.  A step
+    // of the persistent grid takes TILE launch rows (signal, block) as the OLS tile does and, for p = 0 .. P - 1 in ascending
+    // order, loads the shifted blocks with the OLS load (pregate included: read again for every partition), runs the passes,
+    // unpacks the bin pairs (k, N - k) as the CONV product stage does and adds their products with row (d, p) of the spectra
+    // into register accumulators per (tile row, bin pair), laid out as WGRAD's.  A partition in which no row of the tile reads
+    // a sample of [0, T) is skipped whole (a uniform test: no load, no passes); a row whose own block is empty loads zeros
+    // and its filter loads and products are predicated off, so a row's sum has exactly the terms of its own live partitions,
+    // in ascending p, whatever tile it shares: bit-identical for any batch, slab and grid.  Then the C2R fold of the sums,
+    // the passes again and the OLS store (postgate included).  No scratch, no atomics, no LDS beyond the tile's; the input
+    // spectra are recomputed, never stored, so the work grows with P.  part_walk below; the main tile loop is not run.
+    static constexpr bool PART = PART_;
+    static_assert(!PART_ || (CONV_ && OLS_ && !WGRAD_ && TILE_ <= 64), "PART: the partitioned twin of an OLS tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -1715,6 +1731,178 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
     }
 }
 
+// The walk of a TileCfg::PART workgroup (see there): the whole kernel body behind the table set-up.
+template <class C>
+MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx<typename C::T>* twr, const int tid_entry) {
+    using T = typename C::T;
+    using V = cpx<T>;
+    constexpr int PAIRS = C::N / 2 + 1, NN = 2 * C::N;
+    constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
+    const int D = p.stft_center, Q = p.herm_d0, P = p.herm_d1;
+    const int F = p.ols_blocks, S = p.ols_step, s0 = p.ols_start, len = p.stft_len;
+    const int o = p.stft_hop, Lo = p.stft_frames;
+    const bool corr = (p.spec_q & 1) != 0;
+    const T cj = corr ? (T)-1 : (T)1;
+    const T s = (T)p.scale;
+    const V* w = (const V*)p.r2c_tw;
+    const V* hs = (const V*)p.spec_wt;
+    V cur[1][C::R(0)];
+    for (long long t = blockIdx.x; t < p.n_tiles; t += gridDim.x) {
+        // (the thread index is made opaque once per PARTITION and once more for the fold and the store: what is derived from
+        //  it -- LDS and spectrum offsets, the twiddles w[k] -- is then recomputed per partition instead of staying live
+        //  across the passes beside the accumulators; see tile_kernel)
+        // A block's work is its live partitions, which grow with f (correlation: shrink): walked row by row, a grid whose size
+        // is a multiple of F would hand one workgroup the same f every round.  One-row tiles are therefore walked block-major,
+        // the dearest f of every signal first: position t is block t / signals (from the dear end) of signal t % signals.
+        long long r0 = t * C::TILE;
+        if constexpr (C::TILE == 1) {
+            const long long ns = p.n_rows / F, rk = t / ns;
+            r0 = (t - rk * ns) * F + (corr ? rk : F - 1 - rk);
+        }
+        const long long b0 = r0 / F;
+        const int nv = p.n_rows - r0 < C::TILE ? (int)(p.n_rows - r0) : C::TILE;
+        // (signal, block) of the tile's first row once, uniform; a row further on wraps into the signals that follow
+        const int fr0 = (int)(r0 - b0 * F);
+        const T* x0 = (const T*)p.in + b0 * len;
+        const T* g0 = (C::GATE & 1) ? (const T*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
+        const unsigned d0 = (unsigned)(((long long)p.spec_bands + b0) % (long long)D);  // (uniform; d0 + c < 2^31)
+        // first sample of the block that row c of the tile loads for partition pp (|.| < 2^31: T, P Q <= 2^30, F S < T + 2N);
+        // the block holds a sample of its row when it starts after -n and before T
+        auto start = [&](int c, int pp) -> long long {
+            int fr = fr0 + c;
+            if (fr >= F) fr -= fr / F * F;
+            return (long long)s0 + (long long)fr * S + (corr ? (long long)pp * Q : -(long long)pp * Q);
+        };
+        auto live = [&](long long st) { return st > -(long long)NN && st < (long long)len; };
+        V acc_a[IT], acc_b[IT];
+#pragma unroll
+        for (int i = 0; i < IT; ++i) acc_a[i] = acc_b[i] = {(T)0, (T)0};
+#pragma unroll 1
+        for (int pp = 0; pp < P; ++pp) {
+            unsigned long long alive = 0;  // (uniform: every work item walks the same rows; bit c: row c reads a sample)
+            for (int c = 0; c < nv; ++c) alive |= (unsigned long long)live(start(c, pp)) << c;
+            if (!alive) continue;
+            int tid = tid_entry;
+#ifndef MIFFT_NO_OPAQUE_TID
+            asm volatile("" : "+v"(tid));  // (at every length: the accumulators leave less room than a plain tile has)
+#endif
+            // packed element m of row c: the samples st + 2 m and st + 2 m + 1 of its signal, zeros outside [0, T)
+            for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
+                const int c = f / C::N, m = f - c * C::N;
+                V x = {(T)0, (T)0};
+                if (c < nv) {
+                    const int db = fr0 + c >= F ? (fr0 + c) / F : 0;
+                    const T* xe = x0 + (long long)db * len;
+                    const T* ge = g0 + (long long)db * len;
+                    const long long i = start(c, pp) + 2 * m;
+                    if (i >= 0 && i + 1 < len) {
+                        x = gload_pair(xe + i);
+                        if constexpr (C::GATE & 1) {
+                            const V g = gload_pair(ge + i);
+                            x = {g.x * x.x, g.y * x.y};
+                        }
+                    } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
+                        if (i >= 0 && i < len) {
+                            x.x = xe[i];
+                            if constexpr (C::GATE & 1) x.x = ge[i] * x.x;
+                        }
+                        if (i + 1 >= 0 && i + 1 < len) {
+                            x.y = xe[i + 1];
+                            if constexpr (C::GATE & 1) x.y = ge[i + 1] * x.y;
+                        }
+                    }
+                }
+                lds[lds_index<C, -1>(c, m)] = x;
+            }
+            __syncthreads();
+            run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+#pragma unroll
+            for (int i = 0; i < IT; ++i) {
+                const int f = tid + i * C::THREADS;
+                if ((IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) && f < nv * PAIRS) {
+                    const int c = C::TILE == 1 ? 0 : f / PAIRS, k = f - c * PAIRS, m = k ? C::N - k : 0;
+                    if ((alive >> c) & 1) {
+                        const unsigned dc = fr0 + c >= F ? (unsigned)(fr0 + c) / (unsigned)F : 0u;
+                        const V* hr = hs + ((long long)((d0 + dc) % (unsigned)D) * P + pp) * (C::N + 1);
+                        const V ga = hr[k], gb = hr[C::N - k];  // (k = 0: bin N, the last of the row)
+                        const V zk = lds[lds_index<C, C::NP - 1>(c, k)], zm = lds[lds_index<C, C::NP - 1>(c, m)];
+                        // X[k] and X[N-k], as the R2C store unpacks them
+                        const T ex = (T)0.5 * (zk.x + zm.x), ey = (T)0.5 * (zk.y - zm.y);
+                        const T ox = (T)0.5 * (zk.y + zm.y), oy = (T)-0.5 * (zk.x - zm.x);
+                        const V wk = w[k];
+                        const T tx = wk.x * ox - wk.y * oy, ty = wk.x * oy + wk.y * ox;
+                        const V xa = {ex + tx, ey + ty}, xb = {ex - tx, ty - ey};
+                        // times H (conjugated: correlation)
+                        const V pa = cmul(xa, V{ga.x, cj * ga.y}), pb = cmul(xb, V{gb.x, cj * gb.y});
+                        acc_a[i].x += pa.x;
+                        acc_a[i].y += pa.y;
+                        acc_b[i].x += pb.x;
+                        acc_b[i].y += pb.y;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        int tid = tid_entry;
+#ifndef MIFFT_NO_OPAQUE_TID
+        asm volatile("" : "+v"(tid));
+#endif
+        // the C2R fold of the sums, as the CONV product stage folds one product (rows from nv on: zeros)
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            const int f = tid + i * C::THREADS;
+            if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
+                const int c = C::TILE == 1 ? 0 : f / PAIRS, k = f - c * PAIRS, m = k ? C::N - k : 0;
+                V a = acc_a[i], b = acc_b[i];
+                if (k == 0) a.y = b.y = (T)0;
+                const V wk = w[k];
+                const T fx = a.x + b.x, fy = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
+                const T px = dx * wk.x + dy * wk.y, py = dy * wk.x - dx * wk.y;
+                lds[lds_index<C, C::NP - 1>(c, k)] = {fx - py, -(fy + px)};
+                if (k != 0 && 2 * k != C::N) lds[lds_index<C, C::NP - 1>(c, m)] = {fx + py, fy - px};
+            }
+        }
+        __syncthreads();
+        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        // the OLS store: sample i of block fr goes to out[b Lo + fr S + i - c] for c <= i < c + S and fr S + i - c < Lo only
+        T* out0 = (T*)p.out + b0 * Lo;
+        const T* q0 = (C::GATE & 2) ? (const T*)p.gate_out + b0 * Lo : out0;  // (else unused)
+        for (int f = tid; f < nv * C::N; f += C::THREADS) {
+            const int c = f / C::N, j = f - c * C::N, u = 2 * j - o;
+            if (u + 1 < 0 || u >= S) continue;
+            int fr = fr0 + c, db = 0;
+            if (fr >= F) {
+                db = fr / F;
+                fr -= db * F;
+            }
+            const int tt = fr * S + u;  // (< Lo + 2N: 32 bits hold it)
+            const bool w0 = u >= 0 && tt < Lo, w1 = u + 1 < S && tt + 1 < Lo;
+            if (!w0 && !w1) continue;
+            const V v = lds[lds_index<C, C::NP - 1>(c, j)];
+            T y0 = v.x * s, y1 = -(v.y * s);
+            T* q = out0 + (long long)db * Lo + tt;
+            const T* bq = q0 + (long long)db * Lo + tt;
+            if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                if constexpr (C::GATE & 2) {
+                    const V g = gload_pair(bq);
+                    y0 = g.x * y0, y1 = g.y * y1;
+                }
+                gstore<false>((V*)q, V{y0, y1});
+            } else {
+                if (w0) {
+                    if constexpr (C::GATE & 2) y0 = bq[0] * y0;
+                    q[0] = y0;
+                }
+                if (w1) {
+                    if constexpr (C::GATE & 2) y1 = bq[1] * y1;
+                    q[1] = y1;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 template <class C>
 __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TileParams p) {
     using T = typename C::T;
@@ -1770,6 +1958,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
     MIFFT_STAMP(C, -1);
     if constexpr (C::WGRAD) {  // (the filter gradient walks pairs of blocks, not tiles of rows: its own loop)
         wgrad_walk<C>(p, lds, twr, tid0);
+        return;
+    }
+    if constexpr (C::PART) {  // (the partitioned convolution transforms several blocks per stored one: its own loop)
+        part_walk<C>(p, lds, twr, tid0);
         return;
     }
     V pre[C::PREFETCH ? C::IPT(0) : 1][C::R(0)];

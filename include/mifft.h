@@ -583,7 +583,34 @@ typedef enum {
  * Refused before any device work: every check of the 8-word payload (F = 0; L > n among them) or of the 12-word one (F >= 1)
  * with its status; MIFFT_ERR_BAD_BASES: a gates word of 0 or above 3; a non-zero word 12 .. 15; F = 0 with a non-zero word 9
  * or 10.  The tag in front of 13, 14 or 15 words is no convolution payload.  MIFFT_JIT=0 refuses the plan as it does the
- * ungated ones. */
+ * ungated ones.
+ *
+ * Partitioned overlap-save: the same tag in front of exactly 20 words, for filters longer than half a block (K > n / 2 + 1,
+ * the K = L of Hyena-style models beyond one FFT).  The filter is cut into P partitions of Q taps, k_p = k[p Q .. (p + 1) Q)
+ * (the last one zero-filled), and H holds one spectrum per channel and partition: (D, P, n / 2 + 1) complex values,
+ * H[d][p] = rfft(k_p of channel d, n).  Output block f of a signal row of T samples is
+ *     Y_f = sum over p of rfft(blk_{f,p}, n) * H[d][p],   blk_{f,p}[i] = x[s0 + f S - p Q + i]  (0 <= i < n, zero outside [0, T))
+ *     y = irfft(Y_f, n);   out[f S + j] = y[c + j]   for j < S and f S + j < Lo
+ * (mode bit 0, correlation: the block starts at s0 + f S + p Q and multiplies by conj(H[d][p])).  A pair (f, p) whose block
+ * holds no sample of [0, T) contributes nothing and is neither loaded nor transformed.
+ *     word  0 .. 15 as the gated overlap-save payload: tag, D, c, S, mode, H_LO, H_HI, F >= 1, s0, Lo, gates, four zeros --
+ *                   except that the gates word 11 may be 0 (no gates: the exec takes the device address of x as ever)
+ *     word 16       Q: taps per partition, 1 <= Q <= n - 1
+ *     word 17       P: partitions, P >= 1, P Q <= 2^30
+ *     word 18, 19   reserved, 0
+ * S <= n - Q + 1 (what no wrap-around touches; the caller picks c = Q - 1, s0 = o - c for a convolution, c = 0, s0 = o for a
+ * correlation) and c + S <= n.  The overlap-save rule "every block reads a sample of its row" does not apply: a block without
+ * a live partition stores zeros; Lo <= 2^30 instead.  Still ONE launch, no scratch, no atomics and no LDS beyond the tile's:
+ * TILE launch rows per step of the persistent grid as in overlap-save, the P shifted blocks transformed one after the other
+ * in the same LDS tile, the products summed in registers in ascending p -- a fixed order, so a signal row's result is
+ * bit-identical for any batch, first / count and grid -- and one inverse per stored block.  The input spectra are recomputed,
+ * never stored: the work grows with P (about P / 2 forward transforms per stored block for a causal K = T).  Gates are the
+ * 16-word form's, bit for bit (the pregate is read again for every partition); a gated plan takes a mifft_gated_args.
+ * The kernel is TileCfg::PART on the OLS tile: rows<n>[_f64]_r2c_<radices>_conv_pols[_g<1|2|3>]_jit, run time only.
+ * Refused before any device work, with the statuses of the 12- and 16-word forms: their checks of the flags, n, D, batch % D,
+ * mode, H, S, c + S, F and Lo against F and S; MIFFT_ERR_BAD_BASES: Q outside 1 .. n - 1, S > n - Q + 1, P < 1 or
+ * P Q > 2^30, Lo > 2^30, a gates word above 3, a non-zero word 12 .. 15, 18 or 19.  The tag in front of 17, 18, 19 or 21
+ * words is no convolution payload; the 8-, 12- and 16-word payloads mean what they meant. */
 #define MIFFT_CONV_TAG_LO 0x4F4E5601u
 #define MIFFT_CONV_TAG_HI 0x7FF84D43u
 /* the argument block of a gated convolution exec (above); the magic word is "MIFFTGA1" */
