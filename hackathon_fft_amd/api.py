@@ -34,6 +34,7 @@ _DTYPE_CODE = {torch.float32: 0, torch.float64: 1, torch.uint8: 2, torch.int32: 
 if hasattr(torch, "uint16"):
     _DTYPE_CODE[torch.uint16] = 6
 _OUT_DTYPES = (torch.float32, torch.float64)
+_IO_DTYPES = (torch.bfloat16, torch.float16)  # the 16-bit storage types of a convolution plan (io_dtype; float32 inside)
 
 FLAG_FAITHFUL_STAGES = 1
 FLAG_HALF_SPECTRUM = 2  # MIFFT_FLAG_HALF_SPECTRUM: numpy's one-sided rfftn / irfftn layouts (include/mifft.h)
@@ -529,7 +530,11 @@ class Plan:
     samples from c on are stored at f S of the row's Lo output samples.
     ``conv`` with Q and P behind the nine values: partitioned overlap-save, the 20-word payload (plan_fftconv(partition=)).
     ``conv_gates`` = 1, 2 or 3 beside either form: the 16-word payload, bit 0 a pregate of x's shape multiplied into the load,
-    bit 1 a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run)."""
+    bit 1 a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run).
+    Bits 8..15 of ``mode`` are the storage type of such a plan's rows (0, or the code of float16 / bfloat16 under float32:
+    ``ConvPlan.io_dtype``)."""
+
+    io_dtype = None  # (a convolution plan with 16-bit rows in memory: ConvPlan / ConvGradPlan; None on every other plan)
 
     def __init__(self, in_dtype, out_dtype, in_shape, out_shape, *, bases=None, inverse=False,
                  device: int = 0, flags: int = 0, whole_batch: int = 0, half_spectrum: bool = False, axes=None,
@@ -1029,8 +1034,9 @@ def fft(output: "torch.Tensor", x: "torch.Tensor", ctx: Optional[DeviceContext] 
                                           "plan.run(out, x, pregate=, postgate=) instead of fft(out, x, plan=plan)")
     if ctx is None:
         ctx = DeviceContext(plan.device)
-    _check_tensor(x, plan.in_shape, plan.in_dtype, plan.device, "x")
-    _check_tensor(output, plan.out_shape, plan.out_dtype, plan.device, "output")
+    io = getattr(plan, "io_dtype", None)  # (a half-storage convolution plan: 16-bit rows around float32 arithmetic)
+    _check_tensor(x, plan.in_shape, io or plan.in_dtype, plan.device, "x")
+    _check_tensor(output, plan.out_shape, io or plan.out_dtype, plan.device, "output")
     if count is None:
         count = plan.out_shape[0] - first
     check(_lib.lib().mifft_exec_batch(plan._h, x.data_ptr(), output.data_ptr(), int(first), int(count),
@@ -1743,11 +1749,15 @@ class ConvPlan(Plan):
     through ``run``, which takes the gate tensors of that exec; ``fft(out, x, plan=plan)`` refuses it.
     A partitioned plan (``plan_fftconv(taps=K, partition=Q)``) has ``partition`` = Q taps per partition, ``partitions`` =
     ceil(K / Q), ``step`` = n - Q + 1 and a ``filter_spectrum`` of (channels, partitions, n // 2 + 1, 2): partition p holds
-    rfft(k[p Q : (p + 1) Q], n).  ``partition`` is None and ``partitions`` 1 on every other plan."""
+    rfft(k[p Q : (p + 1) Q], n).  ``partition`` is None and ``partitions`` 1 on every other plan.
+    A half-storage plan (``plan_fftconv(torch.float32, ..., io_dtype=torch.bfloat16)`` or ``torch.float16``) has that
+    ``io_dtype``: ``x``, the gates and ``out`` are tensors of it, widened in the kernel's load and rounded once, to nearest
+    even, in its store; ``filter_spectrum`` and the arithmetic stay float32.  ``io_dtype`` is None on every other plan."""
 
     def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, pregate=False,
-                 postgate=False, partition=None):
+                 postgate=False, partition=None, io_dtype=None):
         self.ctx = ctx
+        self.io_dtype = io_dtype
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         self.taps, self.step, self.blocks = taps, None, 1
@@ -1758,7 +1768,7 @@ class ConvPlan(Plan):
         with torch.cuda.stream(ctx.stream):
             shape = (channels, n // 2 + 1, 2) if partition is None else (channels, self.partitions, n // 2 + 1, 2)
             self.filter_spectrum = torch.zeros(shape, dtype=dtype, device=f"cuda:{ctx.device}")
-        mode, addr = 1 if correlate else 0, self.filter_spectrum.data_ptr()
+        mode, addr = (1 if correlate else 0) | _io_mode_bits(io_dtype), self.filter_spectrum.data_ptr()
         if taps is None:
             conv = (n, channels, offset, out_length, mode, addr)
         elif partition is not None:
@@ -1774,7 +1784,8 @@ class ConvPlan(Plan):
             postgate: Optional["torch.Tensor"] = None, first: Optional[int] = None, count: Optional[int] = None) -> None:
         """The exec of a gated plan, enqueued on the plan's stream: ``out[r] = postgate[r] * conv(pregate[r] * x[r])`` for the
         signal rows ``first`` .. ``first + count - 1`` (default: all).  ``pregate`` has ``in_shape``, ``postgate`` ``out_shape``,
-        both of the plan's dtype, contiguous, on its device; each is given exactly where the plan has it.  All four tensors
+        both of the plan's dtype (``io_dtype`` where the plan has one, as ``x`` and ``out`` then are), contiguous, on its device;
+        each is given exactly where the plan has it.  All four tensors
         are the WHOLE batch's: the library offsets them by ``first`` rows.  A gate may alias ``x``, not ``out``; none is written."""
         if not self.conv_gates:
             raise MifftError(ERR_UNSUPPORTED, "run() is the exec of a gated plan (plan_fftconv(pregate=True) / postgate=True); "
@@ -1784,12 +1795,13 @@ class ConvPlan(Plan):
                 raise MifftError(-12, f"the plan has a {what}: run(..., {what}=) is missing")
             if not want and t is not None:
                 raise MifftError(ERR_UNSUPPORTED, f"the plan has no {what}: plan_fftconv(..., {what}=True) makes one that has")
-        _check_tensor(x, self.in_shape, self.in_dtype, self.device, "x")
-        _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
+        sdt = self.io_dtype or self.in_dtype
+        _check_tensor(x, self.in_shape, sdt, self.device, "x")
+        _check_tensor(out, self.out_shape, sdt, self.device, "out")
         if pregate is not None:
-            _check_tensor(pregate, self.in_shape, self.in_dtype, self.device, "pregate")
+            _check_tensor(pregate, self.in_shape, sdt, self.device, "pregate")
         if postgate is not None:
-            _check_tensor(postgate, self.out_shape, self.out_dtype, self.device, "postgate")
+            _check_tensor(postgate, self.out_shape, sdt, self.device, "postgate")
         first = 0 if first is None else int(first)
         count = self.out_shape[0] - first if count is None else int(count)
         args = GatedArgs(GATED_ARGS_MAGIC, x.data_ptr(), pregate.data_ptr() if pregate is not None else None,
@@ -1855,6 +1867,22 @@ class ConvPlan(Plan):
             self.filter_spectrum.copy_(Hr.to(device=self.filter_spectrum.device, dtype=self.out_dtype))
 
 
+def _io_mode_bits(io_dtype) -> int:
+    """bits 8..15 of a convolution payload's mode word: the code of the storage type, 0 without one"""
+    return 0 if io_dtype is None else _DTYPE_CODE[io_dtype] << 8
+
+
+def _check_io_dtype(who: str, dtype, io_dtype) -> None:
+    """``io_dtype`` is None, or bfloat16 / float16 beside ``dtype`` = float32 (status -4 otherwise)"""
+    if io_dtype is None:
+        return
+    if io_dtype not in _IO_DTYPES:
+        raise MifftError(-4, f"{who}: io_dtype is torch.bfloat16 or torch.float16 (or None), got {io_dtype}")
+    if dtype != torch.float32:
+        raise MifftError(-4, f"{who}: io_dtype = {io_dtype} stores 16-bit rows around float32 arithmetic: dtype must be "
+                             f"torch.float32, got {dtype}")
+
+
 def _fftconv_ols_geometry(n: int, K: int, offset: int, out_length: int, correlate: bool) -> tuple:
     """(c, S, s0, F) of an overlap-save plan: S = n - K + 1 samples per block are free of wrap-around, from c = K - 1 on
     (correlation: from 0 on); block 0 starts c samples before the first wanted one"""
@@ -1890,7 +1918,7 @@ def _fftconv_part_check(who: str, n: int, taps, partition, length: int, offset: 
 
 def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
                  out_length: Optional[int] = None, correlate: bool = False, ctx: Optional[DeviceContext] = None,
-                 pregate: bool = False, postgate: bool = False, partition: Optional[int] = None) -> ConvPlan:
+                 pregate: bool = False, postgate: bool = False, partition: Optional[int] = None, io_dtype=None) -> ConvPlan:
     """Plan of the fused FFT convolution (no reference counterpart; MIFFT_CONV_TAG in include/mifft.h) of ``batch * channels``
     real rows of ``length`` samples, row-major (batch, channels, length), at the FFT length ``n`` (see fftconv_length):
     ``y[r] = irfft(rfft(x[r], n) * G[r % channels], n)[offset : offset + out_length]`` in ONE kernel launch, G the plan's
@@ -1910,12 +1938,17 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     ``taps`` may then be any K >= 1, 1 <= Q <= n - 1; the filter is cut into ceil(K / Q) partitions of Q taps, every block of n
     samples stores n - Q + 1, and the kernel transforms one shifted input block per live partition for every block it stores
     -- still one launch and no intermediate, but the work grows with K / Q.  Gates as above (``run``); without them ``fft``.
+    ``io_dtype`` = torch.bfloat16 or torch.float16 (with ``dtype`` = torch.float32 only) makes it a half-storage plan of any
+    of these kinds: ``x``, the gates and ``out`` are tensors of ``io_dtype``, widened exactly in the load and rounded once
+    (to nearest even) in the store; the arithmetic and ``filter_spectrum`` stay float32, and the result equals the float32
+    plan's on the widened tensors, rounded with ``.to(io_dtype)``, bit for bit.  Still one launch and no intermediate.
     The plan-level API carries no autograd; ``plan_fftconv_grad`` of the same arguments is the plan of its filter gradient,
     and the opposite-``correlate`` plan on rows of ``out_length`` samples its input gradient (what ``fftconv`` does)."""
     batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
     out_length = length if out_length is None else int(out_length)
     if dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"a convolution plan reads and writes float32 or float64, got {dtype}")
+    _check_io_dtype("plan_fftconv", dtype, io_dtype)
     if batch < 1 or channels < 1:
         raise MifftError(-8, f"plan_fftconv: batch = {batch} and channels = {channels} must be positive")
     if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
@@ -1926,7 +1959,7 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
         if ctx is None:
             ctx = DeviceContext()
         return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, pregate=pregate,
-                        postgate=postgate, partition=partition)
+                        postgate=postgate, partition=partition, io_dtype=io_dtype)
     if taps is not None:
         taps = int(taps)
         if taps < 1 or taps > n - 1:
@@ -1941,7 +1974,7 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
         if ctx is None:
             ctx = DeviceContext()
         return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, pregate=pregate,
-                        postgate=postgate)
+                        postgate=postgate, io_dtype=io_dtype)
     if length < 2 or length > n:
         raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples at n = {n}: 2 <= length <= n")
     if offset < 0 or out_length < 1 or offset + out_length > n:
@@ -1949,7 +1982,8 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
                              f"offset + out_length <= n = {n}")
     if ctx is None:
         ctx = DeviceContext()
-    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, pregate=pregate, postgate=postgate)
+    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, pregate=pregate, postgate=postgate,
+                    io_dtype=io_dtype)
 
 
 def _fftconv_pick(who: str, L: int, K: int, dtype, n: Optional[int], block: Optional[int]) -> tuple:
@@ -2024,7 +2058,7 @@ def _fftconv_window(mode: str, L: int, K: int) -> tuple:
 
 def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mode: str = "causal",
             correlate: bool = False, block: Optional[int] = None, pregate: Optional["torch.Tensor"] = None,
-            postgate: Optional["torch.Tensor"] = None, skip=None, partition=None) -> "torch.Tensor":
+            postgate: Optional["torch.Tensor"] = None, skip=None, partition=None, io_dtype=None) -> "torch.Tensor":
     """Convolution by FFT along the last dim of a real ``x`` of shape (..., D, L) with ``k`` of shape (D, K), one filter per
     channel, or of shape (..., L) with a 1-D ``k``: one kernel launch per call (plus the transform of the filter).
     ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one gives the circular result.
@@ -2055,7 +2089,18 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     ``postgate * (conv(pregate * x, k) + skip * (pregate * x))``.  ``pregate`` has exactly ``x``'s shape, ``postgate`` exactly
     the result's (ValueError otherwise: nothing is broadcast, a gate broadcast and then copied would cost what the fusion
     saves); both live on ``x``'s device and are converted to the working dtype as ``x`` is.  ``skip`` is a float or a real (D,)
-    tensor, one value per channel, added to every bin of the filter spectrum (the term costs no kernel work)."""
+    tensor, one value per channel, added to every bin of the filter spectrum (the term costs no kernel work).
+    ``io_dtype`` = torch.bfloat16 or torch.float16 is the half-precision route, on every path above: ``x`` and the gates are
+    read as tensors of ``io_dtype`` (without a copy when they already are, converted otherwise), widened exactly in the
+    kernel's load, the arithmetic and the filter spectrum are float32, and the result is rounded once (to nearest even) in
+    the kernel's store and has ``io_dtype`` -- the bits of ``fftconv(x.float(), k.float(), ...).to(io_dtype)`` in the same
+    single launch.  Half-precision callers (autocast) should pass ``io_dtype=x.dtype``: without it a bfloat16 / float16
+    ``x`` is still converted to float64, as ever.  Autograd with ``io_dtype``: the gradient of ``x`` (and the pregate route)
+    is one launch of the opposite-``correlate`` half-storage plan on the incoming gradient (converted to ``io_dtype`` if it
+    arrives otherwise); the gradient of ``k`` and ``skip`` comes from the half-storage filter-gradient kernel on ``x`` and the
+    incoming gradient directly when there are no gates; with gates the products pregate * x and postgate * gradient are
+    formed in float32 (widen, then multiply) and feed the float32 filter-gradient plan, so that no product is rounded to 16
+    bits.  Every returned gradient has the dtype of its tensor."""
     if x.is_complex() or k.is_complex():
         raise MifftError(-3, "fftconv expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -2072,7 +2117,10 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         raise MifftError(-2, f"fftconv: x has {logical[-2]} channels, k has {D} filters")
     if L < 2 or K < 1:
         raise MifftError(-2, f"fftconv: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
-    dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if io_dtype is not None and io_dtype not in _IO_DTYPES:
+        raise MifftError(-4, f"fftconv: io_dtype is torch.bfloat16 or torch.float16 (or None), got {io_dtype}")
+    dtype = torch.float32 if io_dtype is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    sdt = io_dtype or dtype  # (what x, the gates and the result are in memory)
     n, taps, Q = _fftconv_pick_part("fftconv", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
     rows = 1
@@ -2104,17 +2152,18 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         # (the forward of the Function runs with grad mode off: it comes back here and takes the lines below)
         skip_t = skip if isinstance(skip, torch.Tensor) else None
         return _FFTConvFunction.apply(x, k, pregate, postgate, skip_t, None if skip_t is not None else skip,
-                                      (n, taps, mode, bool(correlate), Q))
-    xr = x.to(dtype).contiguous().reshape(rows, L, 1)
-    out = torch.empty((rows, out_length, 1), dtype=dtype, device=xr.device)
+                                      (n, taps, mode, bool(correlate), Q, io_dtype))
+    xr = x.to(sdt).contiguous().reshape(rows, L, 1)
+    out = torch.empty((rows, out_length, 1), dtype=sdt, device=xr.device)
     gates = (1 if pregate is not None else 0) | (2 if postgate is not None else 0)
     with _PLAN_CACHE_LOCK:
         key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-               int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q)
+               int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q, io_dtype)
         plan = _PLAN_CACHE.get(key)
         if plan is None:
             plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
-                                correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2))
+                                correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2),
+                                io_dtype=io_dtype)
             _plan_cache_insert(key, plan)
         else:
             _PLAN_CACHE.move_to_end(key)
@@ -2122,8 +2171,8 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         if skip is not None:
             plan.add_skip(skip)
         if gates:
-            a = pregate.to(dtype).contiguous().reshape(rows, L, 1) if pregate is not None else None
-            b = postgate.to(dtype).contiguous().reshape(rows, out_length, 1) if postgate is not None else None
+            a = pregate.to(sdt).contiguous().reshape(rows, L, 1) if pregate is not None else None
+            b = postgate.to(sdt).contiguous().reshape(rows, out_length, 1) if postgate is not None else None
             plan.run(out, xr, pregate=a, postgate=b)
         else:
             fft(out, xr, DeviceContext(device), plan=plan)
@@ -2135,10 +2184,14 @@ class ConvGradPlan(Plan):
     of ``channels * partials`` persistent workgroups (MIFFT_CONV_GRAD_TAG in include/mifft.h).  ``partials`` partial sums
     per channel (the library's choice unless given), ``blocks`` per row and ``step`` samples per block as on ``ConvPlan``
     (a single block: 1 and None).  ``in_shape`` (batch * channels, length, 1) is x's, ``grad_shape``
-    (batch * channels, out_length, 1) the incoming gradient's, ``out_shape`` (partials, channels, n // 2 + 1, 2)."""
+    (batch * channels, out_length, 1) the incoming gradient's, ``out_shape`` (partials, channels, n // 2 + 1, 2).
+    With ``io_dtype`` (torch.bfloat16 / torch.float16 under float32) ``x`` and ``gy`` are tensors of it, widened exactly in
+    the kernel's loads; the result stays float32.  None on every other plan."""
 
-    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, partials=None):
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, partials=None,
+                 io_dtype=None):
         self.ctx = ctx
+        self.io_dtype = io_dtype
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         self.taps, self.step, self.blocks = taps, None, 1
@@ -2147,7 +2200,7 @@ class ConvGradPlan(Plan):
             c, S, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
             self.step = S
         rows = batch * channels
-        words = [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, channels, c, S, 1 if correlate else 0, self.blocks, s0 & 0xFFFFFFFF,
+        words = [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, channels, c, S, (1 if correlate else 0) | _io_mode_bits(io_dtype), self.blocks, s0 & 0xFFFFFFFF,
                  out_length, 0 if partials is None else int(partials)] + [0] * 6
         self.in_dtype = self.out_dtype = dtype
         self.in_shape, self.grad_shape = (rows, length, 1), (rows, out_length, 1)
@@ -2170,9 +2223,10 @@ class ConvGradPlan(Plan):
 
     def run(self, out: "torch.Tensor", x: "torch.Tensor", gy: "torch.Tensor") -> None:
         """fills ``out`` of ``out_shape`` with the unscaled partial spectra sum conj(rfft(x-block)) rfft(gy-block), enqueued on
-        the plan's stream; ``x`` of ``in_shape`` and ``gy`` of ``grad_shape``, the plan's dtype, contiguous; neither is written"""
-        _check_tensor(x, self.in_shape, self.in_dtype, self.device, "x")
-        _check_tensor(gy, self.grad_shape, self.in_dtype, self.device, "gy")
+        the plan's stream; ``x`` of ``in_shape`` and ``gy`` of ``grad_shape``, the plan's dtype (``io_dtype`` where it has one),
+        contiguous; neither is written"""
+        _check_tensor(x, self.in_shape, self.io_dtype or self.in_dtype, self.device, "x")
+        _check_tensor(gy, self.grad_shape, self.io_dtype or self.in_dtype, self.device, "gy")
         _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
         args = ConvGradArgs(CONV_GRAD_ARGS_MAGIC, x.data_ptr(), gy.data_ptr())
         check(_lib.lib().mifft_exec_batch(self._h, ctypes.addressof(args), out.data_ptr(), 0, self.in_shape[0],
@@ -2202,8 +2256,9 @@ class PartConvGradPlan:
     (where o - p Q is negative), cropped to the samples that can meet.  ``plans[p]`` is None where none can: those taps are
     exact zeros.  Every sub-plan sums in an order fixed by its own shape, so two runs give the same bits."""
 
-    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition, partials=None):
-        self.ctx, self.dtype = ctx, dtype
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition, partials=None,
+                 io_dtype=None):
+        self.ctx, self.dtype, self.io_dtype = ctx, dtype, io_dtype  # (io_dtype: of x and gy, as on every ConvGradPlan below)
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         self.taps, self.partition, self.partitions = taps, partition, -(-taps // partition)
@@ -2214,7 +2269,8 @@ class PartConvGradPlan:
         self.slices = [_fftconv_part_grad_slice(length, partition, offset, out_length, correlate, p) for p in range(self.partitions)]
         self.plans = [None if sl is None else
                       plan_fftconv_grad(dtype, batch, channels, max(sl[1] - sl[0], 2), n, taps=partition, offset=sl[4],
-                                        out_length=sl[3] - sl[2], correlate=correlate, partials=partials, ctx=ctx)
+                                        out_length=sl[3] - sl[2], correlate=correlate, partials=partials, ctx=ctx,
+                                        io_dtype=io_dtype)
                       for sl in self.slices]
 
     @property
@@ -2236,8 +2292,8 @@ class PartConvGradPlan:
         K = int(K)
         if K < 1 or K > self.taps:
             raise MifftError(-2, f"filter_grad: K = {K} taps on a partitioned plan of taps = {self.taps}: 1 <= K <= {self.taps}")
-        _check_tensor(x, self.in_shape, self.dtype, self.device, "x")
-        _check_tensor(gy, self.grad_shape, self.dtype, self.device, "gy")
+        _check_tensor(x, self.in_shape, self.io_dtype or self.dtype, self.device, "x")
+        _check_tensor(gy, self.grad_shape, self.io_dtype or self.dtype, self.device, "gy")
         Q, parts = self.partition, []
         with torch.cuda.stream(self.ctx.stream):
             for p in range(-(-K // Q)):
@@ -2275,7 +2331,7 @@ def _fftconv_part_grad_slice(L: int, Q: int, o: int, Lo: int, correlate: bool, p
 
 def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
                       out_length: Optional[int] = None, correlate: bool = False, partials: Optional[int] = None,
-                      ctx: Optional[DeviceContext] = None, partition: Optional[int] = None):
+                      ctx: Optional[DeviceContext] = None, partition: Optional[int] = None, io_dtype=None):
     """Plan of the fused filter gradient (no reference counterpart) of the ``plan_fftconv`` plan of the same arguments:
     ``gk[d, j] = sum over b and t of gy[b, d, t] * u[b, d, o + t - j]`` (``correlate``: ``o + t + j``), computed as
     ``irfft(sum_b conj(rfft(u[b, d], n)) * rfft(gy[b, d] put at o, n), n)[:K]`` in ONE launch that reads ``u`` and ``gy`` once
@@ -2284,11 +2340,15 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
     gives the gradient of the partitioned plan as a ``PartConvGradPlan``: one such launch per partition.  ``partials`` workgroups share a channel's
     sum (default: enough that channels * partials fills the device; capped by the (row, block) pairs of a channel); the
     order of every sum is fixed by the plan, so two runs give the same bits.  Gates are not fused: ``u`` = pregate * x and
-    ``gy`` = postgate * (the incoming gradient) are the caller's.  Every argument error is raised before any device work."""
+    ``gy`` = postgate * (the incoming gradient) are the caller's.  ``io_dtype`` = torch.bfloat16 or torch.float16 (with
+    ``dtype`` = torch.float32 only): ``u`` and ``gy`` are tensors of it, widened exactly in the kernel's loads; the result
+    stays float32 and equals the float32 plan's on the widened tensors bit for bit.  Every argument error is raised before
+    any device work."""
     batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
     out_length = length if out_length is None else int(out_length)
     if dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"a filter-gradient plan reads and writes float32 or float64, got {dtype}")
+    _check_io_dtype("plan_fftconv_grad", dtype, io_dtype)
     if batch < 1 or channels < 1:
         raise MifftError(-8, f"plan_fftconv_grad: batch = {batch} and channels = {channels} must be positive")
     if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
@@ -2301,7 +2361,7 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
         if ctx is None:
             ctx = DeviceContext()
         return PartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition,
-                                partials=partials)
+                                partials=partials, io_dtype=io_dtype)
     blocks = 1
     if taps is not None:
         taps = int(taps)
@@ -2328,17 +2388,18 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
         partials = min(partials, batch * blocks)  # (capped by the pairs of a channel)
     if ctx is None:
         ctx = DeviceContext()
-    return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, partials=partials)
+    return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, partials=partials,
+                        io_dtype=io_dtype)
 
 
-def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None):
+def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None):
     """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK)"""
     key = ("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-           int(torch.cuda.current_stream(device).cuda_stream), taps, Q)
+           int(torch.cuda.current_stream(device).cuda_stream), taps, Q, io_dtype)
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         plan = plan_fftconv_grad(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
-                                 correlate=correlate, ctx=DeviceContext(device))
+                                 correlate=correlate, ctx=DeviceContext(device), io_dtype=io_dtype)
         _plan_cache_insert(key, plan)
     else:
         _PLAN_CACHE.move_to_end(key)
@@ -2346,14 +2407,17 @@ def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate
 
 
 def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Optional[int] = None, mode: str = "causal",
-                        correlate: bool = False, block: Optional[int] = None, partition=None) -> "torch.Tensor":
+                        correlate: bool = False, block: Optional[int] = None, partition=None, io_dtype=None) -> "torch.Tensor":
     """The gradient of ``sum(gy * fftconv(x, k, n=n, mode=mode, correlate=correlate, block=block))`` with respect to a filter
     ``k`` of ``K`` taps, by the fused filter-gradient kernel in one launch (plus a sum of partials and one irfftn, both on
     ``channels`` rows): ``x`` (..., D, L) and ``gy`` of the result's shape (..., D, Lo) give (D, K); a 1-D ``x`` (L,) with
     ``gy`` (Lo,) gives (K,), the gradient of a 1-D filter.  (A 1-D filter shared by rows (..., L): reshape to (-1, 1, L) and take
     row 0.)  The choice of ``n`` / overlap-save mirrors ``fftconv``'s for the same arguments, so this is the gradient of THAT
     call, circular where it is.  With ``partition=`` (as ``fftconv``'s) it is the gradient of the partitioned call: one launch
-    per partition.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s."""
+    per partition.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s.
+    ``io_dtype`` = torch.bfloat16 or torch.float16: ``x`` and ``gy`` are read as tensors of it (no copy when they already
+    are), widened exactly in the kernel's loads, and the result is float32 -- the bits of the float32 call on the widened
+    tensors.  The partitioned route stays composed, one half-storage launch per partition."""
     if x.is_complex() or gy.is_complex():
         raise MifftError(-3, "fftconv_filter_grad expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -2368,7 +2432,10 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     D = int(logical[-2]) if x.dim() >= 2 else 1
     if L < 2 or K < 1:
         raise MifftError(-2, f"fftconv_filter_grad: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
-    dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if io_dtype is not None and io_dtype not in _IO_DTYPES:
+        raise MifftError(-4, f"fftconv_filter_grad: io_dtype is torch.bfloat16 or torch.float16 (or None), got {io_dtype}")
+    dtype = torch.float32 if io_dtype is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    sdt = io_dtype or dtype  # (what x and gy are in memory)
     n, taps, Q = _fftconv_pick_part("fftconv_filter_grad", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
     if tuple(gy.shape) != logical[:-1] + (out_length,):
@@ -2384,10 +2451,10 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
         raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
     if gy.device != x.device:
         raise MifftError(-10, f"fftconv_filter_grad: gy lives on {gy.device}, x on {x.device}")
-    xr = x.detach().to(dtype).contiguous().reshape(rows, L, 1)
-    gr = gy.detach().to(dtype).contiguous().reshape(rows, out_length, 1)
+    xr = x.detach().to(sdt).contiguous().reshape(rows, L, 1)
+    gr = gy.detach().to(sdt).contiguous().reshape(rows, out_length, 1)
     with _PLAN_CACHE_LOCK:
-        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q)
+        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q, io_dtype)
         gk = plan.filter_grad(xr, gr, K)
     return gk if x.dim() >= 2 else gk.reshape(K)
 
@@ -2397,14 +2464,19 @@ class _FFTConvFunction(torch.autograd.Function):
     gv = b gy and G = rfft(k, n) + d: gu = the adjoint convolution of gv (one launch of the opposite-correlate plan),
     gx = a gu, ga = x gu, gb = gy v with v recomputed without the postgate, gk and gd from the fused filter gradient of
     (u, gv).  The filter spectra of the cached plans are rewritten from the saved k and skip by every launch here: a second
-    layer of the same shape may have overwritten them since the forward."""
+    layer of the same shape may have overwritten them since the forward.
+    With ``io_dtype`` (the sixth value of ``cfg``) x, a, b, gy and every launch's result are tensors of it: gu comes from the
+    half-storage plan (b fused into its load, a into its store when only x wants a gradient; modes with o > 0 pad gy and b
+    separately instead of their product), the products of 16-bit tensors (a gu, x gu, gy v) are torch's, computed in float32
+    and rounded once, and the filter gradient reads x and gy through the half-storage kernel when there are no gates; with
+    gates u = a x and gv = b gy are float32 products of the widened tensors for the float32 filter-gradient plan."""
 
     @staticmethod
     def forward(ctx, x, k, pregate, postgate, skip_t, skip_f, cfg):
-        n, taps, mode, correlate, Q = cfg
+        n, taps, mode, correlate, Q, io = cfg
         ctx.cfg, ctx.skip_f = cfg, skip_f
         ctx.save_for_backward(x, k, pregate, postgate, skip_t)
-        return fftconv(x, k, mode=mode, correlate=correlate, pregate=pregate, postgate=postgate,
+        return fftconv(x, k, mode=mode, correlate=correlate, pregate=pregate, postgate=postgate, io_dtype=io,
                        skip=skip_t if skip_t is not None else skip_f,
                        **({"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}))
 
@@ -2412,30 +2484,33 @@ class _FFTConvFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, k, a, b, skip_t = ctx.saved_tensors
-        n, taps, mode, correlate, Q = ctx.cfg
+        n, taps, mode, correlate, Q, io = ctx.cfg
         skip = skip_t.detach() if skip_t is not None else ctx.skip_f
         need_x, need_k, need_a, need_b, need_d = ctx.needs_input_grad[:5]
         logical = tuple(x.shape)
         L, K = int(logical[-1]), int(k.shape[-1])
         D = int(k.shape[0]) if k.dim() == 2 else 1
-        dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+        dtype = torch.float32 if io is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+        sdt = io or dtype  # (what the tensors of every launch here are in memory)
         o, Lo = _fftconv_window(mode, L, K)
         rows = x.numel() // L
         device = x.device.index
         sel = {"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}
-        gyr = gy.to(dtype).contiguous().reshape(rows, Lo)  # (sum().backward() hands in an expanded tensor)
-        xr = x.to(dtype).contiguous().reshape(rows, L)
-        ar = None if a is None else a.to(dtype).contiguous().reshape(rows, L)
-        br = None if b is None else b.to(dtype).contiguous().reshape(rows, Lo)
+        gyr = gy.to(sdt).contiguous().reshape(rows, Lo)  # (sum().backward() hands in an expanded tensor)
+        xr = x.to(sdt).contiguous().reshape(rows, L)
+        ar = None if a is None else a.to(sdt).contiguous().reshape(rows, L)
+        br = None if b is None else b.to(sdt).contiguous().reshape(rows, Lo)
         gx = gk = ga = gb = gd = None
         gv = None
-        if need_k or need_d or (o > 0 and (need_x or need_a)):
+        if io is None and (need_k or need_d or (o > 0 and (need_x or need_a))):
             gv = gyr if br is None else br * gyr
         if need_x or need_a:
             # gu: the adjoint of u -> crop(conv(u, k') , o, Lo), one launch of the existing kernels on the gradient put at o
             fuse_a = ar is not None and need_x and not need_a
-            if o > 0:
+            if o > 0 and io is None:
                 src, pre = torch.nn.functional.pad(gv, (o, 0)), None
+            elif o > 0:  # (16-bit rows: gy and b padded apart, multiplied in the kernel's load, so that no product is rounded)
+                src, pre = torch.nn.functional.pad(gyr, (o, 0)), None if br is None else torch.nn.functional.pad(br, (o, 0))
             else:
                 src, pre = gyr, br
             if src.shape[-1] < 2:
@@ -2443,14 +2518,15 @@ class _FFTConvFunction(torch.autograd.Function):
                 pre = None if pre is None else torch.nn.functional.pad(pre, (0, 1))
             Lin = int(src.shape[-1])
             gates = (1 if pre is not None else 0) | (2 if fuse_a else 0)
-            out = torch.empty((rows, L, 1), dtype=dtype, device=x.device)
+            out = torch.empty((rows, L, 1), dtype=sdt, device=x.device)
             with _PLAN_CACHE_LOCK:
                 key = ("fftconv", dtype, rows, D, Lin, n, 0, L, not correlate, device,
-                       int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q)
+                       int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q, io)
                 plan = _PLAN_CACHE.get(key)
                 if plan is None:
                     plan = plan_fftconv(dtype, rows // D, D, Lin, n, taps=taps, offset=0, out_length=L, correlate=not correlate,
-                                        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2), partition=Q)
+                                        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2), partition=Q,
+                                        io_dtype=io)
                     _plan_cache_insert(key, plan)
                 else:
                     _PLAN_CACHE.move_to_end(key)
@@ -2472,12 +2548,20 @@ class _FFTConvFunction(torch.autograd.Function):
                 gx = None
         if need_b:  # gb = gy v, v = conv(u, k) + d u recomputed by one forward launch without the postgate
             v = fftconv(x.detach(), k.detach(), mode=mode, correlate=correlate, pregate=None if a is None else a.detach(),
-                        skip=skip, **sel)
+                        skip=skip, io_dtype=io, **sel)
             gb = gyr * v.reshape(rows, Lo)
         if need_k or need_d:
-            u = xr if ar is None else ar * xr
+            gio = io
+            if io is not None and (ar is not None or br is not None):  # (float32 products of the widened tensors: see the class)
+                gio = None
+                u = xr.float() if ar is None else ar.float() * xr.float()
+                gv = gyr.float() if br is None else br.float() * gyr.float()
+            elif io is not None:
+                u, gv = xr, gyr
+            else:
+                u = xr if ar is None else ar * xr
             with _PLAN_CACHE_LOCK:
-                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q)
+                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q, gio)
                 g = gplan.filter_grad(u.reshape(rows, L, 1), gv.reshape(rows, Lo, 1), K)
             if need_k:
                 gk = g.reshape(k.shape).to(k.dtype)

@@ -19,6 +19,10 @@
 // The 20-word payload is partitioned overlap-save (TileCfg::PART), for filters longer than half a block: the filter is P
 // partitions of Q taps, H holds (D, P, n / 2 + 1) complex values, and every stored block sums the products of P shifted input
 // blocks with the P spectra in registers before the one inverse.  Gated or not (word 11); one launch, no scratch.
+//
+// Bits 8..15 of the mode word of every form, the filter-gradient payload included, are the STORAGE type of the rows: 0 the
+// plan's float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan (Plan::conv_io, TileCfg::IT): x, the gates and out are then
+// 2-byte elements, widened in the tile's load and rounded once in its store; H and the arithmetic stay float.
 #include <algorithm>
 
 #include "mifft_config.h"
@@ -36,6 +40,24 @@ bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len)
 }
 
 // what the convolution payloads share: the flag, direction, dtype and component checks and the limits of n
+// the mode word of both payloads: bit 0 correlate, bits 8..15 the storage type (0, MIFFT_F16 or MIFFT_BF16; F32 plans only)
+static int conv_mode_check(Plan& p, uint32_t mode, const char* what, const char* bit0, std::string& why) {
+    const uint32_t io = (mode >> 8) & 0xffu;
+    if ((mode & ~0xff01u) || (io != 0 && io != MIFFT_F16 && io != MIFFT_BF16)) {
+        why = std::string("the mode word of a ") + what + " payload has bit 0 (" + bit0 +
+              ") and, in bits 8..15, a storage type (0, MIFFT_F16 or MIFFT_BF16) alone, not " + std::to_string(mode);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (io != 0 && p.out_dtype != MIFFT_F32) {
+        why = std::string("the storage type ") + std::to_string(io) + " in the mode word of a " + what +
+              " payload: 16-bit rows are widened to float, so the plan must be MIFFT_F32";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    p.conv_io = (int)io;
+    p.conv_mode = mode & 1u;
+    return MIFFT_OK;
+}
+
 static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
     const struct {
         uint32_t bits;
@@ -124,10 +146,7 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(D) + " filter rows";
         return MIFFT_ERR_BAD_BATCH;
     }
-    if (mode & ~1u) {
-        why = "the mode word of a convolution payload has bit 0 (correlate) alone, not " + std::to_string(mode);
-        return MIFFT_ERR_BAD_BASES;
-    }
+    if (const int rc = conv_mode_check(p, mode, "convolution", "correlate", why)) return rc;
     if (addr == 0) {
         why = "the filter spectrum address H of a convolution payload is null";
         return MIFFT_ERR_BAD_BASES;
@@ -227,7 +246,6 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
     p.conv_S = S;
     p.conv_F = F;
     p.conv_s0 = s0;
-    p.conv_mode = mode;
     p.conv_gates = gated ? bases_flat[11] : 0u;
     p.conv_h = (const void*)(uintptr_t)addr;
     return MIFFT_OK;
@@ -289,10 +307,7 @@ int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
         why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(D) + " filter rows";
         return MIFFT_ERR_BAD_BATCH;
     }
-    if (mode & ~1u) {
-        why = "the mode word of a filter-gradient payload has bit 0 (the forward correlated) alone, not " + std::to_string(mode);
-        return MIFFT_ERR_BAD_BASES;
-    }
+    if (const int rc = conv_mode_check(p, mode, "filter-gradient", "the forward correlated", why)) return rc;
     if (F < 1 || Lo < 1 || Lo > (1ll << 30)) {
         why = "F = " + std::to_string(F) + " blocks and Lo = " + std::to_string(Lo) +
               " samples per row of gy in a filter-gradient payload: F >= 1 and 1 <= Lo <= 2^30";
@@ -334,7 +349,6 @@ int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
     p.conv_S = single ? 0 : S;
     p.conv_F = F;
     p.conv_s0 = s0;
-    p.conv_mode = mode;
     p.conv_P = P;
     return MIFFT_OK;
 }

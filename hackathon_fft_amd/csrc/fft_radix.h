@@ -36,10 +36,17 @@ struct alignas(2 * sizeof(T)) cpx {
     T x, y;
 };
 
-// bfloat16 as an INPUT element type (MIFFT_BF16): the upper half of a binary32, widened exactly
+// bfloat16 as an INPUT element type (MIFFT_BF16): the upper half of a binary32, widened exactly -- and as the STORAGE type
+// of a convolution tile (TileCfg::CONV), rounded from float to nearest even on the bits: the half below the kept one plus
+// the kept half's last bit carries into it; the largest finite floats round to infinity; a NaN becomes the quiet NaN 0x7fc0
 struct bf16_t {
     unsigned short bits;
     MIFFT_DEV operator float() const { return __builtin_bit_cast(float, (unsigned)bits << 16); }
+    MIFFT_DEV static bf16_t from_float(float f) {
+        const unsigned u = __builtin_bit_cast(unsigned, f);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return {(unsigned short)0x7fc0};
+        return {(unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
+    }
 };
 
 template <typename T> MIFFT_DEV cpx<T> operator+(cpx<T> a, cpx<T> b) { return {a.x + b.x, a.y + b.y}; }

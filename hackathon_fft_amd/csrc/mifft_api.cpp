@@ -25,7 +25,9 @@ int hip_error(hipError_t e, const char* what) {
 
 size_t Plan::in_elem_bytes() const { return dtype_size(in_dtype) * (size_t)in_components; }
 size_t Plan::out_elem_bytes() const { return dtype_size(out_dtype) * 2; }
+size_t Plan::conv_elem_bytes() const { return conv_io ? 2 : dtype_size(out_dtype); }
 size_t Plan::in_row_bytes() const {
+    if (stft() && (conv_D || conv_grad)) return (size_t)dims[0] * conv_elem_bytes();  // (rows of the storage type)
     if (stft()) return (size_t)dims[0] * dtype_size(in_dtype);
     if (istft()) return (size_t)prod_half * in_elem_bytes();
     if (dct_any()) return (size_t)prod * dtype_size(in_dtype);
@@ -33,7 +35,7 @@ size_t Plan::in_row_bytes() const {
 }
 size_t Plan::out_row_bytes() const {
     if (stft() && conv_grad) return 0;  // (the result is no row per batch entry: mifft_plan_out_bytes)
-    if (stft() && conv_D) return (size_t)conv_Lo * dtype_size(out_dtype);
+    if (stft() && conv_D) return (size_t)conv_Lo * conv_elem_bytes();
     if (stft() && mdct) return (size_t)(stft_frames() * mdct) * dtype_size(out_dtype);
     if (stft() && spec_power) return (size_t)(stft_frames() * stft_out_width()) * dtype_size(out_dtype);
     if (stft()) return (size_t)prod_half * out_elem_bytes();
@@ -166,7 +168,7 @@ static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first
     const void* gy = nullptr;
     if (const int rc = unpack_conv_grad_args(x, gy)) return rc;
     const char *xb = (const char*)x, *gb = (const char*)gy, *ob = (const char*)out;
-    const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv_Lo * dtype_size(p.out_dtype),
+    const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv_Lo * p.conv_elem_bytes(),
                  on = conv_grad_out_bytes(p);
     if (xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
     if (gb < ob + on && ob < gb + gn) return set_error(MIFFT_ERR_ALIAS, "gy and out must not overlap");

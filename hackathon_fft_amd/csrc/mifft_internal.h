@@ -206,6 +206,11 @@ struct Plan {
     int64_t conv_D = 0, conv_o = 0, conv_Lo = 0;
     int64_t conv_S = 0, conv_F = 1, conv_s0 = 0;
     uint32_t conv_mode = 0;
+    // Bits 8..15 of the mode word: the STORAGE type of x, the gates and out (a filter-gradient plan: of x and gy), 0 the plan's
+    // float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan: 2-byte elements widened in the load and rounded once in the
+    // store (TileCfg::CONV).  in_dtype and out_dtype stay F32; conv_elem_bytes is what a sample occupies in memory.
+    int conv_io = 0;
+    size_t conv_elem_bytes() const;
     const void* conv_h = nullptr;
     // The 16-word payload (gated): conv_gates bit 0 the pregate (a tensor of x's shape that multiplies x as it is loaded), bit 1
     // the postgate (one of out's shape that multiplies the result as it is stored); the tensors are arguments of every exec

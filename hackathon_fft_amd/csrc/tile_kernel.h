@@ -142,6 +142,65 @@ MIFFT_DEV double log2_t(double v) { return __ocml_log2_f64(v); }
 template <class A, class B> struct same_t { static constexpr bool value = false; };
 template <class A> struct same_t<A, A> { static constexpr bool value = true; };
 
+// The element accesses of a TileCfg::CONV tile, whose rows are stored as ST: T itself -- then these are the plain accesses above,
+// instruction for instruction -- or a 16-bit float (_Float16, bf16_t) under T = float.  A load widens exactly; a store rounds
+// once, to nearest even (float16: overflow to infinity, subnormals kept; NaN stays NaN).  Pairs are one 4-byte access.
+template <typename T, typename ST>
+MIFFT_DEV T swiden(ST v) {
+    if constexpr (same_t<ST, bf16_t>::value) return (T)(float)v;
+    else return (T)v;
+}
+template <typename ST, typename T>
+MIFFT_DEV ST snarrow(T v) {
+    if constexpr (same_t<ST, bf16_t>::value) {
+        return bf16_t::from_float(v);
+    } else {
+        if constexpr (same_t<ST, _Float16>::value && !same_t<T, _Float16>::value) {
+            // The float the store computed stays a float before it is rounded.  Left to itself the compiler selects
+            // v_fma_mixlo_f16 for "postgate * y, then narrow": the exact product rounded ONCE to float16, where the float32
+            // kernel followed by a conversion rounds twice -- a different sample about once in 2^13.  An empty statement
+            // that only names the register keeps the multiplication and v_cvt_f16_f32 apart (no instruction is emitted).
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(v));
+#endif
+        }
+        return (ST)v;
+    }
+}
+template <typename T, typename ST>
+MIFFT_DEV T sload(const ST* p) {
+    return swiden<T, ST>(*p);
+}
+// ... at an address aligned to ONE element, as gload_pair
+template <typename T, typename ST>
+MIFFT_DEV cpx<T> sload_pair(const ST* p) {
+    if constexpr (same_t<ST, T>::value) {
+        return gload_pair(p);
+    } else {
+        static_assert(sizeof(ST) == 2, "16-bit storage");
+        typedef unsigned short bits2u __attribute__((ext_vector_type(2), aligned(2)));
+        const bits2u v = *(const bits2u*)p;
+        const unsigned short lo = v.x, hi = v.y;
+        return {swiden<T, ST>(__builtin_bit_cast(ST, lo)), swiden<T, ST>(__builtin_bit_cast(ST, hi))};
+    }
+}
+template <typename ST, typename T>
+MIFFT_DEV void sstore(ST* p, T v) {
+    *p = snarrow<ST, T>(v);
+}
+// ... at an address aligned to TWO elements
+template <typename ST, typename T>
+MIFFT_DEV void sstore_pair(ST* p, T a, T b) {
+    if constexpr (same_t<ST, T>::value) {
+        gstore<false>((cpx<T>*)p, cpx<T>{a, b});
+    } else {
+        static_assert(sizeof(ST) == 2, "16-bit storage");
+        typedef unsigned short bits2 __attribute__((ext_vector_type(2)));
+        const bits2 v = {__builtin_bit_cast(unsigned short, snarrow<ST, T>(a)), __builtin_bit_cast(unsigned short, snarrow<ST, T>(b))};
+        *(bits2*)p = v;
+    }
+}
+
 // one input element of a FOREIGN element type IT (uint8 / int8 / int16 / uint16 / int32 / half / bfloat16, or float under a
 // double plan), real or interleaved complex, widened to cpx<T> -- the reference's `x.load(...).cast[out_dtype]()`,
 // fft/fft/_fft.mojo:243-257
@@ -581,9 +640,14 @@ struct TileCfg {
     // access, every other wanted sample as one real.  x is read once, y written once; G is re-read by every row through
     // L2 and the Infinity Cache.  No LDS beyond the R2C tile's.  A row's result depends on its own data and filter row alone.
     static constexpr bool CONV = CONV_;
-    static_assert(!CONV_ || (R2C_ && !FIRST_DIRECT_ && DCT_ == 0 && !STFT_ && SPEC_ == 0 && NT_ == 0 && same_t<IT_, T_>::value &&
-                             R0_ <= 32 && R1_ <= 32),
-                  "CONV: packed real rows of the plan's own float type, staged in LDS by the zero-extending load");
+    static_assert(!CONV_ || (R2C_ && !FIRST_DIRECT_ && DCT_ == 0 && !STFT_ && SPEC_ == 0 && NT_ == 0 && R0_ <= 32 && R1_ <= 32 &&
+                             (same_t<IT_, T_>::value ||
+                              (same_t<T_, float>::value && (same_t<IT_, _Float16>::value || same_t<IT_, bf16_t>::value)))),
+                  "CONV: packed real rows of the plan's own float type, or of a 16-bit float under float, staged in LDS by the "
+                  "zero-extending load");
+    // The STORAGE type of a CONV tile is IT: x, both gates and the result (WGRAD: x and gy) are arrays of IT, widened exactly
+    // in the loads and rounded once, to nearest even, in the stores (sload / sstore above).  The filter spectra, the tables,
+    // the LDS tile, the accumulators and WGRAD's result stay T.
     // OLS (with CONV): overlap-save.  A signal row of T samples is convolved as F blocks of 2N samples, each one launch row
     // and one CONV tile row: block f loads the samples s0 + f S .. s0 + f S + 2N - 1 of its signal (zeros outside the row,
     // never loaded; one pair load where both samples lie inside, as aligned as the block's start), and of its circular result
@@ -1596,6 +1660,7 @@ MIFFT_DEV void run_pass(const TileParams& p, cpx<typename C::T>* lds, const cpx<
 template <class C>
 MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx<typename C::T>* twr, const int tid_entry) {
     using T = typename C::T;
+    using ST = typename C::IT;  // (the storage type of x and gy: TileCfg::CONV)
     using V = cpx<T>;
     constexpr int PAIRS = C::N / 2 + 1;
     constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
@@ -1607,8 +1672,8 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
     const long long q_end = q + len + (sl < rem ? 1 : 0);
     const int F = C::OLS ? p.ols_blocks : 1, S = p.ols_step, s0 = C::OLS ? p.ols_start : 0;
     const int c0 = p.stft_hop, Lo = p.stft_frames, L = p.stft_len;
-    const T* x = (const T*)p.in;
-    const T* gy = (const T*)p.gate_in;
+    const ST* x = (const ST*)p.in;
+    const ST* gy = (const ST*)p.gate_in;
     const V* w = (const V*)p.r2c_tw;
     V acc_a[IT], acc_b[IT];
 #pragma unroll
@@ -1649,13 +1714,13 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
                     db = fr / F;
                     fr -= db * F;
                 }
-                const T* xe = x + ((b0 + db) * D + d) * (long long)L;
+                const ST* xe = x + ((b0 + db) * D + d) * (long long)L;
                 const int i = s0 + fr * S + 2 * m;
                 if (i >= 0 && i + 1 < L) {
-                    v = gload_pair(xe + i);
+                    v = sload_pair<T>(xe + i);
                 } else {
-                    if (i >= 0 && i < L) v.x = xe[i];
-                    if (i + 1 >= 0 && i + 1 < L) v.y = xe[i + 1];
+                    if (i >= 0 && i < L) v.x = sload<T>(xe + i);
+                    if (i + 1 >= 0 && i + 1 < L) v.y = sload<T>(&xe[i + 1]);
                 }
             }
             lds[lds_index<C, -1>(c, m)] = v;
@@ -1678,12 +1743,12 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
                 }
                 const int u = 2 * m - c0, t = fr * S + u;
                 const bool w0 = u >= 0 && u < S && t < Lo, w1 = u + 1 >= 0 && u + 1 < S && t + 1 < Lo;
-                const T* ge = gy + ((b0 + db) * D + d) * (long long)Lo;
+                const ST* ge = gy + ((b0 + db) * D + d) * (long long)Lo;
                 if (w0 && w1) {
-                    v = gload_pair(ge + t);
+                    v = sload_pair<T>(ge + t);
                 } else {
-                    if (w0) v.x = ge[t];
-                    if (w1) v.y = ge[t + 1];
+                    if (w0) v.x = sload<T>(ge + t);
+                    if (w1) v.y = sload<T>(&ge[t + 1]);
                 }
             }
             lds[lds_index<C, -1>(c, m)] = v;
@@ -1735,6 +1800,7 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
 template <class C>
 MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx<typename C::T>* twr, const int tid_entry) {
     using T = typename C::T;
+    using ST = typename C::IT;  // (the storage type of x, the gates and out: TileCfg::CONV)
     using V = cpx<T>;
     constexpr int PAIRS = C::N / 2 + 1, NN = 2 * C::N;
     constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
@@ -1763,8 +1829,8 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
         const int nv = p.n_rows - r0 < C::TILE ? (int)(p.n_rows - r0) : C::TILE;
         // (signal, block) of the tile's first row once, uniform; a row further on wraps into the signals that follow
         const int fr0 = (int)(r0 - b0 * F);
-        const T* x0 = (const T*)p.in + b0 * len;
-        const T* g0 = (C::GATE & 1) ? (const T*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
+        const ST* x0 = (const ST*)p.in + b0 * len;
+        const ST* g0 = (C::GATE & 1) ? (const ST*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
         const unsigned d0 = (unsigned)(((long long)p.spec_bands + b0) % (long long)D);  // (uniform; d0 + c < 2^31)
         // first sample of the block that row c of the tile loads for partition pp (|.| < 2^31: T, P Q <= 2^30, F S < T + 2N);
         // the block holds a sample of its row when it starts after -n and before T
@@ -1792,23 +1858,23 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
                 V x = {(T)0, (T)0};
                 if (c < nv) {
                     const int db = fr0 + c >= F ? (fr0 + c) / F : 0;
-                    const T* xe = x0 + (long long)db * len;
-                    const T* ge = g0 + (long long)db * len;
+                    const ST* xe = x0 + (long long)db * len;
+                    const ST* ge = g0 + (long long)db * len;
                     const long long i = start(c, pp) + 2 * m;
                     if (i >= 0 && i + 1 < len) {
-                        x = gload_pair(xe + i);
+                        x = sload_pair<T>(xe + i);
                         if constexpr (C::GATE & 1) {
-                            const V g = gload_pair(ge + i);
+                            const V g = sload_pair<T>(ge + i);
                             x = {g.x * x.x, g.y * x.y};
                         }
                     } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
                         if (i >= 0 && i < len) {
-                            x.x = xe[i];
-                            if constexpr (C::GATE & 1) x.x = ge[i] * x.x;
+                            x.x = sload<T>(xe + i);
+                            if constexpr (C::GATE & 1) x.x = sload<T>(ge + i) * x.x;
                         }
                         if (i + 1 >= 0 && i + 1 < len) {
-                            x.y = xe[i + 1];
-                            if constexpr (C::GATE & 1) x.y = ge[i + 1] * x.y;
+                            x.y = sload<T>(&xe[i + 1]);
+                            if constexpr (C::GATE & 1) x.y = sload<T>(&ge[i + 1]) * x.y;
                         }
                     }
                 }
@@ -1865,8 +1931,8 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
         __syncthreads();
         run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
         // the OLS store: sample i of block fr goes to out[b Lo + fr S + i - c] for c <= i < c + S and fr S + i - c < Lo only
-        T* out0 = (T*)p.out + b0 * Lo;
-        const T* q0 = (C::GATE & 2) ? (const T*)p.gate_out + b0 * Lo : out0;  // (else unused)
+        ST* out0 = (ST*)p.out + b0 * Lo;
+        const ST* q0 = (C::GATE & 2) ? (const ST*)p.gate_out + b0 * Lo : out0;  // (else unused)
         for (int f = tid; f < nv * C::N; f += C::THREADS) {
             const int c = f / C::N, j = f - c * C::N, u = 2 * j - o;
             if (u + 1 < 0 || u >= S) continue;
@@ -1880,22 +1946,22 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
             if (!w0 && !w1) continue;
             const V v = lds[lds_index<C, C::NP - 1>(c, j)];
             T y0 = v.x * s, y1 = -(v.y * s);
-            T* q = out0 + (long long)db * Lo + tt;
-            const T* bq = q0 + (long long)db * Lo + tt;
-            if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+            ST* q = out0 + (long long)db * Lo + tt;
+            const ST* bq = q0 + (long long)db * Lo + tt;
+            if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(ST) - 1)) == 0) {
                 if constexpr (C::GATE & 2) {
-                    const V g = gload_pair(bq);
+                    const V g = sload_pair<T>(bq);
                     y0 = g.x * y0, y1 = g.y * y1;
                 }
-                gstore<false>((V*)q, V{y0, y1});
+                sstore_pair(q, y0, y1);
             } else {
                 if (w0) {
-                    if constexpr (C::GATE & 2) y0 = bq[0] * y0;
-                    q[0] = y0;
+                    if constexpr (C::GATE & 2) y0 = sload<T>(bq) * y0;
+                    sstore(q, y0);
                 }
                 if (w1) {
-                    if constexpr (C::GATE & 2) y1 = bq[1] * y1;
-                    q[1] = y1;
+                    if constexpr (C::GATE & 2) y1 = sload<T>(bq + 1) * y1;
+                    sstore(q + 1, y1);
                 }
             }
         }
@@ -2320,8 +2386,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             const int F = p.ols_blocks, S = p.ols_step, len = p.stft_len;
             const long long r0 = base / C::N, b0 = r0 / F;
             const int fr0 = (int)(r0 - b0 * F);
-            const T* x0 = (const T*)p.in + b0 * len;
-            const T* g0 = (C::GATE & 1) ? (const T*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
+            using ST = typename C::IT;  // (the storage type of x and the gates: TileCfg::CONV)
+            const ST* x0 = (const ST*)p.in + b0 * len;
+            const ST* g0 = (C::GATE & 1) ? (const ST*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
             for (int f = tid; f < nv * C::N; f += C::THREADS) {
                 const int c = f / C::N, m = f - c * C::N;
                 int fr = fr0 + c, db = 0;
@@ -2329,24 +2396,24 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     db = fr / F;
                     fr -= db * F;
                 }
-                const T* xe = x0 + (long long)db * len;
-                const T* ge = g0 + (long long)db * len;
+                const ST* xe = x0 + (long long)db * len;
+                const ST* ge = g0 + (long long)db * len;
                 const int i = p.ols_start + fr * S + 2 * m;  // (-2N < s0 + fr S < T <= 2^30: 32 bits hold it)
                 V x = {(T)0, (T)0};
                 if (i >= 0 && i + 1 < len) {
-                    x = gload_pair(xe + i);
+                    x = sload_pair<T>(xe + i);
                     if constexpr (C::GATE & 1) {
-                        const V g = gload_pair(ge + i);
+                        const V g = sload_pair<T>(ge + i);
                         x = {g.x * x.x, g.y * x.y};
                     }
                 } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
                     if (i >= 0 && i < len) {
-                        x.x = xe[i];
-                        if constexpr (C::GATE & 1) x.x = ge[i] * x.x;
+                        x.x = sload<T>(xe + i);
+                        if constexpr (C::GATE & 1) x.x = sload<T>(ge + i) * x.x;
                     }
                     if (i + 1 >= 0 && i + 1 < len) {
-                        x.y = xe[i + 1];
-                        if constexpr (C::GATE & 1) x.y = ge[i + 1] * x.y;
+                        x.y = sload<T>(&xe[i + 1]);
+                        if constexpr (C::GATE & 1) x.y = sload<T>(&ge[i + 1]) * x.y;
                     }
                 }
                 lds[lds_index<C, -1>(c, m)] = x;
@@ -2355,22 +2422,23 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
         } else if constexpr (C::CONV) {
             // packed element m of row c: the reals 2 m and 2 m + 1 of a row of L samples, zeros from sample L on
             const int L = p.stft_len;
-            const T* x0 = (const T*)p.in + (base / C::N) * L;
-            const T* g0 = (C::GATE & 1) ? (const T*)p.gate_in + (base / C::N) * L : x0;  // (else unused)
+            using ST = typename C::IT;  // (the storage type of x and the gates: TileCfg::CONV)
+            const ST* x0 = (const ST*)p.in + (base / C::N) * L;
+            const ST* g0 = (C::GATE & 1) ? (const ST*)p.gate_in + (base / C::N) * L : x0;  // (else unused)
             for (int f = tid; f < nv * C::N; f += C::THREADS) {
                 const int c = f / C::N, m = f - c * C::N;
-                const T* xr = x0 + (long long)c * L;
-                const T* gr = g0 + (long long)c * L;
+                const ST* xr = x0 + (long long)c * L;
+                const ST* gr = g0 + (long long)c * L;
                 V x = {(T)0, (T)0};
                 if (2 * m + 1 < L) {
-                    x = gload_pair(xr + 2 * m);
+                    x = sload_pair<T>(xr + 2 * m);
                     if constexpr (C::GATE & 1) {
-                        const V g = gload_pair(gr + 2 * m);
+                        const V g = sload_pair<T>(gr + 2 * m);
                         x = {g.x * x.x, g.y * x.y};
                     }
                 } else if (2 * m < L) {
-                    x.x = xr[2 * m];
-                    if constexpr (C::GATE & 1) x.x = gr[2 * m] * x.x;
+                    x.x = sload<T>(xr + 2 * m);
+                    if constexpr (C::GATE & 1) x.x = sload<T>(gr + 2 * m) * x.x;
                 }
                 lds[lds_index<C, -1>(c, m)] = x;
             }
@@ -2617,11 +2685,12 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             // imaginary part.  Samples o .. o + Lo - 1 go to a row of Lo reals.
             const int o = p.stft_hop, Lo = p.stft_frames;
             const T s = (T)p.scale;
+            using ST = typename C::IT;  // (the storage type of out and the postgate: TileCfg::CONV)
             if constexpr (C::OLS) {
                 // sample i of block fr goes to out[b Lo + fr S + i - c] for c <= i < c + S and fr S + i - c < Lo only
                 const int F = p.ols_blocks, S = p.ols_step;
-                T* out0 = (T*)p.out + sig0 * Lo;
-                const T* b0 = (C::GATE & 2) ? (const T*)p.gate_out + sig0 * Lo : out0;  // (else unused)
+                ST* out0 = (ST*)p.out + sig0 * Lo;
+                const ST* b0 = (C::GATE & 2) ? (const ST*)p.gate_out + sig0 * Lo : out0;  // (else unused)
                 for (int f = tid; f < nv * C::N; f += C::THREADS) {
                     const int c = f / C::N, j = f - c * C::N, u = 2 * j - o;
                     if (u + 1 < 0 || u >= S) continue;
@@ -2635,49 +2704,49 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     if (!w0 && !w1) continue;
                     const V v = lds[lds_index<C, C::NP - 1>(c, j)];
                     T y0 = v.x * s, y1 = -(v.y * s);
-                    T* q = out0 + (long long)db * Lo + t;
-                    const T* bq = b0 + (long long)db * Lo + t;
-                    if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                    ST* q = out0 + (long long)db * Lo + t;
+                    const ST* bq = b0 + (long long)db * Lo + t;
+                    if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(ST) - 1)) == 0) {
                         if constexpr (C::GATE & 2) {
-                            const V g = gload_pair(bq);
+                            const V g = sload_pair<T>(bq);
                             y0 = g.x * y0, y1 = g.y * y1;
                         }
-                        gstore<false>((V*)q, V{y0, y1});
+                        sstore_pair(q, y0, y1);
                     } else {
                         if (w0) {
-                            if constexpr (C::GATE & 2) y0 = bq[0] * y0;
-                            q[0] = y0;
+                            if constexpr (C::GATE & 2) y0 = sload<T>(bq) * y0;
+                            sstore(q, y0);
                         }
                         if (w1) {
-                            if constexpr (C::GATE & 2) y1 = bq[1] * y1;
-                            q[1] = y1;
+                            if constexpr (C::GATE & 2) y1 = sload<T>(bq + 1) * y1;
+                            sstore(q + 1, y1);
                         }
                     }
                 }
             } else {
-                T* out0 = (T*)p.out + row0 * Lo;
-                const T* b0 = (C::GATE & 2) ? (const T*)p.gate_out + row0 * Lo : out0;  // (else unused)
+                ST* out0 = (ST*)p.out + row0 * Lo;
+                const ST* b0 = (C::GATE & 2) ? (const ST*)p.gate_out + row0 * Lo : out0;  // (else unused)
                 for (int f = tid; f < nv * C::N; f += C::THREADS) {
                     const int c = f / C::N, j = f - c * C::N, t = 2 * j - o;
                     if (t + 1 < 0 || t >= Lo) continue;
                     const V v = lds[lds_index<C, C::NP - 1>(c, j)];
                     T y0 = v.x * s, y1 = -(v.y * s);
-                    T* q = out0 + (long long)c * Lo + t;
-                    const T* bq = b0 + (long long)c * Lo + t;
-                    if (t >= 0 && t + 1 < Lo && ((unsigned long long)q & (2 * sizeof(T) - 1)) == 0) {
+                    ST* q = out0 + (long long)c * Lo + t;
+                    const ST* bq = b0 + (long long)c * Lo + t;
+                    if (t >= 0 && t + 1 < Lo && ((unsigned long long)q & (2 * sizeof(ST) - 1)) == 0) {
                         if constexpr (C::GATE & 2) {
-                            const V g = gload_pair(bq);
+                            const V g = sload_pair<T>(bq);
                             y0 = g.x * y0, y1 = g.y * y1;
                         }
-                        gstore<false>((V*)q, V{y0, y1});
+                        sstore_pair(q, y0, y1);
                     } else {
                         if (t >= 0) {
-                            if constexpr (C::GATE & 2) y0 = bq[0] * y0;
-                            q[0] = y0;
+                            if constexpr (C::GATE & 2) y0 = sload<T>(bq) * y0;
+                            sstore(q, y0);
                         }
                         if (t + 1 < Lo) {
-                            if constexpr (C::GATE & 2) y1 = bq[1] * y1;
-                            q[1] = y1;
+                            if constexpr (C::GATE & 2) y1 = sload<T>(bq + 1) * y1;
+                            sstore(q + 1, y1);
                         }
                     }
                 }

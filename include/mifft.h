@@ -486,7 +486,8 @@ typedef enum {
  * The imaginary parts of the products at bins 0 and n / 2 are ignored, as numpy's irfft ignores them.
  *   - bases_len[0] is exactly 8 words of 32 bits:  TAG_LO | TAG_HI | D | o | Lo | mode | H_LO | H_HI.  The two tag words are
  *     the halves of a NaN that no window value can have (window values are finite), in the place of w[0]; D, o, Lo and mode
- *     are plain unsigned words (mode: bit 0 = correlate, every other bit 0); H_HI : H_LO is the 64-bit DEVICE address of H.
+ *     are plain unsigned words (mode: bit 0 = correlate, bits 8..15 the storage type of "Half-precision storage" below, every
+ *     other bit 0); H_HI : H_LO is the 64-bit DEVICE address of H.
  *     No other payload of a MIFFT_FLAG_STFT plan has length 8 with these first two words; every other payload means what it
  *     meant and keeps its refusals;
  *   - bases_len[1] is 0 (the default estimate) or radices of n, as for an STFT plan.
@@ -507,7 +508,7 @@ typedef enum {
  * rows (even, 8 .. 16384, F64 up to 12288, n / 2 without a prime factor above 32); L > n; ndim != 2; inverse != 0; a hop, a
  * centre bit, MIFFT_FLAG_STFT_POWER, MIFFT_FLAG_ISTFT, MIFFT_FLAG_FAITHFUL_STAGES, MIFFT_FLAG_HALF_SPECTRUM, MIFFT_FLAG_DCT,
  * MIFFT_FLAG_DCT_ND, MIFFT_FLAG_DCT_ORTHO or a keep bit; MIFFT_JIT=0.  MIFFT_ERR_BAD_BASES: Lo < 1 or o + Lo > n; D < 1; a
- * mode word with a bit other than bit 0; a null H address or one not aligned to one complex element (or radices that do not
+ * mode word with a bit other than bit 0 and the storage type in bits 8..15; a null H address or one not aligned to one complex element (or radices that do not
  * multiply to n).  MIFFT_ERR_BAD_BATCH: batch not a multiple of D.  MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.
  * MIFFT_ERR_BAD_COMPONENTS: in_components != 1.  MIFFT_ERR_TOO_LARGE: D > 2^30.
  *
@@ -517,7 +518,7 @@ typedef enum {
  *     word  2      D, the filter rows; signal row r takes filter row r % D
  *     word  3      c, the first sample of every block's circular result that is stored
  *     word  4      S, the samples stored per block, which is also the step between blocks
- *     word  5      mode; bit 0 = correlate (multiply by the conjugate), every other bit 0
+ *     word  5      mode; bit 0 = correlate (multiply by the conjugate), bits 8..15 the storage type (below), every other bit 0
  *     word  6, 7   H_LO, H_HI: the device address of the filter spectra, D rows of n / 2 + 1 complex values, as above
  *     word  8      F, the blocks per signal row
  *     word  9      s0 as a two's-complement int32: the index in x of block 0's first sample; it may be negative
@@ -610,7 +611,26 @@ typedef enum {
  * Refused before any device work, with the statuses of the 12- and 16-word forms: their checks of the flags, n, D, batch % D,
  * mode, H, S, c + S, F and Lo against F and S; MIFFT_ERR_BAD_BASES: Q outside 1 .. n - 1, S > n - Q + 1, P < 1 or
  * P Q > 2^30, Lo > 2^30, a gates word above 3, a non-zero word 12 .. 15, 18 or 19.  The tag in front of 17, 18, 19 or 21
- * words is no convolution payload; the 8-, 12- and 16-word payloads mean what they meant. */
+ * words is no convolution payload; the 8-, 12- and 16-word payloads mean what they meant.
+ *
+ * Half-precision storage: bits 8..15 of the MODE word (word 5) of all four forms -- 8, 12, 16 and 20 words -- and of the
+ * MIFFT_CONV_GRAD_TAG form below name the STORAGE type of the rows: 0 the plan's float type (what the word has always
+ * meant), MIFFT_F16 (7) or MIFFT_BF16 (8).  Bit 0 stays correlate; every other bit, and every other value in bits 8..15, is
+ * MIFFT_ERR_BAD_BASES as before (mode = 2 among them); a storage type on a plan that is not MIFFT_F32 is
+ * MIFFT_ERR_BAD_DTYPE.  in_dtype == out_dtype == MIFFT_F32 as ever: the arithmetic, H, the tables and the LDS tile are
+ * float.  With a storage type x, both gates and out are arrays of 2-byte elements:
+ *   - a load reads a pair of storage elements (4 bytes, aligned to one element) where it read a pair of floats, one element
+ *     (2 bytes) at the row ends, and widens each exactly; the pregate is the same single float multiplication of the widened
+ *     sample by the widened gate; a position the load zero-extends reads nothing;
+ *   - a store computes the finished sample in float exactly as the float plan does (v * 1/n, then the postgate), rounds it
+ *     ONCE to the storage type -- to nearest even; MIFFT_F16: overflow gives infinity, subnormals are kept; a NaN stays one
+ *     -- and writes a pair where the address is aligned to two storage elements (4 bytes), element by element elsewhere;
+ *     every output sample is written exactly once.
+ * So the result equals, bit for bit, the F32 plan's on the widened tensors, rounded to nearest even.  What changes besides:
+ * the kernel (the float plan's name with `_h16` or `_b16` before `_jit`, e.g. rows16384_r2c_16x8x8x8_conv_ols_g3_b16_jit; run time
+ * only, MIFFT_JIT=0 refuses the plan); mifft_plan_in_bytes() / _out_bytes(), which count 2 bytes per element;
+ * mifft_exec_batch's offsets, first * L and first * Lo in STORAGE elements for x, out and both gates; the alias checks,
+ * which use the storage sizes.  One storage type per plan: x, the gates and out share it. */
 #define MIFFT_CONV_TAG_LO 0x4F4E5601u
 #define MIFFT_CONV_TAG_HI 0x7FF84D43u
 /* the argument block of a gated convolution exec (above); the magic word is "MIFFTGA1" */
@@ -637,7 +657,7 @@ typedef struct mifft_gated_args {
  *     word  2      D >= 1 filter rows, batch % D == 0
  *     word  3      c: the first stored sample of every block (a single block: the forward plan's o)
  *     word  4      S: the samples stored per block (a single block: Lo), S >= 1, c + S <= n
- *     word  5      mode: bit 0, the forward plan correlated
+ *     word  5      mode: bit 0, the forward plan correlated; bits 8..15 the storage type of x and gv (below)
  *     word  6      F >= 1 blocks per row, (F - 1) S < Lo <= F S
  *     word  7      s0: the first sample of block 0 (signed), -n < s0 and s0 + (F - 1) S < L
  *     word  8      Lo >= 1: samples per row of gv
@@ -661,6 +681,11 @@ typedef struct mifft_gated_args {
  * Refused before any device work, with the forward plan's statuses: the flag, direction, dtype and component checks, the
  * limits of n (even, 8 .. 16384, float64 to 12288, n / 2 without a prime factor above 32), D and batch % D; MIFFT_ERR_BAD_BASES for the geometry rules above, a mode word beyond bit 0, P beyond its range or a non-zero
  * reserved word.  The 8-, 12- and 16-word MIFFT_CONV_TAG payloads are what they were.
+ * Half-precision storage: bits 8..15 of the mode word, as in the MIFFT_CONV_TAG forms above (0, MIFFT_F16 or MIFFT_BF16; an
+ * F32 plan only: MIFFT_ERR_BAD_DTYPE otherwise; any other value or bit MIFFT_ERR_BAD_BASES).  x and gv are then arrays of
+ * 2-byte elements, widened exactly in both block loads; the sums and the result stay float: mifft_plan_in_bytes() counts 2
+ * bytes per element of x, mifft_plan_out_bytes() is unchanged, the alias checks use the storage sizes, and the kernel's name
+ * carries `_h16` / `_b16` before `_jit`.  The result equals the F32 plan's on the widened tensors bit for bit.
  */
 #define MIFFT_CONV_GRAD_TAG_LO 0x44524701u
 #define MIFFT_CONV_GRAD_TAG_HI 0x7FF84D47u
