@@ -16,11 +16,12 @@ from __future__ import annotations
 import collections
 import ctypes
 import enum
+import functools
 import hashlib
 import math
 import threading
 from fractions import Fraction
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -521,18 +522,18 @@ class Plan:
     2 <= T <= (F - 1) M, ``inverse=True`` implied; ``stft_window`` as for ``mdct``, ``imdct_gain`` the factor on the synthesis
     window (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan in include/mifft.h, _check_imdct_layout, plan_imdct).  ``bases`` has
     three lists: two empty ones and the radices of M // 2 (or an empty one).
-    ``conv`` = (n, D, o, Lo, mode, address) (no reference counterpart): the fused FFT convolution of real rows,
+    ``conv`` = a ``ConvRequest`` (no reference counterpart): the fused FFT convolution of real rows,
     x (batch, L, 1) -> out (batch, Lo, 1), samples o .. o + Lo - 1 of irfft(rfft(x, n) * G[row % D], n) against the D filter
     spectra at the device ``address`` (mode bit 0: their conjugates); the caller keeps that buffer alive (MIFFT_CONV_TAG in
     include/mifft.h, plan_fftconv).  ``bases`` has two lists, an empty one and the radices of n (or an empty one).
-    Nine values, (n, D, c, S, mode, address, F, s0, Lo), are the overlap-save form (the 12-word payload): x (batch, T, 1) with
-    T possibly beyond n, F blocks of n samples per row, block f from sample s0 + f S on, of whose circular result the S
-    samples from c on are stored at f S of the row's Lo output samples.
-    ``conv`` with Q and P behind the nine values: partitioned overlap-save, the 20-word payload (plan_fftconv(partition=)).
-    ``conv_gates`` = 1, 2 or 3 beside either form: the 16-word payload, bit 0 a pregate of x's shape multiplied into the load,
-    bit 1 a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run).
-    Bits 8..15 of ``mode`` are the storage type of such a plan's rows (0, or the code of float16 / bfloat16 under float32:
-    ``ConvPlan.io_dtype``)."""
+    With ``S`` > 0 it is the overlap-save form: x (batch, T, 1) with T possibly beyond n, ``F`` blocks of n samples per row,
+    block f from sample ``s0`` + f S on, of whose circular result the S samples from ``o`` (= c) on are stored at f S of the
+    row's Lo output samples; with ``Q`` > 0 besides, partitioned overlap-save in ``P`` partitions of Q taps
+    (plan_fftconv(partition=)).  ``gates`` = 1, 2 or 3 on any form: bit 0 a pregate of x's shape multiplied into the load, bit 1
+    a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run).  Bits 8..15 of
+    ``mode`` are the storage type of the rows (0, or the code of float16 / bfloat16 under float32: ``ConvPlan.io_dtype``).
+    ``grad`` makes it the request of that convolution's filter gradient (``partials``; MIFFT_CONV_GRAD_TAG, ConvGradPlan),
+    whose ``out_shape`` is the incoming gradient's.  ``_conv_payload`` is the words of either."""
 
     io_dtype = None  # (a convolution plan with 16-bit rows in memory: ConvPlan / ConvGradPlan; None on every other plan)
 
@@ -541,7 +542,7 @@ class Plan:
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0, dst: bool = False, conv=None, conv_gates: int = 0):
+                 imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct = int(mdct), int(imdct)
         if dct_type not in (2, 4):
@@ -625,40 +626,13 @@ class Plan:
                      (FLAG_STFT_POWER if stft_power is not None else 0))
             stft, istft = True, False
         if conv is not None:  # (with any other mode as well: the library refuses the pair)
-            conv = tuple(int(v) for v in conv)
-            part = len(conv) == 11  # (partitioned overlap-save: the nine values, then Q and P; the 20-word payload)
-            ols = len(conv) == 9 or part  # (overlap-save: n, D, c, S, mode, address, F, s0, Lo; the 12-word payload)
-            if len(conv) not in (6, 9, 11):
-                raise MifftError(-5, "conv = (n, D, o, Lo, mode, address), (n, D, c, S, mode, address, F, s0, Lo) or the latter with "
-                                     f"Q and P behind it, got {len(conv)} values")
-            n_fft, D, o, Lo, mode, addr = conv[:6]
-            step = Lo
-            if ols:
-                blocks, start, Lo = conv[6:9]
             if len(in_shape) != 3 or len(out_shape) != 3 or in_shape[-1] != 1 or out_shape[-1] != 1:
                 raise MifftError(-1, f"convolution layouts are (batch, L, 1) -> (batch, Lo, 1), got {in_shape} -> {out_shape}")
-            if in_shape[0] != out_shape[0] or out_shape[1] != Lo:
-                raise MifftError(-2, f"x {in_shape} against out {out_shape} with Lo = {Lo}")
+            if in_shape[0] != out_shape[0] or out_shape[1] != conv.Lo:
+                raise MifftError(-2, f"x {in_shape} against out {out_shape} with Lo = {conv.Lo}")
             if axes is not None:
                 raise MifftError(ERR_UNSUPPORTED, "a convolution plan extends dim 0 and transforms dim 1: no axes")
-            for v, what in ((D, "D"), (o, "o"), (Lo, "Lo"), (mode, "mode")) + (((step, "S"), (blocks, "F")) if ols else ()):
-                if not 0 <= v < 1 << 32:
-                    raise MifftError(-5, f"{what} = {v} of a convolution plan does not fit an unsigned 32-bit word")
-            stft_dims = (in_shape[1], n_fft)
-            words = [CONV_TAG_LO, CONV_TAG_HI, D, o, step, mode, addr & 0xFFFFFFFF, (addr >> 32) & 0xFFFFFFFF]
-            if ols:
-                if not -(1 << 31) <= start < 1 << 31:
-                    raise MifftError(-5, f"s0 = {start} of a convolution plan does not fit a signed 32-bit word")
-                words += [blocks, start & 0xFFFFFFFF, Lo, 0]
-            if conv_gates:  # (the 16-word payload: word 8 is F, 0 for the single block; word 11 the gates)
-                if conv_gates not in (1, 2, 3):
-                    raise MifftError(-5, f"conv_gates = {conv_gates}: bit 0 the pregate, bit 1 the postgate (1, 2 or 3)")
-                words = (words + [0, 0, 0])[:11] + [int(conv_gates), 0, 0, 0, 0]
-            if part:  # (words 16 and 17 behind the 16 of the gated form, whose gates word 11 may be 0 here)
-                for v, what in ((conv[9], "Q"), (conv[10], "P")):
-                    if not 0 <= v < 1 << 32:
-                        raise MifftError(-5, f"{what} = {v} of a convolution plan does not fit an unsigned 32-bit word")
-                words = (words + [0] * 4)[:16] + [conv[9], conv[10], 0, 0]
+            stft_dims, words = (in_shape[1], conv.n), _conv_payload(conv)
             flags = (int(flags) | FLAG_STFT | (FLAG_ISTFT if istft else 0) | (FLAG_DCT_ND if dctn else 0) |
                      (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
                      (FLAG_STFT_POWER if stft_power is not None else 0))
@@ -716,8 +690,8 @@ class Plan:
         self.dst = bool(dst) and (dct or dctn) and not stft and not istft
         self.mdct = mdct
         self.imdct = imdct
-        self.conv = None if conv is None else tuple(int(v) for v in conv)
-        self.conv_gates = int(conv_gates) if conv is not None else 0
+        self.conv = conv
+        self.conv_gates = conv.gates if conv is not None else 0
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
@@ -1660,15 +1634,76 @@ def _fftconv_ok(n: int) -> bool:
     return h == 1
 
 
+@functools.lru_cache(maxsize=None)
 def _fftconv_accepted(n: int, dtype) -> bool:
     """the library's own answer, from the checks it makes before it looks for a device (device -1 is none): the packed rows
-    of float64 refuse some sixty lengths below 12288 that those of float32 take (434 is the first)"""
+    of float64 refuse some sixty lengths below 12288 that those of float32 take (434 is the first).  Asked once per (n, dtype)."""
     code = _DTYPE_CODE[dtype]
     h = ctypes.c_void_p()
     flat = (ctypes.c_uint32 * 8)(CONV_TAG_LO, CONV_TAG_HI, 1, 0, 1, 0, 16, 0)
     rc = _lib.lib().mifft_plan_create(ctypes.byref(h), -1, code, code, 2, (ctypes.c_int64 * 2)(2, n), 1, 1, 0, flat,
                                       (ctypes.c_int32 * 2)(8, 0), FLAG_STFT)
     return rc == -10
+
+
+def _fftconv_check_length(who: str, what: str, n: int, dtype) -> None:
+    """the one refusal of an FFT length (``what``: the argument it came in), before any device work"""
+    if not (_fftconv_ok(n) and _fftconv_accepted(n, dtype)):
+        raise MifftError(ERR_UNSUPPORTED, f"{who}: {what} = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
+                                          "n // 2 without a prime factor above 32): see fftconv_length")
+
+
+class ConvRequest(NamedTuple):
+    """What a convolution plan is asked for (``Plan(conv=)``): the FFT length ``n``, ``D`` filter rows, the stored samples
+    ``o`` .. of ``Lo`` per row; on an overlap-save plan ``S`` > 0 samples stored per block from sample ``o`` (= c) of its
+    result on, ``F`` blocks per row and the first block's start ``s0`` (a single block: 0, 1, 0); ``Q`` > 0 taps per partition
+    and ``P`` partitions on a partitioned one; the ``mode`` word, the device ``address`` of the filter spectra, the ``gates`` bits.  ``grad``: the
+    filter gradient of that convolution instead, in ``partials`` sums per channel (0: the library's choice)."""
+    n: int
+    D: int
+    o: int
+    Lo: int
+    S: int = 0
+    F: int = 1
+    s0: int = 0
+    Q: int = 0
+    P: int = 0
+    mode: int = 0
+    address: int = 0
+    gates: int = 0
+    grad: bool = False
+    partials: int = 0
+
+
+def _conv_payload(r: ConvRequest) -> list:
+    """The payload words of a request, MIFFT_CONV_TAG's 8 (a single block), 12 (overlap-save), 16 (either, gated) or 20
+    (partitioned) or MIFFT_CONV_GRAD_TAG's 16 (include/mifft.h); status -5 for a value that does not fit its word.  Pure: no
+    device, no library call."""
+    r = ConvRequest(*(int(v) for v in r))
+    blocks = r.S > 0 or r.Q > 0
+    fields = ("D", "o", "Lo", "mode") + (("S", "F") if blocks else ())
+    for what in fields:
+        if not 0 <= getattr(r, what) < 1 << 32:
+            raise MifftError(-5, f"{what} = {getattr(r, what)} of a convolution plan does not fit an unsigned 32-bit word")
+    if blocks and not -(1 << 31) <= r.s0 < 1 << 31:
+        raise MifftError(-5, f"s0 = {r.s0} of a convolution plan does not fit a signed 32-bit word")
+    if r.gates not in (0, 1, 2, 3):
+        raise MifftError(-5, f"conv_gates = {r.gates}: bit 0 the pregate, bit 1 the postgate (1, 2 or 3)")
+    for what in ("Q", "P", "partials"):
+        if not 0 <= getattr(r, what) < 1 << 32:
+            raise MifftError(-5, f"{what} = {getattr(r, what)} of a convolution plan does not fit an unsigned 32-bit word")
+    if r.grad:  # (always the block geometry: a single block stores its Lo samples)
+        return [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, r.D, r.o, r.S or r.Lo, r.mode, r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.partials] + [0] * 6
+    words = [CONV_TAG_LO, CONV_TAG_HI, r.D, r.o, r.S if blocks else r.Lo, r.mode, r.address & 0xFFFFFFFF, (r.address >> 32) & 0xFFFFFFFF]
+    if blocks:
+        words += [r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.gates]
+    elif r.gates:  # (word 8, F, is 0 for the single block: o and Lo are words 3 and 4)
+        words += [0, 0, 0, r.gates]
+    if r.gates or r.Q:
+        words += [0, 0, 0, 0]
+    if r.Q:
+        words += [r.Q, r.P, 0, 0]
+    return words
 
 
 def fftconv_length(m: int, dtype=torch.float32) -> int:
@@ -1768,17 +1803,11 @@ class ConvPlan(Plan):
         with torch.cuda.stream(ctx.stream):
             shape = (channels, n // 2 + 1, 2) if partition is None else (channels, self.partitions, n // 2 + 1, 2)
             self.filter_spectrum = torch.zeros(shape, dtype=dtype, device=f"cuda:{ctx.device}")
-        mode, addr = (1 if correlate else 0) | _io_mode_bits(io_dtype), self.filter_spectrum.data_ptr()
-        if taps is None:
-            conv = (n, channels, offset, out_length, mode, addr)
-        elif partition is not None:
-            c, self.step, s0, self.blocks, P = _fftconv_part_geometry(n, partition, taps, offset, out_length, correlate)
-            conv = (n, channels, c, self.step, mode, addr, self.blocks, s0, out_length, partition, P)
-        else:
-            c, self.step, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
-            conv = (n, channels, c, self.step, mode, addr, self.blocks, s0, out_length)
+        req = _fftconv_request(n, channels, offset, out_length, correlate, taps, partition, io_dtype)
+        self.step, self.blocks = req.S or None, req.F
         super().__init__(dtype, dtype, (batch * channels, length, 1), (batch * channels, out_length, 1), device=ctx.device,
-                         conv=conv, conv_gates=(1 if self.pregate else 0) | (2 if self.postgate else 0))
+                         conv=req._replace(address=self.filter_spectrum.data_ptr(),
+                                           gates=(1 if self.pregate else 0) | (2 if self.postgate else 0)))
 
     def run(self, out: "torch.Tensor", x: "torch.Tensor", *, pregate: Optional["torch.Tensor"] = None,
             postgate: Optional["torch.Tensor"] = None, first: Optional[int] = None, count: Optional[int] = None) -> None:
@@ -1897,23 +1926,59 @@ def _fftconv_part_geometry(n: int, Q: int, K: int, offset: int, out_length: int,
     return _fftconv_ols_geometry(n, Q, offset, out_length, correlate) + (-(-K // Q),)
 
 
-def _fftconv_part_check(who: str, n: int, taps, partition, length: int, offset: int, out_length: int, correlate: bool) -> tuple:
-    """the argument checks of a partitioned plan (``taps`` = K, ``partition`` = Q), before any device work: (K, Q)"""
+def _fftconv_request(n: int, channels: int, offset: int, out_length: int, correlate: bool, taps, partition, io_dtype) -> ConvRequest:
+    """the request of ``plan_fftconv``'s / ``plan_fftconv_grad``'s arguments; address, gates and partials are the plan's to add"""
+    r = ConvRequest(n, channels, offset, out_length, mode=(1 if correlate else 0) | _io_mode_bits(io_dtype))
     if taps is None:
-        raise MifftError(-2, f"{who}: partition = {partition} goes with taps = K, the length of the filter")
-    K, Q = int(taps), int(partition)
-    if Q < 1 or Q > n - 1:
-        raise MifftError(-2, f"{who}: partition = {Q} taps per partition at the block length n = {n}: 1 <= partition <= n - 1")
-    if K < 1 or -(-K // Q) * Q > 1 << 30:
-        raise MifftError(-2, f"{who}: taps = {K} in partitions of {Q}: 1 <= taps, and at most 2^30 taps in whole partitions")
-    if length < 2 or length > 1 << 30:
-        raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {length} samples: 2 <= length <= 2^30")
-    full = length if correlate else length + K - 1
-    if offset < 0 or out_length < 1 or offset + out_length > full or out_length > 1 << 30:
-        raise MifftError(-5, f"{who}: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length <= 2^30, "
-                             f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
-                             f"{length} samples with {K} taps)")
-    return K, Q
+        return r
+    if partition is None:
+        c, S, s0, F = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
+        return r._replace(o=c, S=S, F=F, s0=s0)
+    c, S, s0, F, P = _fftconv_part_geometry(n, partition, taps, offset, out_length, correlate)
+    return r._replace(o=c, S=S, F=F, s0=s0, Q=partition, P=P)
+
+
+def _fftconv_plan_args(who: str, kind: str, dtype, batch, channels, length, n, taps, offset, out_length, correlate, partition,
+                       io_dtype) -> tuple:
+    """The argument checks ``plan_fftconv`` and ``plan_fftconv_grad`` (``who``; ``kind`` its noun) share, all before any
+    device work: (batch, channels, length, n, taps, offset, out_length, partition) as integers, ``out_length`` defaulted."""
+    batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
+    out_length = length if out_length is None else int(out_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"a {kind} plan reads and writes float32 or float64, got {dtype}")
+    _check_io_dtype(who, dtype, io_dtype)
+    if batch < 1 or channels < 1:
+        raise MifftError(-8, f"{who}: batch = {batch} and channels = {channels} must be positive")
+    _fftconv_check_length(who, "n", n, dtype)
+    if partition is not None:  # (``taps`` = K in partitions of Q taps)
+        if taps is None:
+            raise MifftError(-2, f"{who}: partition = {partition} goes with taps = K, the length of the filter")
+        taps, partition = int(taps), int(partition)
+        if partition < 1 or partition > n - 1:
+            raise MifftError(-2, f"{who}: partition = {partition} taps per partition at the block length n = {n}: 1 <= partition <= n - 1")
+        if taps < 1 or -(-taps // partition) * partition > 1 << 30:
+            raise MifftError(-2, f"{who}: taps = {taps} in partitions of {partition}: 1 <= taps, and at most 2^30 taps in whole partitions")
+    elif taps is not None:
+        taps = int(taps)
+        if taps < 1 or taps > n - 1:
+            raise MifftError(-2, f"{who}: taps = {taps} at the block length n = {n}: 1 <= taps <= n - 1")
+    if taps is None:  # (a single block: everything inside the FFT length)
+        if length < 2 or length > n:
+            raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {length} samples at n = {n}: 2 <= length <= n")
+        if offset < 0 or out_length < 1 or offset + out_length > n:
+            raise MifftError(-5, f"{who}: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
+                                 f"offset + out_length <= n = {n}")
+    else:  # (blocks: the window lies in the full linear result; a partitioned plan bounds out_length as well)
+        if length < 2 or length > 1 << 30:
+            raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {length} samples: 2 <= length <= 2^30")
+        full = length if correlate else length + taps - 1
+        cap = partition is not None and out_length > 1 << 30
+        if offset < 0 or out_length < 1 or offset + out_length > full or cap:
+            raise MifftError(-5, f"{who}: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length"
+                                 f"{' <= 2^30' if partition is not None else ''}, "
+                                 f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
+                                 f"{length} samples with {taps} taps)")
+    return batch, channels, length, n, taps, offset, out_length, partition
 
 
 def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
@@ -1944,46 +2009,10 @@ def plan_fftconv(dtype, batch: int, channels: int, length: int, n: int, *, taps:
     plan's on the widened tensors, rounded with ``.to(io_dtype)``, bit for bit.  Still one launch and no intermediate.
     The plan-level API carries no autograd; ``plan_fftconv_grad`` of the same arguments is the plan of its filter gradient,
     and the opposite-``correlate`` plan on rows of ``out_length`` samples its input gradient (what ``fftconv`` does)."""
-    batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
-    out_length = length if out_length is None else int(out_length)
-    if dtype not in _OUT_DTYPES:
-        raise MifftError(-4, f"a convolution plan reads and writes float32 or float64, got {dtype}")
-    _check_io_dtype("plan_fftconv", dtype, io_dtype)
-    if batch < 1 or channels < 1:
-        raise MifftError(-8, f"plan_fftconv: batch = {batch} and channels = {channels} must be positive")
-    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
-        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
-                                          "n // 2 without a prime factor above 32): see fftconv_length")
-    if partition is not None:
-        taps, partition = _fftconv_part_check("plan_fftconv", n, taps, partition, length, offset, out_length, correlate)
-        if ctx is None:
-            ctx = DeviceContext()
-        return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, pregate=pregate,
-                        postgate=postgate, partition=partition, io_dtype=io_dtype)
-    if taps is not None:
-        taps = int(taps)
-        if taps < 1 or taps > n - 1:
-            raise MifftError(-2, f"plan_fftconv: taps = {taps} at the block length n = {n}: 1 <= taps <= n - 1")
-        if length < 2 or length > 1 << 30:
-            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples: 2 <= length <= 2^30")
-        full = length if correlate else length + taps - 1
-        if offset < 0 or out_length < 1 or offset + out_length > full:
-            raise MifftError(-5, f"plan_fftconv: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
-                                 f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
-                                 f"{length} samples with {taps} taps)")
-        if ctx is None:
-            ctx = DeviceContext()
-        return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, pregate=pregate,
-                        postgate=postgate, io_dtype=io_dtype)
-    if length < 2 or length > n:
-        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv: rows of {length} samples at n = {n}: 2 <= length <= n")
-    if offset < 0 or out_length < 1 or offset + out_length > n:
-        raise MifftError(-5, f"plan_fftconv: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
-                             f"offset + out_length <= n = {n}")
-    if ctx is None:
-        ctx = DeviceContext()
-    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, pregate=pregate, postgate=postgate,
-                    io_dtype=io_dtype)
+    batch, channels, length, n, taps, offset, out_length, partition = _fftconv_plan_args(
+        "plan_fftconv", "convolution", dtype, batch, channels, length, n, taps, offset, out_length, correlate, partition, io_dtype)
+    return ConvPlan(dtype, batch, channels, length, n, offset, out_length, correlate, DeviceContext() if ctx is None else ctx, taps=taps,
+                    pregate=pregate, postgate=postgate, partition=partition, io_dtype=io_dtype)
 
 
 def _fftconv_pick(who: str, L: int, K: int, dtype, n: Optional[int], block: Optional[int]) -> tuple:
@@ -2008,9 +2037,7 @@ def _fftconv_pick(who: str, L: int, K: int, dtype, n: Optional[int], block: Opti
         raise MifftError(-2, f"{who}: a filter of K = {K} taps does not fit overlap-save blocks of {n} points (K <= block - 1)")
     if K > n:
         raise MifftError(-2, f"{who}: a filter of K = {K} taps does not fit the FFT length n = {n}")
-    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
-        raise MifftError(ERR_UNSUPPORTED, f"{who}: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
-                                          "n // 2 without a prime factor above 32): see fftconv_length")
+    _fftconv_check_length(who, "n", n, dtype)
     if taps is None and L > n:
         raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {L} samples are longer than the FFT length n = {n}")
     return n, taps
@@ -2037,9 +2064,7 @@ def _fftconv_pick_part(who: str, L: int, K: int, dtype, n: Optional[int], block:
     else:
         Q = int(partition)
         n = int(block) if block is not None else (8192 if dtype == torch.float64 else _FFTCONV_MAX)
-    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
-        raise MifftError(ERR_UNSUPPORTED, f"{who}: block = {n} is no accepted FFT length (even, 8 .. 16384, float64 to 12288, "
-                                          "n // 2 without a prime factor above 32): see fftconv_length")
+    _fftconv_check_length(who, "block", n, dtype)
     if Q < 1 or Q > n - 1:
         raise MifftError(-2, f"{who}: partition = {Q} taps per partition does not fit blocks of {n} points (1 <= partition <= block - 1)")
     return n, K, Q
@@ -2054,6 +2079,44 @@ def _fftconv_window(mode: str, L: int, K: int) -> tuple:
     if mode == "same":
         return (K - 1) // 2, L
     return min(L, K) - 1, max(L, K) - min(L, K) + 1  # "valid"
+
+
+def _fftconv_dtypes(x: "torch.Tensor", io_dtype) -> tuple:
+    """(the working dtype, what x, the gates and the result are in memory): float32 around ``io_dtype``; else x's own float
+    type, or float64"""
+    dtype = torch.float32 if io_dtype is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    return dtype, io_dtype or dtype
+
+
+def _fftconv_selector(n: int, taps, Q) -> dict:
+    """the ``n`` / ``block`` / ``partition`` arguments that make ``fftconv`` take the path (n, taps, Q) again"""
+    return {"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}
+
+
+def _fftconv_fwd_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, gates, Q=None, io_dtype=None):
+    """the cached forward plan of ``fftconv`` (the caller holds _PLAN_CACHE_LOCK)"""
+    key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
+           int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q, io_dtype)
+    plan = _PLAN_CACHE.get(key)
+    if plan is None:
+        plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
+                            correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2),
+                            io_dtype=io_dtype)
+        _plan_cache_insert(key, plan)
+    else:
+        _PLAN_CACHE.move_to_end(key)
+    return plan
+
+
+def _fftconv_exec(plan: ConvPlan, out, x, k, skip, pregate=None, postgate=None) -> None:
+    """one call's use of a cached plan: the filter's spectrum, the skip term, the launch (gated: ``run``)"""
+    plan.set_filter(k)
+    if skip is not None:
+        plan.add_skip(skip)
+    if plan.conv_gates:
+        plan.run(out, x, pregate=pregate, postgate=postgate)
+    else:
+        fft(out, x, DeviceContext(plan.device), plan=plan)
 
 
 def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mode: str = "causal",
@@ -2119,13 +2182,10 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         raise MifftError(-2, f"fftconv: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
     if io_dtype is not None and io_dtype not in _IO_DTYPES:
         raise MifftError(-4, f"fftconv: io_dtype is torch.bfloat16 or torch.float16 (or None), got {io_dtype}")
-    dtype = torch.float32 if io_dtype is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-    sdt = io_dtype or dtype  # (what x, the gates and the result are in memory)
+    dtype, sdt = _fftconv_dtypes(x, io_dtype)
     n, taps, Q = _fftconv_pick_part("fftconv", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
-    rows = 1
-    for m in logical[:-1]:
-        rows *= m
+    rows = math.prod(logical[:-1])
     if rows < 1:
         raise MifftError(-8, f"fftconv: no rows in {logical}")
     for g, shape, what, of in ((pregate, logical, "pregate", "x"), (postgate, logical[:-1] + (out_length,), "postgate", "the result")):
@@ -2157,25 +2217,10 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     out = torch.empty((rows, out_length, 1), dtype=sdt, device=xr.device)
     gates = (1 if pregate is not None else 0) | (2 if postgate is not None else 0)
     with _PLAN_CACHE_LOCK:
-        key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-               int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q, io_dtype)
-        plan = _PLAN_CACHE.get(key)
-        if plan is None:
-            plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
-                                correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2),
-                                io_dtype=io_dtype)
-            _plan_cache_insert(key, plan)
-        else:
-            _PLAN_CACHE.move_to_end(key)
-        plan.set_filter(k)
-        if skip is not None:
-            plan.add_skip(skip)
-        if gates:
-            a = pregate.to(sdt).contiguous().reshape(rows, L, 1) if pregate is not None else None
-            b = postgate.to(sdt).contiguous().reshape(rows, out_length, 1) if postgate is not None else None
-            plan.run(out, xr, pregate=a, postgate=b)
-        else:
-            fft(out, xr, DeviceContext(device), plan=plan)
+        plan = _fftconv_fwd_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, gates, Q, io_dtype)
+        a = pregate.to(sdt).contiguous().reshape(rows, L, 1) if pregate is not None else None
+        b = postgate.to(sdt).contiguous().reshape(rows, out_length, 1) if postgate is not None else None
+        _fftconv_exec(plan, out, xr, k, skip, a, b)
     return out.reshape(logical[:-1] + (out_length,))
 
 
@@ -2194,25 +2239,12 @@ class ConvGradPlan(Plan):
         self.io_dtype = io_dtype
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
-        self.taps, self.step, self.blocks = taps, None, 1
-        c, S, s0 = offset, out_length, 0
-        if taps is not None:
-            c, S, s0, self.blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)
-            self.step = S
+        req = _fftconv_request(n, channels, offset, out_length, correlate, taps, None, io_dtype)
+        self.taps, self.step, self.blocks = taps, req.S or None, req.F
         rows = batch * channels
-        words = [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, channels, c, S, (1 if correlate else 0) | _io_mode_bits(io_dtype), self.blocks, s0 & 0xFFFFFFFF,
-                 out_length, 0 if partials is None else int(partials)] + [0] * 6
-        self.in_dtype = self.out_dtype = dtype
-        self.in_shape, self.grad_shape = (rows, length, 1), (rows, out_length, 1)
-        self.inverse, self.device, self.flags, self.axes, self.whole_batch = False, int(ctx.device), FLAG_STFT, None, 0
-        self.half_spectrum = self.dct = self.dctn = self.istft = self.spectrogram = self.dst = False
-        self.stft, self.dct_type, self.mdct, self.imdct, self.conv, self.conv_gates = True, 2, 0, 0, None, 0
-        self._ndim = 2
-        h = ctypes.c_void_p()
-        check(_lib.lib().mifft_plan_create_slab(ctypes.byref(h), self.device, _DTYPE_CODE[dtype], _DTYPE_CODE[dtype], 2,
-                                                (ctypes.c_int64 * 2)(length, n), rows, 1, 0, (ctypes.c_uint32 * 16)(*words),
-                                                (ctypes.c_int32 * 2)(16, 0), FLAG_STFT, 0))
-        self._h = h
+        super().__init__(dtype, dtype, (rows, length, 1), (rows, out_length, 1), device=ctx.device,
+                         conv=req._replace(grad=True, partials=0 if partials is None else int(partials)))
+        self.grad_shape = self.out_shape  # (what Plan takes for the other side of x; the result's shape needs the built plan)
         self.partials = self.pass_geometry(1)[3] // channels
         self.out_shape = (self.partials, channels, n // 2 + 1, 2)
 
@@ -2344,52 +2376,21 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
     ``dtype`` = torch.float32 only): ``u`` and ``gy`` are tensors of it, widened exactly in the kernel's loads; the result
     stays float32 and equals the float32 plan's on the widened tensors bit for bit.  Every argument error is raised before
     any device work."""
-    batch, channels, length, n, offset = int(batch), int(channels), int(length), int(n), int(offset)
-    out_length = length if out_length is None else int(out_length)
-    if dtype not in _OUT_DTYPES:
-        raise MifftError(-4, f"a filter-gradient plan reads and writes float32 or float64, got {dtype}")
-    _check_io_dtype("plan_fftconv_grad", dtype, io_dtype)
-    if batch < 1 or channels < 1:
-        raise MifftError(-8, f"plan_fftconv_grad: batch = {batch} and channels = {channels} must be positive")
-    if not _fftconv_ok(n) or (dtype == torch.float64 and n > 12288):
-        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: n = {n} is no accepted FFT length (even, 8 .. 16384, float64 to "
-                                          "12288, n // 2 without a prime factor above 32): see fftconv_length")
-    if partition is not None:  # (the composed gradient of a partitioned plan: PartConvGradPlan)
-        taps, partition = _fftconv_part_check("plan_fftconv_grad", n, taps, partition, length, offset, out_length, correlate)
-        if partials is not None and not 1 <= int(partials) <= 65535:
-            raise MifftError(-5, f"plan_fftconv_grad: partials = {partials}: 1 .. 65535")
-        if ctx is None:
-            ctx = DeviceContext()
-        return PartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition,
-                                partials=partials, io_dtype=io_dtype)
-    blocks = 1
-    if taps is not None:
-        taps = int(taps)
-        if taps < 1 or taps > n - 1:
-            raise MifftError(-2, f"plan_fftconv_grad: taps = {taps} at the block length n = {n}: 1 <= taps <= n - 1")
-        if length < 2 or length > 1 << 30:
-            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: rows of {length} samples: 2 <= length <= 2^30")
-        full = length if correlate else length + taps - 1
-        if offset < 0 or out_length < 1 or offset + out_length > full:
-            raise MifftError(-5, f"plan_fftconv_grad: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
-                                 f"offset + out_length <= {full} (the {'correlation' if correlate else 'full convolution'} of "
-                                 f"{length} samples with {taps} taps)")
-        blocks = _fftconv_ols_geometry(n, taps, offset, out_length, correlate)[3]
-    else:
-        if length < 2 or length > n:
-            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad: rows of {length} samples at n = {n}: 2 <= length <= n")
-        if offset < 0 or out_length < 1 or offset + out_length > n:
-            raise MifftError(-5, f"plan_fftconv_grad: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
-                                 f"offset + out_length <= n = {n}")
+    batch, channels, length, n, taps, offset, out_length, partition = _fftconv_plan_args(
+        "plan_fftconv_grad", "filter-gradient", dtype, batch, channels, length, n, taps, offset, out_length, correlate, partition,
+        io_dtype)
     if partials is not None:
         partials = int(partials)
         if partials < 1 or partials > 65535:
             raise MifftError(-5, f"plan_fftconv_grad: partials = {partials}: 1 .. 65535")
-        partials = min(partials, batch * blocks)  # (capped by the pairs of a channel)
-    if ctx is None:
-        ctx = DeviceContext()
-    return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=taps, partials=partials,
-                        io_dtype=io_dtype)
+    if partition is not None:  # (the composed gradient of a partitioned plan: PartConvGradPlan)
+        return PartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, DeviceContext() if ctx is None else ctx, taps,
+                                partition, partials=partials, io_dtype=io_dtype)
+    if partials is not None:  # (capped by the pairs of a channel)
+        blocks = 1 if taps is None else _fftconv_ols_geometry(n, taps, offset, out_length, correlate)[3]
+        partials = min(partials, batch * blocks)
+    return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, DeviceContext() if ctx is None else ctx, taps=taps,
+                        partials=partials, io_dtype=io_dtype)
 
 
 def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None):
@@ -2434,16 +2435,13 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
         raise MifftError(-2, f"fftconv_filter_grad: rows of {L} samples (at least 2) and filters of {K} taps (at least 1)")
     if io_dtype is not None and io_dtype not in _IO_DTYPES:
         raise MifftError(-4, f"fftconv_filter_grad: io_dtype is torch.bfloat16 or torch.float16 (or None), got {io_dtype}")
-    dtype = torch.float32 if io_dtype is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-    sdt = io_dtype or dtype  # (what x and gy are in memory)
+    dtype, sdt = _fftconv_dtypes(x, io_dtype)
     n, taps, Q = _fftconv_pick_part("fftconv_filter_grad", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
     if tuple(gy.shape) != logical[:-1] + (out_length,):
         raise ValueError(f"fftconv_filter_grad: gy is {tuple(gy.shape)}, the result of that fftconv call is "
                          f"{logical[:-1] + (out_length,)}")
-    rows = 1
-    for m in logical[:-1]:
-        rows *= m
+    rows = math.prod(logical[:-1])
     if rows < 1:
         raise MifftError(-8, f"fftconv_filter_grad: no rows in {logical}")
     device = DeviceContext(x.device.index if x.is_cuda else None).device
@@ -2477,8 +2475,7 @@ class _FFTConvFunction(torch.autograd.Function):
         ctx.cfg, ctx.skip_f = cfg, skip_f
         ctx.save_for_backward(x, k, pregate, postgate, skip_t)
         return fftconv(x, k, mode=mode, correlate=correlate, pregate=pregate, postgate=postgate, io_dtype=io,
-                       skip=skip_t if skip_t is not None else skip_f,
-                       **({"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}))
+                       skip=skip_t if skip_t is not None else skip_f, **_fftconv_selector(n, taps, Q))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -2490,12 +2487,10 @@ class _FFTConvFunction(torch.autograd.Function):
         logical = tuple(x.shape)
         L, K = int(logical[-1]), int(k.shape[-1])
         D = int(k.shape[0]) if k.dim() == 2 else 1
-        dtype = torch.float32 if io is not None else x.dtype if x.dtype in _OUT_DTYPES else torch.float64
-        sdt = io or dtype  # (what the tensors of every launch here are in memory)
+        dtype, sdt = _fftconv_dtypes(x, io)
         o, Lo = _fftconv_window(mode, L, K)
-        rows = x.numel() // L
+        rows = math.prod(logical[:-1])
         device = x.device.index
-        sel = {"block": n, "partition": Q} if Q is not None else {"block": n} if taps is not None else {"n": n}
         gyr = gy.to(sdt).contiguous().reshape(rows, Lo)  # (sum().backward() hands in an expanded tensor)
         xr = x.to(sdt).contiguous().reshape(rows, L)
         ar = None if a is None else a.to(sdt).contiguous().reshape(rows, L)
@@ -2520,24 +2515,9 @@ class _FFTConvFunction(torch.autograd.Function):
             gates = (1 if pre is not None else 0) | (2 if fuse_a else 0)
             out = torch.empty((rows, L, 1), dtype=sdt, device=x.device)
             with _PLAN_CACHE_LOCK:
-                key = ("fftconv", dtype, rows, D, Lin, n, 0, L, not correlate, device,
-                       int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q, io)
-                plan = _PLAN_CACHE.get(key)
-                if plan is None:
-                    plan = plan_fftconv(dtype, rows // D, D, Lin, n, taps=taps, offset=0, out_length=L, correlate=not correlate,
-                                        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2), partition=Q,
-                                        io_dtype=io)
-                    _plan_cache_insert(key, plan)
-                else:
-                    _PLAN_CACHE.move_to_end(key)
-                plan.set_filter(k.detach())
-                if skip is not None:
-                    plan.add_skip(skip)
-                if gates:
-                    plan.run(out, src.reshape(rows, Lin, 1), pregate=None if pre is None else pre.reshape(rows, Lin, 1),
-                             postgate=ar.reshape(rows, L, 1) if fuse_a else None)
-                else:
-                    fft(out, src.reshape(rows, Lin, 1), DeviceContext(device), plan=plan)
+                plan = _fftconv_fwd_plan(dtype, rows, D, Lin, n, taps, 0, L, not correlate, device, gates, Q, io)
+                _fftconv_exec(plan, out, src.reshape(rows, Lin, 1), k.detach(), skip,
+                              None if pre is None else pre.reshape(rows, Lin, 1), ar.reshape(rows, L, 1) if fuse_a else None)
             gu = out.reshape(rows, L)
             if ar is None or fuse_a:
                 gx = gu
@@ -2548,7 +2528,7 @@ class _FFTConvFunction(torch.autograd.Function):
                 gx = None
         if need_b:  # gb = gy v, v = conv(u, k) + d u recomputed by one forward launch without the postgate
             v = fftconv(x.detach(), k.detach(), mode=mode, correlate=correlate, pregate=None if a is None else a.detach(),
-                        skip=skip, io_dtype=io, **sel)
+                        skip=skip, io_dtype=io, **_fftconv_selector(n, taps, Q))
             gb = gyr * v.reshape(rows, Lo)
         if need_k or need_d:
             gio = io

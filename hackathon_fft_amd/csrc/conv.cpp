@@ -21,7 +21,7 @@
 // blocks with the P spectra in registers before the one inverse.  Gated or not (word 11); one launch, no scratch.
 //
 // Bits 8..15 of the mode word of every form, the filter-gradient payload included, are the STORAGE type of the rows: 0 the
-// plan's float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan (Plan::conv_io, TileCfg::IT): x, the gates and out are then
+// plan's float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan (ConvRequest::io, TileCfg::IT): x, the gates and out are then
 // 2-byte elements, widened in the tile's load and rounded once in its store; H and the arithmetic stay float.
 #include <algorithm>
 
@@ -40,24 +40,6 @@ bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len)
 }
 
 // what the convolution payloads share: the flag, direction, dtype and component checks and the limits of n
-// the mode word of both payloads: bit 0 correlate, bits 8..15 the storage type (0, MIFFT_F16 or MIFFT_BF16; F32 plans only)
-static int conv_mode_check(Plan& p, uint32_t mode, const char* what, const char* bit0, std::string& why) {
-    const uint32_t io = (mode >> 8) & 0xffu;
-    if ((mode & ~0xff01u) || (io != 0 && io != MIFFT_F16 && io != MIFFT_BF16)) {
-        why = std::string("the mode word of a ") + what + " payload has bit 0 (" + bit0 +
-              ") and, in bits 8..15, a storage type (0, MIFFT_F16 or MIFFT_BF16) alone, not " + std::to_string(mode);
-        return MIFFT_ERR_BAD_BASES;
-    }
-    if (io != 0 && p.out_dtype != MIFFT_F32) {
-        why = std::string("the storage type ") + std::to_string(io) + " in the mode word of a " + what +
-              " payload: 16-bit rows are widened to float, so the plan must be MIFFT_F32";
-        return MIFFT_ERR_BAD_DTYPE;
-    }
-    p.conv_io = (int)io;
-    p.conv_mode = mode & 1u;
-    return MIFFT_OK;
-}
-
 static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
     const struct {
         uint32_t bits;
@@ -104,150 +86,197 @@ static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
     return MIFFT_OK;
 }
 
-int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
-               std::string& why) {
-    if (const int rc = conv_header_check(p, "MIFFT_CONV_TAG", why)) return rc;
+// ---- the rules: one set for both tags ------------------------------------------------------------------------------------------
+// the mode word: bit 0 correlate, bits 8..15 the storage type (0, MIFFT_F16 or MIFFT_BF16; F32 plans only)
+static int conv_mode_check(const Plan& p, ConvRequest& r, const char* noun, std::string& why) {
+    const uint32_t mode = r.mode, io = (mode >> 8) & 0xffu;
+    if ((mode & ~0xff01u) || (io != 0 && io != MIFFT_F16 && io != MIFFT_BF16)) {
+        why = std::string("the mode word of a ") + noun + " payload has bit 0 (" + (r.grad ? "the forward correlated" : "correlate") +
+              ") and, in bits 8..15, a storage type (0, MIFFT_F16 or MIFFT_BF16) alone, not " + std::to_string(mode);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (io != 0 && p.out_dtype != MIFFT_F32) {
+        why = std::string("the storage type ") + std::to_string(io) + " in the mode word of a " + noun +
+              " payload: 16-bit rows are widened to float, so the plan must be MIFFT_F32";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    r.io = (int)io;
+    r.mode = mode & 1u;
+    return MIFFT_OK;
+}
+
+// The geometry of a decoded request `r` against the plan's dims {L, n} and batch; `noun` is "convolution" or
+// "filter-gradient".  `blocks`: the words gave c, S, F, s0 and the row's Lo (always in a gradient payload); else o and Lo of
+// a single block; `part`: the 20-word form (whatever its Q says).  On success r is the plan's request: mode split, and S = 0 where a gradient's one block holds the whole row.
+static int conv_geometry_check(const Plan& p, ConvRequest& r, bool blocks, bool part, const char* noun, std::string& why) {
     const int64_t L = p.dims[0], n = p.dims[1];
-    const bool part = bases_len[0] == 20;  // (partitioned overlap-save: always blocks, F >= 1; word 11 = 0: no gates)
-    const bool gated = bases_len[0] == 16 || (part && bases_flat[11] != 0);  // (16 words: word 8 says which form it is, F = 0 the single block)
-    const bool ols = bases_len[0] == 12 || part || (gated && bases_flat[8] != 0);  // (overlap-save: rows of T = L samples in blocks of n)
-    if (ols && (L < 2 || L > (1ll << 30))) {
-        why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save convolution payload: 2 <= T <= 2^30";
+    const std::string payload = std::string(noun) + " payload";
+    const std::string of_blocks = (r.grad ? "a " : "an overlap-save ") + payload;
+    // (one block that holds the whole row is CONV's geometry; everything else, a single block of a longer row included, OLS's)
+    const bool whole = r.grad && r.F == 1 && r.s0 == 0 && r.S == r.Lo && L <= n;
+    if (blocks && !whole && (L < 2 || L > (1ll << 30))) {
+        why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save " + payload + ": 2 <= T <= 2^30";
         return L < 2 ? MIFFT_ERR_BAD_DIM : MIFFT_ERR_TOO_LARGE;
     }
-    if (!ols && L > n) {
+    if (!blocks && L > n) {
         why = "rows of L = " + std::to_string(L) + " samples are longer than the FFT length n = " + std::to_string(n) +
               " (L > n: rfft(x, n) would crop)";
         return MIFFT_ERR_UNSUPPORTED;
     }
-    const int64_t D = bases_flat[2], o = bases_flat[3], Lo = bases_flat[4];
-    const uint32_t mode = bases_flat[5];
-    const uint64_t addr = (uint64_t)bases_flat[6] | ((uint64_t)bases_flat[7] << 32);
-    if (ols) {  // (words 3 and 4 are c and S; Lo is word 10)
-        if (Lo < 1 || o + Lo > n) {
-            why = "the stored part c = " + std::to_string(o) + ", S = " + std::to_string(Lo) +
-                  " of every block of an overlap-save convolution payload: S >= 1 and c + S <= n = " + std::to_string(n);
+    if (blocks) {
+        if (r.S < 1 || r.o + r.S > n) {
+            why = "the stored part c = " + std::to_string(r.o) + ", S = " + std::to_string(r.S) + " of every block of " + of_blocks +
+                  ": S >= 1 and c + S <= n = " + std::to_string(n);
             return MIFFT_ERR_BAD_BASES;
         }
-    } else if (Lo < 1 || o + Lo > n) {
-        why = "the output window o = " + std::to_string(o) + ", Lo = " + std::to_string(Lo) +
-              " of a convolution payload: Lo >= 1 and o + Lo <= n = " + std::to_string(n);
+    } else if (r.Lo < 1 || r.o + r.Lo > n) {
+        why = "the output window o = " + std::to_string(r.o) + ", Lo = " + std::to_string(r.Lo) + " of a " + payload +
+              ": Lo >= 1 and o + Lo <= n = " + std::to_string(n);
         return MIFFT_ERR_BAD_BASES;
     }
-    if (D < 1) {
-        why = "D = 0 filter rows in a convolution payload: D >= 1";
+    if (r.D < 1) {
+        why = "D = 0 filter rows in a " + payload + ": D >= 1";
         return MIFFT_ERR_BAD_BASES;
     }
-    if (D > (1ll << 30)) {
-        why = "D = " + std::to_string(D) + " filter rows: at most 2^30";
+    if (r.D > (1ll << 30)) {
+        why = "D = " + std::to_string(r.D) + " filter rows: at most 2^30";
         return MIFFT_ERR_TOO_LARGE;
     }
-    if (p.batch % D != 0) {
-        why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(D) + " filter rows";
+    if (p.batch % r.D != 0) {
+        why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(r.D) + " filter rows";
         return MIFFT_ERR_BAD_BATCH;
     }
-    if (const int rc = conv_mode_check(p, mode, "convolution", "correlate", why)) return rc;
-    if (addr == 0) {
-        why = "the filter spectrum address H of a convolution payload is null";
+    if (const int rc = conv_mode_check(p, r, noun, why)) return rc;
+    const uint64_t addr = (uint64_t)(uintptr_t)r.h;
+    if (!r.grad && addr == 0) {
+        why = "the filter spectrum address H of a " + payload + " is null";
         return MIFFT_ERR_BAD_BASES;
     }
-    if (addr % (2 * dtype_size(p.out_dtype)) != 0) {
-        why = "the filter spectrum address H of a convolution payload is not aligned to one complex element (" +
+    if (!r.grad && addr % (2 * dtype_size(p.out_dtype)) != 0) {
+        why = "the filter spectrum address H of a " + payload + " is not aligned to one complex element (" +
               std::to_string(2 * dtype_size(p.out_dtype)) + " bytes)";
         return MIFFT_ERR_BAD_BASES;
     }
-    int64_t F = 1, s0 = 0, S = 0, rowLo = Lo;
-    if (ols) {
-        S = Lo;
-        F = bases_flat[8];
-        s0 = (int32_t)bases_flat[9];
-        rowLo = bases_flat[10];
-        if (F < 1 || rowLo < 1) {
-            why = "F = " + std::to_string(F) + " blocks and Lo = " + std::to_string(rowLo) +
-                  " output samples per row in an overlap-save convolution payload: F >= 1 and Lo >= 1";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        if (rowLo <= (F - 1) * S || rowLo > F * S) {
-            why = "Lo = " + std::to_string(rowLo) + " output samples per row against F = " + std::to_string(F) + " blocks of S = " +
-                  std::to_string(S) + ": (F - 1) S < Lo <= F S (the last block stores at least one sample)";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        // (partitioned: a block without a live partition stores zeros, so this rule does not apply; Lo is bounded instead)
-        if (!part && (s0 <= -n || s0 + (F - 1) * S >= L)) {
-            why = "block start s0 = " + std::to_string(s0) + " with F = " + std::to_string(F) + " blocks every S = " +
-                  std::to_string(S) + " samples: a block reads no sample of its row (-n < s0 and s0 + (F - 1) S < T = " +
-                  std::to_string(L) + ")";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        if (part && rowLo > (1ll << 30)) {
-            why = "Lo = " + std::to_string(rowLo) + " output samples per row in a partitioned convolution payload: at most 2^30";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        if (!gated && bases_flat[11] != 0) {
-            why = "the reserved word 11 of an overlap-save convolution payload must be 0, not " + std::to_string(bases_flat[11]);
-            return MIFFT_ERR_BAD_BASES;
-        }
+    if (!blocks) return MIFFT_OK;
+    const std::string row_samples = r.grad ? " samples per row of gy" : " output samples per row";
+    if (r.F < 1 || r.Lo < 1 || (r.grad && r.Lo > (1ll << 30))) {
+        why = "F = " + std::to_string(r.F) + " blocks and Lo = " + std::to_string(r.Lo) + row_samples + " in " + of_blocks +
+              (r.grad ? ": F >= 1 and 1 <= Lo <= 2^30" : ": F >= 1 and Lo >= 1");
+        return MIFFT_ERR_BAD_BASES;
     }
-    if (gated) {
-        if (!ols && (bases_flat[9] != 0 || bases_flat[10] != 0)) {
-            why = "words 9 and 10 (s0 = " + std::to_string(bases_flat[9]) + ", Lo = " + std::to_string(bases_flat[10]) +
-                  ") of a gated convolution payload with F = 0 (a single block: o and Lo are words 3 and 4) must be 0";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        if (bases_flat[11] < 1 || bases_flat[11] > 3) {
-            why = "the gates word 11 of a gated convolution payload has bit 0 (pregate) and bit 1 (postgate), at least one of them, not " +
-                  std::to_string(bases_flat[11]);
-            return MIFFT_ERR_BAD_BASES;
-        }
-        for (int w = 12; w < 16; ++w)
-            if (bases_flat[w] != 0) {
-                why = "the reserved word " + std::to_string(w) + " of a gated convolution payload must be 0, not " +
-                      std::to_string(bases_flat[w]);
-                return MIFFT_ERR_BAD_BASES;
-            }
+    if (r.Lo <= (r.F - 1) * r.S || r.Lo > r.F * r.S) {
+        why = "Lo = " + std::to_string(r.Lo) + row_samples + " against F = " + std::to_string(r.F) + " blocks of S = " +
+              std::to_string(r.S) + ": (F - 1) S < Lo <= F S (the last block " + (r.grad ? "stored" : "stores") + " at least one sample)";
+        return MIFFT_ERR_BAD_BASES;
     }
-    int64_t Q = 0, parts = 0;
-    if (part) {
-        Q = bases_flat[16];
-        parts = bases_flat[17];
-        if (Q < 1 || Q > n - 1) {
-            why = "Q = " + std::to_string(Q) + " taps per partition in a partitioned convolution payload: 1 <= Q <= n - 1 = " +
-                  std::to_string(n - 1);
-            return MIFFT_ERR_BAD_BASES;
-        }
-        if (S > n - Q + 1) {
-            why = "S = " + std::to_string(S) + " samples stored per block against Q = " + std::to_string(Q) +
-                  " taps per partition: S <= n - Q + 1 = " + std::to_string(n - Q + 1) + " (the rest wraps around)";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        if (parts < 1 || parts * Q > (1ll << 30)) {
-            why = "P = " + std::to_string(parts) + " partitions of Q = " + std::to_string(Q) +
-                  " taps in a partitioned convolution payload: P >= 1 and P Q <= 2^30";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        for (int w = 12; w < 20; ++w)
-            if (w != 16 && w != 17 && bases_flat[w] != 0) {
-                why = "the reserved word " + std::to_string(w) + " of a partitioned convolution payload must be 0, not " +
-                      std::to_string(bases_flat[w]);
-                return MIFFT_ERR_BAD_BASES;
-            }
+    // (partitioned: a block without a live partition stores zeros, so this rule does not apply; Lo is bounded instead)
+    if (!part && (r.s0 <= -n || r.s0 + (r.F - 1) * r.S >= L)) {
+        why = "block start s0 = " + std::to_string(r.s0) + " with F = " + std::to_string(r.F) + " blocks every S = " +
+              std::to_string(r.S) + " samples: a block reads no sample of its row (-n < s0 and s0 + (F - 1) S < T = " +
+              std::to_string(L) + ")";
+        return MIFFT_ERR_BAD_BASES;
     }
+    if (part && r.Lo > (1ll << 30)) {
+        why = "Lo = " + std::to_string(r.Lo) + " output samples per row in a partitioned " + payload + ": at most 2^30";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (whole) r.S = 0;
+    return MIFFT_OK;
+}
+
+// the partitions of a 20-word payload against its blocks
+static int conv_partition_check(const Plan& p, const ConvRequest& r, std::string& why) {
+    const int64_t n = p.dims[1];
+    if (r.Q < 1 || r.Q > n - 1) {
+        why = "Q = " + std::to_string(r.Q) + " taps per partition in a partitioned convolution payload: 1 <= Q <= n - 1 = " +
+              std::to_string(n - 1);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.S > n - r.Q + 1) {
+        why = "S = " + std::to_string(r.S) + " samples stored per block against Q = " + std::to_string(r.Q) +
+              " taps per partition: S <= n - Q + 1 = " + std::to_string(n - r.Q + 1) + " (the rest wraps around)";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.parts < 1 || r.parts * r.Q > (1ll << 30)) {
+        why = "P = " + std::to_string(r.parts) + " partitions of Q = " + std::to_string(r.Q) +
+              " taps in a partitioned convolution payload: P >= 1 and P Q <= 2^30";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    return MIFFT_OK;
+}
+
+// ---- the word layouts: the only code that knows which word sits where --------------------------------------------------------------
+// the words first .. last - 1 of a payload are reserved, but for `keep` (a bit per word)
+static int conv_reserved_check(const uint32_t* w, int first, int last, uint32_t keep, const char* form, std::string& why) {
+    for (int i = first; i < last; ++i)
+        if (!((keep >> i) & 1u) && w[i] != 0) {
+            why = "the reserved word " + std::to_string(i) + " of " + form + " payload must be 0, not " + std::to_string(w[i]);
+            return MIFFT_ERR_BAD_BASES;
+        }
+    return MIFFT_OK;
+}
+
+// the user radices of n behind the payload
+static int conv_radices(const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why) {
     if (bases_len[1] < 0) {
         why = "negative bases_len";
         return MIFFT_ERR_NO_BASES;
     }
     radices.clear();
     for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
-    p.conv_D = D;
-    p.conv_o = o;
-    p.conv_Lo = rowLo;
-    p.conv_Q = Q;
-    p.conv_parts = parts;
-    p.conv_S = S;
-    p.conv_F = F;
-    p.conv_s0 = s0;
-    p.conv_gates = gated ? bases_flat[11] : 0u;
-    p.conv_h = (const void*)(uintptr_t)addr;
+    return MIFFT_OK;
+}
+
+// MIFFT_CONV_TAG: 8 words D | o | Lo | mode | H behind the tag; 12: D | c | S | mode | H | F | s0 | Lo | 0; 16: the twelve with
+// F = 0 for a single block (o and Lo in words 3 and 4, words 9 and 10 zero) and the gates in word 11, then four zeros; 20: the
+// sixteen, gates or 0 in word 11, then Q | P | 0 | 0
+int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
+               std::string& why) {
+    if (const int rc = conv_header_check(p, "MIFFT_CONV_TAG", why)) return rc;
+    const uint32_t* w = bases_flat;
+    const int len = bases_len[0];
+    const bool part = len == 20;
+    const bool blocks = len == 12 || part || (len == 16 && w[8] != 0);
+    ConvRequest r;
+    r.D = w[2];
+    r.o = w[3];
+    r.mode = w[5];
+    r.h = (const void*)(uintptr_t)((uint64_t)w[6] | ((uint64_t)w[7] << 32));
+    if (blocks) {
+        r.S = w[4];
+        r.F = w[8];
+        r.s0 = (int32_t)w[9];
+        r.Lo = w[10];
+    } else {
+        r.Lo = w[4];
+    }
+    if (len >= 16) r.gates = w[11];
+    if (part) {
+        r.Q = w[16];
+        r.parts = w[17];
+    }
+    if (const int rc = conv_geometry_check(p, r, blocks, part, "convolution", why)) return rc;
+    if (len == 12)
+        if (const int rc = conv_reserved_check(w, 11, 12, 0, "an overlap-save convolution", why)) return rc;
+    if (r.gated() || len == 16) {
+        if (!blocks && (w[9] != 0 || w[10] != 0)) {
+            why = "words 9 and 10 (s0 = " + std::to_string(w[9]) + ", Lo = " + std::to_string(w[10]) +
+                  ") of a gated convolution payload with F = 0 (a single block: o and Lo are words 3 and 4) must be 0";
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (r.gates < 1 || r.gates > 3) {
+            why = "the gates word 11 of a gated convolution payload has bit 0 (pregate) and bit 1 (postgate), at least one of them, not " +
+                  std::to_string(r.gates);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (const int rc = conv_reserved_check(w, 12, 16, 0, "a gated convolution", why)) return rc;
+    }
+    if (part) {
+        if (const int rc = conv_partition_check(p, r, why)) return rc;
+        if (const int rc = conv_reserved_check(w, 12, 20, 3u << 16, "a partitioned convolution", why)) return rc;
+    }
+    if (const int rc = conv_radices(bases_flat, bases_len, radices, why)) return rc;
+    p.conv = r;
     return MIFFT_OK;
 }
 
@@ -258,7 +287,7 @@ int build_conv(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     ps.dim_index = 1;
     ps.N = n;
     ps.inner = 1;
-    ps.outer = p.conv_F;  // (overlap-save: the block rows of one signal row; else 1)
+    ps.outer = p.conv.F;  // (overlap-save: the block rows of one signal row; else 1)
     ps.radices = ordered;
     ps.processed = processed;
     ps.first = true;
@@ -277,90 +306,39 @@ bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases
     return bases_len[0] == 16 && bases_flat[0] == MIFFT_CONV_GRAD_TAG_LO && bases_flat[1] == MIFFT_CONV_GRAD_TAG_HI;
 }
 
+// MIFFT_CONV_GRAD_TAG: 16 words, D | c | S | mode | F | s0 | Lo | P behind the tag, then six zeros
 int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
                     std::string& why) {
     if (const int rc = conv_header_check(p, "MIFFT_CONV_GRAD_TAG", why)) return rc;
-    const int64_t L = p.dims[0], n = p.dims[1];
-    const int64_t D = bases_flat[2], c = bases_flat[3], S = bases_flat[4], F = bases_flat[6], s0 = (int32_t)bases_flat[7];
-    const int64_t Lo = bases_flat[8], P = bases_flat[9];
-    const uint32_t mode = bases_flat[5];
-    // (one block that holds the whole row is CONV's geometry; everything else, a single block of a longer row included, OLS's)
-    const bool single = F == 1 && s0 == 0 && S == Lo && L <= n;
-    if (!single && (L < 2 || L > (1ll << 30))) {
-        why = "signal rows of T = " + std::to_string(L) + " samples in an overlap-save filter-gradient payload: 2 <= T <= 2^30";
-        return L < 2 ? MIFFT_ERR_BAD_DIM : MIFFT_ERR_TOO_LARGE;
-    }
-    if (S < 1 || c + S > n) {
-        why = "the stored part c = " + std::to_string(c) + ", S = " + std::to_string(S) +
-              " of every block of a filter-gradient payload: S >= 1 and c + S <= n = " + std::to_string(n);
-        return MIFFT_ERR_BAD_BASES;
-    }
-    if (D < 1) {
-        why = "D = 0 filter rows in a filter-gradient payload: D >= 1";
-        return MIFFT_ERR_BAD_BASES;
-    }
-    if (D > (1ll << 30)) {
-        why = "D = " + std::to_string(D) + " filter rows: at most 2^30";
-        return MIFFT_ERR_TOO_LARGE;
-    }
-    if (p.batch % D != 0) {
-        why = "batch = " + std::to_string(p.batch) + " rows is not a multiple of D = " + std::to_string(D) + " filter rows";
-        return MIFFT_ERR_BAD_BATCH;
-    }
-    if (const int rc = conv_mode_check(p, mode, "filter-gradient", "the forward correlated", why)) return rc;
-    if (F < 1 || Lo < 1 || Lo > (1ll << 30)) {
-        why = "F = " + std::to_string(F) + " blocks and Lo = " + std::to_string(Lo) +
-              " samples per row of gy in a filter-gradient payload: F >= 1 and 1 <= Lo <= 2^30";
-        return MIFFT_ERR_BAD_BASES;
-    }
-    if (Lo <= (F - 1) * S || Lo > F * S) {
-        why = "Lo = " + std::to_string(Lo) + " samples per row of gy against F = " + std::to_string(F) + " blocks of S = " +
-              std::to_string(S) + ": (F - 1) S < Lo <= F S (the last block stored at least one sample)";
-        return MIFFT_ERR_BAD_BASES;
-    }
-    if (s0 <= -n || s0 + (F - 1) * S >= L) {
-        why = "block start s0 = " + std::to_string(s0) + " with F = " + std::to_string(F) + " blocks every S = " +
-              std::to_string(S) + " samples: a block reads no sample of its row (-n < s0 and s0 + (F - 1) S < T = " +
-              std::to_string(L) + ")";
-        return MIFFT_ERR_BAD_BASES;
-    }
-    const int64_t pairs = p.batch / D * F;  // (of one channel)
-    if (P > 65535 || P > pairs) {
-        why = "P = " + std::to_string(P) + " partial sums per channel in a filter-gradient payload: at most 65535 and at most the " +
+    const uint32_t* w = bases_flat;
+    ConvRequest r;
+    r.grad = true;
+    r.D = w[2];
+    r.o = w[3];
+    r.S = w[4];
+    r.mode = w[5];
+    r.F = w[6];
+    r.s0 = (int32_t)w[7];
+    r.Lo = w[8];
+    r.P = w[9];
+    if (const int rc = conv_geometry_check(p, r, true, false, "filter-gradient", why)) return rc;
+    const int64_t pairs = p.batch / r.D * r.F;  // (of one channel)
+    if (r.P > 65535 || r.P > pairs) {
+        why = "P = " + std::to_string(r.P) + " partial sums per channel in a filter-gradient payload: at most 65535 and at most the " +
               std::to_string(pairs) + " (row, block) pairs of a channel (0: the library's choice)";
         return MIFFT_ERR_BAD_BASES;
     }
-    for (int w = 10; w < 16; ++w)
-        if (bases_flat[w] != 0) {
-            why = "the reserved word " + std::to_string(w) + " of a filter-gradient payload must be 0, not " +
-                  std::to_string(bases_flat[w]);
-            return MIFFT_ERR_BAD_BASES;
-        }
-    if (bases_len[1] < 0) {
-        why = "negative bases_len";
-        return MIFFT_ERR_NO_BASES;
-    }
-    radices.clear();
-    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
-    p.conv_grad = true;
-    p.conv_D = D;
-    p.conv_o = c;
-    p.conv_Lo = Lo;
-    p.conv_S = single ? 0 : S;
-    p.conv_F = F;
-    p.conv_s0 = s0;
-    p.conv_P = P;
+    if (const int rc = conv_reserved_check(w, 10, 16, 0, "a filter-gradient", why)) return rc;
+    if (const int rc = conv_radices(bases_flat, bases_len, radices, why)) return rc;
+    p.conv = r;
     return MIFFT_OK;
 }
 
 // P of a built pass when the payload left it to the library: D P workgroups fill the device (as many as the persistent
 // grid of a row pass would have), every slice keeps at least one full step of TILE pairs, at most 65535
 static int64_t conv_grad_partials(const Plan& p, const DimPass& ps) {
-    long long per_cu = (160 * 1024) / (long long)(ps.lds_bytes ? ps.lds_bytes : 1);
-    per_cu = std::min<long long>(per_cu, 2048 / ps.threads);
-    per_cu = std::max<long long>(1, std::min<long long>(per_cu, 16));
-    const int64_t want = (int64_t)p.num_cus * per_cu, pairs = p.batch / p.conv_D * p.conv_F;
-    const int64_t P = (want + p.conv_D - 1) / p.conv_D;
+    const int64_t want = (int64_t)p.num_cus * pass_wg_per_cu(ps), pairs = p.batch / p.conv.D * p.conv.F;
+    const int64_t P = (want + p.conv.D - 1) / p.conv.D;
     return std::max<int64_t>(1, std::min<int64_t>({P, pairs / ps.tile, (int64_t)65535}));
 }
 
@@ -368,7 +346,7 @@ static int64_t conv_grad_partials(const Plan& p, const DimPass& ps) {
 int build_conv_grad(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
     const int rc = build_conv(p, ordered, processed, why);
     if (rc) return rc;
-    if (p.conv_P == 0) p.conv_P = conv_grad_partials(p, p.passes[0]);
+    if (p.conv.P == 0) p.conv.P = conv_grad_partials(p, p.passes[0]);
     return MIFFT_OK;
 }
 

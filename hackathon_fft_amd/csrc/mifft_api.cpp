@@ -25,17 +25,16 @@ int hip_error(hipError_t e, const char* what) {
 
 size_t Plan::in_elem_bytes() const { return dtype_size(in_dtype) * (size_t)in_components; }
 size_t Plan::out_elem_bytes() const { return dtype_size(out_dtype) * 2; }
-size_t Plan::conv_elem_bytes() const { return conv_io ? 2 : dtype_size(out_dtype); }
 size_t Plan::in_row_bytes() const {
-    if (stft() && (conv_D || conv_grad)) return (size_t)dims[0] * conv_elem_bytes();  // (rows of the storage type)
+    if (stft() && conv.is_conv()) return (size_t)dims[0] * conv.elem_bytes(out_dtype);  // (rows of the storage type)
     if (stft()) return (size_t)dims[0] * dtype_size(in_dtype);
     if (istft()) return (size_t)prod_half * in_elem_bytes();
     if (dct_any()) return (size_t)prod * dtype_size(in_dtype);
     return (size_t)(half_spectrum() && inverse ? prod_half : prod) * in_elem_bytes();
 }
 size_t Plan::out_row_bytes() const {
-    if (stft() && conv_grad) return 0;  // (the result is no row per batch entry: mifft_plan_out_bytes)
-    if (stft() && conv_D) return (size_t)conv_Lo * conv_elem_bytes();
+    if (stft() && conv.gradient()) return 0;  // (the result is no row per batch entry: mifft_plan_out_bytes)
+    if (stft() && conv.is_conv()) return (size_t)conv.Lo * conv.elem_bytes(out_dtype);
     if (stft() && mdct) return (size_t)(stft_frames() * mdct) * dtype_size(out_dtype);
     if (stft() && spec_power) return (size_t)(stft_frames() * stft_out_width()) * dtype_size(out_dtype);
     if (stft()) return (size_t)prod_half * out_elem_bytes();
@@ -109,7 +108,7 @@ struct DeviceGuard {
     }
 };
 
-// The exec of a gated convolution plan (conv.cpp; Plan::conv_gates): the `x` of mifft_exec / mifft_exec_batch is the HOST
+// The exec of a gated convolution plan (conv.cpp; ConvRequest::gates): the `x` of mifft_exec / mifft_exec_batch is the HOST
 // address of a mifft_gated_args, which names x and the gates of this exec.  Refused without a launch: a device address (the
 // signal itself, as an ungated plan takes it) or a block without the magic word, MIFFT_ERR_UNSUPPORTED; a gate the plan has
 // and the block lacks, MIFFT_ERR_NULL; a gate the plan did not ask for, MIFFT_ERR_UNSUPPORTED.  On success `x` is the signal.
@@ -125,7 +124,7 @@ static int unpack_gated_args(const Plan& p, const void*& x, const void*& pregate
     const mifft_gated_args* g = (const mifft_gated_args*)x;
     if (g->magic != MIFFT_GATED_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + kHow);
     if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_gated_args.x is NULL");
-    const bool want_a = p.conv_gates & 1u, want_b = p.conv_gates & 2u;
+    const bool want_a = p.conv.gates & 1u, want_b = p.conv.gates & 2u;
     if (want_a && !g->pregate) return set_error(MIFFT_ERR_NULL, "the plan has a pregate (gates bit 0): mifft_gated_args.pregate is NULL");
     if (want_b && !g->postgate) return set_error(MIFFT_ERR_NULL, "the plan has a postgate (gates bit 1): mifft_gated_args.postgate is NULL");
     if (!want_a && g->pregate) return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_gated_args.pregate is set, but the plan has no pregate (gates bit 0)");
@@ -136,7 +135,7 @@ static int unpack_gated_args(const Plan& p, const void*& x, const void*& pregate
     return MIFFT_OK;
 }
 
-// The exec of a filter-gradient plan (conv.cpp; Plan::conv_grad): `x` is the HOST address of a mifft_conv_grad_args, refused
+// The exec of a filter-gradient plan (conv.cpp; ConvRequest::grad): `x` is the HOST address of a mifft_conv_grad_args, refused
 // without a launch as above.  On success `x` and `gy` are the two inputs.
 static int unpack_conv_grad_args(const void*& x, const void*& gy) {
     static const char* kHow =
@@ -158,7 +157,7 @@ static int unpack_conv_grad_args(const void*& x, const void*& gy) {
 
 // the bytes of a filter-gradient plan's result: (P D, n / 2 + 1) complex values
 static size_t conv_grad_out_bytes(const Plan& p) {
-    return (size_t)(p.conv_P * p.conv_D) * (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
+    return (size_t)(p.conv.P * p.conv.D) * (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
 }
 
 static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first, int64_t count, void* stream) {
@@ -168,7 +167,7 @@ static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first
     const void* gy = nullptr;
     if (const int rc = unpack_conv_grad_args(x, gy)) return rc;
     const char *xb = (const char*)x, *gb = (const char*)gy, *ob = (const char*)out;
-    const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv_Lo * p.conv_elem_bytes(),
+    const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv.Lo * p.conv.elem_bytes(p.out_dtype),
                  on = conv_grad_out_bytes(p);
     if (xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
     if (gb < ob + on && ob < gb + gn) return set_error(MIFFT_ERR_ALIAS, "gy and out must not overlap");
@@ -511,14 +510,14 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     const Plan& p = plan->p;
     if (first < 0 || count < 0 || first + count > p.batch)
         return set_error(MIFFT_ERR_BAD_BATCH, "batch range out of bounds");
-    if (p.conv_grad) {  // (`x`: the HOST address of the exec's mifft_conv_grad_args; the whole batch or nothing)
+    if (p.conv.gradient()) {  // (`x`: the HOST address of the exec's mifft_conv_grad_args; the whole batch or nothing)
         if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
         return exec_conv_grad(p, x, out, first, count, stream);
     }
     if (count == 0) return MIFFT_OK;
     if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
     const void *pregate = nullptr, *postgate = nullptr;
-    if (p.conv_gates) {  // (a gated convolution: `x` is the HOST address of the exec's mifft_gated_args)
+    if (p.conv.gated()) {  // (a gated convolution: `x` is the HOST address of the exec's mifft_gated_args)
         const int rc = unpack_gated_args(p, x, pregate, postgate);  // (x: now the signal itself)
         if (rc) return rc;
     }
@@ -540,7 +539,7 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     hipStream_t s = (hipStream_t)stream;
     char* sb = p.d_scratch ? (char*)p.d_scratch + (size_t)first * p.scratch_row_bytes() : nullptr;
     auto buf = [&](int which) -> char* { return which == 0 ? (char*)xb : which == 2 ? sb : ob; };
-    if (p.conv_D) return launch_jit_conv(p, p.passes[0], xb, ob, ab, bb, first, count, s);  // (the filter row of row i: (first + i) % D)
+    if (p.conv.is_conv()) return launch_jit_conv(p, p.passes[0], xb, ob, ab, bb, first, count, s);  // (the filter row of row i: (first + i) % D)
     for (const DimPass& ps : p.passes) {
         const void* src = ps.src_buf >= 0 ? buf(ps.src_buf) : (ps.first ? (const char*)xb : ob);
         void* dst = ps.dst_buf >= 0 ? buf(ps.dst_buf) : ob;
@@ -612,7 +611,7 @@ size_t mifft_plan_in_bytes(const mifft_plan* plan) {
 }
 
 size_t mifft_plan_out_bytes(const mifft_plan* plan) {
-    if (plan && plan->p.conv_grad) return conv_grad_out_bytes(plan->p);
+    if (plan && plan->p.conv.gradient()) return conv_grad_out_bytes(plan->p);
     return plan ? (size_t)plan->p.batch * plan->p.out_row_bytes() : 0;
 }
 

@@ -127,6 +127,40 @@ struct DimPass {
                                // a runtime-specialised half-store kernel
 };
 
+// The request of a fused FFT convolution plan (a MIFFT_FLAG_STFT plan whose payload starts with MIFFT_CONV_TAG or
+// MIFFT_CONV_GRAD_TAG), as conv_check / conv_grad_check decoded it; dims = {L, n}.  x is (batch, L, 1) real, out
+// (batch, Lo, 1): the samples o .. o + Lo - 1 of irfft(rfft(x, n) G, n), row r against row r % D of the caller's device
+// buffer h (D rows of n / 2 + 1 complex values; never copied, never freed); mode bit 0: G = conj(H).
+struct ConvRequest {
+    int64_t D = 0, o = 0, Lo = 0;  // (D = 0: the plan is no convolution)
+    // overlap-save (S > 0): dims = {T, n}; every row is F blocks of n samples, block f from sample s0 + f S on (zeros outside
+    // the row), of whose circular result the S samples from o (= c) on are stored at f S of the row's Lo output samples.
+    // A single block has S = 0, F = 1, s0 = 0, in a filter-gradient plan as well.
+    int64_t S = 0, F = 1, s0 = 0;
+    // partitioned overlap-save (Q > 0): the filter is `parts` partitions of Q taps, h (D, parts, n / 2 + 1) complex values;
+    // block f sums, over the partitions p, the block of n samples from s0 + f S - p Q on (correlation: + p Q) times spectrum (d, p)
+    int64_t Q = 0, parts = 0;
+    // the filter gradient of the convolution the fields above describe (h unused), as P partial sums per channel: x and gy
+    // (mifft_conv_grad_args) -> (P D, n / 2 + 1) complex values, unscaled
+    int64_t P = 0;
+    bool grad = false;
+    uint32_t mode = 0;
+    // bits 8..15 of the mode word: the STORAGE type of x, the gates and out (a filter-gradient plan: of x and gy), 0 the plan's
+    // float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan: 2-byte elements widened in the load and rounded once in the
+    // store (TileCfg::CONV).  in_dtype and out_dtype stay F32; elem_bytes is what a sample occupies in memory.
+    int io = 0;
+    // bit 0 the pregate (a tensor of x's shape that multiplies x as it is loaded), bit 1 the postgate (one of out's shape that
+    // multiplies the result as it is stored); the tensors are arguments of every exec (mifft_gated_args), never plan state
+    uint32_t gates = 0;
+    const void* h = nullptr;
+    bool is_conv() const { return D > 0; }  // (forward or gradient)
+    bool overlap_save() const { return S > 0; }
+    bool partitioned() const { return Q > 0; }
+    bool gated() const { return gates != 0; }
+    bool gradient() const { return grad; }
+    size_t elem_bytes(int float_dtype) const;
+};
+
 struct Plan {
     int device = 0;
     int in_dtype = MIFFT_F32, out_dtype = MIFFT_F32;
@@ -184,7 +218,7 @@ struct Plan {
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
     int64_t stft_frames() const {
-        if (conv_D) return conv_F;  // (no frames, no hop: one row per batch entry, or the blocks of an overlap-save row)
+        if (conv.is_conv()) return conv.F;  // (no frames, no hop: one row per batch entry, or the blocks of an overlap-save row)
         if (mdct) return (dims[0] + mdct - 1) / mdct + 1;
         return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop();
     }
@@ -196,35 +230,8 @@ struct Plan {
     // a MIFFT_FLAG_ISTFT plan whose window payload is tagged with MIFFT_MDCT_TAG: the inverse MDCT of imdct = M = dims[2] / 2
     // coefficients per frame, dims = {T, F, 2 M}; x is (batch, F, M, 1) real, out (batch, T, 1).  0: not one.  Set by imdct_check.
     int64_t imdct = 0;
-    // a MIFFT_FLAG_STFT plan whose payload starts with MIFFT_CONV_TAG: the fused FFT convolution, dims = {L, n}; x is
-    // (batch, L, 1) real, out (batch, conv_Lo, 1): the samples conv_o .. conv_o + conv_Lo - 1 of irfft(rfft(x, n) G, n), row r
-    // against row r % conv_D of the caller's device buffer conv_h (conv_D rows of n / 2 + 1 complex values; never copied, never
-    // freed); conv_mode bit 0: G = conj(H).  conv_D = 0: not one.  Set by conv_check.
-    // The 12-word payload (overlap-save, conv_S > 0): dims = {T, n}, x is (batch, T, 1); every row is conv_F blocks of n
-    // samples, block f from sample conv_s0 + f conv_S on (zeros outside the row), of whose circular result the conv_S samples
-    // from conv_o (= c) on are stored at f conv_S of the row's conv_Lo output samples.  conv_S = 0, conv_F = 1: single block.
-    int64_t conv_D = 0, conv_o = 0, conv_Lo = 0;
-    int64_t conv_S = 0, conv_F = 1, conv_s0 = 0;
-    uint32_t conv_mode = 0;
-    // Bits 8..15 of the mode word: the STORAGE type of x, the gates and out (a filter-gradient plan: of x and gy), 0 the plan's
-    // float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan: 2-byte elements widened in the load and rounded once in the
-    // store (TileCfg::CONV).  in_dtype and out_dtype stay F32; conv_elem_bytes is what a sample occupies in memory.
-    int conv_io = 0;
-    size_t conv_elem_bytes() const;
-    const void* conv_h = nullptr;
-    // The 16-word payload (gated): conv_gates bit 0 the pregate (a tensor of x's shape that multiplies x as it is loaded), bit 1
-    // the postgate (one of out's shape that multiplies the result as it is stored); the tensors are arguments of every exec
-    // (mifft_gated_args), never plan state.  Its word 8 is F: 0 the single block (conv_S = 0), >= 1 overlap-save.  0: ungated.
-    uint32_t conv_gates = 0;
-    // The 20-word payload (partitioned overlap-save, conv_Q > 0): the filter is conv_parts partitions of conv_Q taps, conv_h
-    // (conv_D, conv_parts, n / 2 + 1) complex values; block f of a row sums, over the partitions p, the block of n samples
-    // from conv_s0 + f conv_S - p conv_Q on (correlation: + p conv_Q) times spectrum (d, p).  conv_gates as above, or 0.
-    int64_t conv_Q = 0, conv_parts = 0;
-    // The MIFFT_CONV_GRAD_TAG payload: the plan computes the filter gradient of the convolution the fields above describe
-    // (conv_h unused) as conv_P partial sums per channel: x and gy (mifft_conv_grad_args) -> (conv_P conv_D, n / 2 + 1)
-    // complex values, unscaled.  A single block has conv_S = 0, conv_F = 1, conv_s0 = 0 as in the forward plan.
-    bool conv_grad = false;
-    int64_t conv_P = 0;
+    // a MIFFT_FLAG_STFT plan whose payload starts with MIFFT_CONV_TAG or MIFFT_CONV_GRAD_TAG: the decoded request (conv.cpp)
+    ConvRequest conv;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
     bool dct4 = false;
     // a MIFFT_FLAG_DCT / MIFFT_FLAG_DCT_ND plan whose `bases` start with MIFFT_DST_TAG (DST-II and its inverse, along every
@@ -411,7 +418,7 @@ bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
 // bases_len[0] a tagged length (8, 12: overlap-save, 16: gated, or 20: partitioned) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
-// be refused without a device, leaving the request in plan.conv_* and the user radices of n in `radices`.  build_conv: the
+// be refused without a device, leaving the request in plan.conv and the user radices of n in `radices`.  build_conv: the
 // one pass.  select_jit_conv_rows is the packed-row kernel with TileCfg::CONV (kernels_jit.cpp; run time only),
 // conv_rows_supported the same check without a device; launch_jit_conv is its launch, which -- unlike a DimPass::launch --
 // knows the first row of the exec, for the filter row of every launch row, and takes the exec's two gates (null where the plan
@@ -429,6 +436,8 @@ bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases
 int conv_grad_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
 int build_conv_grad(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, const void* gy, void* out, hipStream_t stream);
+// workgroups per CU of a built tile-kernel pass's persistent grid (kernels_jit.cpp): the launches' rule, and build_conv_grad's
+long long pass_wg_per_cu(const DimPass& pass);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }
@@ -495,6 +504,7 @@ inline size_t dtype_size(int dt) {
     }
     return 0;
 }
+inline size_t ConvRequest::elem_bytes(int float_dtype) const { return io ? 2 : dtype_size(float_dtype); }
 
 }  // namespace mifft
 

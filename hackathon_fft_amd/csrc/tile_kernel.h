@@ -250,7 +250,9 @@ struct TileParams {
     // herm_js columns): the pass transforms the columns whose index along it is at most herm_dj / 2 and owns those below the
     // middle.  The column space is herm_rows rows of herm_L = herm_dj * herm_js columns; the first herm_H = (herm_dj / 2 + 1)
     // * herm_js columns of every row are covered by herm_tpr tiles, tiles_per_outer = rows * herm_tpr.
-    int herm_d0, herm_d1, herm_d2;
+    union { int herm_d0; int conv_Q; };      // PART: taps per partition
+    union { int herm_d1; int conv_parts; };  // PART: partitions of the filter
+    int herm_d2;
     int herm_dj, herm_js, herm_L, herm_H, herm_tpr;
     // HS configurations (the pass BEFORE a HERM last pass; a plane: its column side): results with an output index above
     // store_lim are not stored -- the last pass reads only the half of that dimension up to its middle and writes the rest
@@ -274,7 +276,10 @@ struct TileParams {
     // length) and is multiplied by stft_win, 2 N values of type T.  stft_center: 0 no frame leaves its entry, 1 the signal is
     // reflected at both ends (N <= stft_len - 1: one reflection), 2 zeros beyond both ends.
     const void* stft_win;
-    int stft_frames, stft_hop, stft_len, stft_center;
+    union { int stft_frames; int conv_Lo; };  // CONV: output samples per (signal) row, the pitch of `out` and gate_out
+    union { int stft_hop; int conv_o; };      // CONV: the first stored sample of every (block's) circular result, o / c
+    union { int stft_len; int conv_len; };    // CONV: samples per input row, L / T, the pitch of `in` and gate_in
+    union { int stft_center; int conv_D; };   // CONV: filter rows; row r takes filter row r % D
     // ISTFT configurations reuse the four integers (frames per entry F, hop, output samples per entry T, centred or not) and
     // stft_win (the synthesis table, below); tiles_per_outer is the tiles of ONE entry, ceil(F / TILE), and istft_env the
     // reciprocal envelope 1 / sum w^2 at every padded sample 0 .. 2 N + hop (F - 1) - 1, type T
@@ -282,44 +287,46 @@ struct TileParams {
     // SPEC configurations with a filterbank (TileCfg::FB): band m < spec_bands is sum_j spec_wt[spec_off[m] + j] *
     // P[spec_lo[m] + j], j < spec_len[m] (spec_lo[m] + spec_len[m] <= N + 1; weights of type T).  Without one the four
     // pointers are null and spec_bands is 0.
-    const void* spec_wt;
+    union { const void* spec_wt; const void* conv_h; };  // CONV: the filter spectra, (D[, parts], N + 1) complex values of type T
     const int* spec_lo;
     const int* spec_len;
     const int* spec_off;
-    int spec_bands;
+    // CONV: the first (signal) row of the launch modulo D; WGRAD: the partial sums per channel, P
+    union { int spec_bands; int conv_row0; int wgrad_partials; };
     // LOG configurations: y = fma(spec_a, log2(max(v + spec_add, spec_amin)), spec_c) on every value the SPEC / FB store
     // would have written; the four are exact values of type T (spec_amin a normal one, so the logarithm sees no denormal).
     // POST configurations (with FB): spec_post is a dense, row-major (spec_bands, spec_q) matrix of type T applied to the
     // bands of every frame, spec_bands <= N - 1; the store writes spec_q reals per frame.
     double spec_add, spec_amin, spec_a, spec_c;
     const void* spec_post;
-    int spec_q;
-    // CONV configurations (an R2C tile that is neither STFT nor SPEC) reuse seven of the fields above, so that the layout of
-    // the kernel argument stays what every other kernel was built for: stft_len = L samples per input row, stft_hop = o and
-    // stft_frames = Lo (the samples o .. o + Lo - 1 of every result are stored, rows of Lo reals), stft_center = D filter
-    // rows, spec_wt = the filter spectra, D rows of N + 1 complex values of type T (the caller's buffer), spec_bands = the
-    // launch's first row modulo D (row r of the launch takes filter row (spec_bands + r) % D), spec_q bit 0 = correlate
-    // (multiply by the conjugate).  scale is 1 / 2N; inverse is 0.
-    // OLS configurations (CONV's overlap-save twin) keep that mapping with stft_len = T samples per signal row (T may exceed
-    // 2N), stft_hop = c (the first sample of every block's circular result that is stored) and stft_frames = Lo (output
-    // samples per signal row), and add the three fields below: launch row r is block r % ols_blocks of signal r / ols_blocks;
-    // block f loads the 2N samples from ols_start + f * ols_step on (zeros outside [0, T)) and stores the samples
-    // c .. c + ols_step - 1 of its result to out[f * ols_step ..] of its signal's row, up to Lo.  spec_bands counts signals,
-    // not launch rows: signal b of the launch takes filter row (spec_bands + b) % D.
+    union { int spec_q; int conv_mode; };  // CONV: bit 0 = correlate (multiply by the conjugate)
+    // CONV configurations (an R2C tile that is neither STFT nor SPEC) read the conv_* names declared above on the bytes of
+    // fields no such tile uses otherwise, so that the layout of the kernel argument stays what every other kernel was built
+    // for.  Every form sets conv_len, conv_o, conv_Lo, conv_D, conv_h, conv_mode and conv_row0: the samples o .. o + Lo - 1
+    // of every result are stored, row r of the launch against filter row (conv_row0 + r) % D.  scale is 1 / 2N; inverse is 0.
+    // OLS configurations add the three fields below: launch row r is block r % ols_blocks of signal r / ols_blocks; block f
+    // loads the 2N samples from ols_start + f * ols_step on (zeros outside [0, conv_len)) and stores the samples
+    // conv_o .. conv_o + ols_step - 1 of its result to out[f * ols_step ..] of its signal's row, up to conv_Lo.  conv_row0
+    // counts signals, not launch rows.
     int ols_step, ols_blocks, ols_start;
-    // WGRAD configurations (the filter gradient of CONV / OLS) keep CONV's mapping and always carry the three ols_* fields
-    // (a single block: ols_blocks = 1, ols_start = 0, ols_step = Lo); `in` is x, gate_in is gy (rows of stft_frames = Lo
-    // reals), n_rows the pairs of ONE channel, B F, and spec_bands the partials P: workgroup w is slice w % P of channel
+    // WGRAD configurations (the filter gradient of CONV / OLS) always carry the three ols_* fields (a single block:
+    // ols_blocks = 1, ols_start = 0, ols_step = Lo) and wgrad_partials = P in the place of conv_row0; conv_h is null.  `in` is
+    // x, gate_in is gy (rows of conv_Lo reals), n_rows the pairs of ONE channel, B F: workgroup w is slice w % P of channel
     // w / P and stores row (w % P) D + w / P of `out`, (P D) rows of N + 1 complex values.
-    // PART configurations (partitioned overlap-save) keep OLS's mapping and reuse two fields no row tile reads: herm_d0 = Q
-    // taps per partition and herm_d1 = P partitions; spec_wt is (D, P, N + 1) complex values.
-    // GATE configurations (CONV / OLS with elementwise gates; the arguments of one exec, not plan state): gate_in has the
-    // shape of `in` (rows of stft_len reals) and multiplies every sample as it is loaded, gate_out the shape of `out` (rows of
-    // stft_frames reals) and multiplies every sample as it is stored.  Both point, as `in` and `out` do, at the exec's first
-    // signal row; null where the configuration has no such gate.
+    // PART configurations (partitioned overlap-save) are OLS's with conv_Q and conv_parts set.
+    // GATE configurations (CONV / OLS / PART with elementwise gates; the arguments of one exec, not plan state): gate_in has
+    // the shape of `in` and multiplies every sample as it is loaded, gate_out the shape of `out` and multiplies every sample as
+    // it is stored.  Both point, as `in` and `out` do, at the exec's first signal row; null where there is no such gate.
     const void* gate_in;
     const void* gate_out;
 };
+// (the conv_* names are other names of the same bytes: nothing moves)
+static_assert(sizeof(TileParams) == 352 && __builtin_offsetof(TileParams, conv_Q) == __builtin_offsetof(TileParams, herm_d0) &&
+                  __builtin_offsetof(TileParams, conv_o) == __builtin_offsetof(TileParams, stft_hop) &&
+                  __builtin_offsetof(TileParams, conv_h) == __builtin_offsetof(TileParams, spec_wt) &&
+                  __builtin_offsetof(TileParams, wgrad_partials) == __builtin_offsetof(TileParams, spec_bands) &&
+                  __builtin_offsetof(TileParams, conv_mode) == __builtin_offsetof(TileParams, spec_q),
+              "TileParams: a CONV name left the field it shares");
 
 // the log stage of a TileCfg::LOG store: fma(a, log2(max(v + add, amin)), c)
 template <typename T>
@@ -1664,14 +1671,14 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
     using V = cpx<T>;
     constexpr int PAIRS = C::N / 2 + 1;
     constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
-    const int D = p.stft_center, P = p.spec_bands;
+    const int D = p.conv_D, P = p.wgrad_partials;
     const int d = (int)blockIdx.x / P, sl = (int)blockIdx.x - d * P;
     // slice sl of the channel's pairs: a contiguous ascending range
     const long long Q = p.n_rows, len = Q / P, rem = Q - len * P;
     long long q = sl * len + (sl < rem ? sl : rem);
     const long long q_end = q + len + (sl < rem ? 1 : 0);
     const int F = C::OLS ? p.ols_blocks : 1, S = p.ols_step, s0 = C::OLS ? p.ols_start : 0;
-    const int c0 = p.stft_hop, Lo = p.stft_frames, L = p.stft_len;
+    const int c0 = p.conv_o, Lo = p.conv_Lo, L = p.conv_len;
     const ST* x = (const ST*)p.in;
     const ST* gy = (const ST*)p.gate_in;
     const V* w = (const V*)p.r2c_tw;
@@ -1769,7 +1776,7 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
     }
     // the TILE rows in ascending order, through the tile's LDS: first the bins k, then the bins N - k
     V* out = (V*)p.out + ((long long)sl * D + d) * (C::N + 1);
-    const T cj = (p.spec_q & 1) ? (T)-1 : (T)1;
+    const T cj = (p.conv_mode & 1) ? (T)-1 : (T)1;
     static_assert(C::TILE * PAIRS <= C::DATA_ELEMS, "WGRAD: one accumulator per (row, bin pair) fits the tile");
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -1804,14 +1811,14 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
     using V = cpx<T>;
     constexpr int PAIRS = C::N / 2 + 1, NN = 2 * C::N;
     constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
-    const int D = p.stft_center, Q = p.herm_d0, P = p.herm_d1;
-    const int F = p.ols_blocks, S = p.ols_step, s0 = p.ols_start, len = p.stft_len;
-    const int o = p.stft_hop, Lo = p.stft_frames;
-    const bool corr = (p.spec_q & 1) != 0;
+    const int D = p.conv_D, Q = p.conv_Q, P = p.conv_parts;
+    const int F = p.ols_blocks, S = p.ols_step, s0 = p.ols_start, len = p.conv_len;
+    const int o = p.conv_o, Lo = p.conv_Lo;
+    const bool corr = (p.conv_mode & 1) != 0;
     const T cj = corr ? (T)-1 : (T)1;
     const T s = (T)p.scale;
     const V* w = (const V*)p.r2c_tw;
-    const V* hs = (const V*)p.spec_wt;
+    const V* hs = (const V*)p.conv_h;
     V cur[1][C::R(0)];
     for (long long t = blockIdx.x; t < p.n_tiles; t += gridDim.x) {
         // (the thread index is made opaque once per PARTITION and once more for the fold and the store: what is derived from
@@ -1831,7 +1838,7 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
         const int fr0 = (int)(r0 - b0 * F);
         const ST* x0 = (const ST*)p.in + b0 * len;
         const ST* g0 = (C::GATE & 1) ? (const ST*)p.gate_in + b0 * len : x0;  // (the gate of the same signal row; else unused)
-        const unsigned d0 = (unsigned)(((long long)p.spec_bands + b0) % (long long)D);  // (uniform; d0 + c < 2^31)
+        const unsigned d0 = (unsigned)(((long long)p.conv_row0 + b0) % (long long)D);  // (uniform; d0 + c < 2^31)
         // first sample of the block that row c of the tile loads for partition pp (|.| < 2^31: T, P Q <= 2^30, F S < T + 2N);
         // the block holds a sample of its row when it starts after -n and before T
         auto start = [&](int c, int pp) -> long long {
@@ -2383,7 +2390,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
         } else if constexpr (C::OLS) {
             // (signal, block) of the tile's first row once, uniform; a row further on wraps into the signals that follow.
             // Packed element m of block fr: the samples st + 2 m and st + 2 m + 1 of its signal, st = s0 + fr S
-            const int F = p.ols_blocks, S = p.ols_step, len = p.stft_len;
+            const int F = p.ols_blocks, S = p.ols_step, len = p.conv_len;
             const long long r0 = base / C::N, b0 = r0 / F;
             const int fr0 = (int)(r0 - b0 * F);
             using ST = typename C::IT;  // (the storage type of x and the gates: TileCfg::CONV)
@@ -2421,7 +2428,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             __syncthreads();
         } else if constexpr (C::CONV) {
             // packed element m of row c: the reals 2 m and 2 m + 1 of a row of L samples, zeros from sample L on
-            const int L = p.stft_len;
+            const int L = p.conv_len;
             using ST = typename C::IT;  // (the storage type of x and the gates: TileCfg::CONV)
             const ST* x0 = (const ST*)p.in + (base / C::N) * L;
             const ST* g0 = (C::GATE & 1) ? (const ST*)p.gate_in + (base / C::N) * L : x0;  // (else unused)
@@ -2630,14 +2637,14 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             constexpr int PAIRS = C::N / 2 + 1;
             constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS, G = IT < 4 ? IT : 4;
             const long long row0 = base / C::N;
-            const unsigned D = (unsigned)p.stft_center;
+            const unsigned D = (unsigned)p.conv_D;
             // OLS: the filter row follows the signal row0 / F, and row c of the tile lies (ofr0 + c) / F signals further on
             const unsigned OF = C::OLS ? (unsigned)p.ols_blocks : 1u;
             const long long sig0 = C::OLS ? row0 / (long long)OF : row0;
             const unsigned ofr0 = C::OLS ? (unsigned)(row0 - sig0 * (long long)OF) : 0u;
-            const unsigned d0 = (unsigned)(((long long)p.spec_bands + sig0) % (long long)D);  // (uniform; d0 + c < 2^31)
-            const V* hs = (const V*)p.spec_wt;
-            const T cj = (p.spec_q & 1) ? (T)-1 : (T)1;
+            const unsigned d0 = (unsigned)(((long long)p.conv_row0 + sig0) % (long long)D);  // (uniform; d0 + c < 2^31)
+            const V* hs = (const V*)p.conv_h;
+            const T cj = (p.conv_mode & 1) ? (T)-1 : (T)1;
 #pragma unroll 1
             for (int i0 = 0; i0 < IT; i0 += G) {
                 V ga[G], gb[G];
@@ -2683,7 +2690,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             run_pass<C, 0>(p, lds, twr, cur, base, nv, tid, obase, fs_row, drain, slice);
             // conj(z) of the packed result, unscaled: sample 2 j is the real part of element j, sample 2 j + 1 minus its
             // imaginary part.  Samples o .. o + Lo - 1 go to a row of Lo reals.
-            const int o = p.stft_hop, Lo = p.stft_frames;
+            const int o = p.conv_o, Lo = p.conv_Lo;
             const T s = (T)p.scale;
             using ST = typename C::IT;  // (the storage type of out and the postgate: TileCfg::CONV)
             if constexpr (C::OLS) {

@@ -268,6 +268,7 @@ def test_plan_fftconv_validates_before_device_work():
                              ((torch.float32, 2, 3, 40, 74), {}, UNSUPPORTED),
                              ((torch.float32, 2, 3, 40, 63), {}, UNSUPPORTED),
                              ((torch.float64, 2, 3, 40, 16384), {}, UNSUPPORTED),
+                             ((torch.float64, 2, 3, 40, 434), {}, UNSUPPORTED),  # (one of the lengths only float64 lacks)
                              ((torch.float32, 2, 3, 65, 64), {}, UNSUPPORTED),
                              ((torch.float32, 0, 3, 40, 64), {}, -8),
                              ((torch.float32, 2, 0, 40, 64), {}, -8),
@@ -281,3 +282,64 @@ def test_plan_fftconv_validates_before_device_work():
         with pytest.raises(mf.MifftError) as e:
             mf.plan_fftconv(torch.float32, 2, 3, 40, 64)
         assert e.value.status == -10
+
+
+# ---- the payload encoder -------------------------------------------------------------------------------------------------------
+GRAD_LO, GRAD_HI = 0x44524701, 0x7FF84D47
+_ADDR = 0x7F0012345600  # (words 6 and 7: 0x12345600, 0x7F00)
+_H = [0x12345600, 0x7F00]
+# one request per payload form; T = 1000 samples, K = Q = 33 taps at n = 64: c = 32, S = 32, s0 = -32, F = 32, P = 31.
+# The words are those the plan classes assembled for these arguments before the encoder existed, written out.
+_PAYLOADS = (
+    ("8 words", torch.float32, 40, dict(n=64, D=3, o=5, Lo=40, mode=1, address=_ADDR),
+     [TAG_LO, TAG_HI, 3, 5, 40, 1] + _H),
+    ("12 words", torch.float32, 1000, dict(n=64, D=3, o=32, Lo=1000, S=32, F=32, s0=-32, address=_ADDR),
+     [TAG_LO, TAG_HI, 3, 32, 32, 0] + _H + [32, 4294967264, 1000, 0]),
+    ("12 words, float64, 'same': s0 = -16", torch.float64, 1000, dict(n=64, D=3, o=32, Lo=1000, S=32, F=32, s0=-16, address=_ADDR),
+     [TAG_LO, TAG_HI, 3, 32, 32, 0] + _H + [32, 4294967280, 1000, 0]),
+    ("16 words, a single block", torch.float32, 40, dict(n=64, D=3, o=5, Lo=40, address=_ADDR, gates=3),
+     [TAG_LO, TAG_HI, 3, 5, 40, 0] + _H + [0, 0, 0, 3, 0, 0, 0, 0]),
+    ("16 words, overlap-save", torch.float32, 1000, dict(n=64, D=3, o=32, Lo=1000, S=32, F=32, s0=-32, address=_ADDR, gates=1),
+     [TAG_LO, TAG_HI, 3, 32, 32, 0] + _H + [32, 4294967264, 1000, 1, 0, 0, 0, 0]),
+    ("20 words", torch.float32, 1000, dict(n=64, D=3, o=32, Lo=1000, S=32, F=32, s0=-32, Q=33, P=31, address=_ADDR),
+     [TAG_LO, TAG_HI, 3, 32, 32, 0] + _H + [32, 4294967264, 1000, 0, 0, 0, 0, 0, 33, 31, 0, 0]),
+    ("20 words, gated", torch.float32, 1000, dict(n=64, D=3, o=32, Lo=1000, S=32, F=32, s0=-32, Q=33, P=31, address=_ADDR, gates=2),
+     [TAG_LO, TAG_HI, 3, 32, 32, 0] + _H + [32, 4294967264, 1000, 2, 0, 0, 0, 0, 33, 31, 0, 0]),
+    ("12 words, bfloat16 rows, correlation", torch.float32, 1000,
+     dict(n=64, D=3, o=0, Lo=1000, S=32, F=32, s0=0, mode=1 | (8 << 8), address=_ADDR),
+     [TAG_LO, TAG_HI, 3, 0, 32, 2049] + _H + [32, 0, 1000, 0]),
+    ("gradient, a single block", torch.float32, 40, dict(n=64, D=3, o=5, Lo=40, grad=True),
+     [GRAD_LO, GRAD_HI, 3, 5, 40, 0, 1, 0, 40, 0, 0, 0, 0, 0, 0, 0]),
+    ("gradient, overlap-save, partials", torch.float32, 1000, dict(n=64, D=3, o=32, Lo=1000, S=32, F=32, s0=-32, grad=True, partials=7),
+     [GRAD_LO, GRAD_HI, 3, 32, 32, 0, 32, 4294967264, 1000, 7, 0, 0, 0, 0, 0, 0]),
+    ("gradient, float16 rows, correlation", torch.float32, 1000,
+     dict(n=64, D=3, o=0, Lo=1000, S=32, F=32, s0=0, mode=1 | (7 << 8), grad=True),
+     [GRAD_LO, GRAD_HI, 3, 0, 32, 1793, 32, 0, 1000, 0, 0, 0, 0, 0, 0, 0]),
+)
+
+
+@pytest.mark.parametrize("what,dtype,L,fields,words", _PAYLOADS, ids=[p[0] for p in _PAYLOADS])
+def test_the_payload_words_of_every_form(what, dtype, L, fields, words):
+    req = mf.api.ConvRequest(**fields)
+    assert mf.api._conv_payload(req) == words
+    # the library passes every check on them and stops for want of a device
+    lib, h, code = _lib.lib(), ctypes.c_void_p(), mf.api._DTYPE_CODE[dtype]
+    rc = lib.mifft_plan_create(ctypes.byref(h), -1, code, code, 2, (ctypes.c_int64 * 2)(L, req.n), 6, 1, 0,
+                               (ctypes.c_uint32 * len(words))(*words), (ctypes.c_int32 * 2)(len(words), 0), STFT)
+    assert rc == -10, lib.mifft_last_error().decode()
+
+
+def test_the_requests_of_the_plan_arguments_and_what_fits_no_word():
+    # the geometry of plan_fftconv's arguments lands in the fields the payloads above were written from
+    assert (8, 7) == (mf.api._DTYPE_CODE[torch.bfloat16], mf.api._DTYPE_CODE[torch.float16])
+    request = mf.api._fftconv_request
+    assert request(64, 3, 5, 40, True, None, None, None) == mf.api.ConvRequest(64, 3, 5, 40, mode=1)
+    assert request(64, 3, 0, 1000, False, 33, None, None) == mf.api.ConvRequest(64, 3, 32, 1000, S=32, F=32, s0=-32)
+    assert request(64, 3, 16, 1000, False, 33, None, None) == mf.api.ConvRequest(64, 3, 32, 1000, S=32, F=32, s0=-16)
+    assert request(64, 3, 0, 1000, False, 1000, 33, None) == mf.api.ConvRequest(64, 3, 32, 1000, S=32, F=32, s0=-32, Q=33, P=31)
+    assert request(64, 3, 0, 1000, True, 33, None, torch.bfloat16) == mf.api.ConvRequest(64, 3, 0, 1000, S=32, F=32, mode=2049)
+    for bad in (dict(D=1 << 32), dict(o=-1), dict(S=1 << 32, F=1), dict(S=32, s0=1 << 31), dict(S=32, s0=-(1 << 31) - 1), dict(gates=4),
+                dict(S=32, Q=-1), dict(grad=True, partials=1 << 32)):
+        with pytest.raises(mf.MifftError) as e:
+            mf.api._conv_payload(mf.api.ConvRequest(**{**dict(n=64, D=3, o=0, Lo=40), **bad}))
+        assert e.value.status == -5, bad
