@@ -60,8 +60,9 @@ CONV_TAG_LO = 0x4F4E5601       # MIFFT_CONV_TAG_LO / _HI: the NaN in front of th
 CONV_TAG_HI = 0x7FF84D43       # fused FFT convolution (TAG | D | o | Lo | mode | the device address of the filter spectra)
 GATED_ARGS_MAGIC = 0x314147544646494D  # MIFFT_GATED_ARGS_MAGIC ("MIFFTGA1")
 CONV_GRAD_TAG_LO = 0x44524701  # MIFFT_CONV_GRAD_TAG_LO / _HI: the NaN in front of the 16-word payload of a FLAG_STFT plan that is the
-CONV_GRAD_TAG_HI = 0x7FF84D47  # filter gradient of a fused convolution (TAG | D | c | S | mode | F | s0 | Lo | P | 0 x 6)
+CONV_GRAD_TAG_HI = 0x7FF84D47  # filter gradient of a fused convolution (TAG | D | c | S | mode | F | s0 | Lo | P | 0 | gates | 0 x 4)
 CONV_GRAD_ARGS_MAGIC = 0x314757544646494D  # MIFFT_CONV_GRAD_ARGS_MAGIC ("MIFFTWG1")
+CONV_GRAD_GATED_ARGS_MAGIC = 0x324757544646494D  # MIFFT_CONV_GRAD_GATED_ARGS_MAGIC ("MIFFTWG2")
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -74,6 +75,12 @@ class GatedArgs(ctypes.Structure):
 class ConvGradArgs(ctypes.Structure):
     """mifft_conv_grad_args: what the exec of a filter-gradient plan takes, by host address, in the place of x"""
     _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("gy", ctypes.c_void_p)]
+
+
+class ConvGradGatedArgs(ctypes.Structure):
+    """mifft_conv_grad_gated_args: what the exec of a filter-gradient plan with gates takes, by host address, in the place of x"""
+    _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("gy", ctypes.c_void_p), ("pregate", ctypes.c_void_p),
+                ("postgate", ctypes.c_void_p)]
 
 
 def FLAG_KEEP_DIM(d: int) -> int:
@@ -1658,7 +1665,8 @@ class ConvRequest(NamedTuple):
     ``o`` .. of ``Lo`` per row; on an overlap-save plan ``S`` > 0 samples stored per block from sample ``o`` (= c) of its
     result on, ``F`` blocks per row and the first block's start ``s0`` (a single block: 0, 1, 0); ``Q`` > 0 taps per partition
     and ``P`` partitions on a partitioned one; the ``mode`` word, the device ``address`` of the filter spectra, the ``gates`` bits.  ``grad``: the
-    filter gradient of that convolution instead, in ``partials`` sums per channel (0: the library's choice)."""
+    filter gradient of that convolution instead, in ``partials`` sums per channel (0: the library's choice), ``gates`` fused
+    into its loads of x and gy."""
     n: int
     D: int
     o: int
@@ -1693,7 +1701,8 @@ def _conv_payload(r: ConvRequest) -> list:
         if not 0 <= getattr(r, what) < 1 << 32:
             raise MifftError(-5, f"{what} = {getattr(r, what)} of a convolution plan does not fit an unsigned 32-bit word")
     if r.grad:  # (always the block geometry: a single block stores its Lo samples)
-        return [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, r.D, r.o, r.S or r.Lo, r.mode, r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.partials] + [0] * 6
+        return [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, r.D, r.o, r.S or r.Lo, r.mode, r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.partials,
+                0, r.gates, 0, 0, 0, 0]
     words = [CONV_TAG_LO, CONV_TAG_HI, r.D, r.o, r.S if blocks else r.Lo, r.mode, r.address & 0xFFFFFFFF, (r.address >> 32) & 0xFFFFFFFF]
     if blocks:
         words += [r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.gates]
@@ -2133,7 +2142,7 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     and whose backward computes only the gradients asked for: the gradient of ``x`` and ``pregate`` by ONE launch of the
     opposite-``correlate`` plan on the incoming gradient (``postgate`` fused into its load; ``pregate`` into its store when
     only ``x`` wants a gradient), the gradient of ``k`` and ``skip`` by the fused filter-gradient kernel
-    (``fftconv_filter_grad``; with gates its two inputs are torch products), the gradient of ``postgate`` from one forward
+    (``fftconv_filter_grad``; the gates are fused into its two loads), the gradient of ``postgate`` from one forward
     launch recomputed without it.  Modes "same" and "valid" first zero-embed the incoming gradient into the window of the
     full result with one torch pad and then take the route of "full".  No double backward, no torch.compile / functorch
     rules.  Otherwise the result carries no grad_fn and the call is what it has always been.
@@ -2161,9 +2170,9 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     ``x`` is still converted to float64, as ever.  Autograd with ``io_dtype``: the gradient of ``x`` (and the pregate route)
     is one launch of the opposite-``correlate`` half-storage plan on the incoming gradient (converted to ``io_dtype`` if it
     arrives otherwise); the gradient of ``k`` and ``skip`` comes from the half-storage filter-gradient kernel on ``x`` and the
-    incoming gradient directly when there are no gates; with gates the products pregate * x and postgate * gradient are
-    formed in float32 (widen, then multiply) and feed the float32 filter-gradient plan, so that no product is rounded to 16
-    bits.  Every returned gradient has the dtype of its tensor."""
+    incoming gradient directly; with gates the same kernel reads them too and forms the products pregate * x and
+    postgate * gradient in float32 in its loads (widen, then multiply), so that no product is rounded to 16 bits and no
+    float32 copy is made.  Every returned gradient has the dtype of its tensor."""
     if x.is_complex() or k.is_complex():
         raise MifftError(-3, "fftconv expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -2231,19 +2240,25 @@ class ConvGradPlan(Plan):
     (a single block: 1 and None).  ``in_shape`` (batch * channels, length, 1) is x's, ``grad_shape``
     (batch * channels, out_length, 1) the incoming gradient's, ``out_shape`` (partials, channels, n // 2 + 1, 2).
     With ``io_dtype`` (torch.bfloat16 / torch.float16 under float32) ``x`` and ``gy`` are tensors of it, widened exactly in
-    the kernel's loads; the result stays float32.  None on every other plan."""
+    the kernel's loads; the result stays float32.  None on every other plan.
+    A gated plan (``plan_fftconv_grad(pregate=True)`` and / or ``postgate=True``) has ``pregate`` / ``postgate`` True: it is
+    the filter gradient of the gated forward plan, and ``run`` / ``filter_grad`` take the gate tensors of that exec, which
+    the kernel multiplies into its loads of ``x`` and ``gy`` -- the bits of the ungated plan on the torch products
+    ``pregate * x`` and ``postgate * gy``, in the same single launch and grid, without the products in memory."""
 
     def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps=None, partials=None,
-                 io_dtype=None):
+                 io_dtype=None, pregate=False, postgate=False):
         self.ctx = ctx
         self.io_dtype = io_dtype
+        self.pregate, self.postgate = bool(pregate), bool(postgate)
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         req = _fftconv_request(n, channels, offset, out_length, correlate, taps, None, io_dtype)
         self.taps, self.step, self.blocks = taps, req.S or None, req.F
         rows = batch * channels
         super().__init__(dtype, dtype, (rows, length, 1), (rows, out_length, 1), device=ctx.device,
-                         conv=req._replace(grad=True, partials=0 if partials is None else int(partials)))
+                         conv=req._replace(grad=True, partials=0 if partials is None else int(partials),
+                                           gates=(1 if self.pregate else 0) | (2 if self.postgate else 0)))
         self.grad_shape = self.out_shape  # (what Plan takes for the other side of x; the result's shape needs the built plan)
         self.partials = self.pass_geometry(1)[3] // channels
         self.out_shape = (self.partials, channels, n // 2 + 1, 2)
@@ -2253,27 +2268,47 @@ class ConvGradPlan(Plan):
         ``channels * partials`` workgroups; workgroup (d, p) walks ceil(its pairs / tile) steps"""
         return super().pass_geometry(dim, self.in_shape[0] if count is None else count)
 
-    def run(self, out: "torch.Tensor", x: "torch.Tensor", gy: "torch.Tensor") -> None:
+    def run(self, out: "torch.Tensor", x: "torch.Tensor", gy: "torch.Tensor", *, pregate: Optional["torch.Tensor"] = None,
+            postgate: Optional["torch.Tensor"] = None) -> None:
         """fills ``out`` of ``out_shape`` with the unscaled partial spectra sum conj(rfft(x-block)) rfft(gy-block), enqueued on
         the plan's stream; ``x`` of ``in_shape`` and ``gy`` of ``grad_shape``, the plan's dtype (``io_dtype`` where it has one),
-        contiguous; neither is written"""
-        _check_tensor(x, self.in_shape, self.io_dtype or self.in_dtype, self.device, "x")
-        _check_tensor(gy, self.grad_shape, self.io_dtype or self.in_dtype, self.device, "gy")
+        contiguous; neither is written.  On a gated plan ``pregate`` of ``in_shape`` multiplies ``x`` and ``postgate`` of
+        ``grad_shape`` multiplies ``gy`` as the kernel loads them, both of the dtype of ``x``, each given exactly where the
+        plan has it (status -12 for a missing one, ERR_UNSUPPORTED for one the plan has none of).  A gate may alias ``x``,
+        ``gy`` or the other gate, not ``out``."""
+        for t, want, what in ((pregate, self.pregate, "pregate"), (postgate, self.postgate, "postgate")):
+            if want and t is None:
+                raise MifftError(-12, f"the plan has a {what}: run(..., {what}=) is missing")
+            if not want and t is not None:
+                raise MifftError(ERR_UNSUPPORTED, f"the plan has no {what}: plan_fftconv_grad(..., {what}=True) makes one that has")
+        sdt = self.io_dtype or self.in_dtype
+        _check_tensor(x, self.in_shape, sdt, self.device, "x")
+        _check_tensor(gy, self.grad_shape, sdt, self.device, "gy")
+        if pregate is not None:
+            _check_tensor(pregate, self.in_shape, sdt, self.device, "pregate")
+        if postgate is not None:
+            _check_tensor(postgate, self.grad_shape, sdt, self.device, "postgate")
         _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
-        args = ConvGradArgs(CONV_GRAD_ARGS_MAGIC, x.data_ptr(), gy.data_ptr())
+        if self.conv_gates:
+            args = ConvGradGatedArgs(CONV_GRAD_GATED_ARGS_MAGIC, x.data_ptr(), gy.data_ptr(),
+                                     pregate.data_ptr() if pregate is not None else None,
+                                     postgate.data_ptr() if postgate is not None else None)
+        else:
+            args = ConvGradArgs(CONV_GRAD_ARGS_MAGIC, x.data_ptr(), gy.data_ptr())
         check(_lib.lib().mifft_exec_batch(self._h, ctypes.addressof(args), out.data_ptr(), 0, self.in_shape[0],
                                           self.ctx.stream.cuda_stream))
 
-    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int) -> "torch.Tensor":
-        """the real (channels, K) gradient of the filter: ``run``, the sum of the partials, the library's own irfftn, the
-        first K lags (lag 0 is also the gradient of a skip term)"""
+    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int, *, pregate: Optional["torch.Tensor"] = None,
+                    postgate: Optional["torch.Tensor"] = None) -> "torch.Tensor":
+        """the real (channels, K) gradient of the filter: ``run`` (with the gates of a gated plan), the sum of the partials,
+        the library's own irfftn, the first K lags (lag 0 is also the gradient of a skip term)"""
         K = int(K)
         if K < 1 or K > self.n or (self.taps is not None and K > self.taps):
             raise MifftError(-2, f"filter_grad: K = {K} taps at n = {self.n}" +
                                  (f" on an overlap-save plan of taps = {self.taps}" if self.taps is not None else "") +
                                  ": 1 <= K <= " + str(self.n if self.taps is None else self.taps))
         out = torch.empty(self.out_shape, dtype=self.out_dtype, device=x.device)
-        self.run(out, x, gy)
+        self.run(out, x, gy, pregate=pregate, postgate=postgate)
         with torch.cuda.stream(self.ctx.stream):
             A = out[0] if self.partials == 1 else out.sum(0)
             return irfftn(A, self.n)[:, :K]
@@ -2286,11 +2321,14 @@ class PartConvGradPlan:
     taps against the same rows with the window moved by p Q samples: ``gk[p Q + j] = sum_t gy[t] u[o - p Q + t - j]``
     (correlation: ``u[o + p Q + t + j]``), which is the existing plan on a contiguous slice of ``u`` (correlation) or of ``gy``
     (where o - p Q is negative), cropped to the samples that can meet.  ``plans[p]`` is None where none can: those taps are
-    exact zeros.  Every sub-plan sums in an order fixed by its own shape, so two runs give the same bits."""
+    exact zeros.  Every sub-plan sums in an order fixed by its own shape, so two runs give the same bits.
+    ``pregate`` / ``postgate`` are passed on to every sub-plan, which fuses them into its loads; the gate tensors are sliced as
+    ``x`` and ``gy`` are.  Still composed, one launch per partition."""
 
     def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition, partials=None,
-                 io_dtype=None):
+                 io_dtype=None, pregate=False, postgate=False):
         self.ctx, self.dtype, self.io_dtype = ctx, dtype, io_dtype  # (io_dtype: of x and gy, as on every ConvGradPlan below)
+        self.pregate, self.postgate = bool(pregate), bool(postgate)
         self.channels, self.length, self.n = channels, length, n
         self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
         self.taps, self.partition, self.partitions = taps, partition, -(-taps // partition)
@@ -2302,7 +2340,7 @@ class PartConvGradPlan:
         self.plans = [None if sl is None else
                       plan_fftconv_grad(dtype, batch, channels, max(sl[1] - sl[0], 2), n, taps=partition, offset=sl[4],
                                         out_length=sl[3] - sl[2], correlate=correlate, partials=partials, ctx=ctx,
-                                        io_dtype=io_dtype)
+                                        io_dtype=io_dtype, pregate=self.pregate, postgate=self.postgate)
                       for sl in self.slices]
 
     @property
@@ -2318,14 +2356,25 @@ class PartConvGradPlan:
             if pl is not None:
                 pl.close()
 
-    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int) -> "torch.Tensor":
+    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int, *, pregate: Optional["torch.Tensor"] = None,
+                    postgate: Optional["torch.Tensor"] = None) -> "torch.Tensor":
         """the real (channels, K) gradient of the filter, K <= taps: ``ConvGradPlan.filter_grad`` of every partition on its
-        slices of ``x`` of ``in_shape`` and ``gy`` of ``grad_shape`` (copied where they are no whole rows), concatenated"""
+        slices of ``x`` of ``in_shape`` and ``gy`` of ``grad_shape`` (copied where they are no whole rows), concatenated.
+        On a gated plan ``pregate`` of ``in_shape`` and ``postgate`` of ``grad_shape`` are sliced as ``x`` and ``gy`` are."""
         K = int(K)
         if K < 1 or K > self.taps:
             raise MifftError(-2, f"filter_grad: K = {K} taps on a partitioned plan of taps = {self.taps}: 1 <= K <= {self.taps}")
+        for t, want, what in ((pregate, self.pregate, "pregate"), (postgate, self.postgate, "postgate")):
+            if want and t is None:
+                raise MifftError(-12, f"the plan has a {what}: filter_grad(..., {what}=) is missing")
+            if not want and t is not None:
+                raise MifftError(ERR_UNSUPPORTED, f"the plan has no {what}: plan_fftconv_grad(..., {what}=True) makes one that has")
         _check_tensor(x, self.in_shape, self.io_dtype or self.dtype, self.device, "x")
         _check_tensor(gy, self.grad_shape, self.io_dtype or self.dtype, self.device, "gy")
+        if pregate is not None:
+            _check_tensor(pregate, self.in_shape, self.io_dtype or self.dtype, self.device, "pregate")
+        if postgate is not None:
+            _check_tensor(postgate, self.grad_shape, self.io_dtype or self.dtype, self.device, "postgate")
         Q, parts = self.partition, []
         with torch.cuda.stream(self.ctx.stream):
             for p in range(-(-K // Q)):
@@ -2334,12 +2383,25 @@ class PartConvGradPlan:
                 if plan is None:
                     parts.append(torch.zeros((self.channels, Kp), dtype=self.dtype, device=x.device))
                     continue
-                u0, u1, g0, g1, _ = sl
-                us, gs = x[:, u0:u1], gy[:, g0:g1]
-                if u1 - u0 < 2:  # (rows of at least two samples: a zero behind the one)
-                    us = torch.nn.functional.pad(us, (0, 0, 0, 2 - (u1 - u0)))
-                parts.append(plan.filter_grad(us.contiguous(), gs.contiguous(), Kp))
+                us, gs, pa, pb = _fftconv_part_grad_operands(sl, x, gy, pregate, postgate)
+                parts.append(plan.filter_grad(us, gs, Kp, pregate=pa, postgate=pb))
             return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+def _fftconv_part_grad_operands(sl: tuple, x, gy, pregate=None, postgate=None) -> tuple:
+    """(us, gs, a, b), contiguous: what partition ``sl`` = (u0, u1, g0, g1, offset) of the composed filter gradient reads of
+    ``x`` (rows, L, 1) and ``gy`` (rows, Lo, 1) -- x[:, u0:u1], padded to rows of two samples, and gy[:, g0:g1] -- and of the
+    gates, the pregate sliced and padded exactly as ``x``, the postgate sliced exactly as ``gy`` (None stays None)"""
+    u0, u1, g0, g1, _ = sl
+
+    def of_x(t):
+        t = t[:, u0:u1]
+        if u1 - u0 < 2:  # (rows of at least two samples: a zero behind the one)
+            t = torch.nn.functional.pad(t, (0, 0, 0, 2 - (u1 - u0)))
+        return t.contiguous()
+
+    return (of_x(x), gy[:, g0:g1].contiguous(), None if pregate is None else of_x(pregate),
+            None if postgate is None else postgate[:, g0:g1].contiguous())
 
 
 def _fftconv_part_grad_slice(L: int, Q: int, o: int, Lo: int, correlate: bool, p: int):
@@ -2363,7 +2425,8 @@ def _fftconv_part_grad_slice(L: int, Q: int, o: int, Lo: int, correlate: bool, p
 
 def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
                       out_length: Optional[int] = None, correlate: bool = False, partials: Optional[int] = None,
-                      ctx: Optional[DeviceContext] = None, partition: Optional[int] = None, io_dtype=None):
+                      ctx: Optional[DeviceContext] = None, partition: Optional[int] = None, io_dtype=None,
+                      pregate: bool = False, postgate: bool = False):
     """Plan of the fused filter gradient (no reference counterpart) of the ``plan_fftconv`` plan of the same arguments:
     ``gk[d, j] = sum over b and t of gy[b, d, t] * u[b, d, o + t - j]`` (``correlate``: ``o + t + j``), computed as
     ``irfft(sum_b conj(rfft(u[b, d], n)) * rfft(gy[b, d] put at o, n), n)[:K]`` in ONE launch that reads ``u`` and ``gy`` once
@@ -2371,8 +2434,13 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
     circular where that is, block by block on an overlap-save plan (``taps=K``).  ``partition=Q`` (with ``taps=K``, any K >= 1)
     gives the gradient of the partitioned plan as a ``PartConvGradPlan``: one such launch per partition.  ``partials`` workgroups share a channel's
     sum (default: enough that channels * partials fills the device; capped by the (row, block) pairs of a channel); the
-    order of every sum is fixed by the plan, so two runs give the same bits.  Gates are not fused: ``u`` = pregate * x and
-    ``gy`` = postgate * (the incoming gradient) are the caller's.  ``io_dtype`` = torch.bfloat16 or torch.float16 (with
+    order of every sum is fixed by the plan, so two runs give the same bits.  ``pregate`` / ``postgate`` = True make it the
+    filter gradient of the gated forward plan ``y = b * conv(a * x)``: ``u`` = a * x and the gradient b * gy are formed in the
+    kernel's two block loads (word 11 of the payload), one multiplication per sample, so the result has the bits of the ungated
+    plan on the torch products ``a * x`` and ``b * gy`` (with ``io_dtype``: of the float32 plan on the float32 products of
+    the widened tensors) without either product in memory; ``run`` / ``filter_grad`` of such a plan take ``pregate=`` of
+    ``in_shape`` and / or ``postgate=`` of ``grad_shape`` with every exec.  A partitioned plan passes the gates on to its
+    per-partition plans.  ``io_dtype`` = torch.bfloat16 or torch.float16 (with
     ``dtype`` = torch.float32 only): ``u`` and ``gy`` are tensors of it, widened exactly in the kernel's loads; the result
     stays float32 and equals the float32 plan's on the widened tensors bit for bit.  Every argument error is raised before
     any device work."""
@@ -2385,22 +2453,23 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
             raise MifftError(-5, f"plan_fftconv_grad: partials = {partials}: 1 .. 65535")
     if partition is not None:  # (the composed gradient of a partitioned plan: PartConvGradPlan)
         return PartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, DeviceContext() if ctx is None else ctx, taps,
-                                partition, partials=partials, io_dtype=io_dtype)
+                                partition, partials=partials, io_dtype=io_dtype, pregate=pregate, postgate=postgate)
     if partials is not None:  # (capped by the pairs of a channel)
         blocks = 1 if taps is None else _fftconv_ols_geometry(n, taps, offset, out_length, correlate)[3]
         partials = min(partials, batch * blocks)
     return ConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, DeviceContext() if ctx is None else ctx, taps=taps,
-                        partials=partials, io_dtype=io_dtype)
+                        partials=partials, io_dtype=io_dtype, pregate=pregate, postgate=postgate)
 
 
-def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None):
+def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None, gates=0):
     """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK)"""
     key = ("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-           int(torch.cuda.current_stream(device).cuda_stream), taps, Q, io_dtype)
+           int(torch.cuda.current_stream(device).cuda_stream), taps, Q, io_dtype, gates)
     plan = _PLAN_CACHE.get(key)
     if plan is None:
         plan = plan_fftconv_grad(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
-                                 correlate=correlate, ctx=DeviceContext(device), io_dtype=io_dtype)
+                                 correlate=correlate, ctx=DeviceContext(device), io_dtype=io_dtype, pregate=bool(gates & 1),
+                                 postgate=bool(gates & 2))
         _plan_cache_insert(key, plan)
     else:
         _PLAN_CACHE.move_to_end(key)
@@ -2408,7 +2477,8 @@ def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate
 
 
 def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Optional[int] = None, mode: str = "causal",
-                        correlate: bool = False, block: Optional[int] = None, partition=None, io_dtype=None) -> "torch.Tensor":
+                        correlate: bool = False, block: Optional[int] = None, partition=None, io_dtype=None,
+                        pregate: Optional["torch.Tensor"] = None, postgate: Optional["torch.Tensor"] = None) -> "torch.Tensor":
     """The gradient of ``sum(gy * fftconv(x, k, n=n, mode=mode, correlate=correlate, block=block))`` with respect to a filter
     ``k`` of ``K`` taps, by the fused filter-gradient kernel in one launch (plus a sum of partials and one irfftn, both on
     ``channels`` rows): ``x`` (..., D, L) and ``gy`` of the result's shape (..., D, Lo) give (D, K); a 1-D ``x`` (L,) with
@@ -2418,7 +2488,11 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     per partition.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s.
     ``io_dtype`` = torch.bfloat16 or torch.float16: ``x`` and ``gy`` are read as tensors of it (no copy when they already
     are), widened exactly in the kernel's loads, and the result is float32 -- the bits of the float32 call on the widened
-    tensors.  The partitioned route stays composed, one half-storage launch per partition."""
+    tensors.  The partitioned route stays composed, one half-storage launch per partition.
+    ``pregate`` / ``postgate``: the gradient of ``sum(gy * fftconv(x, k, pregate=a, postgate=b, ...))`` instead, the gates
+    fused into the kernel's loads of ``x`` and ``gy`` (the bits of this call on ``a * x`` and ``b * gy``).  ``pregate`` has
+    exactly ``x``'s shape, ``postgate`` exactly ``gy``'s (ValueError otherwise: nothing is broadcast); both are real, live on
+    ``x``'s device and are converted as ``x`` is."""
     if x.is_complex() or gy.is_complex():
         raise MifftError(-3, "fftconv_filter_grad expects real tensors (complex rows are out of scope)")
     if mode not in _FFTCONV_MODES:
@@ -2441,6 +2515,16 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     if tuple(gy.shape) != logical[:-1] + (out_length,):
         raise ValueError(f"fftconv_filter_grad: gy is {tuple(gy.shape)}, the result of that fftconv call is "
                          f"{logical[:-1] + (out_length,)}")
+    for g, shape, what, of in ((pregate, logical, "pregate", "x"), (postgate, tuple(gy.shape), "postgate", "gy")):
+        if g is None:
+            continue
+        if g.is_complex():
+            raise MifftError(-3, f"fftconv_filter_grad: {what} must be real")
+        if tuple(g.shape) != shape:
+            raise ValueError(f"fftconv_filter_grad: {what} is {tuple(g.shape)}, {of} is {shape}: a gate has exactly that shape "
+                             "(nothing is broadcast)")
+        if g.device != x.device:
+            raise MifftError(-10, f"fftconv_filter_grad: {what} lives on {g.device}, x on {x.device}")
     rows = math.prod(logical[:-1])
     if rows < 1:
         raise MifftError(-8, f"fftconv_filter_grad: no rows in {logical}")
@@ -2451,9 +2535,12 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
         raise MifftError(-10, f"fftconv_filter_grad: gy lives on {gy.device}, x on {x.device}")
     xr = x.detach().to(sdt).contiguous().reshape(rows, L, 1)
     gr = gy.detach().to(sdt).contiguous().reshape(rows, out_length, 1)
+    a = None if pregate is None else pregate.detach().to(sdt).contiguous().reshape(rows, L, 1)
+    b = None if postgate is None else postgate.detach().to(sdt).contiguous().reshape(rows, out_length, 1)
+    gates = (1 if a is not None else 0) | (2 if b is not None else 0)
     with _PLAN_CACHE_LOCK:
-        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q, io_dtype)
-        gk = plan.filter_grad(xr, gr, K)
+        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q, io_dtype, gates)
+        gk = plan.filter_grad(xr, gr, K, pregate=a, postgate=b)
     return gk if x.dim() >= 2 else gk.reshape(K)
 
 
@@ -2461,13 +2548,16 @@ class _FFTConvFunction(torch.autograd.Function):
     """``fftconv`` with a backward (first order).  forward: the plain call, grad mode off.  backward, with u = a x,
     gv = b gy and G = rfft(k, n) + d: gu = the adjoint convolution of gv (one launch of the opposite-correlate plan),
     gx = a gu, ga = x gu, gb = gy v with v recomputed without the postgate, gk and gd from the fused filter gradient of
-    (u, gv).  The filter spectra of the cached plans are rewritten from the saved k and skip by every launch here: a second
+    (u, gv), both formed in its loads.  The filter spectra of the cached plans are rewritten from the saved k and skip by every launch here: a second
     layer of the same shape may have overwritten them since the forward.
     With ``io_dtype`` (the sixth value of ``cfg``) x, a, b, gy and every launch's result are tensors of it: gu comes from the
     half-storage plan (b fused into its load, a into its store when only x wants a gradient; modes with o > 0 pad gy and b
     separately instead of their product), the products of 16-bit tensors (a gu, x gu, gy v) are torch's, computed in float32
-    and rounded once, and the filter gradient reads x and gy through the half-storage kernel when there are no gates; with
-    gates u = a x and gv = b gy are float32 products of the widened tensors for the float32 filter-gradient plan."""
+    and rounded once, and the filter gradient reads x and gy through the half-storage kernel.
+    With gates the filter gradient is the gated filter-gradient plan on (x, gy, a, b) directly (``plan_fftconv_grad(pregate=,
+    postgate=)``): the kernel forms a x and b gy in its loads -- on 16-bit rows as float32 products of the widened samples, so
+    no product is rounded to 16 bits -- and neither product nor any float32 copy reaches memory.  The torch product
+    gv = b gy is formed only for the gx route of a mode with o > 0 on float rows, which pads it."""
 
     @staticmethod
     def forward(ctx, x, k, pregate, postgate, skip_t, skip_f, cfg):
@@ -2497,7 +2587,7 @@ class _FFTConvFunction(torch.autograd.Function):
         br = None if b is None else b.to(sdt).contiguous().reshape(rows, Lo)
         gx = gk = ga = gb = gd = None
         gv = None
-        if io is None and (need_k or need_d or (o > 0 and (need_x or need_a))):
+        if io is None and o > 0 and (need_x or need_a):  # (the one route that reads the product: it is padded below)
             gv = gyr if br is None else br * gyr
         if need_x or need_a:
             # gu: the adjoint of u -> crop(conv(u, k') , o, Lo), one launch of the existing kernels on the gradient put at o
@@ -2530,19 +2620,13 @@ class _FFTConvFunction(torch.autograd.Function):
             v = fftconv(x.detach(), k.detach(), mode=mode, correlate=correlate, pregate=None if a is None else a.detach(),
                         skip=skip, io_dtype=io, **_fftconv_selector(n, taps, Q))
             gb = gyr * v.reshape(rows, Lo)
-        if need_k or need_d:
-            gio = io
-            if io is not None and (ar is not None or br is not None):  # (float32 products of the widened tensors: see the class)
-                gio = None
-                u = xr.float() if ar is None else ar.float() * xr.float()
-                gv = gyr.float() if br is None else br.float() * gyr.float()
-            elif io is not None:
-                u, gv = xr, gyr
-            else:
-                u = xr if ar is None else ar * xr
+        if need_k or need_d:  # (the gates go to the kernel's loads: the sums are those of the products a x and b gy, bit for bit)
+            gates = (1 if ar is not None else 0) | (2 if br is not None else 0)
             with _PLAN_CACHE_LOCK:
-                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q, gio)
-                g = gplan.filter_grad(u.reshape(rows, L, 1), gv.reshape(rows, Lo, 1), K)
+                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q, io, gates)
+                g = gplan.filter_grad(xr.reshape(rows, L, 1), gyr.reshape(rows, Lo, 1), K,
+                                      pregate=None if ar is None else ar.reshape(rows, L, 1),
+                                      postgate=None if br is None else br.reshape(rows, Lo, 1))
             if need_k:
                 gk = g.reshape(k.shape).to(k.dtype)
             if need_d:

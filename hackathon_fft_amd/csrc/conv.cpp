@@ -20,6 +20,9 @@
 // partitions of Q taps, H holds (D, P, n / 2 + 1) complex values, and every stored block sums the products of P shifted input
 // blocks with the P spectra in registers before the one inverse.  Gated or not (word 11); one launch, no scratch.
 //
+// The filter-gradient payload (MIFFT_CONV_GRAD_TAG, below) carries the forward plan's gates in its word 11: the kernel multiplies
+// x by the pregate and gy by the postgate as it loads them, and the exec takes a mifft_conv_grad_gated_args.
+//
 // Bits 8..15 of the mode word of every form, the filter-gradient payload included, are the STORAGE type of the rows: 0 the
 // plan's float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan (ConvRequest::io, TileCfg::IT): x, the gates and out are then
 // 2-byte elements, widened in the tile's load and rounded once in its store; H and the arithmetic stay float.
@@ -300,13 +303,14 @@ int build_conv(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     return MIFFT_OK;
 }
 
-// ---- the filter gradient: TAG_LO | TAG_HI | D | c | S | mode | F | s0 | Lo | P | 0 x 6 (MIFFT_CONV_GRAD_TAG, include/mifft.h) ----
+// ---- the filter gradient: TAG_LO | TAG_HI | D | c | S | mode | F | s0 | Lo | P | 0 | gates | 0 x 4 (MIFFT_CONV_GRAD_TAG, include/mifft.h) ----
 bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
     if (ndim != 2 || !bases_flat || !bases_len) return false;
     return bases_len[0] == 16 && bases_flat[0] == MIFFT_CONV_GRAD_TAG_LO && bases_flat[1] == MIFFT_CONV_GRAD_TAG_HI;
 }
 
-// MIFFT_CONV_GRAD_TAG: 16 words, D | c | S | mode | F | s0 | Lo | P behind the tag, then six zeros
+// MIFFT_CONV_GRAD_TAG: 16 words, D | c | S | mode | F | s0 | Lo | P behind the tag, a zero, the gates of the forward plan (0: none,
+// what every payload had there before there were any), then four zeros
 int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
                     std::string& why) {
     if (const int rc = conv_header_check(p, "MIFFT_CONV_GRAD_TAG", why)) return rc;
@@ -321,6 +325,7 @@ int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
     r.s0 = (int32_t)w[7];
     r.Lo = w[8];
     r.P = w[9];
+    r.gates = w[11];
     if (const int rc = conv_geometry_check(p, r, true, false, "filter-gradient", why)) return rc;
     const int64_t pairs = p.batch / r.D * r.F;  // (of one channel)
     if (r.P > 65535 || r.P > pairs) {
@@ -328,7 +333,12 @@ int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
               std::to_string(pairs) + " (row, block) pairs of a channel (0: the library's choice)";
         return MIFFT_ERR_BAD_BASES;
     }
-    if (const int rc = conv_reserved_check(w, 10, 16, 0, "a filter-gradient", why)) return rc;
+    if (r.gates > 3) {
+        why = "the gates word 11 of a filter-gradient payload has bit 0 (pregate) and bit 1 (postgate) alone (0: ungated), not " +
+              std::to_string(r.gates);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (const int rc = conv_reserved_check(w, 10, 16, 1u << 11, "a filter-gradient", why)) return rc;
     if (const int rc = conv_radices(bases_flat, bases_len, radices, why)) return rc;
     p.conv = r;
     return MIFFT_OK;

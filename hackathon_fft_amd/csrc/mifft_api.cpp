@@ -136,21 +136,51 @@ static int unpack_gated_args(const Plan& p, const void*& x, const void*& pregate
 }
 
 // The exec of a filter-gradient plan (conv.cpp; ConvRequest::grad): `x` is the HOST address of a mifft_conv_grad_args, refused
-// without a launch as above.  On success `x` and `gy` are the two inputs.
-static int unpack_conv_grad_args(const void*& x, const void*& gy) {
+// without a launch as above.  On success `x` and `gy` are the two inputs.  A plan with gates (word 11 of its payload) takes a
+// mifft_conv_grad_gated_args, a block with a magic word of its own, instead -- the old block, which has no room for a gate, is
+// refused as a block without the magic word is -- and the gate rules are unpack_gated_args's.
+static int unpack_conv_grad_args(const Plan& p, const void*& x, const void*& gy, const void*& pregate, const void*& postgate) {
     static const char* kHow =
         "the exec of a filter-gradient plan takes the host address of a mifft_conv_grad_args (magic, x, gy) in the place of "
         "x: include/mifft.h";
+    static const char* kHowGated =
+        "the exec of a gated filter-gradient plan takes the host address of a mifft_conv_grad_gated_args (magic, x, gy, pregate, "
+        "postgate) in the place of x: include/mifft.h";
+    const bool gated = p.conv.gated();
+    const char* how = gated ? kHowGated : kHow;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, x) != hipSuccess)
         (void)hipGetLastError();  // (memory the runtime has never seen: host memory)
     else if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray)
-        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("x is a device address: ") + kHow);
-    const mifft_conv_grad_args* g = (const mifft_conv_grad_args*)x;
-    if (g->magic != MIFFT_CONV_GRAD_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + kHow);
-    if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.x is NULL");
-    if (!g->gy) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.gy is NULL");
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("x is a device address: ") + how);
+    pregate = postgate = nullptr;
+    if (!gated) {
+        const mifft_conv_grad_args* g = (const mifft_conv_grad_args*)x;
+        if (g->magic != MIFFT_CONV_GRAD_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + how);
+        if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.x is NULL");
+        if (!g->gy) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.gy is NULL");
+        gy = g->gy;
+        x = g->x;
+        return MIFFT_OK;
+    }
+    const mifft_conv_grad_gated_args* g = (const mifft_conv_grad_gated_args*)x;  // (the magic word is the first member of both)
+    if (g->magic == MIFFT_CONV_GRAD_ARGS_MAGIC)
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("a mifft_conv_grad_args names no gates: ") + how);
+    if (g->magic != MIFFT_CONV_GRAD_GATED_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + how);
+    if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_gated_args.x is NULL");
+    if (!g->gy) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_gated_args.gy is NULL");
+    const bool want_a = p.conv.gates & 1u, want_b = p.conv.gates & 2u;
+    if (want_a && !g->pregate)
+        return set_error(MIFFT_ERR_NULL, "the plan has a pregate (gates bit 0): mifft_conv_grad_gated_args.pregate is NULL");
+    if (want_b && !g->postgate)
+        return set_error(MIFFT_ERR_NULL, "the plan has a postgate (gates bit 1): mifft_conv_grad_gated_args.postgate is NULL");
+    if (!want_a && g->pregate)
+        return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_conv_grad_gated_args.pregate is set, but the plan has no pregate (gates bit 0)");
+    if (!want_b && g->postgate)
+        return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_conv_grad_gated_args.postgate is set, but the plan has no postgate (gates bit 1)");
     gy = g->gy;
+    pregate = g->pregate;
+    postgate = g->postgate;
     x = g->x;
     return MIFFT_OK;
 }
@@ -164,16 +194,20 @@ static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first
     if (first != 0 || count != p.batch)
         return set_error(MIFFT_ERR_BAD_BATCH, "the exec of a filter-gradient plan covers the whole batch (first = 0, count = batch): "
                                               "a slab would be a partial sum");
-    const void* gy = nullptr;
-    if (const int rc = unpack_conv_grad_args(x, gy)) return rc;
+    const void *gy = nullptr, *pregate = nullptr, *postgate = nullptr;
+    if (const int rc = unpack_conv_grad_args(p, x, gy, pregate, postgate)) return rc;
     const char *xb = (const char*)x, *gb = (const char*)gy, *ob = (const char*)out;
     const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv.Lo * p.conv.elem_bytes(p.out_dtype),
                  on = conv_grad_out_bytes(p);
     if (xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
     if (gb < ob + on && ob < gb + gn) return set_error(MIFFT_ERR_ALIAS, "gy and out must not overlap");
+    // (the pregate has x's size, the postgate gy's; either may alias x, gy or the other: none is written)
+    const char *ab = (const char*)pregate, *bb = (const char*)postgate;
+    if (ab && ab < ob + on && ob < ab + xn) return set_error(MIFFT_ERR_ALIAS, "the pregate and out must not overlap");
+    if (bb && bb < ob + on && ob < bb + gn) return set_error(MIFFT_ERR_ALIAS, "the postgate and out must not overlap");
     DeviceGuard guard(p.device);
     MIFFT_HIP_TRY(guard.err);
-    return launch_jit_conv_grad(p, p.passes[0], x, gy, out, (hipStream_t)stream);
+    return launch_jit_conv_grad(p, p.passes[0], x, gy, pregate, postgate, out, (hipStream_t)stream);
 }
 
 static int device_count_quiet() {

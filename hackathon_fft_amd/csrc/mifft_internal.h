@@ -141,16 +141,17 @@ struct ConvRequest {
     // block f sums, over the partitions p, the block of n samples from s0 + f S - p Q on (correlation: + p Q) times spectrum (d, p)
     int64_t Q = 0, parts = 0;
     // the filter gradient of the convolution the fields above describe (h unused), as P partial sums per channel: x and gy
-    // (mifft_conv_grad_args) -> (P D, n / 2 + 1) complex values, unscaled
+    // (mifft_conv_grad_args; with gates mifft_conv_grad_gated_args) -> (P D, n / 2 + 1) complex values, unscaled
     int64_t P = 0;
     bool grad = false;
     uint32_t mode = 0;
-    // bits 8..15 of the mode word: the STORAGE type of x, the gates and out (a filter-gradient plan: of x and gy), 0 the plan's
+    // bits 8..15 of the mode word: the STORAGE type of x, the gates and out (a filter-gradient plan: of x, gy and the gates), 0 the plan's
     // float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan: 2-byte elements widened in the load and rounded once in the
     // store (TileCfg::CONV).  in_dtype and out_dtype stay F32; elem_bytes is what a sample occupies in memory.
     int io = 0;
     // bit 0 the pregate (a tensor of x's shape that multiplies x as it is loaded), bit 1 the postgate (one of out's shape that
-    // multiplies the result as it is stored); the tensors are arguments of every exec (mifft_gated_args), never plan state
+    // multiplies the result as it is stored); the tensors are arguments of every exec (mifft_gated_args), never plan state.
+    // In a filter-gradient plan they are the forward plan's gates, fused into the loads of x and of gy
     uint32_t gates = 0;
     const void* h = nullptr;
     bool is_conv() const { return D > 0; }  // (forward or gradient)
@@ -435,7 +436,8 @@ int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void*
 bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
 int conv_grad_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
 int build_conv_grad(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
-int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, const void* gy, void* out, hipStream_t stream);
+int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, const void* gy, const void* pregate,
+                         const void* postgate, void* out, hipStream_t stream);
 // workgroups per CU of a built tile-kernel pass's persistent grid (kernels_jit.cpp): the launches' rule, and build_conv_grad's
 long long pass_wg_per_cu(const DimPass& pass);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even

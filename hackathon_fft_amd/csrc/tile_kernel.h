@@ -287,7 +287,8 @@ struct TileParams {
     // SPEC configurations with a filterbank (TileCfg::FB): band m < spec_bands is sum_j spec_wt[spec_off[m] + j] *
     // P[spec_lo[m] + j], j < spec_len[m] (spec_lo[m] + spec_len[m] <= N + 1; weights of type T).  Without one the four
     // pointers are null and spec_bands is 0.
-    union { const void* spec_wt; const void* conv_h; };  // CONV: the filter spectra, (D[, parts], N + 1) complex values of type T
+    // CONV: the filter spectra, (D[, parts], N + 1) complex values of type T; WGRAD (which has no filter): the pregate
+    union { const void* spec_wt; const void* conv_h; const void* wgrad_pregate; };
     const int* spec_lo;
     const int* spec_len;
     const int* spec_off;
@@ -310,9 +311,11 @@ struct TileParams {
     // counts signals, not launch rows.
     int ols_step, ols_blocks, ols_start;
     // WGRAD configurations (the filter gradient of CONV / OLS) always carry the three ols_* fields (a single block:
-    // ols_blocks = 1, ols_start = 0, ols_step = Lo) and wgrad_partials = P in the place of conv_row0; conv_h is null.  `in` is
-    // x, gate_in is gy (rows of conv_Lo reals), n_rows the pairs of ONE channel, B F: workgroup w is slice w % P of channel
-    // w / P and stores row (w % P) D + w / P of `out`, (P D) rows of N + 1 complex values.
+    // ols_blocks = 1, ols_start = 0, ols_step = Lo) and wgrad_partials = P in the place of conv_row0; there is no filter.  `in`
+    // is x, gate_in is gy (rows of conv_Lo reals), n_rows the pairs of ONE channel, B F: workgroup w is slice w % P of channel
+    // w / P and stores row (w % P) D + w / P of `out`, (P D) rows of N + 1 complex values.  With GATE the gates of the forward
+    // plan multiply the two inputs as they are loaded: wgrad_pregate (in the place of conv_h; x's shape) every sample of x,
+    // gate_out (gy's shape: the forward's `out`) every sample of gy; null where there is no such gate.
     // PART configurations (partitioned overlap-save) are OLS's with conv_Q and conv_parts set.
     // GATE configurations (CONV / OLS / PART with elementwise gates; the arguments of one exec, not plan state): gate_in has
     // the shape of `in` and multiplies every sample as it is loaded, gate_out the shape of `out` and multiplies every sample as
@@ -324,6 +327,7 @@ struct TileParams {
 static_assert(sizeof(TileParams) == 352 && __builtin_offsetof(TileParams, conv_Q) == __builtin_offsetof(TileParams, herm_d0) &&
                   __builtin_offsetof(TileParams, conv_o) == __builtin_offsetof(TileParams, stft_hop) &&
                   __builtin_offsetof(TileParams, conv_h) == __builtin_offsetof(TileParams, spec_wt) &&
+                  __builtin_offsetof(TileParams, wgrad_pregate) == __builtin_offsetof(TileParams, conv_h) &&
                   __builtin_offsetof(TileParams, wgrad_partials) == __builtin_offsetof(TileParams, spec_bands) &&
                   __builtin_offsetof(TileParams, conv_mode) == __builtin_offsetof(TileParams, spec_q),
               "TileParams: a CONV name left the field it shares");
@@ -652,7 +656,7 @@ struct TileCfg {
                               (same_t<T_, float>::value && (same_t<IT_, _Float16>::value || same_t<IT_, bf16_t>::value)))),
                   "CONV: packed real rows of the plan's own float type, or of a 16-bit float under float, staged in LDS by the "
                   "zero-extending load");
-    // The STORAGE type of a CONV tile is IT: x, both gates and the result (WGRAD: x and gy) are arrays of IT, widened exactly
+    // The STORAGE type of a CONV tile is IT: x, both gates and the result (WGRAD: x, gy and both gates) are arrays of IT, widened exactly
     // in the loads and rounded once, to nearest even, in the stores (sload / sstore above).  The filter spectra, the tables,
     // the LDS tile, the accumulators and WGRAD's result stay T.
     // OLS (with CONV): overlap-save.  A signal row of T samples is convolved as F blocks of 2N samples, each one launch row
@@ -674,7 +678,7 @@ struct TileCfg {
     // stored, in pairs, and real by real elsewhere; the gate load stands beside the access it accompanies, issued with it.
     static constexpr int GATE = GATE_;
     static_assert(GATE_ >= 0 && GATE_ <= 3 && (GATE_ == 0 || CONV_), "GATE: the pregate (1) and postgate (2) of a CONV tile");
-    // WGRAD (with CONV, ungated): the filter gradient of the convolution, gk[d][j] = sum over the rows r of channel d and the
+    // WGRAD (with CONV, any GATE, never PART): the filter gradient of the convolution, gk[d][j] = sum over the rows r of channel d and the
     // samples t of gy[r][t] x[r][t - j], as the sum over PAIRS (signal row r, block f) of conj(U) G, U and G the half spectra
     // of the u-block the forward block loaded (CONV's / OLS's load) and of the g-block -- the part of gy the forward block
     // stored, put back where the block had it: gb[i] = gy[r][f S + i - c] for c <= i < c + S, f S + i - c < Lo, zero elsewhere.
@@ -686,8 +690,13 @@ struct TileCfg {
     // tile's own LDS and row (s D + d) of N + 1 bins is stored, unscaled, once (conjugated when the forward correlated).
     // x and gy are read once each; no spectrum of a row reaches memory, no scratch, no atomics; the order of every sum is
     // fixed by the plan, so the result is bit-identical from run to run.  wgrad_walk below; the main tile loop is not run.
+    // With GATE the gates of the forward plan are fused into the two block loads, as CONV's pregate is into its load: bit 0,
+    // every sample read from x is multiplied by the element of TileParams::wgrad_pregate at the same (signal row, sample);
+    // bit 1, every sample read from gy by the element of TileParams::gate_out at the same (signal row, t), gy's coordinates.
+    // One multiplication of its own in T (widened first on a 16-bit storage type) before the value goes to LDS; a position
+    // a load zero-extends reads no gate.  The bins equal the ungated kernel's on the products a . x and b . gy bit for bit.
     static constexpr bool WGRAD = WGRAD_;
-    static_assert(!WGRAD_ || (CONV_ && GATE_ == 0), "WGRAD: the filter-gradient twin of an ungated CONV / OLS tile");
+    static_assert(!WGRAD_ || CONV_, "WGRAD: the filter-gradient twin of a CONV / OLS tile");
     // PART (with CONV and OLS, any GATE): uniformly partitioned overlap-save, for filters longer than half a block.  The filter
     // is P partitions of Q taps with one spectrum each, H[d][p]; output block f of a signal is the sum over p of the spectrum of
     // the n samples from s0 + f S - p Q on (correlation: + p Q) times H[d][p] (its conjugate), folded and inverted ONCE.  A step
@@ -1681,6 +1690,8 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
     const int c0 = p.conv_o, Lo = p.conv_Lo, L = p.conv_len;
     const ST* x = (const ST*)p.in;
     const ST* gy = (const ST*)p.gate_in;
+    const ST* ga0 = (C::GATE & 1) ? (const ST*)p.wgrad_pregate : x;  // (the gates of the same rows; else unused)
+    const ST* gb0 = (C::GATE & 2) ? (const ST*)p.gate_out : gy;
     const V* w = (const V*)p.r2c_tw;
     V acc_a[IT], acc_b[IT];
 #pragma unroll
@@ -1721,13 +1732,25 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
                     db = fr / F;
                     fr -= db * F;
                 }
-                const ST* xe = x + ((b0 + db) * D + d) * (long long)L;
+                const long long row = ((b0 + db) * D + d) * (long long)L;
+                const ST* xe = x + row;
+                const ST* ae = ga0 + row;
                 const int i = s0 + fr * S + 2 * m;
                 if (i >= 0 && i + 1 < L) {
                     v = sload_pair<T>(xe + i);
-                } else {
-                    if (i >= 0 && i < L) v.x = sload<T>(xe + i);
-                    if (i + 1 >= 0 && i + 1 < L) v.y = sload<T>(&xe[i + 1]);
+                    if constexpr (C::GATE & 1) {
+                        const V g = sload_pair<T>(ae + i);
+                        v = {g.x * v.x, g.y * v.y};
+                    }
+                } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
+                    if (i >= 0 && i < L) {
+                        v.x = sload<T>(xe + i);
+                        if constexpr (C::GATE & 1) v.x = sload<T>(ae + i) * v.x;
+                    }
+                    if (i + 1 >= 0 && i + 1 < L) {
+                        v.y = sload<T>(&xe[i + 1]);
+                        if constexpr (C::GATE & 1) v.y = sload<T>(&ae[i + 1]) * v.y;
+                    }
                 }
             }
             lds[lds_index<C, -1>(c, m)] = v;
@@ -1750,12 +1773,24 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
                 }
                 const int u = 2 * m - c0, t = fr * S + u;
                 const bool w0 = u >= 0 && u < S && t < Lo, w1 = u + 1 >= 0 && u + 1 < S && t + 1 < Lo;
-                const ST* ge = gy + ((b0 + db) * D + d) * (long long)Lo;
+                const long long row = ((b0 + db) * D + d) * (long long)Lo;
+                const ST* ge = gy + row;
+                const ST* be = gb0 + row;  // (the postgate in gy's coordinates: the same (row, t))
                 if (w0 && w1) {
                     v = sload_pair<T>(ge + t);
+                    if constexpr (C::GATE & 2) {
+                        const V g = sload_pair<T>(be + t);
+                        v = {g.x * v.x, g.y * v.y};
+                    }
                 } else {
-                    if (w0) v.x = sload<T>(ge + t);
-                    if (w1) v.y = sload<T>(&ge[t + 1]);
+                    if (w0) {
+                        v.x = sload<T>(ge + t);
+                        if constexpr (C::GATE & 2) v.x = sload<T>(be + t) * v.x;
+                    }
+                    if (w1) {
+                        v.y = sload<T>(&ge[t + 1]);
+                        if constexpr (C::GATE & 2) v.y = sload<T>(&be[t + 1]) * v.y;
+                    }
                 }
             }
             lds[lds_index<C, -1>(c, m)] = v;

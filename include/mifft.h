@@ -663,7 +663,10 @@ typedef struct mifft_gated_args {
  *     word  8      Lo >= 1: samples per row of gv
  *     word  9      P: partial sums per channel, 1 <= P <= min(65535, batch / D * F); 0: the library picks it, so that D P
  *                  workgroups fill the device when D alone does not
- *     word 10 .. 15 reserved, 0
+ *     word 10      reserved, 0
+ *     word 11      gates: 0 none (every payload written before there were any), bit 0 the forward plan's pregate, bit 1 its
+ *                  postgate (1, 2 or 3); above 3 MIFFT_ERR_BAD_BASES.  See GATES below
+ *     word 12 .. 15 reserved, 0
  * A single block is F = 1, s0 = 0, S = Lo, c = o with L <= n; anything else runs the overlap-save geometry (2 <= T <= 2^30).
  * x is (batch, L, 1) real, gv (batch, Lo, 1) real, out (P D, n / 2 + 1, 2), all of the plan's float type (in_dtype ==
  * out_dtype, in_components = 1, inverse = 0).  ONE launch of D P persistent workgroups, no scratch, no atomics: workgroup
@@ -679,13 +682,28 @@ typedef struct mifft_gated_args {
  * answers {tile (pairs per step), threads, steps of all workgroups, grid = D P}: P is grid / D.  mifft_plan_out_bytes() is
  * the size of the (P D, n / 2 + 1, 2) result.
  * Refused before any device work, with the forward plan's statuses: the flag, direction, dtype and component checks, the
- * limits of n (even, 8 .. 16384, float64 to 12288, n / 2 without a prime factor above 32), D and batch % D; MIFFT_ERR_BAD_BASES for the geometry rules above, a mode word beyond bit 0, P beyond its range or a non-zero
- * reserved word.  The 8-, 12- and 16-word MIFFT_CONV_TAG payloads are what they were.
+ * limits of n (even, 8 .. 16384, float64 to 12288, n / 2 without a prime factor above 32), D and batch % D; MIFFT_ERR_BAD_BASES for the geometry rules above, a mode word beyond bit 0, P beyond its range, a gates
+ * word above 3 or a non-zero reserved word.  The 8-, 12- and 16-word MIFFT_CONV_TAG payloads are what they were.
  * Half-precision storage: bits 8..15 of the mode word, as in the MIFFT_CONV_TAG forms above (0, MIFFT_F16 or MIFFT_BF16; an
  * F32 plan only: MIFFT_ERR_BAD_DTYPE otherwise; any other value or bit MIFFT_ERR_BAD_BASES).  x and gv are then arrays of
  * 2-byte elements, widened exactly in both block loads; the sums and the result stay float: mifft_plan_in_bytes() counts 2
  * bytes per element of x, mifft_plan_out_bytes() is unchanged, the alias checks use the storage sizes, and the kernel's name
  * carries `_h16` / `_b16` before `_jit`.  The result equals the F32 plan's on the widened tensors bit for bit.
+ * GATES (word 11): the filter gradient of the gated forward plan y = b . conv(a . x) without the products u = a . x and
+ * gv = b . gy in memory.  The u-block load multiplies every sample it reads from x by the element of the pregate at the same
+ * (row, sample), the g-block load every sample it reads from gy by the element of the postgate at the same (row, t) -- one
+ * multiplication of its own in the plan's float type (a storage type is widened first), a position a load zero-extends reads
+ * no gate -- so the result equals the ungated plan's on the products a . x and b . gy bit for bit (with a storage type: on the
+ * float products of the widened tensors).  The pregate has x's shape and size, the postgate gy's; with a storage type both
+ * are 2-byte arrays as x and gy are.  Still one launch, the same grid, no scratch.  The kernel is
+ * rows<n>[_f64]_r2c_<radices>_wgrad[_ols]_g<1|2|3>[_h16|_b16]_jit, run time only.
+ * THE EXEC of a plan with gates takes the HOST address of a mifft_conv_grad_gated_args, a block with a magic word of its own:
+ *     mifft_conv_grad_gated_args g = { MIFFT_CONV_GRAD_GATED_ARGS_MAGIC, x, gy, pregate, postgate };   mifft_exec(plan, &g, out, stream);
+ * the whole batch as above.  MIFFT_ERR_UNSUPPORTED with a message that names mifft_conv_grad_gated_args: a
+ * mifft_conv_grad_args block, a device address, a block without the magic word; MIFFT_ERR_NULL: a gate the plan has and the
+ * block lacks, a null x or gy; MIFFT_ERR_UNSUPPORTED: a gate the plan did not ask for; MIFFT_ERR_ALIAS: x, gy or a gate
+ * overlapping out (storage sizes).  Nothing is launched in any of these cases.  The gates may alias x, gy or each other: none
+ * is written.  A plan without gates takes the mifft_conv_grad_args block as ever.
  */
 #define MIFFT_CONV_GRAD_TAG_LO 0x44524701u
 #define MIFFT_CONV_GRAD_TAG_HI 0x7FF84D47u
@@ -696,6 +714,15 @@ typedef struct mifft_conv_grad_args {
     const void* x;   /* (batch, L, 1) reals on the plan's device: what the forward plan read */
     const void* gy;  /* (batch, Lo, 1) reals: the gradient of what it stored */
 } mifft_conv_grad_args;
+/* the argument block of a GATED filter-gradient exec (word 11 of the payload non-zero); the magic word is "MIFFTWG2" */
+#define MIFFT_CONV_GRAD_GATED_ARGS_MAGIC 0x324757544646494Dull
+typedef struct mifft_conv_grad_gated_args {
+    uint64_t magic;       /* MIFFT_CONV_GRAD_GATED_ARGS_MAGIC */
+    const void* x;        /* (batch, L, 1) reals on the plan's device: the forward plan's x, before its pregate */
+    const void* gy;       /* (batch, Lo, 1) reals: the gradient of the forward plan's out, before its postgate */
+    const void* pregate;  /* x's shape and dtype, or NULL where the plan has no pregate */
+    const void* postgate; /* gy's shape and dtype, or NULL where the plan has no postgate */
+} mifft_conv_grad_gated_args;
 
 typedef struct mifft_plan mifft_plan;
 

@@ -205,7 +205,9 @@ static_assert(MIFFT_GATED_ARGS_MAGIC == 0x314147544646494Dull && sizeof(mifft_ga
 // MIFFT_CONV_GRAD_TAG in front of 16 words -- TAG | D | c | S | mode | F | s0 | Lo | P | 0 x 6 -- on the same kind of plan: the
 // filter gradient of such a convolution, x (batch, L, 1) and gy (batch, Lo, 1) -> out (P D, n / 2 + 1, 2), unscaled partial
 // sums of conj(U) G per channel.  The exec takes the host address of a mifft_conv_grad_args {MIFFT_CONV_GRAD_ARGS_MAGIC, x, gy}
-// as its x and covers the whole batch (include/mifft.h).
+// as its x and covers the whole batch (include/mifft.h).  Word 11 of the payload: the forward plan's gates (0 none, bit 0 the
+// pregate, bit 1 the postgate), multiplied into the loads of x and gy; such a plan's exec takes a mifft_conv_grad_gated_args
+// {MIFFT_CONV_GRAD_GATED_ARGS_MAGIC, x, gy, pregate, postgate}.
 static_assert(MIFFT_CONV_GRAD_TAG_LO == 0x44524701u && MIFFT_CONV_GRAD_TAG_HI == 0x7FF84D47u &&
                   (MIFFT_CONV_GRAD_TAG_HI & 0x7FF80000u) == 0x7FF80000u && MIFFT_CONV_GRAD_TAG_HI != MIFFT_CONV_TAG_HI &&
                   MIFFT_CONV_GRAD_TAG_HI != MIFFT_MDCT_TAG_HI && MIFFT_CONV_GRAD_TAG_HI != MIFFT_STFT_EXT_TAG_HI,
@@ -213,6 +215,8 @@ static_assert(MIFFT_CONV_GRAD_TAG_LO == 0x44524701u && MIFFT_CONV_GRAD_TAG_HI ==
 constexpr uint64_t kConvGradTag = ((uint64_t)MIFFT_CONV_GRAD_TAG_HI << 32) | MIFFT_CONV_GRAD_TAG_LO;
 static_assert(MIFFT_CONV_GRAD_ARGS_MAGIC == 0x314757544646494Dull && sizeof(mifft_conv_grad_args) == 8 + 2 * sizeof(void*),
               "mifft_conv_grad_args is the magic word \"MIFFTWG1\" and two pointers");
+static_assert(MIFFT_CONV_GRAD_GATED_ARGS_MAGIC == 0x324757544646494Dull && sizeof(mifft_conv_grad_gated_args) == 8 + 4 * sizeof(void*),
+              "mifft_conv_grad_gated_args is the magic word \"MIFFTWG2\" and four pointers");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
