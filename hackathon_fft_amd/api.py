@@ -63,6 +63,9 @@ CONV_GRAD_TAG_LO = 0x44524701  # MIFFT_CONV_GRAD_TAG_LO / _HI: the NaN in front 
 CONV_GRAD_TAG_HI = 0x7FF84D47  # filter gradient of a fused convolution (TAG | D | c | S | mode | F | s0 | Lo | P | 0 | gates | 0 x 4)
 CONV_GRAD_ARGS_MAGIC = 0x314757544646494D  # MIFFT_CONV_GRAD_ARGS_MAGIC ("MIFFTWG1")
 CONV_GRAD_GATED_ARGS_MAGIC = 0x324757544646494D  # MIFFT_CONV_GRAD_GATED_ARGS_MAGIC ("MIFFTWG2")
+STFT_ADJ_TAG_LO = 0x4A444101   # MIFFT_STFT_ADJ_TAG_LO / _HI: the NaN behind the window of a FLAG_ISTFT plan that is the adjoint of
+STFT_ADJ_TAG_HI = 0x7FF84D41   # the STFT (w | TAG | gain | mode, 0)
+STFT_ADJ_ARGS_MAGIC = 0x314153544646494D  # MIFFT_STFT_ADJ_ARGS_MAGIC ("MIFFTSA1")
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
 
@@ -81,6 +84,11 @@ class ConvGradGatedArgs(ctypes.Structure):
     """mifft_conv_grad_gated_args: what the exec of a filter-gradient plan with gates takes, by host address, in the place of x"""
     _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("gy", ctypes.c_void_p), ("pregate", ctypes.c_void_p),
                 ("postgate", ctypes.c_void_p)]
+
+
+class StftAdjArgs(ctypes.Structure):
+    """mifft_stft_adj_args: what the exec of an STFT adjoint plan takes, by host address, in the place of x"""
+    _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("mult", ctypes.c_void_p), ("edge", ctypes.c_void_p)]
 
 
 def FLAG_KEEP_DIM(d: int) -> int:
@@ -442,6 +450,33 @@ def _check_istft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> 
     return (T, F, n)
 
 
+def _check_stft_adjoint_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> tuple:
+    """Layouts of an STFT adjoint plan (MIFFT_STFT_ADJ_TAG on MIFFT_FLAG_ISTFT): x (batch, F, n // 2 + 1, 2) -> out
+    (batch, T, 1) real, T the signal's length and F = stft_frames(T, n, hop, center) the forward's frames; returns the dims
+    (T, F, n).  ``center`` is the forward plan's: None, "reflect" or "constant"."""
+    if len(in_shape) != 4 or len(out_shape) != 3:
+        raise MifftError(-1, f"STFT adjoint layouts are (batch, F, n // 2 + 1, 2) -> (batch, T, 1), got {in_shape} -> {out_shape}")
+    if in_shape[-1] != 2:
+        raise MifftError(-3, f"an STFT adjoint reads complex bins (2 components), got {in_shape[-1]}")
+    if out_shape[-1] != 1:
+        raise MifftError(-3, f"an STFT adjoint writes real signals (1 component), got {out_shape[-1]}")
+    if in_shape[0] != out_shape[0]:
+        raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
+    F, n, T = in_shape[1], 2 * (in_shape[2] - 1), out_shape[1]
+    if n < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with frames of fewer than 8 points ({n}) is not supported")
+    FLAG_STFT_HOP(hop)
+    if hop > n:
+        raise MifftError(ERR_UNSUPPORTED, f"the STFT adjoint with hop_length {hop} > n_fft {n} is not supported: the overlap-add "
+                                          f"kernel it runs on has no gaps between its frames")
+    if F != stft_frames(T, n, hop, _stft_center_flags(center) != 0):
+        raise MifftError(-2, f"signals of {T} samples have {stft_frames(T, n, hop, _stft_center_flags(center) != 0)} frames of "
+                             f"{n} every {hop}, x has {F}")
+    if center == "reflect" and n // 2 > T - 1:
+        raise MifftError(-2, f"reflect padding needs n_fft // 2 <= T - 1, got n_fft = {n}, T = {T}")
+    return (T, F, n)
+
+
 def _window_f64(window, n_fft: int) -> "torch.Tensor":
     """a window as n_fft float64 values on the host (a CUDA tensor is copied, which synchronises its stream)"""
     w = torch.as_tensor(window).detach().to(device="cpu", dtype=torch.float64).contiguous()
@@ -549,7 +584,7 @@ class Plan:
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None):
+                 imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None, stft_adjoint: int = 0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct = int(mdct), int(imdct)
         if dct_type not in (2, 4):
@@ -574,15 +609,22 @@ class Plan:
                 if stft_center is None:
                     stft_center = {0: None, FLAG_STFT_CENTER_ZEROS: "constant"}.get(
                         int(flags) & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), "reflect")
-            istft_dims = _check_istft_layout(in_shape, out_shape, istft_hop, stft_center)
+            if stft_adjoint:
+                istft_dims = _check_stft_adjoint_layout(in_shape, out_shape, istft_hop, stft_center)
+            else:
+                istft_dims = _check_istft_layout(in_shape, out_shape, istft_hop, stft_center)
             if axes is not None:
                 raise MifftError(ERR_UNSUPPORTED, "an inverse STFT plan transforms dim 2 and overlap-adds dim 1: no axes")
             gain = float(istft_gain)
-            if stft_window is not None or gain != 1.0:
+            if stft_adjoint:  # (the tagged payload: w | TAG | gain | mode, 0)
+                w = torch.ones(istft_dims[2], dtype=torch.float64) if stft_window is None else _window_f64(stft_window, istft_dims[2])
+                words = window_words(w) + [STFT_ADJ_TAG_LO, STFT_ADJ_TAG_HI] + window_words([gain]) + [int(stft_adjoint), 0]
+            elif stft_window is not None or gain != 1.0:
                 w = torch.ones(istft_dims[2], dtype=torch.float64) if stft_window is None else _window_f64(stft_window, istft_dims[2])
                 words = window_words(w) + (window_words([gain]) if gain != 1.0 else [])
             inverse = True
-            flags = (int(flags) | FLAG_ISTFT | FLAG_STFT_HOP(istft_hop) | _istft_center_flags(stft_center) |
+            flags = (int(flags) | FLAG_ISTFT | FLAG_STFT_HOP(istft_hop) |
+                     (_stft_center_flags(stft_center) if stft_adjoint else _istft_center_flags(stft_center)) |
                      (FLAG_STFT if stft else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
                      (FLAG_HALF_SPECTRUM if half_spectrum else 0))
             stft = False
@@ -697,6 +739,7 @@ class Plan:
         self.dst = bool(dst) and (dct or dctn) and not stft and not istft
         self.mdct = mdct
         self.imdct = imdct
+        self.stft_adjoint = int(stft_adjoint) if istft and not imdct else 0
         self.conv = conv
         self.conv_gates = conv.gates if conv is not None else 0
         self._ndim = len(dims)
@@ -1013,6 +1056,9 @@ def fft(output: "torch.Tensor", x: "torch.Tensor", ctx: Optional[DeviceContext] 
     if getattr(plan, "conv_gates", 0):
         raise MifftError(ERR_UNSUPPORTED, "a gated convolution plan takes its gates with every exec: "
                                           "plan.run(out, x, pregate=, postgate=) instead of fft(out, x, plan=plan)")
+    if getattr(plan, "stft_adjoint", 0):
+        raise MifftError(ERR_UNSUPPORTED, "an STFT adjoint plan takes its factor and edge tensors with every exec: "
+                                          "plan.run(out, g, multiplier=, edge=) or plan.apply(g) instead of fft(out, x, plan=plan)")
     if ctx is None:
         ctx = DeviceContext(plan.device)
     io = getattr(plan, "io_dtype", None)  # (a half-storage convolution plan: 16-bit rows around float32 arithmetic)
@@ -1022,6 +1068,96 @@ def fft(output: "torch.Tensor", x: "torch.Tensor", ctx: Optional[DeviceContext] 
         count = plan.out_shape[0] - first
     check(_lib.lib().mifft_exec_batch(plan._h, x.data_ptr(), output.data_ptr(), int(first), int(count),
                                       ctx.stream.cuda_stream))
+
+
+class StftAdjointPlan(Plan):
+    """The adjoint of an STFT plan (``plan_stft_adjoint``; MIFFT_STFT_ADJ_TAG in include/mifft.h): the gradient with respect to
+    the signal of ``stft`` (``multiplier`` None) or of the power / magnitude spectrogram (``multiplier`` 2 / 1), one launch.
+    ``in_shape`` (batch, frames, n_fft // 2 + 1, 2), ``out_shape`` (batch, length, 1); ``mult_shape`` (batch, frames,
+    n_fft // 2 + 1) with a multiplier, else None; ``edge_shape`` (batch, 2, n_fft // 2) with reflect padding, else None.
+    ``covered`` = min(length, n_fft + hop (frames - 1) - c), c = n_fft // 2 when centred: the samples of every entry that
+    ``run`` writes; the gradient of the others is zero."""
+
+    def __init__(self, dtype, batch, length, n_fft, hop_length, window, center, multiplier, ctx):
+        mode = {None: 1, 2: 2, 1: 3}[multiplier]
+        centred = _stft_center_flags(center) != 0
+        frames = stft_frames(length, n_fft, hop_length, centred)
+        bins = n_fft // 2 + 1
+        super().__init__(dtype, dtype, (batch, frames, bins, 2), (batch, length, 1), device=ctx.device, istft_hop=hop_length,
+                         stft_center=center, stft_window=window, stft_adjoint=mode)
+        self._ctx = ctx
+        self.frames, self.multiplier, self.n_fft, self.hop_length, self.center = frames, multiplier, n_fft, hop_length, center
+        self.mult_shape = (batch, frames, bins) if multiplier is not None else None
+        self.edge_shape = (batch, 2, n_fft // 2) if center == "reflect" else None
+        self._c = n_fft // 2 if centred else 0
+        self.covered = min(length, n_fft + hop_length * (frames - 1) - self._c)
+
+    def run(self, out: "torch.Tensor", g: "torch.Tensor", *, multiplier: Optional["torch.Tensor"] = None,
+            edge: Optional["torch.Tensor"] = None, first: Optional[int] = None, count: Optional[int] = None) -> None:
+        """The raw exec on the plan's stream: ``g`` (in_shape) is the incoming gradient -- or, on a plan with a multiplier,
+        X itself, with the real gradient of abs(X) ** power as ``multiplier`` (mult_shape).  Writes out[:, :covered] and, on a
+        reflect plan, the two strips of padded samples into ``edge`` (edge_shape; side 1 only below the frames' end) for the
+        caller to fold; nothing else.  A tensor the plan needs and does not get is MifftError -12, one it has no use for -15,
+        an input overlapping an output -13."""
+        _check_tensor(g, self.in_shape, self.in_dtype, self.device, "g")
+        _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
+        if multiplier is not None:
+            _check_tensor(multiplier, self.mult_shape or tuple(multiplier.shape), self.out_dtype, self.device, "multiplier")
+        if edge is not None:
+            _check_tensor(edge, self.edge_shape or tuple(edge.shape), self.out_dtype, self.device, "edge")
+        first = 0 if first is None else int(first)
+        count = self.out_shape[0] - first if count is None else int(count)
+        args = StftAdjArgs(STFT_ADJ_ARGS_MAGIC, g.data_ptr(), None if multiplier is None else multiplier.data_ptr(),
+                           None if edge is None else edge.data_ptr())
+        check(_lib.lib().mifft_exec_batch(self._h, ctypes.byref(args), out.data_ptr(), first, count,
+                                          self._ctx.stream.cuda_stream))
+
+    def apply(self, g: "torch.Tensor", multiplier: Optional["torch.Tensor"] = None) -> "torch.Tensor":
+        """The whole gradient, (batch, length): allocates ``out`` and ``edge``, zero-fills the samples no frame covers, launches,
+        and on a reflect plan adds the two flipped edge strips in place -- two torch ops on n_fft // 2 samples per row."""
+        batch, T = self.out_shape[0], self.out_shape[1]
+        with torch.cuda.stream(self._ctx.stream):
+            out = torch.empty(self.out_shape, dtype=self.out_dtype, device=g.device)
+            edge = None if self.edge_shape is None else torch.empty(self.edge_shape, dtype=self.out_dtype, device=g.device)
+            if self.covered < T:
+                out[:, self.covered:].zero_()
+            self.run(out, g, multiplier=multiplier, edge=edge)
+            gx = out.reshape(batch, T)
+            if edge is not None:  # gx[t] += gxp[c - t], 1 <= t <= c;  gx[T - 2 - e] += gxp[c + T + e] for the e below the frames' end
+                c = self._c
+                gx[:, 1:c + 1] += edge[:, 0].flip(-1)
+                e = min(c, self.n_fft + self.hop_length * (self.frames - 1) - c - T)
+                if e > 0:
+                    gx[:, T - 1 - e:T - 1] += edge[:, 1, :e].flip(-1)
+        return gx
+
+
+def plan_stft_adjoint(dtype, batch: int, length: int, n_fft: int, hop_length: int, *, window=None, center=None,
+                      multiplier=None, ctx: Optional[DeviceContext] = None) -> StftAdjointPlan:
+    """Plan of the adjoint of ``plan_stft(dtype, batch, length, n_fft, hop_length, window=, center=)`` (no reference counterpart;
+    MIFFT_STFT_ADJ_TAG in include/mifft.h): the gradient of that plan's result with respect to its signal, an overlap-add of
+    inverse real transforms without the envelope division, in ONE launch, no scratch, no memset, no atomics.  ``window`` and
+    ``center`` (None, "reflect", "constant") are the forward plan's.  ``multiplier``: None -- ``run`` / ``apply`` take the
+    incoming gradient g = dL/dRe X + i dL/dIm X, frames-major (batch, frames, n_fft // 2 + 1, 2); 2 or 1 (the power) -- they
+    take X itself and the real gradient of abs(X) ** power, (batch, frames, n_fft // 2 + 1), which is multiplied in as the bins
+    are loaded (2 m X, or m X / abs(X) with zero where abs(X) is).  An entry's result is bit-identical for any batch and slab.
+    ``hop_length > n_fft`` and float64 frames beyond 10240 samples are refused (-15); every argument error is raised before any
+    device work.  ``fft(out, x, plan=plan)`` refuses such a plan: use ``run`` or ``apply``."""
+    batch, length, n_fft, hop_length = int(batch), int(length), int(n_fft), int(hop_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"an STFT adjoint plan reads and writes float32 or float64, got {dtype}")
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    if multiplier is not None and (isinstance(multiplier, bool) or multiplier not in (1, 2)):
+        raise MifftError(ERR_UNSUPPORTED, f"multiplier must be None, 2 (power) or 1 (magnitude), got {multiplier!r}")
+    multiplier = None if multiplier is None else int(multiplier)
+    FLAG_STFT_HOP(hop_length)
+    _stft_center_flags(center)
+    if window is not None:
+        window = _window_f64(window, n_fft)
+    if ctx is None:
+        ctx = DeviceContext()
+    return StftAdjointPlan(dtype, batch, length, n_fft, hop_length, window, center, multiplier, ctx)
 
 
 def time_fft(output: "torch.Tensor", x: "torch.Tensor", *, plan: Plan, iters: int = 10,
@@ -2772,13 +2908,174 @@ def stft(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_le
     One kernel launch: no padded copy of ``x``, no unfold, no tensor of frames (MIFFT_FLAG_STFT in include/mifft.h).
     Plans are cached per (shape, dtype, n_fft, hop, centring, device, stream) AND the window's contents: every call hashes the
     window's float64 values, so a window changed in place never meets a stale plan.  For a CUDA ``window`` that is one small
-    synchronising device-to-host copy per call: loops should make the plan once with ``plan_stft`` and call ``fft``."""
+    synchronising device-to-host copy per call: loops should make the plan once with ``plan_stft`` and call ``fft``.
+    Differentiable with respect to ``x`` (first order): when grad mode is on and ``x.requires_grad``, the result carries a
+    ``grad_fn`` whose backward is ONE launch of the fused adjoint overlap-add (``plan_stft_adjoint``) on the incoming gradient,
+    made frames-major first (a no-op for a gradient laid out like the view returned here); the gradient comes back in ``x``'s
+    shape and dtype.  The adjoint plan is made, and cached under a key of its own, in the forward: what it cannot do --
+    ``hop_length > n_fft``, float64 frames beyond 10240 samples -- is a MifftError there, while the forward alone works on an
+    ``x`` without requires_grad.  Otherwise the call is what it has always been: same plan, same bits, no ``grad_fn``.  The
+    window is taken by value and gets no gradient; there is no double backward."""
     return _stft_run("stft", x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype,
                      None, None)
 
 
 def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype, power,
               fb, logv=None, post=None) -> "torch.Tensor":
+    """stft and spectrogram: the plain call (_stft_run_plain), through autograd exactly when grad mode is on and ``x`` requires
+    grad; otherwise the call is what it has always been"""
+    args = (who, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype, power, fb, logv, post)
+    if torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad:
+        return (_STFTFunction if power is None else _SpectrogramFunction).apply(x, args)
+    return _stft_run_plain(who, x, *args[1:])
+
+
+def _stft_table(window, win_length: int, n_fft: int, normalized: bool):
+    """the window table of an stft call as n_fft float64 host values (centred, zero-padded, times n_fft ** -0.5 when
+    normalized), or None for the rectangular window of a whole frame"""
+    if window is None and win_length >= n_fft and not normalized:
+        return None
+    wl = torch.ones(win_length, dtype=torch.float64) if window is None else _window_f64(window, win_length)
+    left = (n_fft - win_length) // 2
+    w = torch.zeros(n_fft, dtype=torch.float64)
+    w[left:left + win_length] = wl
+    if normalized:
+        w *= float(n_fft) ** -0.5
+    return w
+
+
+class _StftCall(NamedTuple):
+    """An stft / spectrogram call as its autograd Function keeps it between forward and backward: everything by value -- the
+    window as the float64 table of the forward (None: rectangular), ``fb`` and ``post`` as their float64 host matrices -- so
+    that a window or matrix changed in place afterwards cannot give the backward another transform than the forward's."""
+    who: str
+    out_dtype: object
+    batch: int
+    length: int
+    n_fft: int
+    hop: int
+    center: bool
+    pad_mode: str
+    window: object
+    power: object
+    fb: object
+    logv: object
+    post: object
+    device: int
+
+    @property
+    def frames(self) -> int:
+        return stft_frames(self.length, self.n_fft, self.hop, self.center)
+
+    def run(self, x, power, fb=None, logv=None, post=None):
+        """the plain call on these values (the table is the whole window: win_length = n_fft, nothing left to normalize)"""
+        return _stft_run_plain(self.who, x, self.n_fft, self.hop, self.n_fft, self.window, self.center, self.pad_mode, False, True,
+                               self.out_dtype, power, fb, logv, post)
+
+
+def _stft_call(x, args) -> _StftCall:
+    """the arguments of a call that _stft_run_plain has accepted, by value"""
+    who, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype, power, fb, logv, post = args
+    n_fft = int(n_fft)
+    hop_length = n_fft // 4 if hop_length is None else int(hop_length)
+    win_length = n_fft if win_length is None else int(win_length)
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    T = int(x.shape[-1])
+    fbm = None if fb is None else _fb_f64(fb, n_fft // 2 + 1).clone()
+    postm = None if post is None else _post_f64(post, int(fbm.shape[1])).clone()
+    return _StftCall(who, out_dtype, x.numel() // T, T, n_fft, hop_length, bool(center), pad_mode,
+                     _stft_table(window, win_length, n_fft, normalized), power, fbm, logv, postm, x.device.index)
+
+
+def _stft_adjoint_plan(call: _StftCall, multiplier) -> StftAdjointPlan:
+    """The cached adjoint plan of an stft / spectrogram call, looked up or made under the cache's lock, which the caller
+    holds until its launch is enqueued: a plan the cache evicts is closed.  The forward of the autograd Functions asks for it
+    first, so that what the adjoint cannot do is raised there; the backward asks again, since the plan of the forward may have
+    left the cache in between."""
+    w, device = call.window, call.device
+    mode = call.pad_mode if call.center else None
+    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
+    with _PLAN_CACHE_LOCK:
+        key = ("stft_adjoint", call.out_dtype, (call.batch, call.length), call.n_fft, call.hop, mode, digest, multiplier, device,
+               int(torch.cuda.current_stream(device).cuda_stream))
+        plan = _PLAN_CACHE.get(key)
+        if plan is None:
+            try:
+                plan = plan_stft_adjoint(call.out_dtype, call.batch, call.length, call.n_fft, call.hop, window=w, center=mode,
+                                         multiplier=multiplier, ctx=DeviceContext(device))
+            except MifftError as e:
+                raise MifftError(e.status, f"{call.who}: no gradient with respect to x for these arguments ({e}); the forward "
+                                           f"alone works on an x without requires_grad (or under torch.no_grad())") from None
+            _plan_cache_insert(key, plan)
+        else:
+            _PLAN_CACHE.move_to_end(key)
+    return plan
+
+
+class _STFTFunction(torch.autograd.Function):
+    """stft with the gradient with respect to x: one adjoint launch (StftAdjointPlan, mode 1).  First order."""
+
+    @staticmethod
+    def forward(ctx, x, args):
+        X = _stft_run_plain(args[0], x, *args[1:])
+        ctx.call = _stft_call(x, args)
+        _stft_adjoint_plan(ctx.call, None)
+        ctx.x_shape, ctx.x_dtype = tuple(x.shape), x.dtype
+        return X
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gX):
+        call = ctx.call
+        ctype = torch.complex64 if call.out_dtype == torch.float32 else torch.complex128
+        # frames-major memory: a no-op for a gradient laid out like the view stft returns
+        g = torch.view_as_real(gX.to(ctype).transpose(-1, -2).contiguous())
+        with _PLAN_CACHE_LOCK:
+            plan = _stft_adjoint_plan(call, None)
+            gx = plan.apply(g.reshape(plan.in_shape))
+        return gx.reshape(ctx.x_shape).to(ctx.x_dtype), None
+
+
+class _SpectrogramFunction(torch.autograd.Function):
+    """spectrogram (and so mfcc) with the gradient with respect to x.  Without fb / log / post: one stft launch recomputes X,
+    one adjoint launch (mode 2 or 3) takes the incoming gradient as its factor.  With them the chain down to the bins is torch
+    on band-sized tensors.  First order; the window, the filterbank and ``post`` get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, args):
+        y = _stft_run_plain(args[0], x, *args[1:])
+        ctx.call = _stft_call(x, args)
+        _stft_adjoint_plan(ctx.call, int(ctx.call.power))
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        call = ctx.call
+        dt, dev = call.out_dtype, gy.device
+        g = gy.to(dt).transpose(-1, -2)  # frames-major (..., F, width)
+        if call.post is not None:  # gBands = gy @ post.T
+            g = g @ call.post.to(device=dev, dtype=dt).transpose(0, 1)
+        if call.logv is not None:  # y = a log2(max(v + add, amin)) + c: a / (ln 2 (v + add)) where v + add > amin, 0 elsewhere
+            add, amin, a, _ = call.logv
+            v = call.run(x, call.power, call.fb).transpose(-1, -2)
+            s = v + add
+            g = torch.where(s > amin, g * (a / math.log(2.0)) / s, torch.zeros_like(g))
+        if call.fb is not None:  # gP = gBands @ fb.T
+            g = g @ call.fb.to(device=dev, dtype=dt).transpose(0, 1)
+        m = g.contiguous()
+        Xf = torch.view_as_real(call.run(x, None).transpose(-1, -2).contiguous())
+        with _PLAN_CACHE_LOCK:  # (the recomputing calls above may have pushed the forward's adjoint plan out of the cache)
+            plan = _stft_adjoint_plan(call, int(call.power))
+            gx = plan.apply(Xf.reshape(plan.in_shape), m.reshape(plan.mult_shape))
+        return gx.reshape(tuple(x.shape)).to(x.dtype), None
+
+
+def _stft_run_plain(who: str, x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided, out_dtype, power,
+                    fb, logv=None, post=None) -> "torch.Tensor":
     """stft (``power`` None) and spectrogram (``power`` 1 or 2, ``fb`` None or a (n_fft // 2 + 1, M) float64 host matrix,
     ``logv`` None or (add, amin, a, c), ``post`` None or an (M, Q) matrix)"""
     if not onesided:
@@ -2817,17 +3114,7 @@ def _stft_run(who: str, x, n_fft, hop_length, win_length, window, center, pad_mo
         width = int(post.shape[1])
     in_shape, out_shape = (batch, T, 1), (batch, frames, width, 2 if power is None else 1)
     _check_stft_layout(in_shape, (batch, frames, bins, 2), hop_length, mode)
-    w = None
-    if window is not None or win_length < n_fft or normalized:
-        if window is None:
-            wl = torch.ones(win_length, dtype=torch.float64)
-        else:
-            wl = _window_f64(window, win_length)
-        left = (n_fft - win_length) // 2
-        w = torch.zeros(n_fft, dtype=torch.float64)
-        w[left:left + win_length] = wl
-        if normalized:
-            w *= float(n_fft) ** -0.5
+    w = _stft_table(window, win_length, n_fft, normalized)
     device = DeviceContext(x.device.index if x.is_cuda else None).device
     if not x.is_cuda or x.device.index != device:
         raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
@@ -2878,7 +3165,15 @@ def spectrogram(x: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None,
     writes, exactly as ``stft`` does.  ``power`` other than 1 or 2 is MifftError -15; so is ``power=None``: the complex
     spectrogram is ``stft``.  A filterbank of another shape is -2.  Plans are cached as those of ``stft``, the key extended by
     the power and a digest of the filterbank's values (and of ``post``, and the log stage), so a matrix changed in place never
-    meets a stale plan; loops should make the plan once with ``plan_spectrogram`` and call ``fft``."""
+    meets a stale plan; loops should make the plan once with ``plan_spectrogram`` and call ``fft``.
+    Differentiable with respect to ``x`` (first order), exactly when grad mode is on and ``x.requires_grad``; otherwise the
+    call is what it has always been.  Without ``fb`` / ``log`` / ``post`` the backward is two launches and no torch op on a
+    spectrogram-sized tensor: one ``stft`` launch recomputes X, one adjoint launch (``plan_stft_adjoint(multiplier=power)``) takes
+    the incoming gradient m as a per-bin factor in its load -- 2 m X, or m X / abs(X) with zero where abs(X) is, torch's
+    ``abs`` backward -- so that the product never exists in memory.  With them the chain down to the bins is torch on
+    band-sized tensors first: ``gy @ post.T``, the log stage's derivative (zero where the clamp at ``amin`` holds; its argument
+    recomputed by one forward launch without ``log`` / ``post``), ``@ fb.T``.  The adjoint plan is made in the forward, as in
+    ``stft``, with the same refusals.  The window, ``fb`` and ``post`` are taken by value and get no gradient."""
     if power is None:
         raise MifftError(ERR_UNSUPPORTED, "spectrogram: power=None is the complex spectrogram: use stft")
     power = _spec_power(power)
@@ -2969,7 +3264,8 @@ def mfcc(x: "torch.Tensor", sample_rate: int, n_mfcc: int = 40, *, n_fft: int = 
     one).  ``log=None`` skips the log stage.  torchaudio's and librosa's default ``top_db=80`` clamp is NOT applied: it needs
     the maximum over a whole entry, which one pass over the frames does not have.  Needs n_mels <= n_fft // 2 - 1.
     Returns (..., n_mfcc, F) as the same transposed view as ``spectrogram``.  Every argument error is a MifftError before any
-    device work."""
+    device work.  Differentiable with respect to ``x`` as ``spectrogram`` is (the DCT matrix, the log stage and the filterbank
+    in torch on band-sized tensors, then the fused adjoint); the filterbank and the DCT matrix get no gradient."""
     n_fft = int(n_fft)
     if n_fft % 2 or n_fft < 8:
         raise MifftError(ERR_UNSUPPORTED, f"mfcc with an odd n_fft or one below 8 ({n_fft}) is not supported")

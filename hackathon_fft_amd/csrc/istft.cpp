@@ -56,9 +56,11 @@ static int64_t envelope_first_below(const std::vector<double>& window, int64_t n
     return first;
 }
 
-// checks that need no device: MIFFT_OK, or the status and its reason; the window, the gain and the user radices on the way
-int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
-                std::vector<uint64_t>& radices, std::string& why) {
+// checks that need no device: MIFFT_OK, or the status and its reason; the window, the gain and the user radices on the way.
+// `adj_mode` null: an inverse STFT plan.  Else an STFT adjoint plan (stft_adj_check), whose mode word it receives: the covered
+// length, the envelope's limit and the overlap-add condition do not apply, and the payload is the tagged one.
+static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
+                            double& gain, std::vector<uint64_t>& radices, std::string& why, int* adj_mode) {
     window.clear();
     radices.clear();
     gain = 1.0;
@@ -126,10 +128,54 @@ int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_
         return MIFFT_ERR_BAD_DIM;
     }
     if (F > (1ll << 26)) {  // (before L is formed: L = n + hop (F - 1) stays far inside 64 bits)
-        why = "more than 2^26 frames per entry: the envelope table has one entry per padded sample";
+        why = adj_mode ? "more than 2^26 frames per entry: the frames of an entry are counted in 32 bits"
+                       : "more than 2^26 frames per entry: the envelope table has one entry per padded sample";
         return MIFFT_ERR_TOO_LARGE;
     }
     const int64_t L = p.istft_padded_len(), c = p.istft_trim();
+    if (adj_mode) {  // dims[0] is the SIGNAL's length: the frames lie inside the padded signal, and nothing else is asked of it
+        if (T < 1 || L > T + 2 * c) {
+            why = "T = " + std::to_string(T) + " samples" + (c ? " padded by n / 2 on both sides" : "") + ", but the frames cover " +
+                  std::to_string(L) + " (n + hop (F - 1)): more than the signal has";
+            return MIFFT_ERR_BAD_DIM;
+        }
+        if ((p.flags & MIFFT_FLAG_STFT_CENTER_REFLECT) && c > T - 1) {
+            why = "MIFFT_FLAG_STFT_CENTER_REFLECT with n / 2 = " + std::to_string(c) + " > T - 1 = " + std::to_string(T - 1) +
+                  ": the signal is reflected once at each end";
+            return MIFFT_ERR_BAD_DIM;
+        }
+        if (T + n >= (1ll << 31)) {
+            why = "signals of " + std::to_string(T) + " samples per entry: the padded samples are addressed in 32 bits";
+            return MIFFT_ERR_TOO_LARGE;
+        }
+        const int64_t l0 = bases_len[0];  // (stft_adj_detect: 2 n + 6, the tag behind the window)
+        if (bases_len[1] != 0 || bases_len[2] < 0) {
+            why = "bases_len[1] is 0 (dim 1 is overlap-added, not transformed) and bases_len[2] the radices of n";
+            return bases_len[2] < 0 ? MIFFT_ERR_NO_BASES : MIFFT_ERR_BAD_BASES;
+        }
+        window.resize((size_t)n);
+        for (int64_t j = 0; j < n; ++j)
+            if (!read_f64(bases_flat + 2 * j, window[(size_t)j])) {
+                why = "window value " + std::to_string(j) + " is not finite";
+                return MIFFT_ERR_BAD_BASES;
+            }
+        if (!read_f64(bases_flat + 2 * n + 2, gain) || gain == 0.0) {
+            why = "the gain is finite and not zero, not " + std::to_string(gain);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        const uint32_t mode = bases_flat[2 * n + 4];
+        if (mode < 1 || mode > 3) {
+            why = "the mode word is 1 (the gradient of X), 2 (of |X|^2) or 3 (of |X|), not " + std::to_string(mode);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        if (bases_flat[2 * n + 5] != 0) {
+            why = "the reserved word behind the mode is 0, not " + std::to_string(bases_flat[2 * n + 5]);
+            return MIFFT_ERR_BAD_BASES;
+        }
+        *adj_mode = (int)mode;
+        for (int k = 0; k < bases_len[2]; ++k) radices.push_back(bases_flat[l0 + k]);
+        return MIFFT_OK;
+    }
     if (L > (1ll << 26)) {
         why = "frames that cover " + std::to_string(L) + " samples per entry: the envelope table (one entry per padded sample) is " +
               "limited to 2^26";
@@ -173,6 +219,34 @@ int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_
               " (nonzero overlap-add condition: below 1e-11)";
         return MIFFT_ERR_UNSUPPORTED;
     }
+    return MIFFT_OK;
+}
+
+int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
+                std::vector<uint64_t>& radices, std::string& why) {
+    return istft_check_impl(p, bases_flat, bases_len, window, gain, radices, why, nullptr);
+}
+
+// ---- STFT adjoint plans: the payload w[0 .. n-1] | MIFFT_STFT_ADJ_TAG | gain | mode, 0 on a MIFFT_FLAG_ISTFT plan ------------------
+// The gradient of the framed, windowed, one-sided transform with respect to the signal is an overlap-add of inverse real
+// transforms: the ISTFT pass with TileCfg::ADJ (tile_kernel.h), no envelope, dims[0] the signal's length.  With g~ the incoming
+// gradient whose bins 0 and n / 2 are doubled, frame f contributes w[j] (n / 2) irfft(g~_f)[j]; the pass leaves n irfft(.), so
+// the synthesis table is gain * w / 2 -- gain * w for mode 2, whose factor 2 (d|X|^2 = 2 X) lives there.
+bool stft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 3 || !bases_flat || !bases_len) return false;
+    const int64_t n = dims[2];
+    return (int64_t)bases_len[0] == 2 * n + 6 && bases_flat[2 * n] == MIFFT_STFT_ADJ_TAG_LO && bases_flat[2 * n + 1] == MIFFT_STFT_ADJ_TAG_HI;
+}
+
+int stft_adj_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
+                   std::vector<uint64_t>& radices, std::string& why) {
+    int mode = 0;
+    const int rc = istft_check_impl(p, bases_flat, bases_len, window, gain, radices, why, &mode);
+    if (rc) {
+        why = "an STFT adjoint payload (MIFFT_STFT_ADJ_TAG on a MIFFT_FLAG_ISTFT plan): " + why;
+        return rc;
+    }
+    p.stft_adj = mode;
     return MIFFT_OK;
 }
 
@@ -364,7 +438,16 @@ int build_istft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector
     // the passes run n / 2 points; the fold needs W_n^k, forward (as a half-spectrum row pass)
     hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, true, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && p.stft_adj) {  // ws[j] = gain * w[j] / 2 (mode 2: gain * w[j]) with the sign of the conjugation; no envelope
+        const double g = p.stft_adj == 2 ? gain : 0.5 * gain;
+        std::vector<double> ws((size_t)n);
+        for (int64_t j = 0; j < n; ++j) ws[(size_t)j] = ((j & 1) ? -g : g) * (window.empty() ? 1.0 : window[(size_t)j]);
+        if (p.out_dtype == MIFFT_F64) {
+            e = upload_t<double>(ws, &ps.d_aux2);
+        } else {
+            e = upload_t<float>(std::vector<float>(ws.begin(), ws.end()), &ps.d_aux2);
+        }
+    } else if (e == hipSuccess) {
         try {
             e = p.out_dtype == MIFFT_F64 ? upload_tables_t<double>(n, hop, F, window, gain, &ps.d_aux2, &ps.d_aux3)
                                          : upload_tables_t<float>(n, hop, F, window, gain, &ps.d_aux2, &ps.d_aux3);

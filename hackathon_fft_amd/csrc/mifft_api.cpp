@@ -210,6 +210,50 @@ static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first
     return launch_jit_conv_grad(p, p.passes[0], x, gy, pregate, postgate, out, (hipStream_t)stream);
 }
 
+// The exec of an STFT adjoint plan (istft.cpp; Plan::stft_adj): `x` is the HOST address of a mifft_stft_adj_args, refused
+// without a launch as above.  x is the gradient (mode 1) or X (modes 2, 3); mult is present exactly for modes 2 and 3, edge
+// exactly with the reflect bit.  first / count offset all four tensors by whole entries.
+static int exec_stft_adj(const Plan& p, const void* args, void* out, int64_t first, int64_t count, void* stream) {
+    static const char* kHow =
+        "the exec of an STFT adjoint plan takes the host address of a mifft_stft_adj_args (magic, x, mult, edge) in the place "
+        "of x: include/mifft.h";
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, args) != hipSuccess)
+        (void)hipGetLastError();  // (memory the runtime has never seen: host memory)
+    else if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray)
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("x is a device address: ") + kHow);
+    const mifft_stft_adj_args* a = (const mifft_stft_adj_args*)args;
+    if (a->magic != MIFFT_STFT_ADJ_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + kHow);
+    if (!a->x) return set_error(MIFFT_ERR_NULL, "mifft_stft_adj_args.x is NULL");
+    const bool want_m = p.stft_adj >= 2, want_e = p.stft_adj_edges();
+    if (want_m && !a->mult)
+        return set_error(MIFFT_ERR_NULL, "the STFT adjoint plan has a factor (mode 2 or 3): mifft_stft_adj_args.mult is NULL");
+    if (want_e && !a->edge)
+        return set_error(MIFFT_ERR_NULL, "the STFT adjoint plan stores the reflected edges (MIFFT_FLAG_STFT_CENTER_REFLECT): "
+                                         "mifft_stft_adj_args.edge is NULL");
+    if (!want_m && a->mult)
+        return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_stft_adj_args.mult is set, but the STFT adjoint plan has no factor (mode 1)");
+    if (!want_e && a->edge)
+        return set_error(MIFFT_ERR_UNSUPPORTED, "mifft_stft_adj_args.edge is set, but the STFT adjoint plan stores no edges (no "
+                                                "MIFFT_FLAG_STFT_CENTER_REFLECT)");
+    const size_t esz = dtype_size(p.out_dtype);
+    const size_t x_row = p.in_row_bytes(), m_row = (size_t)p.prod_half * esz, o_row = p.out_row_bytes(), e_row = (size_t)p.dims[2] * esz;
+    const char* xb = (const char*)a->x + (size_t)first * x_row;
+    const char* mb = a->mult ? (const char*)a->mult + (size_t)first * m_row : nullptr;
+    char* ob = (char*)out + (size_t)first * o_row;
+    char* eb = a->edge ? (char*)a->edge + (size_t)first * e_row : nullptr;
+    const size_t xn = (size_t)count * x_row, mn = (size_t)count * m_row, on = (size_t)count * o_row, en = (size_t)count * e_row;
+    auto overlap = [](const char* r, size_t rn, const char* w, size_t wn) { return r && w && r < w + wn && w < r + rn; };
+    if (overlap(xb, xn, ob, on)) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
+    if (overlap(mb, mn, ob, on)) return set_error(MIFFT_ERR_ALIAS, "mult and out must not overlap");
+    if (overlap(xb, xn, eb, en)) return set_error(MIFFT_ERR_ALIAS, "x and edge must not overlap");
+    if (overlap(mb, mn, eb, en)) return set_error(MIFFT_ERR_ALIAS, "mult and edge must not overlap");
+    if (overlap(eb, en, ob, on)) return set_error(MIFFT_ERR_ALIAS, "edge and out must not overlap");
+    DeviceGuard guard(p.device);
+    MIFFT_HIP_TRY(guard.err);
+    return launch_stft_adj(p, p.passes[0], xb, mb, ob, eb, count, (hipStream_t)stream);
+}
+
 static int device_count_quiet() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {
@@ -286,7 +330,9 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     // (a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points)
     const bool mdct = fwd && mdct_detect(ndim, dims, bases_flat, bases_len);
     // (the same tag on a MIFFT_FLAG_ISTFT plan: the inverse, frames of M = n / 2 coefficients overlap-added every M samples)
-    const bool imdct = !fwd && imdct_detect(ndim, bases_flat, bases_len);
+    // (the window of a MIFFT_FLAG_ISTFT plan tagged with MIFFT_STFT_ADJ_TAG: the adjoint of the STFT, the ISTFT pass without envelope)
+    const bool adj = !fwd && stft_adj_detect(ndim, dims, bases_flat, bases_len);
+    const bool imdct = !fwd && !adj && imdct_detect(ndim, bases_flat, bases_len);
     // (a payload that STARTS with MIFFT_CONV_TAG: the fused FFT convolution of rows of dims[0] samples at length dims[1])
     const bool conv = fwd && conv_detect(ndim, bases_flat, bases_len);
     // (or with MIFFT_CONV_GRAD_TAG: the filter gradient of such a convolution)
@@ -295,6 +341,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
              : conv  ? conv_check(p, bases_flat, bases_len, user, why)
              : mdct  ? mdct_check(p, bases_flat, bases_len, window, user, why)
              : imdct ? imdct_check(p, bases_flat, bases_len, window, gain, user, why)
+             : adj   ? stft_adj_check(p, bases_flat, bases_len, window, gain, user, why)
              : fwd   ? stft_check(p, why)
                      : istft_check(p, bases_flat, bases_len, window, gain, user, why);
     if (rc) return fail(rc, why);
@@ -550,6 +597,7 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     }
     if (count == 0) return MIFFT_OK;
     if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
+    if (p.stft_adj) return exec_stft_adj(p, x, out, first, count, stream);  // (`x`: the HOST address of the exec's mifft_stft_adj_args)
     const void *pregate = nullptr, *postgate = nullptr;
     if (p.conv.gated()) {  // (a gated convolution: `x` is the HOST address of the exec's mifft_gated_args)
         const int rc = unpack_gated_args(p, x, pregate, postgate);  // (x: now the signal itself)
@@ -641,11 +689,15 @@ int mifft_plan_num_launches(const mifft_plan* plan) {
 }
 
 size_t mifft_plan_in_bytes(const mifft_plan* plan) {
+    if (plan && plan->p.stft_adj >= 2)  // (X and the real factor beside it)
+        return (size_t)plan->p.batch * (plan->p.in_row_bytes() + (size_t)plan->p.prod_half * dtype_size(plan->p.out_dtype));
     return plan ? (size_t)plan->p.batch * plan->p.in_row_bytes() : 0;
 }
 
 size_t mifft_plan_out_bytes(const mifft_plan* plan) {
     if (plan && plan->p.conv.gradient()) return conv_grad_out_bytes(plan->p);
+    if (plan && plan->p.stft_adj_edges())  // (the signal's gradient and the two edge strips of n / 2 samples)
+        return (size_t)plan->p.batch * (plan->p.out_row_bytes() + (size_t)plan->p.dims[2] * dtype_size(plan->p.out_dtype));
     return plan ? (size_t)plan->p.batch * plan->p.out_row_bytes() : 0;
 }
 

@@ -231,6 +231,13 @@ struct Plan {
     // a MIFFT_FLAG_ISTFT plan whose window payload is tagged with MIFFT_MDCT_TAG: the inverse MDCT of imdct = M = dims[2] / 2
     // coefficients per frame, dims = {T, F, 2 M}; x is (batch, F, M, 1) real, out (batch, T, 1).  0: not one.  Set by imdct_check.
     int64_t imdct = 0;
+    // a MIFFT_FLAG_ISTFT plan whose window payload is tagged with MIFFT_STFT_ADJ_TAG: the adjoint of the STFT of signals of
+    // dims[0] samples, dims = {T, F, n} -- 1: x is the incoming gradient (batch, F, n / 2 + 1, 2); 2 / 3: x is X itself and the
+    // exec brings the real gradient of |X|^2 / |X| as `mult`, (batch, F, n / 2 + 1).  out is (batch, T, 1); with the reflect
+    // bit the exec brings `edge`, (batch, 2, n / 2), too.  The centre bits mean what they mean on the forward.  0: not one.
+    // Set by stft_adj_check.
+    int stft_adj = 0;
+    bool stft_adj_edges() const { return stft_adj && (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) != 0; }
     // a MIFFT_FLAG_STFT plan whose payload starts with MIFFT_CONV_TAG or MIFFT_CONV_GRAD_TAG: the decoded request (conv.cpp)
     ConvRequest conv;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
@@ -454,6 +461,16 @@ int istft_check(const Plan& plan, const uint32_t* bases_flat, const int32_t* bas
                 double& gain, std::vector<uint64_t>& radices, std::string& why);
 int build_istft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                 const std::vector<double>& window, double gain, std::string& why);
+// STFT adjoint plans (the MIFFT_FLAG_ISTFT payload tagged with MIFFT_STFT_ADJ_TAG; istft.cpp).  stft_adj_detect: is
+// bases_len[0] the tagged length 2 n + 6 with the tag behind the window?  (Pure.)  stft_adj_check: istft_check's refusals
+// less the ones an adjoint has no use for (the covered length, the overlap-add condition), each reason naming the adjoint;
+// sets plan.stft_adj.  build_istft builds the pass (no envelope table).  launch_stft_adj is its launch, which takes the
+// exec's factor and edge tensors (null where the plan has none), offset to the exec's first entry as `in` and `out` are.
+bool stft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len);
+int stft_adj_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
+                   std::vector<uint64_t>& radices, std::string& why);
+int launch_stft_adj(const Plan& plan, const DimPass& pass, const void* in, const void* mult, void* out, void* edge,
+                    int64_t count, hipStream_t stream);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

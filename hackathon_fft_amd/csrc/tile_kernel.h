@@ -288,7 +288,9 @@ struct TileParams {
     // P[spec_lo[m] + j], j < spec_len[m] (spec_lo[m] + spec_len[m] <= N + 1; weights of type T).  Without one the four
     // pointers are null and spec_bands is 0.
     // CONV: the filter spectra, (D[, parts], N + 1) complex values of type T; WGRAD (which has no filter): the pregate
-    union { const void* spec_wt; const void* conv_h; const void* wgrad_pregate; };
+    // ISTFT tiles with ADJ >= 2 (the adjoint of a spectrogram): adj_mult, the real per-bin factor, rows of N + 1 values of type T
+    // beside the rows of `in`
+    union { const void* spec_wt; const void* conv_h; const void* wgrad_pregate; const void* adj_mult; };
     const int* spec_lo;
     const int* spec_len;
     const int* spec_off;
@@ -299,7 +301,10 @@ struct TileParams {
     // POST configurations (with FB): spec_post is a dense, row-major (spec_bands, spec_q) matrix of type T applied to the
     // bands of every frame, spec_bands <= N - 1; the store writes spec_q reals per frame.
     double spec_add, spec_amin, spec_a, spec_c;
-    const void* spec_post;
+    // ISTFT tiles with ADJ (the adjoint of the STFT; stft_center 1 = reflect, 2 = zeros): adj_edge, (entries, 2, N) values of
+    // type T, the padded samples before (side 0) and behind (side 1) the entry's stft_len stored ones, written when
+    // stft_center is 1; null otherwise.  An exec's argument, as `out` is.
+    union { const void* spec_post; void* adj_edge; };
     union { int spec_q; int conv_mode; };  // CONV: bit 0 = correlate (multiply by the conjugate)
     // CONV configurations (an R2C tile that is neither STFT nor SPEC) read the conv_* names declared above on the bytes of
     // fields no such tile uses otherwise, so that the layout of the kernel argument stays what every other kernel was built
@@ -328,6 +333,8 @@ static_assert(sizeof(TileParams) == 352 && __builtin_offsetof(TileParams, conv_Q
                   __builtin_offsetof(TileParams, conv_o) == __builtin_offsetof(TileParams, stft_hop) &&
                   __builtin_offsetof(TileParams, conv_h) == __builtin_offsetof(TileParams, spec_wt) &&
                   __builtin_offsetof(TileParams, wgrad_pregate) == __builtin_offsetof(TileParams, conv_h) &&
+                  __builtin_offsetof(TileParams, adj_mult) == __builtin_offsetof(TileParams, spec_wt) &&
+                  __builtin_offsetof(TileParams, adj_edge) == __builtin_offsetof(TileParams, spec_post) &&
                   __builtin_offsetof(TileParams, wgrad_partials) == __builtin_offsetof(TileParams, spec_bands) &&
                   __builtin_offsetof(TileParams, conv_mode) == __builtin_offsetof(TileParams, spec_q),
               "TileParams: a CONV name left the field it shares");
@@ -426,7 +433,8 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           bool FS1_ = false, int RADERM_ = 0, bool HERM_ = false, bool HS_ = false, bool R2C_ = false, bool C2R_ = false,
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
-          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false, bool PART_ = false>
+          bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false, bool PART_ = false,
+          int ADJ_ = 0>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -711,6 +719,19 @@ struct TileCfg {
     // spectra are recomputed, never stored, so the work grows with P.  part_walk below; the main tile loop is not run.
     static constexpr bool PART = PART_;
     static_assert(!PART_ || (CONV_ && OLS_ && !WGRAD_ && TILE_ <= 64), "PART: the partitioned twin of an OLS tile");
+    // ADJ (with ISTFT): the adjoint of the framed, windowed, one-sided transform instead of its inverse -- the gradient of stft
+    // with respect to the signal.  1: `in` is the incoming gradient g = dL/dRe X + i dL/dIm X.  The C2R load doubles the real
+    // parts of bins 0 and N (their imaginary parts drop out as they always have), so the passes leave
+    // Re sum_{k <= N} g[k] e^(+2 pi i j k / 2N) * 2; the synthesis table carries the 1 / 2 (stft_win = gain * w[j] / 2 with the
+    // sign of the conjugation).  The store is the overlap-add without the envelope: istft_env is never read, the sample at
+    // padded position u in [cen, cen + stft_len) goes to out[b, u - cen], and with stft_center == 1 (reflect) the samples below
+    // cen and the N from cen + stft_len on go to adj_edge[b, 0, u] and adj_edge[b, 1, u - cen - stft_len] for the caller to
+    // fold back.  Plain stores, each element once, suppressed in warm-up tiles as the stores to `out` are.
+    // 2 / 3: the adjoint of the power / magnitude spectrogram.  `in` is X itself and adj_mult the incoming real gradient m; the
+    // load multiplies X[k] by m[k] (2: the factor 2 of d|X|^2 is the table's, stft_win = gain * w[j]) or by m[k] / |X[k]|, zero
+    // where |X[k]| is (3), so that the product never exists in memory.
+    static constexpr int ADJ = ADJ_;
+    static_assert(ADJ_ >= 0 && ADJ_ <= 3 && (ADJ_ == 0 || ISTFT_), "ADJ: the adjoint twin of an ISTFT tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -2271,6 +2292,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             for (int i0 = 0; i0 < IT; i0 += G) {
                 int cs[G], ks[G];
                 V xk[G], xm[G];
+                T mk[C::ADJ >= 2 ? G : 1], mm[C::ADJ >= 2 ? G : 1];  // (ADJ >= 2: the real factors of the two bins)
 #pragma unroll
                 for (int j = 0; j < G; ++j) {
                     cs[j] = (IT % G == 0 || i0 + j < IT) ? c : nv;  // (past the last pair: nothing to do)
@@ -2290,6 +2312,11 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                             const V* row = gin + (row0 + c) * p.half_pitch;
                             xk[j] = gload<(C::NT & 1) != 0>(row + k);
                             xm[j] = gload<(C::NT & 1) != 0>(row + (C::N - k));  // (k = 0: X[N], the last bin of the row)
+                            if constexpr (C::ADJ >= 2) {
+                                const T* mrow = (const T*)p.adj_mult + (row0 + c) * p.half_pitch;
+                                mk[j] = gload_real<(C::NT & 1) != 0>(mrow + k);
+                                mm[j] = gload_real<(C::NT & 1) != 0>(mrow + (C::N - k));
+                            }
                         }
                     }
                     c += DC;
@@ -2312,7 +2339,28 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                             a = {wa.x * ar + wa.y * ai, wa.x * ai - wa.y * ar};
                             b = {wb.x * br + wb.y * bi, wb.x * bi - wb.y * br};
                         }
+                        if constexpr (C::ADJ >= 2) {  // g[k] = m[k] X[k] (2; the factor 2 is the table's) or m[k] X[k] / |X[k]| (3)
+                            T sa = mk[j], sb = mm[j];
+                            if constexpr (C::ADJ == 3) {
+                                const T ra = sqrt_t(fma_t(a.x, a.x, a.y * a.y)), rb = sqrt_t(fma_t(b.x, b.x, b.y * b.y));
+                                sa = ra == (T)0 ? (T)0 : sa / ra;
+                                sb = rb == (T)0 ? (T)0 : sb / rb;
+                            }
+                            a = {a.x * sa, a.y * sa};
+                            b = {b.x * sb, b.y * sb};
+                            // (the products stay products: rounded once, as if they had been read from memory, whatever the
+                            //  contraction mode -- mode 2 equals mode 1 on the tensor 2 m X bit for bit; nothing is emitted)
+#if defined(__HIP_DEVICE_COMPILE__)
+                            asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y));
+#endif
+                        }
                         if (kk == 0) a.y = b.y = (T)0;
+                        if constexpr (C::ADJ != 0) {  // bins 0 and N enter the real sum once, every other bin with its mirror image
+                            if (kk == 0) {
+                                a.x += a.x;
+                                b.x += b.x;
+                            }
+                        }
                         const V wk = w[kk];
                         const T ex = a.x + b.x, ey = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
                         const T ox = dx * wk.x + dy * wk.y, oy = dy * wk.x - dx * wk.y;  // O = D * conj(W^k)
@@ -2921,7 +2969,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
             const int span = (nv - 1) * hop + NN;                        // samples the tile's frames touch, from f0 hop on
             const int done = last ? span : nv * hop;                     // finished here; the rest goes to the carry
             const int ncarry = (f0 == 0 || t == t_first) ? 0 : NN - hop;  // partial sums waiting (a run starts from zero)
-            const int u0 = f0 * hop;                                      // (< 2^26, istft_check)
+            const int u0 = f0 * hop;                                      // (< 2^26, istft_check; ADJ: < T + n < 2^31, stft_adj_check)
             const T* ldr = (const T*)lds;
             T* carry = (T*)(lds + C::ISTFT_OFF);
             const T* ws = (const T*)p.stft_win;
@@ -2945,7 +2993,19 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                         carry[i - done] = acc;
                     } else {
                         const int u = u0 + i;
-                        if (!warm && u >= cen && u < cen + len) outb[u - cen] = acc * env[u];
+                        if constexpr (C::ADJ != 0) {  // no envelope; the reflected edges beside the entry's own samples
+                            if (!warm) {
+                                if (u >= cen && u < cen + len) {
+                                    outb[u - cen] = acc;
+                                } else if (p.stft_center == 1) {
+                                    T* edge = (T*)p.adj_edge + obase * NN;  // (2, N) per entry
+                                    if (u < cen) edge[u] = acc;
+                                    else if (u - cen - len < C::N) edge[C::N + (u - cen - len)] = acc;
+                                }
+                            }
+                        } else {
+                            if (!warm && u >= cen && u < cen + len) outb[u - cen] = acc * env[u];
+                        }
                     }
                 }
             }

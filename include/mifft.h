@@ -476,6 +476,56 @@ typedef enum {
  * MIFFT_ERR_BAD_DTYPE: in_dtype != out_dtype.  MIFFT_ERR_BAD_BASES: a tagged bases_len[0] other than 2 (2 M) + 4, a non-zero
  * bases_len[1], a window value or g that is not finite, g = 0 (or radices that do not multiply to M / 2).
  * MIFFT_ERR_TOO_LARGE: F > 2^26 or T >= 2^31. */
+/* THE ADJOINT OF THE STFT (no reference counterpart): the gradient of a MIFFT_FLAG_STFT plan's result with respect to its
+ * signal, as a MIFFT_FLAG_ISTFT plan whose window payload carries the tag MIFFT_STFT_ADJ_TAG.
+ *   flags = MIFFT_FLAG_ISTFT | MIFFT_FLAG_STFT_HOP(hop) [| one centre bit, the FORWARD plan's], ndim = 3, dims = {T, F, n} with T
+ *   the SIGNAL's length, inverse = 1, in_components = 2, in_dtype == out_dtype in {F32, F64};
+ *       x (batch, F, n / 2 + 1, 2)  ->  out (batch, T, 1) [and edge (batch, 2, n / 2)].
+ * With c = n / 2 for a centred forward plan (0 otherwise), L = n + hop (F - 1) <= T + 2 c, and g the incoming gradient in the
+ * convention dL/dRe X + i dL/dIm X:
+ *       p_f[j] = Re sum_{k = 0}^{n / 2} g[b, f, k] exp(+2 pi i j k / n),      j < n,
+ *       gxp[b, u] = sum over the frames f that cover u, ascending, of gain w[u - f hop] p_f[u - f hop],   u < L,
+ *       out[b, t] = gxp[b, c + t]   for c + t < L;   samples t >= L - c are covered by no frame and NOT written (their
+ *       gradient is zero: the caller fills them).
+ * MIFFT_FLAG_STFT_CENTER_REFLECT: the padded samples outside the signal are stored too, edge[b, 0, u] = gxp[b, u] for u < c and
+ * edge[b, 1, e] = gxp[b, c + T + e] for e < c with c + T + e < L (the rest of side 1 is not written), and the caller folds
+ * them back: out[t] += edge[0, c - t] for 1 <= t <= c, out[T - 2 - e] += edge[1, e].  MIFFT_FLAG_STFT_CENTER_ZEROS: they are
+ * dropped.  Neither bit: c = 0.
+ *   - bases_len[0] is exactly 2 n + 6 words: w[0 .. n-1] | TAG | gain | mode, 0 -- binary64 values, low word first; TAG is the
+ *     NaN MIFFT_STFT_ADJ_TAG_HI : MIFFT_STFT_ADJ_TAG_LO; gain, finite and not zero, is a factor on w; mode is one 32-bit word,
+ *     the last one reserved, 0.  Host data, taken by value.  Every other MIFFT_FLAG_ISTFT payload length (0, 2 n, 2 n + 2,
+ *     the IMDCT's 2 n + 4) means what it meant and keeps its refusals;
+ *   - mode 1: x is g.  mode 2: x is X, the forward plan's result, and the exec brings mult = dL/d|X|^2, real,
+ *     (batch, F, n / 2 + 1): g = 2 mult X.  mode 3: mult = dL/d|X|: g = mult X / |X|, zero where |X| is.  The product is
+ *     formed as the bins are loaded and never written;
+ *   - bases_len[1] is 0;  bases_len[2] is 0 (the default estimate) or the radices of n.
+ * The exec takes the HOST address of a mifft_stft_adj_args (below) in the place of x:
+ *     mifft_stft_adj_args a = { MIFFT_STFT_ADJ_ARGS_MAGIC, x, mult, edge };   mifft_exec_batch(plan, &a, out, first, count, stream);
+ * mult is present exactly for modes 2 and 3, edge exactly with MIFFT_FLAG_STFT_CENTER_REFLECT.  Refused with nothing launched:
+ * a device address or a block without the magic word, MIFFT_ERR_UNSUPPORTED; x, or a pointer the plan needs, NULL:
+ * MIFFT_ERR_NULL; a pointer the plan has no use for: MIFFT_ERR_UNSUPPORTED; x or mult overlapping out or edge, or edge
+ * overlapping out, by the sizes of the exec's entries: MIFFT_ERR_ALIAS.  first / count offset all four tensors by whole entries.
+ * ONE launch, no scratch, no memset, no atomics: the inverse STFT's tile (kernel rows<n>[_f64]_c2r_<radices>_istft_adj<mode>_jit,
+ * compiled at run time only) with bins 0 and n / 2 doubled in the load, the synthesis table gain w / 2 (mode 2: gain w, so its
+ * result equals mode 1's on the product 2 mult X bit for bit) and no envelope.  Same runs, warm-up tiles and carry, every
+ * sum in ascending frame order: an entry's result is bit-identical for any batch, first / count and grid; every element named
+ * above is written exactly once with a plain store and nothing else is.  mifft_plan_num_launches() is 1,
+ * mifft_plan_scratch_bytes() 0; mifft_plan_in_bytes() counts x and mult, mifft_plan_out_bytes() out and edge.
+ * Refused before any device work, each reason naming the adjoint.  Everything an inverse STFT plan refuses except its covered
+ * length (T > L - c), its limit L <= 2^26 and its overlap-add condition -- among them inverse = 0, both centre bits, hop > n,
+ * and n beyond the F64 carry limit (10240): MIFFT_ERR_UNSUPPORTED.  MIFFT_ERR_BAD_DIM: L > T + 2 c, or the reflect bit with
+ * n / 2 > T - 1.  MIFFT_ERR_BAD_BASES: a mode other than 1, 2, 3, a non-zero reserved word, a gain that is zero or not finite,
+ * a window value that is not finite.  MIFFT_ERR_TOO_LARGE: T + n >= 2^31. */
+#define MIFFT_STFT_ADJ_TAG_LO 0x4A444101u
+#define MIFFT_STFT_ADJ_TAG_HI 0x7FF84D41u
+/* the argument block of an STFT adjoint exec (above); the magic word is "MIFFTSA1" */
+#define MIFFT_STFT_ADJ_ARGS_MAGIC 0x314153544646494Dull
+typedef struct mifft_stft_adj_args {
+    uint64_t magic;   /* MIFFT_STFT_ADJ_ARGS_MAGIC */
+    const void* x;    /* (batch, F, n / 2 + 1, 2): the gradient (mode 1) or X (modes 2, 3), on the plan's device */
+    const void* mult; /* (batch, F, n / 2 + 1) reals of the plan's type, or NULL in mode 1 */
+    void* edge;       /* (batch, 2, n / 2) reals of the plan's type, or NULL without MIFFT_FLAG_STFT_CENTER_REFLECT */
+} mifft_stft_adj_args;
 /* Fused FFT convolution of real rows (numpy: irfft(rfft(x, n) * G, n)[..., o : o + Lo]; no reference counterpart): a
  * MIFFT_FLAG_STFT plan -- that bit ALONE, no hop, no centre bit -- whose payload starts with the tag MIFFT_CONV_TAG.
  *   flags = MIFFT_FLAG_STFT, ndim = 2, dims = {L, n}, inverse = 0, in_components = 1, in_dtype == out_dtype in {F32, F64};
