@@ -423,21 +423,28 @@ def _istft_center_flags(center) -> int:
     return _stft_center_flags(center)
 
 
-def _check_istft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> tuple:
-    """Layouts of an inverse STFT plan (MIFFT_FLAG_ISTFT): x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real with
-    2 <= T <= n + hop (F - 1) - (centred: n // 2); returns the dims (T, F, n), n = 2 (in_shape[2] - 1)."""
+def _check_frames_to_signal(what: str, in_shape: tuple, out_shape: tuple, hop: int) -> tuple:
+    """what the layouts of an inverse STFT plan and of an STFT adjoint plan (``what``) share: x (batch, F, n // 2 + 1, 2) -> out
+    (batch, T, 1) real; returns (T, F, n), n = 2 (in_shape[2] - 1)"""
     if len(in_shape) != 4 or len(out_shape) != 3:
-        raise MifftError(-1, f"inverse STFT layouts are (batch, F, n // 2 + 1, 2) -> (batch, T, 1), got {in_shape} -> {out_shape}")
+        raise MifftError(-1, f"{what} layouts are (batch, F, n // 2 + 1, 2) -> (batch, T, 1), got {in_shape} -> {out_shape}")
     if in_shape[-1] != 2:
-        raise MifftError(-3, f"an inverse STFT reads complex bins (2 components), got {in_shape[-1]}")
+        raise MifftError(-3, f"an {what} reads complex bins (2 components), got {in_shape[-1]}")
     if out_shape[-1] != 1:
-        raise MifftError(-3, f"an inverse STFT writes real signals (1 component), got {out_shape[-1]}")
+        raise MifftError(-3, f"an {what} writes real signals (1 component), got {out_shape[-1]}")
     if in_shape[0] != out_shape[0]:
         raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
-    F, n, T = in_shape[1], 2 * (in_shape[2] - 1), out_shape[1]
+    n = 2 * (in_shape[2] - 1)
     if n < 8:
         raise MifftError(ERR_UNSUPPORTED, f"STFT with frames of fewer than 8 points ({n}) is not supported")
     FLAG_STFT_HOP(hop)
+    return out_shape[1], in_shape[1], n
+
+
+def _check_istft_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> tuple:
+    """Layouts of an inverse STFT plan (MIFFT_FLAG_ISTFT): x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real with
+    2 <= T <= n + hop (F - 1) - (centred: n // 2); returns the dims (T, F, n), n = 2 (in_shape[2] - 1)."""
+    T, F, n = _check_frames_to_signal("inverse STFT", in_shape, out_shape, hop)
     if hop > n:
         raise MifftError(ERR_UNSUPPORTED, f"hop_length {hop} > n_fft {n}: gaps between the frames")
     centred = _istft_center_flags(center) != 0
@@ -454,18 +461,7 @@ def _check_stft_adjoint_layout(in_shape: tuple, out_shape: tuple, hop: int, cent
     """Layouts of an STFT adjoint plan (MIFFT_STFT_ADJ_TAG on MIFFT_FLAG_ISTFT): x (batch, F, n // 2 + 1, 2) -> out
     (batch, T, 1) real, T the signal's length and F = stft_frames(T, n, hop, center) the forward's frames; returns the dims
     (T, F, n).  ``center`` is the forward plan's: None, "reflect" or "constant"."""
-    if len(in_shape) != 4 or len(out_shape) != 3:
-        raise MifftError(-1, f"STFT adjoint layouts are (batch, F, n // 2 + 1, 2) -> (batch, T, 1), got {in_shape} -> {out_shape}")
-    if in_shape[-1] != 2:
-        raise MifftError(-3, f"an STFT adjoint reads complex bins (2 components), got {in_shape[-1]}")
-    if out_shape[-1] != 1:
-        raise MifftError(-3, f"an STFT adjoint writes real signals (1 component), got {out_shape[-1]}")
-    if in_shape[0] != out_shape[0]:
-        raise MifftError(-2, f"batch {in_shape[0]} of x against {out_shape[0]} of out")
-    F, n, T = in_shape[1], 2 * (in_shape[2] - 1), out_shape[1]
-    if n < 8:
-        raise MifftError(ERR_UNSUPPORTED, f"STFT with frames of fewer than 8 points ({n}) is not supported")
-    FLAG_STFT_HOP(hop)
+    T, F, n = _check_frames_to_signal("STFT adjoint", in_shape, out_shape, hop)
     if hop > n:
         raise MifftError(ERR_UNSUPPORTED, f"the STFT adjoint with hop_length {hop} > n_fft {n} is not supported: the overlap-add "
                                           f"kernel it runs on has no gaps between its frames")
@@ -499,6 +495,97 @@ def words_window(words) -> list:
     return (ctypes.c_double * (len(words) // 2)).from_buffer_copy(raw)[:]
 
 
+class FrameRequest(NamedTuple):
+    """What a framed plan that is no convolution is asked for (``ConvRequest`` is the convolutions'): frames of ``n`` samples
+    every ``hop``, a ``window`` of n values taken by value (float64 on the host; None: rectangular, the sine window
+    mdct_window(hop) for the MDCT pair).  None of the kinds has a reference counterpart.  ``kind``:
+    "stft" (``Plan(stft_hop=)``, plan_stft; MIFFT_FLAG_STFT in include/mifft.h, _check_stft_layout): x (batch, T, 1) real ->
+        out (batch, F, n // 2 + 1, 2); ``center`` None / "reflect" / "constant".  Payload: w, or nothing without a window.
+    "spec" (``stft_power=`` beside it, plan_spectrogram; MIFFT_FLAG_STFT_POWER, _check_spec_layout): the same plan stores
+        abs(X) ** ``power`` (1 or 2), real, out (batch, F, n // 2 + 1, 1) -- or, with ``fb`` of shape (n // 2 + 1, M), the M bands
+        fb.T @ abs(X) ** power per frame, out (batch, F, M, 1).  Payload: w | power | fb, the window written out.  With ``log``
+        (add, amin, a, c) every value v becomes a * log2(max(v + add, amin)) + c first, and with ``post``, an (M, Q) matrix beside
+        ``fb``, the plan stores post.T @ (the bands, after the log stage), out (batch, F, Q, 1); either one makes the payload
+        w | MIFFT_STFT_EXT_TAG | power, M, Q, log?, add, amin, a, c | fb | post.
+    "istft" (``istft_hop=``, plan_istft; MIFFT_FLAG_ISTFT, _check_istft_layout): x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1)
+        real; ``center`` None / False or True / "reflect" / "constant" (centred: n // 2 samples trimmed at both ends); ``gain`` a
+        factor on the synthesis window that stays out of the envelope.  Payload: w | gain, the gain only when it is not 1,
+        nothing without either.
+    "adjoint" (``stft_adjoint=`` beside ``istft_hop``, plan_stft_adjoint; MIFFT_STFT_ADJ_TAG, _check_stft_adjoint_layout): the
+        adjoint of the "stft" plan of these values, ``adjoint`` its mode 1, 2 or 3.  Payload: w | TAG | gain | mode, 0.
+    "mdct" (``mdct=`` M, plan_mdct; MIFFT_MDCT_TAG, _check_mdct_layout): x (batch, T, 1) -> out (batch, F, M, 1), frames of
+        n = 2 M samples every hop = M; ``gain`` the factor on the cosine sum.  Payload: w | TAG | gain.
+    "imdct" (``imdct=`` M, plan_imdct; MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan, _check_imdct_layout): x (batch, F, M, 1) ->
+        out (batch, T, 1) with 2 <= T <= (F - 1) M; ``gain`` the factor on the synthesis window.  Payload: w | TAG | gain.
+    ``bases`` of a forward kind ("stft", "spec", "mdct") has two lists, of an inverse kind three: empty ones and, last, the
+    radices of n (MDCT pair: of M // 2), or an empty one for the default.  ``inverse=True`` is implied by the inverse kinds."""
+    kind: str
+    n: int
+    hop: int
+    center: object = None
+    window: object = None
+    gain: float = 1.0
+    power: object = None
+    fb: object = None
+    log: object = None
+    post: object = None
+    adjoint: int = 0
+
+
+def _frame_payload(r) -> tuple:
+    """(flag bits, payload words, leading lists of ``bases`` that carry no radices) of a ``FrameRequest`` or ``ConvRequest``:
+    the one place that knows the word layouts (include/mifft.h).  Pure: no device, no library call; status -5 for a window of
+    another length than the frames."""
+    if isinstance(r, ConvRequest):
+        return FLAG_STFT, _conv_payload(r), 1
+    if r.kind not in ("stft", "spec", "istft", "adjoint", "mdct", "imdct"):
+        raise MifftError(ERR_UNSUPPORTED, f"unknown kind of framed plan {r.kind!r}")
+    bits = FLAG_STFT_HOP(r.hop)
+    if r.window is not None:
+        w = _f64_words(_window_f64(r.window, r.n))
+    elif r.kind == "stft" or (r.kind == "istft" and float(r.gain) == 1.0):
+        w = []
+    else:  # (every other layout has words behind the window: it is written out)
+        w = _f64_words(mdct_window(r.hop) if r.kind in ("mdct", "imdct") else torch.ones(r.n, dtype=torch.float64))
+    if r.kind in ("mdct", "imdct"):
+        scale = _f64_words(torch.tensor([float(r.gain)], dtype=torch.float64))
+        side = (FLAG_STFT, 1) if r.kind == "mdct" else (FLAG_ISTFT, 2)
+        return bits | side[0] | FLAG_STFT_CENTER_ZEROS, w + [MDCT_TAG_LO, MDCT_TAG_HI] + scale, side[1]
+    if r.kind == "istft":  # (a list of Python floats goes through torch's default dtype: this gain has always travelled as float32's)
+        return bits | FLAG_ISTFT | _istft_center_flags(r.center), w + (_f64_words([float(r.gain)]) if float(r.gain) != 1.0 else []), 2
+    bits |= _stft_center_flags(r.center)
+    if r.kind == "adjoint":
+        return bits | FLAG_ISTFT, w + [STFT_ADJ_TAG_LO, STFT_ADJ_TAG_HI] + _f64_words([float(r.gain)]) + [int(r.adjoint), 0], 2
+    if r.kind == "stft":
+        return bits | FLAG_STFT, w, 1
+    if r.log is None and r.post is None:
+        w = w + _f64_words([float(r.power)])
+    else:
+        head = [float(r.power), 0.0 if r.fb is None else float(r.fb.shape[1]), 0.0 if r.post is None else float(r.post.shape[1]),
+                0.0 if r.log is None else 1.0] + list(r.log or (0.0, 0.0, 0.0, 0.0))
+        w = w + [STFT_EXT_TAG_LO, STFT_EXT_TAG_HI] + _f64_words(torch.tensor(head, dtype=torch.float64))
+    for table in (r.fb, r.post):  # (row by row)
+        if table is not None:
+            w = w + _f64_words(table)
+    return bits | FLAG_STFT | FLAG_STFT_POWER, w, 1
+
+
+def _pack_bases(words: list, bases, lead: int) -> tuple:
+    """``bases`` as the (flat words, list lengths) of mifft_plan_create_slab, (None, None) for the defaults.  A framed plan
+    (``lead`` > 0) sends its payload as the first list, empty lists up to ``lead`` and the radices of the last dim."""
+    if lead and (words or bases is not None):
+        if bases is not None and any(len(bs) for bs in bases[:lead]):
+            raise MifftError(-5, "dims 0 and 1 of an inverse STFT plan are not transformed: their bases lists must be empty"
+                             if lead == 2 else "dim 0 of an STFT plan is framed, not transformed: its bases list must be empty")
+        radices = [int(b) for b in bases[lead]] if bases is not None else []
+        flat, lens = words + radices, [len(words)] + [0] * (lead - 1) + [len(radices)]
+    elif bases is not None:
+        flat, lens = [int(b) for bs in bases for b in bs], [len(bs) for bs in bases]
+    else:
+        return None, None
+    return (ctypes.c_uint32 * max(len(flat), 1))(*flat), (ctypes.c_int32 * len(lens))(*lens)
+
+
 def _dct_norm_flags(norm) -> int:
     """scipy's ``norm`` of a DCT plan as flag bits: None / "backward" (the unnormalised forward) or "ortho" """
     if norm is None or norm == "backward":
@@ -521,6 +608,14 @@ def _keep_flags(rank: int, axes) -> int:
     return sum(FLAG_KEEP_DIM(p - 1) for p in range(1, rank - 1) if p not in ax)
 
 
+_FRAMED_NO_AXES = {"stft": "an STFT plan frames dim 0 and transforms dim 1: no axes",
+                   "istft": "an inverse STFT plan transforms dim 2 and overlap-adds dim 1: no axes",
+                   "mdct": "an MDCT plan frames dim 0 and transforms dim 1: no axes",
+                   "imdct": "an IMDCT plan transforms dim 2 and overlap-adds dim 1: no axes",
+                   "conv": "a convolution plan extends dim 0 and transforms dim 1: no axes"}
+_FRAMED_NO_AXES.update(spec=_FRAMED_NO_AXES["stft"], adjoint=_FRAMED_NO_AXES["istft"])
+
+
 class Plan:
     """_GPUPlan (fft/fft/_ndim_fft_gpu.mojo:153-207): owns the device twiddle tables.
 
@@ -534,36 +629,16 @@ class Plan:
     ``dctn=True`` (no reference counterpart): the N-D DCT-II (``inverse``: its inverse) over the dims of a real
     (batch, d0.., 1) tensor, ``axes`` and ``norm`` as above (MIFFT_FLAG_DCT_ND in include/mifft.h, _check_dctn_layout);
     ``bases`` factor n // 2 for a transformed last dim and n for the others.
-    ``stft_hop`` > 0 (no reference counterpart): the short-time Fourier transform of real signals, x (batch, T, 1) ->
-    out (batch, F, n // 2 + 1, 2), frames of n samples every ``stft_hop``; ``stft_center`` None / "reflect" / "constant";
-    ``stft_window`` None (rectangular) or n values, taken by value (MIFFT_FLAG_STFT in include/mifft.h, _check_stft_layout,
-    plan_stft).  ``bases`` of such a plan has two lists, an empty one and the radices of n (or an empty one: the default).
-    ``stft_power`` 1 or 2 beside ``stft_hop`` (no reference counterpart): the same plan stores abs(X) ** stft_power, real,
-    out (batch, F, n // 2 + 1, 1) -- or, with ``stft_fb`` of shape (n // 2 + 1, M), taken by value as float64, the M bands
-    fb.T @ abs(X) ** stft_power per frame, out (batch, F, M, 1), n taken from the filterbank's rows (MIFFT_FLAG_STFT_POWER in
-    include/mifft.h, _check_spec_layout, plan_spectrogram).  None: the complex STFT plan.
-    ``stft_log`` (add, amin, a, c) beside ``stft_power``: every value v the plan would store becomes
-    a * log2(max(v + add, amin)) + c first; ``stft_post`` an (M, Q) real matrix beside ``stft_fb``, taken by value as float64:
-    the plan stores post.T @ (the M bands, after the log stage if any), out (batch, F, Q, 1).  Either one travels in the tagged
-    payload (MIFFT_STFT_EXT_TAG in include/mifft.h); without them the plan builds the words it has always built.
-    ``istft_hop`` > 0 (no reference counterpart): the inverse, x (batch, F, n // 2 + 1, 2) -> out (batch, T, 1) real,
-    ``inverse=True`` implied; ``stft_center`` None / False or True / "reflect" / "constant" (centred: n // 2 samples trimmed
-    at both ends), ``stft_window`` as above, ``istft_gain`` a factor on the synthesis window that stays out of the envelope
-    (MIFFT_FLAG_ISTFT in include/mifft.h, _check_istft_layout, plan_istft).  ``bases`` has three lists: two empty ones and
-    the radices of n (or an empty one).
+    ``stft_hop`` > 0 (with ``stft_power`` the spectrogram), ``istft_hop`` > 0 (with ``stft_adjoint`` the STFT's adjoint),
+    ``mdct`` = M > 0, ``imdct`` = M > 0: the framed plans, whose keywords ``stft_center``, ``stft_window``, ``stft_fb``,
+    ``stft_log``, ``stft_post``, ``istft_gain``, ``mdct_scale`` and ``imdct_gain`` become the fields of a ``FrameRequest``: see
+    there for each kind's layouts, payload and ``bases``.  MIFFT_FLAG_STFT or MIFFT_FLAG_ISTFT with a hop in ``flags`` is the
+    same request as ``stft_hop`` / ``istft_hop``.
     ``dct_type=4`` beside ``dct=True`` (no reference counterpart): the DCT-IV instead, both directions the same kernel with
     another scale, in_dtype == out_dtype; the request travels as MIFFT_DCT_TYPE4_TAG in front of the radices of n // 2.
     ``dst=True`` beside ``dct=True`` or ``dctn=True`` (no reference counterpart): the sine transform of the same type on the
     same passes (scipy's dst / idst of ``dct_type`` 2 or 4, dstn / idstn of type 2); the request travels as MIFFT_DST_TAG or
     MIFFT_DST_TYPE4_TAG in front of the radices of the first list, and an empty list of such a plan is that dim's default.
-    ``mdct`` = M > 0 (no reference counterpart): the MDCT of real signals, x (batch, T, 1) -> out (batch, F, M, 1),
-    F = mdct_frames(T, M) frames of 2 M samples every M; ``stft_window`` None (the sine window) or 2 M values, ``mdct_scale``
-    the factor on the cosine sum (MIFFT_MDCT_TAG in include/mifft.h, _check_mdct_layout, plan_mdct).  ``bases`` has two
-    lists, an empty one and the radices of M // 2 (or an empty one).
-    ``imdct`` = M > 0 (no reference counterpart): the inverse MDCT, x (batch, F, M, 1) -> out (batch, T, 1) real with
-    2 <= T <= (F - 1) M, ``inverse=True`` implied; ``stft_window`` as for ``mdct``, ``imdct_gain`` the factor on the synthesis
-    window (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan in include/mifft.h, _check_imdct_layout, plan_imdct).  ``bases`` has
-    three lists: two empty ones and the radices of M // 2 (or an empty one).
     ``conv`` = a ``ConvRequest`` (no reference counterpart): the fused FFT convolution of real rows,
     x (batch, L, 1) -> out (batch, Lo, 1), samples o .. o + Lo - 1 of irfft(rfft(x, n) * G[row % D], n) against the D filter
     spectra at the device ``address`` (mode bit 0: their conjugates); the caller keeps that buffer alive (MIFFT_CONV_TAG in
@@ -575,7 +650,8 @@ class Plan:
     a postgate of out's shape multiplied into the store; the gates are arguments of every exec (ConvPlan.run).  Bits 8..15 of
     ``mode`` are the storage type of the rows (0, or the code of float16 / bfloat16 under float32: ``ConvPlan.io_dtype``).
     ``grad`` makes it the request of that convolution's filter gradient (``partials``; MIFFT_CONV_GRAD_TAG, ConvGradPlan),
-    whose ``out_shape`` is the incoming gradient's.  ``_conv_payload`` is the words of either."""
+    whose ``out_shape`` is the incoming gradient's.  ``_conv_payload`` is the words of either; ``_frame_payload`` encodes every
+    framed request."""
 
     io_dtype = None  # (a convolution plan with 16-bit rows in memory: ConvPlan / ConvGradPlan; None on every other plan)
 
@@ -586,115 +662,76 @@ class Plan:
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
                  imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None, stft_adjoint: int = 0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
-        mdct, imdct = int(mdct), int(imdct)
+        mdct, imdct, flags = int(mdct), int(imdct), int(flags)
         if dct_type not in (2, 4):
             raise MifftError(ERR_UNSUPPORTED, f"dct_type must be 2 or 4, got {dct_type!r}")
-        stft = not mdct and conv is None and (int(stft_hop) != 0 or bool(int(flags) & FLAG_STFT))
-        istft = int(istft_hop) != 0 or bool(int(flags) & FLAG_ISTFT)  # (the flag bit is the same request)
-        words = None
-        if imdct:  # (with any other mode as well: the library refuses the pair)
-            istft_dims = _check_imdct_layout(in_shape, out_shape, imdct)
-            if axes is not None:
-                raise MifftError(ERR_UNSUPPORTED, "an IMDCT plan transforms dim 2 and overlap-adds dim 1: no axes")
-            w = mdct_window(imdct) if stft_window is None else _window_f64(stft_window, 2 * imdct)
-            words = window_words(w) + [MDCT_TAG_LO, MDCT_TAG_HI] + window_words(torch.tensor([float(imdct_gain)], dtype=torch.float64))
-            inverse = True
-            flags = (int(flags) | FLAG_ISTFT | FLAG_STFT_HOP(imdct) | FLAG_STFT_CENTER_ZEROS |
-                     (FLAG_STFT if stft or mdct else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
-                     (FLAG_HALF_SPECTRUM if half_spectrum else 0))
-            istft, stft, mdct = True, False, 0
-        elif istft:  # (with any other mode as well: the library refuses the pair)
-            if not int(istft_hop):
-                istft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
-                if stft_center is None:
-                    stft_center = {0: None, FLAG_STFT_CENTER_ZEROS: "constant"}.get(
-                        int(flags) & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), "reflect")
-            if stft_adjoint:
-                istft_dims = _check_stft_adjoint_layout(in_shape, out_shape, istft_hop, stft_center)
+        stft = not mdct and conv is None and (int(stft_hop) != 0 or bool(flags & FLAG_STFT))  # (the flag bit is the same request)
+        istft = int(istft_hop) != 0 or bool(flags & FLAG_ISTFT)
+        # 1. the framed kinds asked for, in the order their checks run; the last one is the plan's.  Any other mode asked for
+        #    beside them travels as its bit, so that the library refuses the pair.
+        kinds = [k for k, asked in (("imdct", imdct), ("adjoint", istft and stft_adjoint), ("istft", istft)) if asked][:1]
+        kinds += ["spec" if stft_power is not None else "stft"] if stft and not kinds else []
+        kinds += (["mdct"] if mdct and not imdct else []) + (["conv"] if conv is not None else [])
+        foreign = ((FLAG_STFT if stft or mdct else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
+                   (FLAG_HALF_SPECTRUM if half_spectrum else 0))
+        kind, framed_dims, words, lead = None, None, [], 0
+        for kind in kinds:
+            # 2. the kind's layout check, which gives the dims and the frame length of its request
+            if kind == "imdct":
+                framed_dims = _check_imdct_layout(in_shape, out_shape, imdct)
+                req = FrameRequest(kind, 2 * imdct, imdct, window=stft_window, gain=imdct_gain)
+            elif kind in ("istft", "adjoint"):
+                if not int(istft_hop):
+                    istft_hop = (flags & FLAG_STFT_HOP_MASK) >> 16
+                    if stft_center is None:
+                        stft_center = {0: None, FLAG_STFT_CENTER_ZEROS: "constant"}.get(
+                            flags & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), "reflect")
+                check_layout = _check_stft_adjoint_layout if kind == "adjoint" else _check_istft_layout
+                framed_dims = check_layout(in_shape, out_shape, istft_hop, stft_center)
+                req = FrameRequest(kind, framed_dims[2], istft_hop, stft_center, stft_window, istft_gain, adjoint=stft_adjoint)
+            elif kind in ("stft", "spec"):
+                if not int(stft_hop):
+                    stft_hop = (flags & FLAG_STFT_HOP_MASK) >> 16
+                    stft_center = {0: None, FLAG_STFT_CENTER_REFLECT: "reflect", FLAG_STFT_CENTER_ZEROS: "constant"}.get(
+                        flags & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), stft_center)
+                if kind == "stft":
+                    if stft_fb is not None:
+                        raise MifftError(ERR_UNSUPPORTED, "stft_fb without stft_power: a filterbank applies to abs(X) ** power")
+                    if stft_log is not None or stft_post is not None:
+                        raise MifftError(ERR_UNSUPPORTED, "stft_log / stft_post without stft_power: they follow abs(X) ** power")
+                    framed_dims = _check_stft_layout(in_shape, out_shape, stft_hop, stft_center)
+                    req = FrameRequest(kind, framed_dims[1], stft_hop, stft_center, stft_window)
+                else:
+                    power = _spec_power(stft_power)
+                    fbm = None if stft_fb is None else _fb_f64(stft_fb)
+                    logv = None if stft_log is None else _spec_log(stft_log)
+                    postm = None if stft_post is None else _post_f64(stft_post, None if fbm is None else int(fbm.shape[1]))
+                    framed_dims = _check_spec_layout(in_shape, out_shape, stft_hop, stft_center, fbm, postm)
+                    req = FrameRequest(kind, framed_dims[1], stft_hop, stft_center, stft_window, power=power, fb=fbm, log=logv,
+                                       post=postm)
+            elif kind == "mdct":
+                framed_dims = _check_mdct_layout(in_shape, out_shape, mdct)
+                req = FrameRequest(kind, 2 * mdct, mdct, window=stft_window, gain=mdct_scale)
             else:
-                istft_dims = _check_istft_layout(in_shape, out_shape, istft_hop, stft_center)
+                if len(in_shape) != 3 or len(out_shape) != 3 or in_shape[-1] != 1 or out_shape[-1] != 1:
+                    raise MifftError(-1, f"convolution layouts are (batch, L, 1) -> (batch, Lo, 1), got {in_shape} -> {out_shape}")
+                if in_shape[0] != out_shape[0] or out_shape[1] != conv.Lo:
+                    raise MifftError(-2, f"x {in_shape} against out {out_shape} with Lo = {conv.Lo}")
+                framed_dims, req = (in_shape[1], conv.n), conv
             if axes is not None:
-                raise MifftError(ERR_UNSUPPORTED, "an inverse STFT plan transforms dim 2 and overlap-adds dim 1: no axes")
-            gain = float(istft_gain)
-            if stft_adjoint:  # (the tagged payload: w | TAG | gain | mode, 0)
-                w = torch.ones(istft_dims[2], dtype=torch.float64) if stft_window is None else _window_f64(stft_window, istft_dims[2])
-                words = window_words(w) + [STFT_ADJ_TAG_LO, STFT_ADJ_TAG_HI] + window_words([gain]) + [int(stft_adjoint), 0]
-            elif stft_window is not None or gain != 1.0:
-                w = torch.ones(istft_dims[2], dtype=torch.float64) if stft_window is None else _window_f64(stft_window, istft_dims[2])
-                words = window_words(w) + (window_words([gain]) if gain != 1.0 else [])
-            inverse = True
-            flags = (int(flags) | FLAG_ISTFT | FLAG_STFT_HOP(istft_hop) |
-                     (_stft_center_flags(stft_center) if stft_adjoint else _istft_center_flags(stft_center)) |
-                     (FLAG_STFT if stft else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
-                     (FLAG_HALF_SPECTRUM if half_spectrum else 0))
-            stft = False
-        if stft:  # (with any other mode as well: the library refuses the pair)
-            if not int(stft_hop):
-                stft_hop = (int(flags) & FLAG_STFT_HOP_MASK) >> 16
-                stft_center = {0: None, FLAG_STFT_CENTER_REFLECT: "reflect", FLAG_STFT_CENTER_ZEROS: "constant"}.get(
-                    int(flags) & (FLAG_STFT_CENTER_REFLECT | FLAG_STFT_CENTER_ZEROS), stft_center)
-            if stft_power is None:
-                if stft_fb is not None:
-                    raise MifftError(ERR_UNSUPPORTED, "stft_fb without stft_power: a filterbank applies to abs(X) ** power")
-                if stft_log is not None or stft_post is not None:
-                    raise MifftError(ERR_UNSUPPORTED, "stft_log / stft_post without stft_power: they follow abs(X) ** power")
-                stft_dims = _check_stft_layout(in_shape, out_shape, stft_hop, stft_center)
-            else:
-                power = _spec_power(stft_power)
-                fbm = None if stft_fb is None else _fb_f64(stft_fb)
-                logv = None if stft_log is None else _spec_log(stft_log)
-                postm = None if stft_post is None else _post_f64(stft_post, None if fbm is None else int(fbm.shape[1]))
-                stft_dims = _check_spec_layout(in_shape, out_shape, stft_hop, stft_center, fbm, postm)
-            if axes is not None:
-                raise MifftError(ERR_UNSUPPORTED, "an STFT plan frames dim 0 and transforms dim 1: no axes")
-            if stft_window is not None:
-                words = window_words(_window_f64(stft_window, stft_dims[1]))
-            if stft_power is not None:  # (the window written out, the power, the filterbank row by row)
-                words = words or _f64_words(torch.ones(stft_dims[1], dtype=torch.float64))
-                if logv is None and postm is None:
-                    words = words + _f64_words([float(power)])
-                else:  # (the tagged payload: TAG | power | M | Q | log | add | amin | a | c, then fb and post)
-                    head = [float(power), 0.0 if fbm is None else float(fbm.shape[1]), 0.0 if postm is None else float(postm.shape[1]),
-                            0.0 if logv is None else 1.0] + list(logv or (0.0, 0.0, 0.0, 0.0))
-                    words = words + [STFT_EXT_TAG_LO, STFT_EXT_TAG_HI] + _f64_words(torch.tensor(head, dtype=torch.float64))
-                if fbm is not None:
-                    words = words + _f64_words(fbm)
-                if postm is not None:
-                    words = words + _f64_words(postm)
-                flags = int(flags) | FLAG_STFT_POWER
-            flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(stft_hop) | _stft_center_flags(stft_center) |
-                     (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0))
-        if mdct:  # (with any other mode as well: the library refuses the pair)
-            stft_dims = _check_mdct_layout(in_shape, out_shape, mdct)
-            if axes is not None:
-                raise MifftError(ERR_UNSUPPORTED, "an MDCT plan frames dim 0 and transforms dim 1: no axes")
-            w = mdct_window(mdct) if stft_window is None else _window_f64(stft_window, 2 * mdct)
-            words = window_words(w) + [MDCT_TAG_LO, MDCT_TAG_HI] + window_words(torch.tensor([float(mdct_scale)], dtype=torch.float64))
-            flags = (int(flags) | FLAG_STFT | FLAG_STFT_HOP(mdct) | FLAG_STFT_CENTER_ZEROS | (FLAG_ISTFT if istft else 0) |
-                     (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
-                     (FLAG_STFT_POWER if stft_power is not None else 0))
-            stft, istft = True, False
-        if conv is not None:  # (with any other mode as well: the library refuses the pair)
-            if len(in_shape) != 3 or len(out_shape) != 3 or in_shape[-1] != 1 or out_shape[-1] != 1:
-                raise MifftError(-1, f"convolution layouts are (batch, L, 1) -> (batch, Lo, 1), got {in_shape} -> {out_shape}")
-            if in_shape[0] != out_shape[0] or out_shape[1] != conv.Lo:
-                raise MifftError(-2, f"x {in_shape} against out {out_shape} with Lo = {conv.Lo}")
-            if axes is not None:
-                raise MifftError(ERR_UNSUPPORTED, "a convolution plan extends dim 0 and transforms dim 1: no axes")
-            stft_dims, words = (in_shape[1], conv.n), _conv_payload(conv)
-            flags = (int(flags) | FLAG_STFT | (FLAG_ISTFT if istft else 0) | (FLAG_DCT_ND if dctn else 0) |
-                     (FLAG_DCT if dct else 0) | (FLAG_HALF_SPECTRUM if half_spectrum else 0) |
-                     (FLAG_STFT_POWER if stft_power is not None else 0))
-            stft, istft, mdct = True, False, 0
+                raise MifftError(ERR_UNSUPPORTED, _FRAMED_NO_AXES[kind])
+            # 3. the payload; a forward tagged kind passes a power on as well, for the library to refuse
+            bits, words, lead = _frame_payload(req)
+            flags |= bits | foreign | (FLAG_STFT_POWER if kind in ("mdct", "conv") and stft_power is not None else 0)
+            inverse = inverse or lead == 2
+        stft, istft = lead == 1, lead == 2  # (which side of the family the plan is on)
         half_spectrum = bool(half_spectrum) or bool(int(flags) & FLAG_HALF_SPECTRUM)  # (the flag bit is the same request)
         dct = bool(dct) or bool(int(flags) & FLAG_DCT)
         dctn = bool(dctn) or bool(int(flags) & FLAG_DCT_ND)
         if dst and not (dct or dctn):
             raise MifftError(ERR_UNSUPPORTED, "dst=True selects the sine transform of a dct=True or dctn=True plan")
-        if istft:
-            dims = istft_dims
-        elif stft:
-            dims = stft_dims
+        if kinds:
+            dims = framed_dims
         elif dctn:  # (with dct or half_spectrum as well: the library refuses the pair)
             dims = _check_dctn_layout(in_shape, out_shape)
             flags = (int(flags) | FLAG_DCT_ND | _dct_norm_flags(norm) | (FLAG_DCT if dct else 0) |
@@ -734,36 +771,18 @@ class Plan:
         self.dctn = dctn
         self.stft = stft
         self.istft = istft
-        self.spectrogram = stft and stft_power is not None and not mdct
+        self.spectrogram = kind == "spec"
         self.dct_type = int(dct_type) if dct and not dctn and not stft and not istft else 2
         self.dst = bool(dst) and (dct or dctn) and not stft and not istft
-        self.mdct = mdct
-        self.imdct = imdct
-        self.stft_adjoint = int(stft_adjoint) if istft and not imdct else 0
+        self.mdct = mdct if kind == "mdct" else 0
+        self.imdct = imdct if kind == "imdct" else 0
+        self.stft_adjoint = int(stft_adjoint) if kind == "adjoint" else 0
         self.conv = conv
         self.conv_gates = conv.gates if conv is not None else 0
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
-        if istft and (words is not None or bases is not None):  # (window [+ gain], nothing, the radices of n)
-            if bases is not None and (len(bases[0]) != 0 or len(bases[1]) != 0):
-                raise MifftError(-5, "dims 0 and 1 of an inverse STFT plan are not transformed: their bases lists must be empty")
-            radices = [int(b) for b in bases[2]] if bases is not None else []
-            flat = (words or []) + radices
-            c_flat = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
-            c_len = (ctypes.c_int32 * 3)(len(words or []), 0, len(radices))
-        elif stft and (words is not None or bases is not None):  # (the window's words, then the radices of n)
-            if bases is not None and len(bases[0]) != 0:
-                raise MifftError(-5, "dim 0 of an STFT plan is framed, not transformed: its bases list must be empty")
-            radices = [int(b) for b in bases[1]] if bases is not None else []
-            flat = (words or []) + radices
-            c_flat = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
-            c_len = (ctypes.c_int32 * 2)(len(words or []), len(radices))
-        elif bases is not None:
-            flat = [int(b) for bs in bases for b in bs]
-            c_flat = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
-            c_len = (ctypes.c_int32 * len(dims))(*[len(bs) for bs in bases])
-        else:
-            c_flat, c_len = None, None
+        # 4. the payload and the radices as the lists of ``bases``, and the one call
+        c_flat, c_len = _pack_bases(words, bases, lead)
         h = ctypes.c_void_p()
         # whole_batch > 0: this plan is one slab of a batch of that many transforms (mifft_plan_create_slab)
         self.whole_batch = int(whole_batch)
@@ -1178,6 +1197,14 @@ def time_fft(output: "torch.Tensor", x: "torch.Tensor", *, plan: Plan, iters: in
 # convenience wrappers: fftn / ifftn / rfftn(shape, radices) call surface
 # ---------------------------------------------------------------------------
 
+def _signal_device(x: "torch.Tensor", name: str) -> int:
+    """the device of a wrapper's input, which has to be the HIP device its plan will be made on"""
+    device = DeviceContext(x.device.index if x.is_cuda else None).device
+    if not x.is_cuda or x.device.index != device:
+        raise MifftError(-10, f"{name} must live on HIP device {device}, got {x.device}")
+    return device
+
+
 def _as_interleaved(x: "torch.Tensor"):
     """complex (batch, d0..) -> real view (batch, d0.., 2); real-typed input must already be (batch, d0.., C)."""
     if x.is_complex():
@@ -1191,41 +1218,50 @@ _PLAN_CACHE_SCRATCH_BYTES = 8 << 30  # ... and at most this much plan-owned scra
 _PLAN_CACHE_LOCK = threading.RLock()
 
 
-def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                 half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2, dst: bool = False) -> Plan:
-    """Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
+def _table_digest(table) -> Optional[bytes]:
+    """what a cache key holds of a contiguous float64 host table that its plan took by value (None: no table): the SHA-1 of
+    its bytes, read in place"""
+    return None if table is None else hashlib.sha1(table.numpy()).digest()
+
+
+def _plan_cached(key_head: tuple, device: int, build, *tables, key_tail: tuple = ()) -> Plan:
+    """The plan kept under ``key_head`` + the digests of the by-value ``tables`` + (device, the current stream's handle) +
+    ``key_tail``, made by ``build()`` and inserted when there is none.  Called under _PLAN_CACHE_LOCK, which the caller holds
+    until its launch is enqueued: the cache closes what it evicts.
+
+    Plans of the convenience wrappers are kept (LRU): a plan is a few small device tables, building one
     costs a hipMalloc + copy per dimension, and its tables must outlive the kernels enqueued with it.
 
     A plan may own mutable device state that its execs share (the scratch tensor of the long-strided and three-launch
     four-step routes, the counters of the opt-in image kernel), so the C ABI allows ONE exec in flight per plan
     (include/mifft.h).  Execs are ordered on a stream; the cache therefore keeps one plan PER STREAM -- two streams (or
     two threads on their own streams) transforming the same shape never share a plan -- and is guarded by a lock."""
-    with _PLAN_CACHE_LOCK:
-        return _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                                   half_spectrum, axes, dct_flags, dct_type, dst)
+    for table in tables:  # (every cached call comes through here: a plain loop, _table_digest written out)
+        key_head += (None if table is None else hashlib.sha1(table.numpy()).digest(),)
+    key = key_head + (device, int(torch.cuda.current_stream(device).cuda_stream)) + key_tail
+    plan = _PLAN_CACHE.get(key)
+    if plan is None:
+        plan = build()
+        _plan_cache_insert(key, plan)
+    else:
+        _PLAN_CACHE.move_to_end(key)
+    return plan
 
 
-def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
-                        half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2,
-                        dst: bool = False) -> Plan:
+def _cached_plan(in_dtype, out_dtype, in_shape, out_shape, radices, inverse, faithful_stages, device,
+                 half_spectrum: bool = False, axes=None, dct_flags: int = 0, dct_type: int = 2, dst: bool = False) -> Plan:
+    """the cached plan_fft plan of the fftn / rfftn / dct families (takes the cache's lock, which is re-entrant: a caller that
+    launches holds it already)"""
     # dct_flags: FLAG_DCT or FLAG_DCT_ND (| FLAG_DCT_ORTHO) of the dct / idct / dctn / idctn wrappers' plans, 0 for every other;
     # dct_type: 4 for the DCT-IV plans of dct / idct (the key of every other plan is what it has always been); dst: the sine
     # twins of dst / idst / dstn / idstn, whose keys alone grow by a word
-    key = (in_dtype, out_dtype, in_shape, out_shape,
-           None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
-           bool(inverse), bool(faithful_stages), device, int(torch.cuda.current_stream(device).cuda_stream),
-           bool(half_spectrum), _keep_flags(len(out_shape), axes), int(dct_flags))
-    if dct_type != 2:
-        key += (int(dct_type),)
-    if dst:
-        key += ("dst",)
-    plan = _PLAN_CACHE.get(key)
-    if plan is None:
+    def build():
+        common = dict(inverse=inverse, faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
+                      axes=axes)
         try:
-            plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, inverse=inverse,
-                            faithful_stages=faithful_stages, ctx=DeviceContext(device), half_spectrum=half_spectrum,
-                            axes=axes, dct=bool(dct_flags & FLAG_DCT), dctn=bool(dct_flags & FLAG_DCT_ND),
-                            norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None, dct_type=dct_type, dst=dst)
+            return plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=radices, dct=bool(dct_flags & FLAG_DCT),
+                            dctn=bool(dct_flags & FLAG_DCT_ND), norm="ortho" if dct_flags & FLAG_DCT_ORTHO else None,
+                            dct_type=dct_type, dst=dst, **common)
         except MifftError as e:
             # plan_fft keeps the reference's behaviour: its default radix estimate (trial division by 2..32 on the GPU,
             # primes <= 97 otherwise, fft/fft/fft.mojo:49-104) rejects lengths with a larger prime factor.  The
@@ -1235,13 +1271,14 @@ def _cached_plan_locked(in_dtype, out_dtype, in_shape, out_shape, radices, inver
                 raise
             dims = _check_half_layout(in_shape, out_shape, inverse) if half_spectrum else in_shape[1:-1]
             bases = [_prime_factors(int(n)) if axes is None or p + 1 in axes else [] for p, n in enumerate(dims)]
-            plan = plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=bases,
-                            inverse=inverse, faithful_stages=faithful_stages, ctx=DeviceContext(device),
-                            half_spectrum=half_spectrum, axes=axes)
-        _plan_cache_insert(key, plan)
-    else:
-        _PLAN_CACHE.move_to_end(key)
-    return plan
+            return plan_fft(in_dtype, out_dtype, in_shape, out_shape, bases=bases, **common)
+
+    head = (in_dtype, out_dtype, in_shape, out_shape, None if radices is None else tuple(tuple(int(b) for b in r) for r in radices),
+            bool(inverse), bool(faithful_stages))
+    tail = ((bool(half_spectrum), _keep_flags(len(out_shape), axes), int(dct_flags)) + ((int(dct_type),) if dct_type != 2 else ()) +
+            (("dst",) if dst else ()))
+    with _PLAN_CACHE_LOCK:
+        return _plan_cached(head, device, build, key_tail=tail)
 
 
 def _plan_cache_insert(key, plan: Plan) -> None:
@@ -1350,7 +1387,7 @@ def _run(x: "torch.Tensor", *, radices, inverse: bool, out_dtype, faithful_stage
     # lookup AND enqueue under the cache lock: another thread that inserts a plan may evict (synchronise + close) only
     # plans that have nothing left to enqueue
     with _PLAN_CACHE_LOCK:
-        plan = _cached_plan_locked(xr.dtype, out_dtype, tuple(xr.shape), out_shape, radices, inverse, faithful_stages,
+        plan = _cached_plan(xr.dtype, out_dtype, tuple(xr.shape), out_shape, radices, inverse, faithful_stages,
                                    xr.device.index, axes=axes)
         fft(out, xr, DeviceContext(xr.device.index), plan=plan)  # asynchronous on the current stream, like torch ops
     out = out.reshape(logical + (2,))
@@ -1411,7 +1448,7 @@ def rfftn(x: "torch.Tensor", radices=None, *, out_dtype=None, faithful_stages: b
     _check_half_layout(in_shape, out_shape, False)
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _cached_plan_locked(xr.dtype, out_dtype, in_shape, out_shape, radices, False, faithful_stages,
+        plan = _cached_plan(xr.dtype, out_dtype, in_shape, out_shape, radices, False, faithful_stages,
                                    xr.device.index, half_spectrum=True, axes=axes)
         fft(out, xr, DeviceContext(xr.device.index), plan=plan)
     return torch.view_as_complex(out.reshape(logical[:-1] + (logical[-1] // 2 + 1, 2)))
@@ -1452,7 +1489,7 @@ def irfftn(X: "torch.Tensor", n: Optional[int] = None, radices=None, *, out_dtyp
     _check_half_layout(in_shape, out_shape, True)
     out = torch.empty(out_shape, dtype=out_dtype, device=Xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _cached_plan_locked(out_dtype, out_dtype, in_shape, out_shape, radices, True, False, Xr.device.index,
+        plan = _cached_plan(out_dtype, out_dtype, in_shape, out_shape, radices, True, False, Xr.device.index,
                                    half_spectrum=True, axes=axes)
         fft(out, Xr, DeviceContext(Xr.device.index), plan=plan)
     return out.reshape(logical[:-1] + (n,))
@@ -1495,7 +1532,7 @@ def _dct_rows(x: "torch.Tensor", type: int, norm, out_dtype, dim: int, inverse: 
     device = DeviceContext(xr.device.index if xr.is_cuda else None).device
     out = torch.empty(shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device, dct_flags=dct_flags,
+        plan = _cached_plan(xr.dtype, out_dtype, shape, shape, None, inverse, False, device, dct_flags=dct_flags,
                                    dct_type=int(type), dst=kind == "dst")
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical)
@@ -1553,7 +1590,7 @@ def _dct_nd(x: "torch.Tensor", type: int, norm, dim, out_dtype, inverse: bool, k
     device = DeviceContext(xr.device.index if xr.is_cuda else None).device
     out = torch.empty(shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _cached_plan_locked(xr.dtype, out_dtype, shape, shape, None, inverse, False, device,
+        plan = _cached_plan(xr.dtype, out_dtype, shape, shape, None, inverse, False, device,
                                    axes=None if len(axes) == len(layout) - 1 else axes, dct_flags=dct_flags,
                                    dst=kind == "dst")
         fft(out, xr, DeviceContext(device), plan=plan)
@@ -1731,29 +1768,18 @@ def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -
     if out_dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"mdct: out_dtype must be float32 or float64, got {out_dtype}")
     logical = tuple(x.shape)
-    T = logical[-1]
-    batch = 1
-    for m in logical[:-1]:
-        batch *= m
+    T, batch = logical[-1], math.prod(logical[:-1])
     if T < 2:
         raise MifftError(-2, f"mdct: signals of {T} samples: at least 2")
     frames = mdct_frames(T, n)
     in_shape, out_shape = (batch, T, 1), (batch, frames, n, 1)
     w = None if window is None else _window_f64(window, 2 * n)
-    device = DeviceContext(x.device.index if x.is_cuda else None).device
-    if not x.is_cuda or x.device.index != device:
-        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    device = _signal_device(x, "x")
     xr = x.to(out_dtype).contiguous().reshape(in_shape)
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
-    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
     with _PLAN_CACHE_LOCK:
-        key = ("mdct", out_dtype, in_shape, n, scale, digest, device, int(torch.cuda.current_stream(device).cuda_stream))
-        plan = _PLAN_CACHE.get(key)
-        if plan is None:
-            plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, mdct=n, mdct_scale=scale, stft_window=w)
-            _plan_cache_insert(key, plan)
-        else:
-            _PLAN_CACHE.move_to_end(key)
+        plan = _plan_cached(("mdct", out_dtype, in_shape, n, scale), device, lambda: Plan(
+            out_dtype, out_dtype, in_shape, out_shape, device=device, mdct=n, mdct_scale=scale, stft_window=w), w)
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical[:-1] + (frames, n))
 
@@ -2240,17 +2266,10 @@ def _fftconv_selector(n: int, taps, Q) -> dict:
 
 def _fftconv_fwd_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, gates, Q=None, io_dtype=None):
     """the cached forward plan of ``fftconv`` (the caller holds _PLAN_CACHE_LOCK)"""
-    key = ("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-           int(torch.cuda.current_stream(device).cuda_stream), taps, gates, Q, io_dtype)
-    plan = _PLAN_CACHE.get(key)
-    if plan is None:
-        plan = plan_fftconv(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
-                            correlate=correlate, ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2),
-                            io_dtype=io_dtype)
-        _plan_cache_insert(key, plan)
-    else:
-        _PLAN_CACHE.move_to_end(key)
-    return plan
+    return _plan_cached(("fftconv", dtype, rows, D, L, n, offset, out_length, bool(correlate)), device, lambda: plan_fftconv(
+        dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q, correlate=correlate,
+        ctx=DeviceContext(device), pregate=bool(gates & 1), postgate=bool(gates & 2), io_dtype=io_dtype),
+        key_tail=(taps, gates, Q, io_dtype))
 
 
 def _fftconv_exec(plan: ConvPlan, out, x, k, skip, pregate=None, postgate=None) -> None:
@@ -2350,9 +2369,7 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
                                  f"{tuple(skip.shape)} {skip.dtype}")
         else:
             skip = float(skip)
-    device = DeviceContext(x.device.index if x.is_cuda else None).device
-    if not x.is_cuda or x.device.index != device:
-        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    device = _signal_device(x, "x")
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, k, pregate, postgate, skip)):
         # (the forward of the Function runs with grad mode off: it comes back here and takes the lines below)
         skip_t = skip if isinstance(skip, torch.Tensor) else None
@@ -2599,17 +2616,10 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
 
 def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None, gates=0):
     """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK)"""
-    key = ("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate), device,
-           int(torch.cuda.current_stream(device).cuda_stream), taps, Q, io_dtype, gates)
-    plan = _PLAN_CACHE.get(key)
-    if plan is None:
-        plan = plan_fftconv_grad(dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q,
-                                 correlate=correlate, ctx=DeviceContext(device), io_dtype=io_dtype, pregate=bool(gates & 1),
-                                 postgate=bool(gates & 2))
-        _plan_cache_insert(key, plan)
-    else:
-        _PLAN_CACHE.move_to_end(key)
-    return plan
+    return _plan_cached(("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate)), device, lambda: plan_fftconv_grad(
+        dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q, correlate=correlate,
+        ctx=DeviceContext(device), io_dtype=io_dtype, pregate=bool(gates & 1), postgate=bool(gates & 2)),
+        key_tail=(taps, Q, io_dtype, gates))
 
 
 def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Optional[int] = None, mode: str = "causal",
@@ -2664,9 +2674,7 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     rows = math.prod(logical[:-1])
     if rows < 1:
         raise MifftError(-8, f"fftconv_filter_grad: no rows in {logical}")
-    device = DeviceContext(x.device.index if x.is_cuda else None).device
-    if not x.is_cuda or x.device.index != device:
-        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    device = _signal_device(x, "x")
     if gy.device != x.device:
         raise MifftError(-10, f"fftconv_filter_grad: gy lives on {gy.device}, x on {x.device}")
     xr = x.detach().to(sdt).contiguous().reshape(rows, L, 1)
@@ -2863,32 +2871,22 @@ def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = 
         raise MifftError(-2, f"imdct: {F} frames of {n} coefficients cover 1 .. {(F - 1) * n} samples, length is {length}")
     w = None if window is None else _window_f64(window, 2 * n)
     dt = X.dtype if X.dtype in _OUT_DTYPES else torch.float64
-    device = DeviceContext(X.device.index if X.is_cuda else None).device
-    if not X.is_cuda or X.device.index != device:
-        raise MifftError(-10, f"X must live on HIP device {device}, got {X.device}")
+    device = _signal_device(X, "X")
     ortho = gain != 2.0 / n
     lead = tuple(X.shape[:-2])
     if length == 1:
         return _imdct_composed(X.to(dt), mdct_window(n) if w is None else w, ortho, length)
-    batch = 1
-    for m in lead:
-        batch *= m
+    batch = math.prod(lead)
     in_shape, out_shape = (batch, F, n, 1), (batch, length, 1)
     Xr = X.to(dt).contiguous().reshape(in_shape)
-    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
     with _PLAN_CACHE_LOCK:
-        key = ("imdct", dt, in_shape, length, gain, digest, device, int(torch.cuda.current_stream(device).cuda_stream))
-        plan = _PLAN_CACHE.get(key)
-        if plan is None:
-            try:
-                plan = Plan(dt, dt, in_shape, out_shape, device=device, imdct=n, imdct_gain=gain, stft_window=w)
-            except MifftError as e:
-                if e.status != ERR_UNSUPPORTED or "LDS" not in str(e):
-                    raise
-                return _imdct_composed(X.to(dt), mdct_window(n) if w is None else w, ortho, length)
-            _plan_cache_insert(key, plan)
-        else:
-            _PLAN_CACHE.move_to_end(key)
+        try:
+            plan = _plan_cached(("imdct", dt, in_shape, length, gain), device, lambda: Plan(
+                dt, dt, in_shape, out_shape, device=device, imdct=n, imdct_gain=gain, stft_window=w), w)
+        except MifftError as e:
+            if e.status != ERR_UNSUPPORTED or "LDS" not in str(e):
+                raise
+            return _imdct_composed(X.to(dt), mdct_window(n) if w is None else w, ortho, length)
         out = torch.empty(out_shape, dtype=dt, device=Xr.device)
         fft(out, Xr, DeviceContext(device), plan=plan)
     return out.reshape(lead + (length,))
@@ -2995,22 +2993,17 @@ def _stft_adjoint_plan(call: _StftCall, multiplier) -> StftAdjointPlan:
     left the cache in between."""
     w, device = call.window, call.device
     mode = call.pad_mode if call.center else None
-    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
-    with _PLAN_CACHE_LOCK:
-        key = ("stft_adjoint", call.out_dtype, (call.batch, call.length), call.n_fft, call.hop, mode, digest, multiplier, device,
-               int(torch.cuda.current_stream(device).cuda_stream))
-        plan = _PLAN_CACHE.get(key)
-        if plan is None:
-            try:
-                plan = plan_stft_adjoint(call.out_dtype, call.batch, call.length, call.n_fft, call.hop, window=w, center=mode,
-                                         multiplier=multiplier, ctx=DeviceContext(device))
-            except MifftError as e:
-                raise MifftError(e.status, f"{call.who}: no gradient with respect to x for these arguments ({e}); the forward "
-                                           f"alone works on an x without requires_grad (or under torch.no_grad())") from None
-            _plan_cache_insert(key, plan)
-        else:
-            _PLAN_CACHE.move_to_end(key)
-    return plan
+    def build():
+        try:
+            return plan_stft_adjoint(call.out_dtype, call.batch, call.length, call.n_fft, call.hop, window=w, center=mode,
+                                     multiplier=multiplier, ctx=DeviceContext(device))
+        except MifftError as e:
+            raise MifftError(e.status, f"{call.who}: no gradient with respect to x for these arguments ({e}); the forward "
+                                       f"alone works on an x without requires_grad (or under torch.no_grad())") from None
+
+    with _PLAN_CACHE_LOCK:  # (the multiplier stands between the window's digest and the device: the head is the finished key's)
+        return _plan_cached(("stft_adjoint", call.out_dtype, (call.batch, call.length), call.n_fft, call.hop, mode,
+                             _table_digest(w), multiplier), device, build)
 
 
 class _STFTFunction(torch.autograd.Function):
@@ -3100,10 +3093,7 @@ def _stft_run_plain(who: str, x, n_fft, hop_length, win_length, window, center, 
         raise MifftError(-4, f"{who}: out_dtype must be float32 or float64, got {out_dtype}")
     mode = (pad_mode if center else None)
     logical = tuple(x.shape)
-    T = logical[-1]
-    batch = 1
-    for m in logical[:-1]:
-        batch *= m
+    T, batch = logical[-1], math.prod(logical[:-1])
     frames = stft_frames(T, n_fft, hop_length, bool(center))
     bins = n_fft // 2 + 1
     if fb is not None:
@@ -3115,26 +3105,18 @@ def _stft_run_plain(who: str, x, n_fft, hop_length, win_length, window, center, 
     in_shape, out_shape = (batch, T, 1), (batch, frames, width, 2 if power is None else 1)
     _check_stft_layout(in_shape, (batch, frames, bins, 2), hop_length, mode)
     w = _stft_table(window, win_length, n_fft, normalized)
-    device = DeviceContext(x.device.index if x.is_cuda else None).device
-    if not x.is_cuda or x.device.index != device:
-        raise MifftError(-10, f"x must live on HIP device {device}, got {x.device}")
+    device = _signal_device(x, "x")
     xr = x.to(out_dtype).contiguous().reshape(in_shape)
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
-    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
+    tail = ()
+    if power is not None:  # (the stft key as it has always been, then what the spectrogram adds)
+        tail += (power, None if fb is None else (tuple(fb.shape), _table_digest(fb)))
+    if logv is not None or post is not None:  # (and what the log stage and the matrix after the bands add)
+        tail += (logv, None if post is None else (tuple(post.shape), _table_digest(post)))
     with _PLAN_CACHE_LOCK:
-        key = ("stft", out_dtype, in_shape, n_fft, hop_length, mode, digest, device,
-               int(torch.cuda.current_stream(device).cuda_stream))
-        if power is not None:  # (the stft key as it has always been, then what the spectrogram adds)
-            key += (power, None if fb is None else (tuple(fb.shape), hashlib.sha1(fb.numpy().tobytes()).digest()))
-        if logv is not None or post is not None:  # (and what the log stage and the matrix after the bands add)
-            key += (logv, None if post is None else (tuple(post.shape), hashlib.sha1(post.numpy().tobytes()).digest()))
-        plan = _PLAN_CACHE.get(key)
-        if plan is None:
-            plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, stft_hop=hop_length, stft_center=mode,
-                        stft_window=w, stft_power=power, stft_fb=fb, stft_log=logv, stft_post=post)
-            _plan_cache_insert(key, plan)
-        else:
-            _PLAN_CACHE.move_to_end(key)
+        plan = _plan_cached(("stft", out_dtype, in_shape, n_fft, hop_length, mode), device, lambda: Plan(
+            out_dtype, out_dtype, in_shape, out_shape, device=device, stft_hop=hop_length, stft_center=mode, stft_window=w,
+            stft_power=power, stft_fb=fb, stft_log=logv, stft_post=post), w, key_tail=tail)
         fft(out, xr, DeviceContext(device), plan=plan)
     if power is not None:
         return out.reshape(logical[:-1] + (frames, width)).transpose(-1, -2)
@@ -3317,10 +3299,7 @@ def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_l
     if out_dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"istft: out_dtype must be float32 or float64, got {out_dtype}")
     logical = tuple(X.shape)
-    frames = logical[-1]
-    batch = 1
-    for m in logical[:-2]:
-        batch *= m
+    frames, batch = logical[-1], math.prod(logical[:-2])
     covered = istft_length(frames, n_fft, hop_length, False) - (n_fft // 2 if center else 0)
     T = istft_length(frames, n_fft, hop_length, bool(center)) if length is None else int(length)
     if T > covered:
@@ -3335,24 +3314,15 @@ def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_l
         w = torch.zeros(n_fft, dtype=torch.float64)
         w[left:left + win_length] = wl
     gain = float(n_fft) ** 0.5 if normalized else 1.0
-    device = DeviceContext(X.device.index if X.is_cuda else None).device
-    if not X.is_cuda or X.device.index != device:
-        raise MifftError(-10, f"X must live on HIP device {device}, got {X.device}")
+    device = _signal_device(X, "X")
     ctype = torch.complex64 if out_dtype == torch.float32 else torch.complex128
     # frames-major memory: a no-op for the view stft returns, one transposing copy otherwise
     xf = X.to(ctype).transpose(-1, -2).contiguous()
     xr = torch.view_as_real(xf).reshape(in_shape)
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
-    digest = None if w is None else hashlib.sha1(w.numpy().tobytes()).digest()
     with _PLAN_CACHE_LOCK:
-        key = ("istft", out_dtype, in_shape, n_fft, hop_length, bool(center), T, gain, digest, device,
-               int(torch.cuda.current_stream(device).cuda_stream))
-        plan = _PLAN_CACHE.get(key)
-        if plan is None:
-            plan = Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, istft_hop=hop_length,
-                        stft_center=bool(center), stft_window=w, istft_gain=gain)
-            _plan_cache_insert(key, plan)
-        else:
-            _PLAN_CACHE.move_to_end(key)
+        plan = _plan_cached(("istft", out_dtype, in_shape, n_fft, hop_length, bool(center), T, gain), device, lambda: Plan(
+            out_dtype, out_dtype, in_shape, out_shape, device=device, istft_hop=hop_length, stft_center=bool(center),
+            stft_window=w, istft_gain=gain), w)
         fft(out, xr, DeviceContext(device), plan=plan)
     return out.reshape(logical[:-2] + (T,))

@@ -44,10 +44,7 @@ bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len)
 
 // what the convolution payloads share: the flag, direction, dtype and component checks and the limits of n
 static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
-    const struct {
-        uint32_t bits;
-        const char* what;
-    } other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: a convolution has no magnitude or power store"},
+    const FlagRefusal other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: a convolution has no magnitude or power store"},
                  {MIFFT_FLAG_STFT_CENTER_REFLECT, "a centre bit (MIFFT_FLAG_STFT_CENTER_REFLECT): a convolution has no frames"},
                  {MIFFT_FLAG_STFT_CENTER_ZEROS, "a centre bit (MIFFT_FLAG_STFT_CENTER_ZEROS): a convolution has no frames"},
                  {MIFFT_FLAG_STFT_HOP_MASK, "a hop (MIFFT_FLAG_STFT_HOP): a convolution has no frames"},
@@ -58,11 +55,7 @@ static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
                  {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
                  {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: a convolution plan extends dim 0 and transforms dim 1"},
                  {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
-    for (const auto& o : other)
-        if (p.flags & o.bits) {
-            why = std::string("a convolution payload (") + tag + ") with " + o.what;
-            return MIFFT_ERR_UNSUPPORTED;
-        }
+    if (const int rc = refuse_flags(p.flags, other, std::string("a convolution payload (") + tag + ") with ", why)) return rc;
     if (p.inverse) {
         why = "a convolution plan runs its own inverse: inverse must be 0";
         return MIFFT_ERR_UNSUPPORTED;
@@ -225,16 +218,14 @@ static int conv_radices(const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "negative bases_len";
         return MIFFT_ERR_NO_BASES;
     }
-    radices.clear();
-    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    read_radices(bases_flat, bases_len[0], bases_len[1], radices);
     return MIFFT_OK;
 }
 
 // MIFFT_CONV_TAG: 8 words D | o | Lo | mode | H behind the tag; 12: D | c | S | mode | H | F | s0 | Lo | 0; 16: the twelve with
 // F = 0 for a single block (o and Lo in words 3 and 4, words 9 and 10 zero) and the gates in word 11, then four zeros; 20: the
 // sixteen, gates or 0 in word 11, then Q | P | 0 | 0
-int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
-               std::string& why) {
+int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
     if (const int rc = conv_header_check(p, "MIFFT_CONV_TAG", why)) return rc;
     const uint32_t* w = bases_flat;
     const int len = bases_len[0];
@@ -278,7 +269,7 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         if (const int rc = conv_partition_check(p, r, why)) return rc;
         if (const int rc = conv_reserved_check(w, 12, 20, 3u << 16, "a partitioned convolution", why)) return rc;
     }
-    if (const int rc = conv_radices(bases_flat, bases_len, radices, why)) return rc;
+    if (const int rc = conv_radices(bases_flat, bases_len, pl.radices, why)) return rc;
     p.conv = r;
     return MIFFT_OK;
 }
@@ -311,8 +302,7 @@ bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases
 
 // MIFFT_CONV_GRAD_TAG: 16 words, D | c | S | mode | F | s0 | Lo | P behind the tag, a zero, the gates of the forward plan (0: none,
 // what every payload had there before there were any), then four zeros
-int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices,
-                    std::string& why) {
+int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
     if (const int rc = conv_header_check(p, "MIFFT_CONV_GRAD_TAG", why)) return rc;
     const uint32_t* w = bases_flat;
     ConvRequest r;
@@ -339,7 +329,7 @@ int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
         return MIFFT_ERR_BAD_BASES;
     }
     if (const int rc = conv_reserved_check(w, 10, 16, 1u << 11, "a filter-gradient", why)) return rc;
-    if (const int rc = conv_radices(bases_flat, bases_len, radices, why)) return rc;
+    if (const int rc = conv_radices(bases_flat, bases_len, pl.radices, why)) return rc;
     p.conv = r;
     return MIFFT_OK;
 }

@@ -19,12 +19,6 @@
 
 namespace mifft {
 
-static bool read_f64(const uint32_t* words, double& v) {
-    const uint64_t bits = (uint64_t)words[0] | ((uint64_t)words[1] << 32);
-    memcpy(&v, &bits, sizeof v);
-    return std::isfinite(v);
-}
-
 // sum over the frames that cover padded sample u of w[u - f hop]^2, ascending f
 static double envelope_at(const std::vector<double>& window, int64_t n, int64_t hop, int64_t F, int64_t u) {
     const int64_t f_hi = std::min<int64_t>(F - 1, u / hop), f_lo = u < n ? 0 : (u - n) / hop + 1;
@@ -59,26 +53,19 @@ static int64_t envelope_first_below(const std::vector<double>& window, int64_t n
 // checks that need no device: MIFFT_OK, or the status and its reason; the window, the gain and the user radices on the way.
 // `adj_mode` null: an inverse STFT plan.  Else an STFT adjoint plan (stft_adj_check), whose mode word it receives: the covered
 // length, the envelope's limit and the overlap-add condition do not apply, and the payload is the tagged one.
-static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                            double& gain, std::vector<uint64_t>& radices, std::string& why, int* adj_mode) {
-    window.clear();
-    radices.clear();
-    gain = 1.0;
-    const struct {
-        uint32_t bits;
-        const char* what;
-    } other[] = {// (MIFFT_FLAG_STFT beside this bit never gets here: stft_check refuses the pair)
+static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why,
+                            int* adj_mode) {
+    pl = FramedPayload();
+    std::vector<double>& window = pl.window;
+    double& gain = pl.gain;
+    const FlagRefusal other[] = {// (MIFFT_FLAG_STFT beside this bit never gets here: stft_check refuses the pair)
                  {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no inverse STFT to be faithful to"},
                  {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an inverse STFT plan reads the half spectrum of every frame anyway"},
                  {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
                  {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
                  {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
                  {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an inverse STFT plan transforms dim 2 and overlap-adds dim 1"}};
-    for (const auto& o : other)
-        if (p.flags & o.bits) {
-            why = std::string("MIFFT_FLAG_ISTFT with ") + o.what;
-            return MIFFT_ERR_UNSUPPORTED;
-        }
+    if (const int rc = refuse_flags(p.flags, other, "MIFFT_FLAG_ISTFT with ", why)) return rc;
     if (!p.inverse) {
         why = "MIFFT_FLAG_ISTFT with inverse = 0: the forward transform is MIFFT_FLAG_STFT";
         return MIFFT_ERR_UNSUPPORTED;
@@ -153,13 +140,9 @@ static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int
             why = "bases_len[1] is 0 (dim 1 is overlap-added, not transformed) and bases_len[2] the radices of n";
             return bases_len[2] < 0 ? MIFFT_ERR_NO_BASES : MIFFT_ERR_BAD_BASES;
         }
-        window.resize((size_t)n);
-        for (int64_t j = 0; j < n; ++j)
-            if (!read_f64(bases_flat + 2 * j, window[(size_t)j])) {
-                why = "window value " + std::to_string(j) + " is not finite";
-                return MIFFT_ERR_BAD_BASES;
-            }
-        if (!read_f64(bases_flat + 2 * n + 2, gain) || gain == 0.0) {
+        if (const int rc = read_window(bases_flat, n, window, why)) return rc;
+        gain = word_pair(bases_flat + 2 * n + 2);
+        if (!std::isfinite(gain) || gain == 0.0) {
             why = "the gain is finite and not zero, not " + std::to_string(gain);
             return MIFFT_ERR_BAD_BASES;
         }
@@ -173,7 +156,7 @@ static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int
             return MIFFT_ERR_BAD_BASES;
         }
         *adj_mode = (int)mode;
-        for (int k = 0; k < bases_len[2]; ++k) radices.push_back(bases_flat[l0 + k]);
+        read_radices(bases_flat, l0, bases_len[2], pl.radices);
         return MIFFT_OK;
     }
     if (L > (1ll << 26)) {
@@ -198,19 +181,16 @@ static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int
             why = "bases_len[1] of an inverse STFT plan is 0 (dim 1 is overlap-added, not transformed) and bases_len[2] the radices of n";
             return bases_len[2] < 0 ? MIFFT_ERR_NO_BASES : MIFFT_ERR_BAD_BASES;
         }
-        if (l0) {
-            window.resize((size_t)n);
-            for (int64_t j = 0; j < n; ++j)
-                if (!read_f64(bases_flat + 2 * j, window[(size_t)j])) {
-                    why = "window value " + std::to_string(j) + " is not finite";
-                    return MIFFT_ERR_BAD_BASES;
-                }
-            if (l0 == 2 * n + 2 && !read_f64(bases_flat + 2 * n, gain)) {
+        if (l0)
+            if (const int rc = read_window(bases_flat, n, window, why)) return rc;
+        if (l0 == 2 * n + 2) {
+            gain = word_pair(bases_flat + 2 * n);
+            if (!std::isfinite(gain)) {
                 why = "the gain is not finite";
                 return MIFFT_ERR_BAD_BASES;
             }
         }
-        for (int k = 0; k < bases_len[2]; ++k) radices.push_back(bases_flat[l0 + k]);
+        read_radices(bases_flat, l0, bases_len[2], pl.radices);
     }
     // ---- NOLA over the samples the plan stores (torch.istft: window_envelop.abs().min() over [c, c + T) against 1e-11) ----
     const int64_t bare = envelope_first_below(window, n, hop, F, c, T, 1e-11);
@@ -222,9 +202,8 @@ static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int
     return MIFFT_OK;
 }
 
-int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
-                std::vector<uint64_t>& radices, std::string& why) {
-    return istft_check_impl(p, bases_flat, bases_len, window, gain, radices, why, nullptr);
+int istft_check(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
+    return istft_check_impl(p, bases_flat, bases_len, pl, why, nullptr);
 }
 
 // ---- STFT adjoint plans: the payload w[0 .. n-1] | MIFFT_STFT_ADJ_TAG | gain | mode, 0 on a MIFFT_FLAG_ISTFT plan ------------------
@@ -238,10 +217,9 @@ bool stft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, 
     return (int64_t)bases_len[0] == 2 * n + 6 && bases_flat[2 * n] == MIFFT_STFT_ADJ_TAG_LO && bases_flat[2 * n + 1] == MIFFT_STFT_ADJ_TAG_HI;
 }
 
-int stft_adj_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
-                   std::vector<uint64_t>& radices, std::string& why) {
+int stft_adj_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
     int mode = 0;
-    const int rc = istft_check_impl(p, bases_flat, bases_len, window, gain, radices, why, &mode);
+    const int rc = istft_check_impl(p, bases_flat, bases_len, pl, why, &mode);
     if (rc) {
         why = "an STFT adjoint payload (MIFFT_STFT_ADJ_TAG on a MIFFT_FLAG_ISTFT plan): " + why;
         return rc;
@@ -292,26 +270,17 @@ bool imdct_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len
     return bases_flat[l0 - 4] == MIFFT_MDCT_TAG_LO && bases_flat[l0 - 3] == MIFFT_MDCT_TAG_HI;
 }
 
-int imdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
-                std::vector<uint64_t>& radices, std::string& why) {
-    window.clear();
-    radices.clear();
+int imdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
+    pl = FramedPayload();
     const char* who = "an IMDCT payload (MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan)";
-    const struct {
-        uint32_t bits;
-        const char* what;
-    } other[] = {{MIFFT_FLAG_STFT_CENTER_REFLECT, "MIFFT_FLAG_STFT_CENTER_REFLECT: the frames of an MDCT see zeros beyond both ends"},
+    const FlagRefusal other[] = {{MIFFT_FLAG_STFT_CENTER_REFLECT, "MIFFT_FLAG_STFT_CENTER_REFLECT: the frames of an MDCT see zeros beyond both ends"},
                  {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no MDCT to be faithful to"},
                  {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an MDCT has no half spectrum"},
                  {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
                  {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
                  {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO: the norm of an IMDCT travels as the gain of its payload"},
                  {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an IMDCT plan transforms dim 2 and overlap-adds dim 1"}};
-    for (const auto& o : other)
-        if (p.flags & o.bits) {
-            why = std::string(who) + " with " + o.what;
-            return MIFFT_ERR_UNSUPPORTED;
-        }
+    if (const int rc = refuse_flags(p.flags, other, std::string(who) + " with ", why)) return rc;
     if (!(p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS)) {
         why = std::string(who) + " without a centre bit: MIFFT_FLAG_STFT_CENTER_ZEROS is required";
         return MIFFT_ERR_UNSUPPORTED;
@@ -374,25 +343,23 @@ int imdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, s
         why = "bases_len[1] of an IMDCT plan is 0 (dim 1 is overlap-added, not transformed) and bases_len[2] the radices of M / 2";
         return bases_len[2] < 0 ? MIFFT_ERR_NO_BASES : MIFFT_ERR_BAD_BASES;
     }
-    window.resize((size_t)n);
-    for (int64_t j = 0; j < n; ++j)
-        if (!read_f64(bases_flat + 2 * j, window[(size_t)j])) {
-            why = "window value " + std::to_string(j) + " is not finite";
-            return MIFFT_ERR_BAD_BASES;
-        }
-    if (!read_f64(bases_flat + 2 * n + 2, gain) || gain == 0.0) {
-        why = "the gain of an IMDCT payload is finite and not zero, not " + std::to_string(gain);
+    if (const int rc = read_window(bases_flat, n, pl.window, why)) return rc;
+    pl.gain = word_pair(bases_flat + 2 * n + 2);
+    if (!std::isfinite(pl.gain) || pl.gain == 0.0) {
+        why = "the gain of an IMDCT payload is finite and not zero, not " + std::to_string(pl.gain);
         return MIFFT_ERR_BAD_BASES;
     }
-    for (int k = 0; k < bases_len[2]; ++k) radices.push_back(bases_flat[l0 + k]);
+    read_radices(bases_flat, l0, bases_len[2], pl.radices);
     p.imdct = M;
     return MIFFT_OK;
 }
 
 // the one pass: a DCT-IV of M points (dim 2) over the F frames of every batch entry, unfolded and overlap-added by its store
-int build_imdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-                const std::vector<double>& window, double gain, std::string& why) {
+int build_imdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
+                std::string& why) {
     const int64_t M = p.imdct;
+    const std::vector<double>& window = pl.window;
+    const double gain = pl.gain;
     DimPass ps;
     ps.dim_index = 2;
     ps.N = M;
@@ -422,9 +389,11 @@ int build_imdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector
 }
 
 // the one pass: dim 2 (n points) over the F frames of every batch entry
-int build_istft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-                const std::vector<double>& window, double gain, std::string& why) {
+int build_istft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
+                std::string& why) {
     const int64_t F = p.dims[1], n = p.dims[2], hop = p.stft_hop();
+    const std::vector<double>& window = pl.window;
+    const double gain = pl.gain;
     DimPass ps;
     ps.dim_index = 2;
     ps.N = n;

@@ -319,53 +319,65 @@ int open_device(Plan& p, std::optional<DeviceGuard>& guard) {
 // STFT and inverse STFT plans (MIFFT_FLAG_STFT, stft.cpp; MIFFT_FLAG_ISTFT, istft.cpp) and the MDCT / IMDCT / fused
 // convolution plans (conv.cpp) their tagged payloads select: their own route to the end.  Everything that can be refused
 // without a device first; `bases` carries the window and the radices of the one transformed dim, the last.
+FramedKind framed_kind(const Plan& p, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (p.stft()) {  // (both mode bits as well: stft_check refuses the pair)
+        // a payload that STARTS with MIFFT_CONV_GRAD_TAG: the filter gradient of a fused FFT convolution; with MIFFT_CONV_TAG:
+        // that convolution, of rows of dims[0] samples at length dims[1]
+        if (conv_grad_detect(p.ndim, bases_flat, bases_len)) return FramedKind::ConvGrad;
+        if (conv_detect(p.ndim, bases_flat, bases_len)) return FramedKind::Conv;
+        // a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points
+        if (mdct_detect(p.ndim, p.dims, bases_flat, bases_len)) return FramedKind::Mdct;
+        return FramedKind::Stft;
+    }
+    // the window of a MIFFT_FLAG_ISTFT plan tagged with MIFFT_STFT_ADJ_TAG: the adjoint of the STFT, the ISTFT pass without
+    // envelope; with MIFFT_MDCT_TAG: the inverse MDCT, frames of M = n / 2 coefficients overlap-added every M samples
+    if (stft_adj_detect(p.ndim, p.dims, bases_flat, bases_len)) return FramedKind::Adjoint;
+    if (imdct_detect(p.ndim, bases_flat, bases_len)) return FramedKind::Imdct;
+    return FramedKind::Istft;
+}
+
 int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::optional<DeviceGuard>& guard) {
     const int ndim = p.ndim;
     const int64_t* dims = p.dims;
-    const bool fwd = p.stft();  // (both bits: stft_check refuses the pair)
+    const FramedKind kind = framed_kind(p, bases_flat, bases_len);
     std::string why;
-    std::vector<double> window, fb, post;
-    std::vector<uint64_t> user;
-    double gain = 1.0;
-    // (a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points)
-    const bool mdct = fwd && mdct_detect(ndim, dims, bases_flat, bases_len);
-    // (the same tag on a MIFFT_FLAG_ISTFT plan: the inverse, frames of M = n / 2 coefficients overlap-added every M samples)
-    // (the window of a MIFFT_FLAG_ISTFT plan tagged with MIFFT_STFT_ADJ_TAG: the adjoint of the STFT, the ISTFT pass without envelope)
-    const bool adj = !fwd && stft_adj_detect(ndim, dims, bases_flat, bases_len);
-    const bool imdct = !fwd && !adj && imdct_detect(ndim, bases_flat, bases_len);
-    // (a payload that STARTS with MIFFT_CONV_TAG: the fused FFT convolution of rows of dims[0] samples at length dims[1])
-    const bool conv = fwd && conv_detect(ndim, bases_flat, bases_len);
-    // (or with MIFFT_CONV_GRAD_TAG: the filter gradient of such a convolution)
-    const bool wgrad = fwd && conv_grad_detect(ndim, bases_flat, bases_len);
-    int rc = wgrad   ? conv_grad_check(p, bases_flat, bases_len, user, why)
-             : conv  ? conv_check(p, bases_flat, bases_len, user, why)
-             : mdct  ? mdct_check(p, bases_flat, bases_len, window, user, why)
-             : imdct ? imdct_check(p, bases_flat, bases_len, window, gain, user, why)
-             : adj   ? stft_adj_check(p, bases_flat, bases_len, window, gain, user, why)
-             : fwd   ? stft_check(p, why)
-                     : istft_check(p, bases_flat, bases_len, window, gain, user, why);
+    FramedPayload pl;
+    int rc = MIFFT_OK;
+    switch (kind) {
+        case FramedKind::ConvGrad: rc = conv_grad_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::Conv: rc = conv_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::Mdct: rc = mdct_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::Imdct: rc = imdct_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::Adjoint: rc = stft_adj_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::Stft: rc = stft_check(p, why); break;
+        case FramedKind::Istft: rc = istft_check(p, bases_flat, bases_len, pl, why); break;
+    }
     if (rc) return fail(rc, why);
     const int td = ndim - 1;  // the transformed dim
-    const int64_t n = mdct || imdct ? dims[td] / 4 : dims[td], frames = fwd ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
-    p.prod = frames * (mdct ? p.mdct : imdct ? p.imdct : n);  // (the rows the one pass transforms)
-    p.prod_half = mdct || imdct ? p.prod : frames * (n / 2 + 1);
-    if (fwd && !mdct && !conv && !wgrad) {
-        rc = stft_unpack_bases(p, bases_flat, bases_len, window, fb, post, user, why);
+    const bool lapped = kind == FramedKind::Mdct || kind == FramedKind::Imdct;
+    const int64_t n = lapped ? dims[td] / 4 : dims[td], frames = p.stft() ? p.stft_frames() : dims[1];  // (MDCT: M / 2 complex points)
+    p.prod = frames * (kind == FramedKind::Mdct ? p.mdct : kind == FramedKind::Imdct ? p.imdct : n);  // (the rows the one pass transforms)
+    p.prod_half = lapped ? p.prod : frames * (n / 2 + 1);
+    if (kind == FramedKind::Stft) {
+        rc = stft_unpack_bases(p, bases_flat, bases_len, pl, why);
         if (rc) return fail(rc, why);
     }
-    if (user.empty()) user = plan_estimate_bases((uint64_t)n, /*gpu_target=*/true);
+    if (pl.radices.empty()) pl.radices = plan_estimate_bases((uint64_t)n, /*gpu_target=*/true);
     std::vector<std::vector<uint32_t>> ordered((size_t)ndim), processed((size_t)ndim);
-    rc = plan_ordered_bases((uint64_t)n, user, ordered[td], processed[td], why);
+    rc = plan_ordered_bases((uint64_t)n, pl.radices, ordered[td], processed[td], why);
     if (rc) return fail(rc, why);
     p.stage_radices = ordered;  // (the other dims are framed / overlap-added, not transformed: no stages)
     rc = open_device(p, guard);
     if (rc) return rc;
-    rc = wgrad   ? build_conv_grad(p, ordered[td], processed[td], why)
-         : conv  ? build_conv(p, ordered[td], processed[td], why)
-         : mdct  ? build_mdct(p, ordered[td], processed[td], window, why)
-         : imdct ? build_imdct(p, ordered[td], processed[td], window, gain, why)
-         : fwd   ? build_stft(p, ordered[td], processed[td], window, fb, post, why)
-                 : build_istft(p, ordered[td], processed[td], window, gain, why);
+    switch (kind) {
+        case FramedKind::ConvGrad: rc = build_conv_grad(p, ordered[td], processed[td], why); break;
+        case FramedKind::Conv: rc = build_conv(p, ordered[td], processed[td], why); break;
+        case FramedKind::Mdct: rc = build_mdct(p, ordered[td], processed[td], pl, why); break;
+        case FramedKind::Imdct: rc = build_imdct(p, ordered[td], processed[td], pl, why); break;
+        case FramedKind::Stft: rc = build_stft(p, ordered[td], processed[td], pl, why); break;
+        case FramedKind::Adjoint:  // (the inverse STFT's pass, without the envelope)
+        case FramedKind::Istft: rc = build_istft(p, ordered[td], processed[td], pl, why); break;
+    }
     return rc ? fail(rc, why) : MIFFT_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -388,6 +389,43 @@ bool select_jit_dct_cols(const Plan& plan, DimPass& pass, std::string& why_not);
 int dctn_check(const Plan& plan, std::string& why);
 int build_dctn(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                const std::vector<std::vector<uint32_t>>& processed, std::string& why);
+// ---- the framed family: MIFFT_FLAG_STFT / MIFFT_FLAG_ISTFT plans and what their tagged payloads select -----------------------
+// Which member a plan is: decided once, by framed_kind (mifft_api.cpp), from the mode bit and the *_detect predicates below.
+enum class FramedKind { Stft, Istft, Adjoint, Mdct, Imdct, Conv, ConvGrad };
+// What a member's check decodes from `bases` for its build: the window (empty: rectangular), the filterbank and the matrix
+// after the bands of a spectrogram plan, the gain of the inverse kinds, the user radices of the one transformed dim (empty:
+// the default estimate).
+struct FramedPayload {
+    std::vector<double> window, fb, post;
+    double gain = 1.0;
+    std::vector<uint64_t> radices;
+};
+// a binary64 value as it travels through `bases`: two 32-bit words, low word first
+inline double word_pair(const uint32_t* w) {
+    const uint64_t bits = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    double v;
+    memcpy(&v, &bits, sizeof v);
+    return v;
+}
+// the n window values at the front of a payload; a value that is not finite is MIFFT_ERR_BAD_BASES (stft.cpp)
+int read_window(const uint32_t* bases_flat, int64_t n, std::vector<double>& window, std::string& why);
+// the `count` user radices `off` words into bases_flat, behind the payload (stft.cpp)
+void read_radices(const uint32_t* bases_flat, int64_t off, int count, std::vector<uint64_t>& radices);
+// A kind's table of the flag bits it refuses, in the order it refuses them: the first one set in `flags` is
+// MIFFT_ERR_UNSUPPORTED, "`prefix` + its text".
+struct FlagRefusal {
+    uint32_t bits;
+    const char* what;
+};
+template <size_t N>
+int refuse_flags(uint32_t flags, const FlagRefusal (&table)[N], const std::string& prefix, std::string& why) {
+    for (const FlagRefusal& o : table)
+        if (flags & o.bits) {
+            why = prefix + o.what;
+            return MIFFT_ERR_UNSUPPORTED;
+        }
+    return MIFFT_OK;
+}
 // plans with MIFFT_FLAG_STFT (stft.cpp): the checks that need no device (flags, shape, the window carried in `bases`), then
 // the single pass.  select_jit_stft_rows is the packed-row kernel with TileCfg::STFT (kernels_jit.cpp; compiled at run time
 // only), stft_rows_supported the same check without a device.  stft_flag_check: the STFT bits of a plan WITHOUT the flag.
@@ -400,28 +438,24 @@ int stft_check(const Plan& plan, std::string& why);
 // MIFFT_FLAG_STFT_POWER also the power and the filterbank (row-major (n / 2 + 1, M); M = 0: `fb` left empty), which set
 // plan.spec_power and plan.spec_bands.  A payload with MIFFT_STFT_EXT_TAG in the power slot also carries the log stage and
 // the (M, Q) matrix `post` (row-major; Q = 0: left empty), which set plan.spec_log, spec_add .. spec_c and plan.spec_post.
-int stft_unpack_bases(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                      std::vector<double>& fb, std::vector<double>& post, std::vector<uint64_t>& radices, std::string& why);
+int stft_unpack_bases(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_stft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, const std::vector<double>& fb, const std::vector<double>& post,
-               std::string& why);
+               const FramedPayload& payload, std::string& why);
 // MDCT plans (the MIFFT_FLAG_STFT payload tagged with MIFFT_MDCT_TAG; stft.cpp).  mdct_detect: is bases_len[0] the tagged
 // length 2 dims[1] + 4 with the tag behind the window?  (Pure; it looks at nothing else.)  mdct_check: everything that can be
 // refused without a device, leaving the window, the scale (plan.mdct_scale) and the user radices of M / 2 in its outputs.
 // build_mdct: the one pass, a DCT-IV tile with the framing, folding load.
 bool mdct_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len);
-int mdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-               std::vector<uint64_t>& radices, std::string& why);
+int mdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_mdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, std::string& why);
+               const FramedPayload& payload, std::string& why);
 // IMDCT plans (the MIFFT_FLAG_ISTFT payload tagged with MIFFT_MDCT_TAG; istft.cpp), in the same manner.  imdct_detect: does
 // the window payload end in TAG | gain?  (Pure; the length itself is imdct_check's business.)  select_jit_imdct_rows is the
 // DCT-IV kernel with TileCfg::IMDCT (run time only), imdct_rows_supported the same check without a device.
 bool imdct_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
-int imdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
-                std::vector<uint64_t>& radices, std::string& why);
+int imdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-                const std::vector<double>& window, double gain, std::string& why);
+                const FramedPayload& payload, std::string& why);
 bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
@@ -432,7 +466,7 @@ bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not
 // knows the first row of the exec, for the filter row of every launch row, and takes the exec's two gates (null where the plan
 // has none), offset to the exec's first signal row as `in` and `out` are.
 bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
-int conv_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
+int conv_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_conv(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 bool conv_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_conv_rows(const Plan& plan, DimPass& pass, std::string& why_not);
@@ -441,7 +475,7 @@ int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void*
 // The filter-gradient plans (MIFFT_CONV_GRAD_TAG): the same trio and the launch of the whole batch; build_conv_grad picks P where the payload says 0
 // for a built pass (pure arithmetic on its tile and the device's size).
 bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
-int conv_grad_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<uint64_t>& radices, std::string& why);
+int conv_grad_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_conv_grad(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, const void* gy, const void* pregate,
                          const void* postgate, void* out, hipStream_t stream);
@@ -457,18 +491,16 @@ inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }
 // built, enters the grid (tile_launch_geometry).
 bool istft_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
 bool select_jit_istft_rows(const Plan& plan, DimPass& pass, std::string& why_not);
-int istft_check(const Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                double& gain, std::vector<uint64_t>& radices, std::string& why);
+int istft_check(const Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_istft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-                const std::vector<double>& window, double gain, std::string& why);
+                const FramedPayload& payload, std::string& why);
 // STFT adjoint plans (the MIFFT_FLAG_ISTFT payload tagged with MIFFT_STFT_ADJ_TAG; istft.cpp).  stft_adj_detect: is
 // bases_len[0] the tagged length 2 n + 6 with the tag behind the window?  (Pure.)  stft_adj_check: istft_check's refusals
 // less the ones an adjoint has no use for (the covered length, the overlap-add condition), each reason naming the adjoint;
 // sets plan.stft_adj.  build_istft builds the pass (no envelope table).  launch_stft_adj is its launch, which takes the
 // exec's factor and edge tensors (null where the plan has none), offset to the exec's first entry as `in` and `out` are.
 bool stft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len);
-int stft_adj_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window, double& gain,
-                   std::vector<uint64_t>& radices, std::string& why);
+int stft_adj_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int launch_stft_adj(const Plan& plan, const DimPass& pass, const void* in, const void* mult, void* out, void* edge,
                     int64_t count, hipStream_t stream);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked

@@ -42,21 +42,14 @@ int stft_flag_check(uint32_t flags, std::string& why) {
 
 // checks that need no device: MIFFT_OK, or the status and its reason
 int stft_check(const Plan& p, std::string& why) {
-    const struct {
-        uint32_t bits;
-        const char* what;
-    } other[] = {{MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no STFT to be faithful to"},
+    const FlagRefusal other[] = {{MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no STFT to be faithful to"},
                  {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an STFT plan stores the half spectrum of every frame anyway"},
                  {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
                  {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
                  {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
                  {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an STFT plan frames dim 0 and transforms dim 1"},
                  {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
-    for (const auto& o : other)
-        if (p.flags & o.bits) {
-            why = std::string("MIFFT_FLAG_STFT with ") + o.what;
-            return MIFFT_ERR_UNSUPPORTED;
-        }
+    if (const int rc = refuse_flags(p.flags, other, "MIFFT_FLAG_STFT with ", why)) return rc;
     if (p.stft_hop() == 0) {
         why = "MIFFT_FLAG_STFT with hop 0: MIFFT_FLAG_STFT_HOP(h) carries the hop, 1 .. 65535";
         return MIFFT_ERR_UNSUPPORTED;
@@ -117,11 +110,21 @@ int stft_check(const Plan& p, std::string& why) {
     return MIFFT_OK;
 }
 
-static double word_pair(const uint32_t* w) {
-    const uint64_t bits = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    double v;
-    memcpy(&v, &bits, sizeof v);
-    return v;
+int read_window(const uint32_t* bases_flat, int64_t n, std::vector<double>& window, std::string& why) {
+    window.resize((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+        window[(size_t)j] = word_pair(bases_flat + 2 * j);
+        if (!std::isfinite(window[(size_t)j])) {
+            why = "window value " + std::to_string(j) + " is not finite";
+            return MIFFT_ERR_BAD_BASES;
+        }
+    }
+    return MIFFT_OK;
+}
+
+void read_radices(const uint32_t* bases_flat, int64_t off, int count, std::vector<uint64_t>& radices) {
+    radices.clear();
+    for (int k = 0; k < count; ++k) radices.push_back(bases_flat[off + k]);
 }
 
 // a header value of the tagged payload that has to be a non-negative integer
@@ -233,14 +236,11 @@ static int stft_unpack_tagged(Plan& p, const uint32_t* bases_flat, int64_t len0,
     return MIFFT_OK;
 }
 
-int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-                      std::vector<double>& fb, std::vector<double>& post, std::vector<uint64_t>& radices, std::string& why) {
+int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
     const int64_t n = p.dims[1], K = n / 2 + 1;
     const bool spec = (p.flags & MIFFT_FLAG_STFT_POWER) != 0;
-    window.clear();
-    fb.clear();
-    post.clear();
-    radices.clear();
+    pl = FramedPayload();
+    std::vector<double>& fb = pl.fb;
     p.spec_power = 0;
     p.spec_bands = 0;
     p.spec_post = 0;
@@ -250,7 +250,7 @@ int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_
     const bool tagged = spec && bases_flat && bases_len && (int64_t)bases_len[0] >= 2 * n + 2 &&
                         bases_flat[2 * n] == MIFFT_STFT_EXT_TAG_LO && bases_flat[2 * n + 1] == MIFFT_STFT_EXT_TAG_HI;
     if (tagged) {
-        const int rc = stft_unpack_tagged(p, bases_flat, (int64_t)bases_len[0], fb, post, why);
+        const int rc = stft_unpack_tagged(p, bases_flat, (int64_t)bases_len[0], fb, pl.post, why);
         if (rc) return rc;
     } else if (spec) {  // the window written out, the power, and M columns of K weights: 2 n + 2 + 2 M K words
         const int64_t len0 = bases_len ? (int64_t)bases_len[0] : 0, rest = len0 - 2 * n - 2;
@@ -278,17 +278,8 @@ int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_
         why = "negative bases_len";
         return MIFFT_ERR_NO_BASES;
     }
-    if (bases_len[0]) {
-        window.resize((size_t)n);
-        for (int64_t j = 0; j < n; ++j) {
-            const double v = word_pair(bases_flat + 2 * j);
-            if (!std::isfinite(v)) {
-                why = "window value " + std::to_string(j) + " is not finite";
-                return MIFFT_ERR_BAD_BASES;
-            }
-            window[(size_t)j] = v;
-        }
-    }
+    if (bases_len[0])
+        if (const int rc = read_window(bases_flat, n, pl.window, why)) return rc;
     if (spec && !tagged) {
         const double power = word_pair(bases_flat + 2 * n);
         if (!(power == 1.0 || power == 2.0)) {  // (NaN included)
@@ -307,7 +298,7 @@ int stft_unpack_bases(Plan& p, const uint32_t* bases_flat, const int32_t* bases_
             fb[i] = v;
         }
     }
-    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    read_radices(bases_flat, bases_len[0], bases_len[1], pl.radices);
     return MIFFT_OK;
 }
 
@@ -328,12 +319,8 @@ bool mdct_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, cons
     return (int64_t)bases_len[0] == 2 * n + 4 && bases_flat[2 * n] == MIFFT_MDCT_TAG_LO && bases_flat[2 * n + 1] == MIFFT_MDCT_TAG_HI;
 }
 
-int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, std::vector<double>& window,
-               std::vector<uint64_t>& radices, std::string& why) {
-    const struct {
-        uint32_t bits;
-        const char* what;
-    } other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: an MDCT has no magnitude or power store"},
+int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
+    const FlagRefusal other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: an MDCT has no magnitude or power store"},
                  {MIFFT_FLAG_STFT_CENTER_REFLECT, "MIFFT_FLAG_STFT_CENTER_REFLECT: the frames of an MDCT see zeros beyond both ends"},
                  {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no MDCT to be faithful to"},
                  {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: an MDCT has no half spectrum"},
@@ -342,11 +329,7 @@ int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
                  {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO: the norm of an MDCT travels as the scale of its payload"},
                  {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: an MDCT plan frames dim 0 and transforms dim 1"},
                  {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
-    for (const auto& o : other)
-        if (p.flags & o.bits) {
-            why = std::string("an MDCT payload (MIFFT_MDCT_TAG) with ") + o.what;
-            return MIFFT_ERR_UNSUPPORTED;
-        }
+    if (const int rc = refuse_flags(p.flags, other, "an MDCT payload (MIFFT_MDCT_TAG) with ", why)) return rc;
     if (!(p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS)) {
         why = "an MDCT payload (MIFFT_MDCT_TAG) without a centre bit: MIFFT_FLAG_STFT_CENTER_ZEROS is required";
         return MIFFT_ERR_UNSUPPORTED;
@@ -390,30 +373,21 @@ int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, st
         why = "negative bases_len";
         return MIFFT_ERR_NO_BASES;
     }
-    window.resize((size_t)n);
-    for (int64_t j = 0; j < n; ++j) {
-        const double v = word_pair(bases_flat + 2 * j);
-        if (!std::isfinite(v)) {
-            why = "window value " + std::to_string(j) + " is not finite";
-            return MIFFT_ERR_BAD_BASES;
-        }
-        window[(size_t)j] = v;
-    }
+    if (const int rc = read_window(bases_flat, n, pl.window, why)) return rc;
     const double scale = word_pair(bases_flat + 2 * n + 2);
     if (!std::isfinite(scale) || scale == 0.0) {
         why = "the scale of an MDCT payload is finite and not zero, not " + std::to_string(scale);
         return MIFFT_ERR_BAD_BASES;
     }
-    radices.clear();
-    for (int k = 0; k < bases_len[1]; ++k) radices.push_back(bases_flat[bases_len[0] + k]);
+    read_radices(bases_flat, bases_len[0], bases_len[1], pl.radices);
     p.mdct = M;
     p.mdct_scale = scale;
     return MIFFT_OK;
 }
 
 // the one pass: a DCT-IV of M points (dim 1) over the F frames of every batch entry, framed, windowed and folded by its load
-int build_mdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, std::string& why) {
+int build_mdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
+               std::string& why) {
     const int64_t M = p.mdct;
     DimPass ps;
     ps.dim_index = 1;
@@ -428,7 +402,7 @@ int build_mdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     hipError_t e = upload_twiddle_table(p.out_dtype, M / 2, false, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, M, &ps.d_aux2);
     if (e == hipSuccess)
-        e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(2 * M, window, &ps.d_aux3) : upload_window_t<float>(2 * M, window, &ps.d_aux3);
+        e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(2 * M, pl.window, &ps.d_aux3) : upload_window_t<float>(2 * M, pl.window, &ps.d_aux3);
     p.passes.push_back(ps);
     if (e != hipSuccess) return hip_error(e, "MDCT table upload");
     return MIFFT_OK;
@@ -465,8 +439,7 @@ static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>
 }
 
 // the one pass: dim 1 (n points) over the F frames of every batch entry
-int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
-               const std::vector<double>& window, const std::vector<double>& fb, const std::vector<double>& post,
+int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
                std::string& why) {
     const int64_t n = p.dims[1];
     DimPass ps;
@@ -483,10 +456,10 @@ int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<
     hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
     if (e == hipSuccess)
-        e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(n, window, &ps.d_aux2) : upload_window_t<float>(n, window, &ps.d_aux2);
+        e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(n, pl.window, &ps.d_aux2) : upload_window_t<float>(n, pl.window, &ps.d_aux2);
     if (e == hipSuccess && p.spec_bands > 0)
-        e = p.out_dtype == MIFFT_F64 ? upload_bands_t<double>(n / 2 + 1, p.spec_bands, fb, post, p.spec_post_off, &ps.d_aux3)
-                                     : upload_bands_t<float>(n / 2 + 1, p.spec_bands, fb, post, p.spec_post_off, &ps.d_aux3);
+        e = p.out_dtype == MIFFT_F64 ? upload_bands_t<double>(n / 2 + 1, p.spec_bands, pl.fb, pl.post, p.spec_post_off, &ps.d_aux3)
+                                     : upload_bands_t<float>(n / 2 + 1, p.spec_bands, pl.fb, pl.post, p.spec_post_off, &ps.d_aux3);
     p.passes.push_back(ps);
     if (e != hipSuccess) return hip_error(e, "STFT table upload");
     return MIFFT_OK;
