@@ -65,6 +65,8 @@ CONV_GRAD_ARGS_MAGIC = 0x314757544646494D  # MIFFT_CONV_GRAD_ARGS_MAGIC ("MIFFTW
 CONV_GRAD_GATED_ARGS_MAGIC = 0x324757544646494D  # MIFFT_CONV_GRAD_GATED_ARGS_MAGIC ("MIFFTWG2")
 STFT_ADJ_TAG_LO = 0x4A444101   # MIFFT_STFT_ADJ_TAG_LO / _HI: the NaN behind the window of a FLAG_ISTFT plan that is the adjoint of
 STFT_ADJ_TAG_HI = 0x7FF84D41   # the STFT (w | TAG | gain | mode, 0)
+ISTFT_ADJ_TAG_LO = 0x4A444901  # MIFFT_ISTFT_ADJ_TAG_LO / _HI: the NaN behind the window of a FLAG_STFT plan that is the adjoint of
+ISTFT_ADJ_TAG_HI = 0x7FF84D4A  # the inverse STFT (w | TAG | gain | frames, 0)
 STFT_ADJ_ARGS_MAGIC = 0x314153544646494D  # MIFFT_STFT_ADJ_ARGS_MAGIC ("MIFFTSA1")
 MAX_DIMS = 6            # MIFFT_MAX_DIMS
 
@@ -473,6 +475,23 @@ def _check_stft_adjoint_layout(in_shape: tuple, out_shape: tuple, hop: int, cent
     return (T, F, n)
 
 
+def _check_istft_adjoint_layout(in_shape: tuple, out_shape: tuple, hop: int, center) -> tuple:
+    """Layouts of an inverse STFT adjoint plan (MIFFT_ISTFT_ADJ_TAG on MIFFT_FLAG_STFT): x (batch, T, 1) real, the incoming
+    gradient -> out (batch, F, n // 2 + 1, 2), with the limits of the inverse plan it is the adjoint of, hop <= n and
+    2 <= T <= n + hop (F - 1) - (centred: n // 2), the bound ``_check_istft_layout`` sets for that plan (the C ABI itself
+    accepts T = 1 for both); returns the dims (T, n).  ``center``: None / False, or True / "constant"."""
+    if len(in_shape) != 3 or len(out_shape) != 4:
+        raise MifftError(-1, f"inverse STFT adjoint layouts are (batch, T, 1) -> (batch, F, n // 2 + 1, 2), got {in_shape} -> "
+                             f"{out_shape}")
+    if center == "reflect":
+        raise MifftError(ERR_UNSUPPORTED, "the inverse STFT adjoint sees zeros beyond both ends: center is None / False, True or "
+                                          "\"constant\", not \"reflect\"")
+    if in_shape[-1] != 1:
+        raise MifftError(-3, f"an inverse STFT adjoint reads real gradients (1 component), got {in_shape[-1]}")
+    _check_istft_layout(out_shape, in_shape, hop, center)
+    return (in_shape[1], 2 * (out_shape[2] - 1))
+
+
 def _window_f64(window, n_fft: int) -> "torch.Tensor":
     """a window as n_fft float64 values on the host (a CUDA tensor is copied, which synchronises its stream)"""
     w = torch.as_tensor(window).detach().to(device="cpu", dtype=torch.float64).contiguous()
@@ -513,6 +532,10 @@ class FrameRequest(NamedTuple):
         nothing without either.
     "adjoint" (``stft_adjoint=`` beside ``istft_hop``, plan_stft_adjoint; MIFFT_STFT_ADJ_TAG, _check_stft_adjoint_layout): the
         adjoint of the "stft" plan of these values, ``adjoint`` its mode 1, 2 or 3.  Payload: w | TAG | gain | mode, 0.
+    "istft_adjoint" (``istft_adjoint=`` F beside ``stft_hop``, plan_istft_adjoint; MIFFT_ISTFT_ADJ_TAG on a MIFFT_FLAG_STFT plan,
+        _check_istft_adjoint_layout): the adjoint of the "istft" plan of these values and ``frames`` = F frames: x (batch, T, 1),
+        the incoming gradient -> out (batch, F, n // 2 + 1, 2); ``center`` None / False or True / "constant"; ``gain`` the
+        inverse plan's.  Payload: w | TAG | gain | frames, 0, the window written out.
     "mdct" (``mdct=`` M, plan_mdct; MIFFT_MDCT_TAG, _check_mdct_layout): x (batch, T, 1) -> out (batch, F, M, 1), frames of
         n = 2 M samples every hop = M; ``gain`` the factor on the cosine sum.  Payload: w | TAG | gain.
     "imdct" (``imdct=`` M, plan_imdct; MIFFT_MDCT_TAG on a MIFFT_FLAG_ISTFT plan, _check_imdct_layout): x (batch, F, M, 1) ->
@@ -530,6 +553,7 @@ class FrameRequest(NamedTuple):
     log: object = None
     post: object = None
     adjoint: int = 0
+    frames: int = 0
 
 
 def _frame_payload(r) -> tuple:
@@ -538,7 +562,7 @@ def _frame_payload(r) -> tuple:
     another length than the frames."""
     if isinstance(r, ConvRequest):
         return FLAG_STFT, _conv_payload(r), 1
-    if r.kind not in ("stft", "spec", "istft", "adjoint", "mdct", "imdct"):
+    if r.kind not in ("stft", "spec", "istft", "adjoint", "istft_adjoint", "mdct", "imdct"):
         raise MifftError(ERR_UNSUPPORTED, f"unknown kind of framed plan {r.kind!r}")
     bits = FLAG_STFT_HOP(r.hop)
     if r.window is not None:
@@ -553,6 +577,14 @@ def _frame_payload(r) -> tuple:
         return bits | side[0] | FLAG_STFT_CENTER_ZEROS, w + [MDCT_TAG_LO, MDCT_TAG_HI] + scale, side[1]
     if r.kind == "istft":  # (a list of Python floats goes through torch's default dtype: this gain has always travelled as float32's)
         return bits | FLAG_ISTFT | _istft_center_flags(r.center), w + (_f64_words([float(r.gain)]) if float(r.gain) != 1.0 else []), 2
+    if r.kind == "istft_adjoint":  # (the gain travels as the inverse plan's does: both plans scale by the same number)
+        if r.center == "reflect" or not 1 <= int(r.frames) < 1 << 32:
+            raise MifftError(ERR_UNSUPPORTED if r.center == "reflect" else -2,
+                             f"an inverse STFT adjoint has center None / False, True or \"constant\" and 1 <= frames < 2^32, got "
+                             f"{r.center!r} and {r.frames}")
+        centred = FLAG_STFT_CENTER_ZEROS if _istft_center_flags(r.center) else 0
+        return (bits | FLAG_STFT | centred,
+                w + [ISTFT_ADJ_TAG_LO, ISTFT_ADJ_TAG_HI] + _f64_words([float(r.gain)]) + [int(r.frames), 0], 1)
     bits |= _stft_center_flags(r.center)
     if r.kind == "adjoint":
         return bits | FLAG_ISTFT, w + [STFT_ADJ_TAG_LO, STFT_ADJ_TAG_HI] + _f64_words([float(r.gain)]) + [int(r.adjoint), 0], 2
@@ -613,7 +645,7 @@ _FRAMED_NO_AXES = {"stft": "an STFT plan frames dim 0 and transforms dim 1: no a
                    "mdct": "an MDCT plan frames dim 0 and transforms dim 1: no axes",
                    "imdct": "an IMDCT plan transforms dim 2 and overlap-adds dim 1: no axes",
                    "conv": "a convolution plan extends dim 0 and transforms dim 1: no axes"}
-_FRAMED_NO_AXES.update(spec=_FRAMED_NO_AXES["stft"], adjoint=_FRAMED_NO_AXES["istft"])
+_FRAMED_NO_AXES.update(spec=_FRAMED_NO_AXES["stft"], adjoint=_FRAMED_NO_AXES["istft"], istft_adjoint=_FRAMED_NO_AXES["stft"])
 
 
 class Plan:
@@ -660,7 +692,8 @@ class Plan:
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None, stft_adjoint: int = 0):
+                 imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None, stft_adjoint: int = 0,
+                 istft_adjoint: int = 0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct, flags = int(mdct), int(imdct), int(flags)
         if dct_type not in (2, 4):
@@ -670,7 +703,7 @@ class Plan:
         # 1. the framed kinds asked for, in the order their checks run; the last one is the plan's.  Any other mode asked for
         #    beside them travels as its bit, so that the library refuses the pair.
         kinds = [k for k, asked in (("imdct", imdct), ("adjoint", istft and stft_adjoint), ("istft", istft)) if asked][:1]
-        kinds += ["spec" if stft_power is not None else "stft"] if stft and not kinds else []
+        kinds += ["istft_adjoint" if istft_adjoint else "spec" if stft_power is not None else "stft"] if stft and not kinds else []
         kinds += (["mdct"] if mdct and not imdct else []) + (["conv"] if conv is not None else [])
         foreign = ((FLAG_STFT if stft or mdct else 0) | (FLAG_DCT_ND if dctn else 0) | (FLAG_DCT if dct else 0) |
                    (FLAG_HALF_SPECTRUM if half_spectrum else 0))
@@ -689,6 +722,14 @@ class Plan:
                 check_layout = _check_stft_adjoint_layout if kind == "adjoint" else _check_istft_layout
                 framed_dims = check_layout(in_shape, out_shape, istft_hop, stft_center)
                 req = FrameRequest(kind, framed_dims[2], istft_hop, stft_center, stft_window, istft_gain, adjoint=stft_adjoint)
+            elif kind == "istft_adjoint":  # (istft_adjoint = F beside stft_hop; the gain is istft_gain, the inverse plan's)
+                if stft_power is not None or stft_fb is not None or stft_log is not None or stft_post is not None:
+                    raise MifftError(ERR_UNSUPPORTED, "istft_adjoint with stft_power / stft_fb / stft_log / stft_post: the adjoint "
+                                                      "of the inverse STFT stores complex bins")
+                framed_dims = _check_istft_adjoint_layout(in_shape, out_shape, stft_hop, stft_center)
+                if out_shape[1] != int(istft_adjoint):
+                    raise MifftError(-2, f"istft_adjoint = {istft_adjoint} frames, out has {out_shape[1]}")
+                req = FrameRequest(kind, framed_dims[1], stft_hop, stft_center, stft_window, istft_gain, frames=int(istft_adjoint))
             elif kind in ("stft", "spec"):
                 if not int(stft_hop):
                     stft_hop = (flags & FLAG_STFT_HOP_MASK) >> 16
@@ -777,6 +818,7 @@ class Plan:
         self.mdct = mdct if kind == "mdct" else 0
         self.imdct = imdct if kind == "imdct" else 0
         self.stft_adjoint = int(stft_adjoint) if kind == "adjoint" else 0
+        self.istft_adjoint = int(istft_adjoint) if kind == "istft_adjoint" else 0
         self.conv = conv
         self.conv_gates = conv.gates if conv is not None else 0
         self._ndim = len(dims)
@@ -1177,6 +1219,44 @@ def plan_stft_adjoint(dtype, batch: int, length: int, n_fft: int, hop_length: in
     if ctx is None:
         ctx = DeviceContext()
     return StftAdjointPlan(dtype, batch, length, n_fft, hop_length, window, center, multiplier, ctx)
+
+
+def plan_istft_adjoint(dtype, batch: int, frames: int, n_fft: int, hop_length: int, *, window=None, center=False,
+                       gain: float = 1.0, length: Optional[int] = None, ctx: Optional[DeviceContext] = None) -> Plan:
+    """Plan of the adjoint of ``plan_istft(dtype, batch, frames, n_fft, hop_length, window=, center=, length=)`` (no reference
+    counterpart; MIFFT_ISTFT_ADJ_TAG in include/mifft.h): the gradient of that plan's result with respect to its frames, the
+    one-sided STFT of gy / envelope, in ONE launch, no scratch, no memset, no atomics.  ``window`` (None: rectangular) and
+    ``center`` (None / False, or True / "constant") are the inverse plan's, ``gain`` its factor on the synthesis window
+    (sqrt(n_fft) for ``normalized=True``), ``length`` its output samples per entry, default istft_length(frames, n_fft,
+    hop_length, center).  The plan has ``in_shape`` (batch, length, 1), the incoming gradient gy, and ``out_shape``
+    (batch, frames, n_fft // 2 + 1, 2), dL/dRe X + i dL/dIm X frames-major, both of ``dtype`` (float32 / float64), and runs
+    through ``fft(out, gy, plan=plan)``, ``first=`` / ``count=`` included.  The load divides by the very envelope table the
+    inverse plan divides by and selects zeros beyond both ends of [0, length): a frame that sees no stored sample is an exact
+    zero, and so are the imaginary parts of bins 0 and n_fft // 2, which the inverse ignores.  A frame's result is
+    bit-identical for any batch and slab.  Everything the inverse plan refuses is refused here -- ``hop_length > n_fft``, a
+    ``length`` beyond what the frames cover, a window that breaks the nonzero overlap-add condition in the output range (-15)
+    -- and so is ``center="reflect"``; every argument error is raised before any device work."""
+    batch, frames, n_fft, hop_length = int(batch), int(frames), int(n_fft), int(hop_length)
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"an inverse STFT adjoint plan reads and writes float32 or float64, got {dtype}")
+    if n_fft % 2 or n_fft < 8:
+        raise MifftError(ERR_UNSUPPORTED, f"STFT with an odd n_fft or one below 8 ({n_fft}) is not supported")
+    FLAG_STFT_HOP(hop_length)
+    gain = float(gain)
+    if not math.isfinite(gain) or gain == 0.0:
+        raise MifftError(-5, f"the gain is finite and not zero, got {gain!r}")
+    if center == "reflect":
+        raise MifftError(ERR_UNSUPPORTED, "plan_istft_adjoint: center is None / False, True or \"constant\", not \"reflect\"")
+    centred = _istft_center_flags(center) != 0
+    T = istft_length(frames, n_fft, hop_length, centred) if length is None else int(length)
+    in_shape, out_shape = (batch, T, 1), (batch, frames, n_fft // 2 + 1, 2)
+    _check_istft_adjoint_layout(in_shape, out_shape, hop_length, center)
+    if window is not None:
+        window = _window_f64(window, n_fft)
+    if ctx is None:
+        ctx = DeviceContext()
+    return Plan(dtype, dtype, in_shape, out_shape, device=ctx.device, stft_hop=hop_length, stft_center=center,
+                stft_window=window, istft_gain=gain, istft_adjoint=frames)
 
 
 def time_fft(output: "torch.Tensor", x: "torch.Tensor", *, plan: Plan, iters: int = 10,
@@ -1756,7 +1836,13 @@ def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -
     orthonormal DCT-IV of the folded frame).  n is even, from 8 to 16384 (float64: 12288), n // 2 without a prime factor above
     32.  Input that is not of ``out_dtype`` (default: that of a float32 / float64 ``x``, else float64) is converted first.
     One kernel launch: the framing, the window and the fold of 2n samples to n happen in the load of a DCT-IV tile.  Plans are
-    cached per (shape, dtype, n, norm, device, stream) and the window's contents; loops should use ``plan_mdct``."""
+    cached per (shape, dtype, n, norm, device, stream) and the window's contents; loops should use ``plan_mdct``.
+    Differentiable with respect to ``x`` (first order): when grad mode is on and ``x.requires_grad``, the result carries a
+    ``grad_fn`` whose backward is ONE launch of the fused inverse (``plan_imdct`` with this call's scale as its gain, the same
+    window and ``length=T``): the two plans are transposes of each other, so there is no kernel of its own.  The adjoint plan
+    is made in the forward, under the key ``imdct`` itself uses, so that a refusal is a MifftError there.  Otherwise the call
+    is what it has always been: same plan, same bits, no ``grad_fn``.  The window is taken by value and gets no gradient;
+    there is no double backward."""
     if x.is_complex():
         raise MifftError(-3, "mdct expects a real tensor")
     if x.dim() < 1:
@@ -1767,21 +1853,121 @@ def mdct(x: "torch.Tensor", n: int, *, window=None, norm=None, out_dtype=None) -
         out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
     if out_dtype not in _OUT_DTYPES:
         raise MifftError(-4, f"mdct: out_dtype must be float32 or float64, got {out_dtype}")
-    logical = tuple(x.shape)
-    T, batch = logical[-1], math.prod(logical[:-1])
+    T = int(x.shape[-1])
     if T < 2:
         raise MifftError(-2, f"mdct: signals of {T} samples: at least 2")
-    frames = mdct_frames(T, n)
-    in_shape, out_shape = (batch, T, 1), (batch, frames, n, 1)
     w = None if window is None else _window_f64(window, 2 * n)
     device = _signal_device(x, "x")
-    xr = x.to(out_dtype).contiguous().reshape(in_shape)
-    out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
+    if torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad:  # (w: a fresh host table, kept by value)
+        return _MDCTFunction.apply(x, (out_dtype, n, scale, None if w is None else w.clone(), device))
+    return _mdct_exec(x, out_dtype, n, scale, w, device)
+
+
+def _mdct_exec(x, dt, n: int, scale: float, w, device: int) -> "torch.Tensor":
+    """the one launch of an accepted mdct call -- and of the backward of imdct, whose adjoint it is: x (..., T) -> (..., F, n)"""
+    lead, T = tuple(x.shape[:-1]), int(x.shape[-1])
+    frames = mdct_frames(T, n)
+    in_shape, out_shape = (math.prod(lead), T, 1), (math.prod(lead), frames, n, 1)
+    xr = x.to(dt).contiguous().reshape(in_shape)
+    out = torch.empty(out_shape, dtype=dt, device=xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _plan_cached(("mdct", out_dtype, in_shape, n, scale), device, lambda: Plan(
-            out_dtype, out_dtype, in_shape, out_shape, device=device, mdct=n, mdct_scale=scale, stft_window=w), w)
-        fft(out, xr, DeviceContext(device), plan=plan)
-    return out.reshape(logical[:-1] + (frames, n))
+        fft(out, xr, DeviceContext(device), plan=_mdct_plan(dt, in_shape, n, scale, w, device))
+    return out.reshape(lead + (frames, n))
+
+
+def _mdct_plan(dt, in_shape: tuple, n: int, scale: float, w, device: int) -> Plan:
+    """the cached MDCT plan of signals (batch, T, 1) (under the cache's lock, which a caller that launches holds already)"""
+    out_shape = (in_shape[0], mdct_frames(in_shape[1], n), n, 1)
+    with _PLAN_CACHE_LOCK:
+        return _plan_cached(("mdct", dt, in_shape, n, scale), device, lambda: Plan(
+            dt, dt, in_shape, out_shape, device=device, mdct=n, mdct_scale=scale, stft_window=w), w)
+
+
+def _imdct_plan(dt, in_shape: tuple, n: int, length: int, gain: float, w, device: int) -> Plan:
+    """the cached IMDCT plan of frames (batch, F, n, 1) and ``length`` samples, likewise"""
+    with _PLAN_CACHE_LOCK:
+        return _plan_cached(("imdct", dt, in_shape, length, gain), device, lambda: Plan(
+            dt, dt, in_shape, (in_shape[0], length, 1), device=device, imdct=n, imdct_gain=gain, stft_window=w), w)
+
+
+class _MDCTFunction(torch.autograd.Function):
+    """mdct with the gradient with respect to x.  The fold and the unfold are transposes of each other and the DCT-IV is
+    symmetric, so the adjoint of the MDCT plan with scale s and window w on T samples is the IMDCT plan with gain s, the same
+    w and length T: one launch, no kernel of its own.  First order."""
+
+    @staticmethod
+    def forward(ctx, x, call):
+        dt, n, scale, w, device = call
+        y = _mdct_exec(x, dt, n, scale, w, device)
+        try:
+            _imdct_plan(dt, (math.prod(y.shape[:-2]), int(y.shape[-2]), n, 1), n, int(x.shape[-1]), scale, w, device)
+        except MifftError as e:
+            raise MifftError(e.status, f"mdct: no gradient with respect to x for these arguments ({e}); the forward alone "
+                                       f"works on an x without requires_grad (or under torch.no_grad())") from None
+        ctx.call, ctx.x_shape, ctx.x_dtype = call, tuple(x.shape), x.dtype
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        dt, n, scale, w, device = ctx.call
+        T, batch, frames = ctx.x_shape[-1], math.prod(ctx.x_shape[:-1]), int(gy.shape[-2])
+        g = gy.to(dt).contiguous().reshape(batch, frames, n, 1)
+        out = torch.empty((batch, T, 1), dtype=dt, device=g.device)
+        with _PLAN_CACHE_LOCK:
+            fft(out, g, DeviceContext(device), plan=_imdct_plan(dt, tuple(g.shape), n, T, scale, w, device))
+        return out.reshape(ctx.x_shape).to(ctx.x_dtype), None
+
+
+class _IMDCTFunction(torch.autograd.Function):
+    """imdct with the gradient with respect to X: the adjoint of the IMDCT plan with gain g and window w, F frames and length T
+    is the MDCT plan with scale g on gy, which yields mdct_frames(T, n) <= F frames; the frames beyond those see no stored
+    sample and have a zero gradient.  One launch.  First order."""
+
+    @staticmethod
+    def forward(ctx, X, call):
+        dt, n, gain, w, length, device = call
+        lead, F = tuple(X.shape[:-2]), int(X.shape[-2])
+        in_shape = (math.prod(lead), F, n, 1)
+        Xr = X.to(dt).contiguous().reshape(in_shape)
+        out = torch.empty((in_shape[0], length, 1), dtype=dt, device=Xr.device)
+        with _PLAN_CACHE_LOCK:
+            try:
+                plan = _imdct_plan(dt, in_shape, n, length, gain, w, device)
+                _mdct_plan(dt, (in_shape[0], _IMDCTFunction._adjoint_samples(in_shape[0], F, n, length), 1), n, gain, w, device)
+            except MifftError as e:
+                raise MifftError(e.status, f"imdct: no gradient with respect to X for these arguments ({e}); the forward alone "
+                                           f"works on an X without requires_grad (or under torch.no_grad())") from None
+            fft(out, Xr, DeviceContext(device), plan=plan)
+        ctx.call, ctx.x_shape, ctx.x_dtype = call, tuple(X.shape), X.dtype
+        return out.reshape(lead + (length,))
+
+    @staticmethod
+    def _adjoint_samples(batch: int, F: int, n: int, length: int) -> int:
+        """samples per entry of the MDCT plan the backward runs: ``length`` -- or, with several entries AND a cropped length,
+        the (F - 1) n samples that make all F frames (gy is continued by zeros to them: see backward)"""
+        return length if mdct_frames(length, n) == F or batch == 1 else (F - 1) * n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        dt, n, gain, w, length, device = ctx.call
+        lead, F = ctx.x_shape[:-2], ctx.x_shape[-2]
+        batch, Fm = math.prod(lead), mdct_frames(length, n)
+        g = gy.to(dt).contiguous().reshape(batch, length, 1)
+        gX = torch.empty((batch, F, n, 1), dtype=dt, device=g.device)
+        if Fm == F or batch == 1:  # the plan's frames are the first Fm of every entry: written in place, only the rest zero-filled
+            gX[:, Fm:].zero_()
+            with _PLAN_CACHE_LOCK:
+                fft(gX[:, :Fm], g, DeviceContext(device), plan=_mdct_plan(dt, tuple(g.shape), n, gain, w, device))
+        else:
+            # (several entries whose rows are longer than the plan's: the plan stores Fm contiguous frames per entry, so gy is
+            # continued by zeros to the (F - 1) n samples that make F frames -- the frames beyond Fm come out as exact zeros)
+            gp = torch.zeros((batch, (F - 1) * n, 1), dtype=dt, device=g.device)
+            gp[:, :length] = g
+            with _PLAN_CACHE_LOCK:
+                fft(gX, gp, DeviceContext(device), plan=_mdct_plan(dt, tuple(gp.shape), n, gain, w, device))
+        return gX.reshape(ctx.x_shape).to(ctx.x_dtype), None
 
 
 # ---------------------------------------------------------------------------
@@ -2857,7 +3043,16 @@ def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = 
     store of a DCT-IV tile; no tensor of frames and no zeroed buffer exist.  Input that is not float32 / float64 is converted
     to float64 first.  Plans are cached per (shape, dtype, n, norm, length, device, stream) and the window's contents; loops
     should use ``plan_imdct``.  Only what the fused plan refuses -- ``length == 1``, or a tile and carry beyond the CU's LDS
-    (no admissible n today) -- runs the earlier composition, one DCT-IV launch plus torch."""
+    (no admissible n today) -- runs the earlier composition, one DCT-IV launch plus torch.
+    Differentiable with respect to ``X`` (first order): when grad mode is on and ``X.requires_grad``, the result carries a
+    ``grad_fn`` whose backward is ONE launch of the fused MDCT (``plan_mdct`` with this call's gain as its scale and the same
+    window) on the incoming gradient; it yields the mdct_frames(length, n) <= F frames that see a stored sample, and the
+    frames beyond them get an exact zero.  The adjoint plan is made in the forward, under the key ``mdct`` itself uses.  With
+    several batch entries AND a ``length`` cropped below the last frames, the plan's rows are shorter than the gradient's, so
+    that case costs one zero-padded copy of gy (to (F - 1) n samples per entry) before its one launch.  The
+    two cases that run the earlier composition raise a MifftError in the forward of a call that wants a gradient; the forward
+    alone works under ``torch.no_grad()``.  Otherwise the call is what it has always been: same plan, same bits, no
+    ``grad_fn``.  The window is taken by value and gets no gradient; there is no double backward."""
     if X.is_complex():
         raise MifftError(-3, "imdct expects a real tensor")
     if X.dim() < 2:
@@ -2874,6 +3069,12 @@ def imdct(X: "torch.Tensor", *, window=None, norm=None, length: Optional[int] = 
     device = _signal_device(X, "X")
     ortho = gain != 2.0 / n
     lead = tuple(X.shape[:-2])
+    wants_grad = torch.is_grad_enabled() and isinstance(X, torch.Tensor) and X.requires_grad
+    if length == 1 and wants_grad:
+        raise MifftError(ERR_UNSUPPORTED, "imdct: no gradient with respect to X for length = 1, which the fused plan refuses; "
+                                          "the forward alone works under torch.no_grad()")
+    if wants_grad:  # (w: a fresh host table, kept by value; the LDS refusal of the fused plan is raised in the forward)
+        return _IMDCTFunction.apply(X, (dt, n, gain, None if w is None else w.clone(), length, device))
     if length == 1:
         return _imdct_composed(X.to(dt), mdct_window(n) if w is None else w, ortho, length)
     batch = math.prod(lead)
@@ -3275,7 +3476,48 @@ def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_l
     The kernel reads frames-major (..., F, n_fft // 2 + 1) memory: when ``X.transpose(-1, -2)`` is contiguous -- exactly the
     view ``stft`` returns -- X is used as it lies, with no copy; otherwise ONE transposing copy is made first.
     One kernel launch: no tensor of frames, no fold, no memset (MIFFT_FLAG_ISTFT in include/mifft.h).  Plans are cached like
-    ``stft``'s: per (shape, dtype, n_fft, hop, centring, length, gain, device, stream) AND the window's contents."""
+    ``stft``'s: per (shape, dtype, n_fft, hop, centring, length, gain, device, stream) AND the window's contents.
+    Differentiable with respect to ``X`` (first order): when grad mode is on and ``X.requires_grad``, the result carries a
+    ``grad_fn`` whose backward is ONE launch of the fused adjoint (``plan_istft_adjoint``) on the incoming gradient: the STFT
+    tile with the reciprocal envelope in its load.  The gradient comes back in ``X``'s shape and dtype, as the transposed view
+    of the frames-major tensor the kernel writes (no transposing copy), in torch's convention dL/dRe X + i dL/dIm X; the
+    imaginary parts of bins 0 and n_fft // 2, which the forward ignores, get an exact zero.  The adjoint plan is made, and
+    cached under a key of its own, in the forward, so that what it refuses is a MifftError there.  Otherwise the call is what
+    it has always been: same plan, same bits, no ``grad_fn``.  The window is taken by value and gets no gradient; there is no
+    double backward."""
+    call = _istft_call(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex, out_dtype)
+    if torch.is_grad_enabled() and isinstance(X, torch.Tensor) and X.requires_grad:
+        return _ISTFTFunction.apply(X, call)
+    return _istft_exec(call, X)
+
+
+class _IstftCall(NamedTuple):
+    """An istft call that has passed its checks, by value (the window as the float64 table of the forward; None:
+    rectangular), as the plain call runs it and as its autograd Function keeps it between forward and backward"""
+    out_dtype: object
+    lead: tuple
+    batch: int
+    frames: int
+    n_fft: int
+    hop: int
+    center: bool
+    length: int
+    gain: float
+    window: object
+    device: int
+
+    @property
+    def in_shape(self) -> tuple:
+        return (self.batch, self.frames, self.n_fft // 2 + 1, 2)
+
+    @property
+    def out_shape(self) -> tuple:
+        return (self.batch, self.length, 1)
+
+
+def _istft_call(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex,
+                out_dtype) -> _IstftCall:
+    """the checks of ``istft``, in the order they have always run, and the call by value"""
     if onesided is not None and not onesided:
         raise MifftError(ERR_UNSUPPORTED, "istft: onesided=False is not supported")
     if return_complex:
@@ -3315,14 +3557,62 @@ def istft(X: "torch.Tensor", n_fft: int, hop_length: Optional[int] = None, win_l
         w[left:left + win_length] = wl
     gain = float(n_fft) ** 0.5 if normalized else 1.0
     device = _signal_device(X, "X")
+    return _IstftCall(out_dtype, logical[:-2], batch, frames, n_fft, hop_length, bool(center), T, gain, w, device)
+
+
+def _istft_exec(call: _IstftCall, X: "torch.Tensor") -> "torch.Tensor":
+    """the one launch of an accepted istft call"""
+    out_dtype, in_shape, out_shape, device, w = call.out_dtype, call.in_shape, call.out_shape, call.device, call.window
     ctype = torch.complex64 if out_dtype == torch.float32 else torch.complex128
     # frames-major memory: a no-op for the view stft returns, one transposing copy otherwise
     xf = X.to(ctype).transpose(-1, -2).contiguous()
     xr = torch.view_as_real(xf).reshape(in_shape)
     out = torch.empty(out_shape, dtype=out_dtype, device=xr.device)
     with _PLAN_CACHE_LOCK:
-        plan = _plan_cached(("istft", out_dtype, in_shape, n_fft, hop_length, bool(center), T, gain), device, lambda: Plan(
-            out_dtype, out_dtype, in_shape, out_shape, device=device, istft_hop=hop_length, stft_center=bool(center),
-            stft_window=w, istft_gain=gain), w)
+        plan = _plan_cached(("istft", out_dtype, in_shape, call.n_fft, call.hop, call.center, call.length, call.gain), device,
+                            lambda: Plan(out_dtype, out_dtype, in_shape, out_shape, device=device, istft_hop=call.hop,
+                                         stft_center=call.center, stft_window=w, istft_gain=call.gain), w)
         fft(out, xr, DeviceContext(device), plan=plan)
-    return out.reshape(logical[:-2] + (T,))
+    return out.reshape(call.lead + (call.length,))
+
+
+def _istft_adjoint_plan(call: _IstftCall) -> Plan:
+    """The cached adjoint plan of an istft call, looked up or made under the cache's lock, which the caller holds until its
+    launch is enqueued.  The forward of _ISTFTFunction asks for it first, so that a refusal is raised there; the backward asks
+    again, since the plan may have left the cache in between."""
+    w, device = call.window, call.device
+    def build():
+        try:
+            return plan_istft_adjoint(call.out_dtype, call.batch, call.frames, call.n_fft, call.hop, window=w, center=call.center,
+                                      gain=call.gain, length=call.length, ctx=DeviceContext(device))
+        except MifftError as e:
+            raise MifftError(e.status, f"istft: no gradient with respect to X for these arguments ({e}); the forward alone "
+                                       f"works on an X without requires_grad (or under torch.no_grad())") from None
+
+    with _PLAN_CACHE_LOCK:
+        return _plan_cached(("istft_adjoint", call.out_dtype, call.in_shape, call.n_fft, call.hop, call.center, call.length,
+                             call.gain), device, build, w)
+
+
+class _ISTFTFunction(torch.autograd.Function):
+    """istft with the gradient with respect to X: one launch of the STFT tile with the envelope in its load
+    (plan_istft_adjoint).  First order."""
+
+    @staticmethod
+    def forward(ctx, X, call):
+        y = _istft_exec(call, X)
+        _istft_adjoint_plan(call)
+        ctx.call, ctx.x_dtype = call, X.dtype
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        call = ctx.call
+        g = gy.to(call.out_dtype).contiguous().reshape(call.out_shape)
+        out = torch.empty(call.in_shape, dtype=call.out_dtype, device=g.device)
+        with _PLAN_CACHE_LOCK:
+            fft(out, g, DeviceContext(call.device), plan=_istft_adjoint_plan(call))
+        # bins-major, X's layout, as the transposed view of the frames-major tensor the kernel wrote
+        gX = torch.view_as_complex(out).reshape(call.lead + (call.frames, call.n_fft // 2 + 1)).transpose(-1, -2)
+        return gX.to(ctx.x_dtype), None

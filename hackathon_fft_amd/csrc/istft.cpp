@@ -235,16 +235,13 @@ static hipError_t upload_t(const std::vector<T>& tab, void** d_table) {
     return e;
 }
 
-// the synthesis table and the reciprocal envelope, formed in binary64 and rounded once to the plan's type T (the only host
-// copy of the L-entry table is of that type; a repeating sample copies its twin's rounded value, which is the same rounding)
+// The reciprocal envelope at every padded sample 0 .. n + hop (F - 1) - 1, formed in binary64 and rounded once to the plan's
+// type T (the only host copy of the L-entry table is of that type; a repeating sample copies its twin's rounded value, which
+// is the same rounding).  The inverse plan and its adjoint both come here, so both divide by the same numbers.
 template <typename T>
-static hipError_t upload_tables_t(int64_t n, int64_t hop, int64_t F, const std::vector<double>& window, double gain, void** d_ws,
-                                  void** d_env) {
+static std::vector<T> envelope_table_t(int64_t n, int64_t hop, int64_t F, const std::vector<double>& window) {
     const int64_t L = n + hop * (F - 1);
-    std::vector<T> ws((size_t)n), inv((size_t)L);
-    // the kernel's last pass leaves conj(z) of the packed frame z_m = y[2m] + i y[2m+1], unscaled: odd reals negated, 1 / n here
-    for (int64_t j = 0; j < n; ++j)
-        ws[(size_t)j] = (T)(((j & 1) ? -gain : gain) * (window.empty() ? 1.0 : window[(size_t)j]) / (double)n);
+    std::vector<T> inv((size_t)L);
     // (samples outside the stored range may have a zero envelope: their entries are never read)
     for (int64_t u = 0; u < L; ++u) {
         if (envelope_repeats(n, hop, F, u)) {
@@ -254,9 +251,166 @@ static hipError_t upload_tables_t(int64_t n, int64_t hop, int64_t F, const std::
         const double e = envelope_at(window, n, hop, F, u);
         inv[(size_t)u] = (T)(e != 0.0 ? 1.0 / e : 0.0);
     }
+    return inv;
+}
+
+// the synthesis table, formed in binary64 and rounded once, and the reciprocal envelope
+template <typename T>
+static hipError_t upload_tables_t(int64_t n, int64_t hop, int64_t F, const std::vector<double>& window, double gain, void** d_ws,
+                                  void** d_env) {
+    std::vector<T> ws((size_t)n);
+    // the kernel's last pass leaves conj(z) of the packed frame z_m = y[2m] + i y[2m+1], unscaled: odd reals negated, 1 / n here
+    for (int64_t j = 0; j < n; ++j)
+        ws[(size_t)j] = (T)(((j & 1) ? -gain : gain) * (window.empty() ? 1.0 : window[(size_t)j]) / (double)n);
     hipError_t e = upload_t<T>(ws, d_ws);
-    if (e == hipSuccess) e = upload_t<T>(inv, d_env);
+    if (e == hipSuccess) e = upload_t<T>(envelope_table_t<T>(n, hop, F, window), d_env);
     return e;
+}
+
+// ---- inverse STFT adjoint plans: the payload w[0 .. n-1] | MIFFT_ISTFT_ADJ_TAG | gain | frames, 0 on a MIFFT_FLAG_STFT plan ---------
+// The gradient of an inverse STFT plan's result with respect to its frames is the one-sided STFT of gy / envelope: the STFT
+// pass with TileCfg::IADJ (tile_kernel.h), whose load multiplies by the inverse plan's reciprocal envelope inside [0, T) and
+// selects zeros outside, and whose store halves bins 0 and n / 2.  dims = {T, n}; the frame count F is the payload's -- that of
+// X, which `length` may have cropped -- not stft_frames' of T.  The analysis table is 2 gain w / n.
+bool istft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 2 || !dims || !bases_flat || !bases_len || dims[1] < 2 || dims[1] > (1 << 20)) return false;
+    const int64_t n = dims[1];
+    return (int64_t)bases_len[0] == 2 * n + 6 && bases_flat[2 * n] == MIFFT_ISTFT_ADJ_TAG_LO && bases_flat[2 * n + 1] == MIFFT_ISTFT_ADJ_TAG_HI;
+}
+
+int istft_adj_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
+    pl = FramedPayload();
+    const char* who = "an inverse STFT adjoint payload (MIFFT_ISTFT_ADJ_TAG)";
+    const FlagRefusal other[] = {{MIFFT_FLAG_STFT_POWER, "MIFFT_FLAG_STFT_POWER: the adjoint stores complex bins"},
+                 {MIFFT_FLAG_STFT_CENTER_REFLECT, "MIFFT_FLAG_STFT_CENTER_REFLECT: a centred adjoint sees zeros beyond both ends "
+                                                  "(MIFFT_FLAG_STFT_CENTER_ZEROS)"},
+                 {MIFFT_FLAG_FAITHFUL_STAGES, "MIFFT_FLAG_FAITHFUL_STAGES: the reference has no STFT to be faithful to"},
+                 {MIFFT_FLAG_HALF_SPECTRUM, "MIFFT_FLAG_HALF_SPECTRUM: the adjoint stores the half spectrum of every frame anyway"},
+                 {MIFFT_FLAG_DCT, "MIFFT_FLAG_DCT"},
+                 {MIFFT_FLAG_DCT_ND, "MIFFT_FLAG_DCT_ND"},
+                 {MIFFT_FLAG_DCT_ORTHO, "MIFFT_FLAG_DCT_ORTHO"},
+                 {MIFFT_FLAG_KEEP_MASK, "MIFFT_FLAG_KEEP_DIM: the adjoint frames dim 0 and transforms dim 1"},
+                 {MIFFT_FLAG_ISTFT, "MIFFT_FLAG_ISTFT: the two mode bits exclude each other"}};
+    if (const int rc = refuse_flags(p.flags, other, std::string(who) + " with ", why)) return rc;
+    const int64_t T = p.dims[0], n = p.dims[1], hop = p.stft_hop();
+    if (hop == 0) {
+        why = std::string(who) + " with hop 0: MIFFT_FLAG_STFT_HOP(h) carries the hop, 1 .. n";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.inverse) {
+        why = std::string(who) + " with inverse = 1: the adjoint of the inverse is a forward plan";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (p.in_components != 1) {
+        why = std::string(who) + " reads real gradients (in_components = 1)";
+        return MIFFT_ERR_BAD_COMPONENTS;
+    }
+    if (p.in_dtype != p.out_dtype) {
+        why = std::string(who) + " reads the plan's own float type (in_dtype == out_dtype)";
+        return MIFFT_ERR_BAD_DTYPE;
+    }
+    if (n % 2 != 0) {
+        why = "STFT with an odd frame length (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (n < 8) {
+        why = "STFT with frames of fewer than 8 points (" + std::to_string(n) + ") is not supported";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (bases_len[1] < 0) {
+        why = "negative bases_len";
+        return MIFFT_ERR_NO_BASES;
+    }
+    if (const int rc = read_window(bases_flat, n, pl.window, why)) return rc;
+    pl.gain = word_pair(bases_flat + 2 * n + 2);
+    if (!std::isfinite(pl.gain) || pl.gain == 0.0) {
+        why = "the gain of " + std::string(who) + " is finite and not zero, not " + std::to_string(pl.gain);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    const int64_t F = bases_flat[2 * n + 4];
+    if (bases_flat[2 * n + 5] != 0) {
+        why = "the reserved word behind the frame count of " + std::string(who) + " is 0, not " + std::to_string(bases_flat[2 * n + 5]);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (F < 1) {
+        why = std::string(who) + " needs at least one frame (the frame count word is 0)";
+        return MIFFT_ERR_BAD_DIM;
+    }
+    // ---- the limits of the inverse plan it is the adjoint of, in that plan's terms ----
+    if (hop > n) {
+        why = std::string(who) + " with hop " + std::to_string(hop) + " > n = " + std::to_string(n) +
+              ": gaps between the frames, where the window envelope is zero";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (F > (1ll << 26)) {
+        why = "more than 2^26 frames per entry: the envelope table has one entry per padded sample";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    const bool centred = (p.flags & MIFFT_FLAG_STFT_CENTER_ZEROS) != 0;
+    const int64_t L = n + hop * (F - 1), c = centred ? n / 2 : 0;
+    if (L > (1ll << 26)) {
+        why = "frames that cover " + std::to_string(L) + " samples per entry: the envelope table (one entry per padded sample) is " +
+              "limited to 2^26";
+        return MIFFT_ERR_TOO_LARGE;
+    }
+    if (T < 1 || T > L - c) {
+        why = "T = " + std::to_string(T) + " samples of gradient, but the frames cover 1 .. " + std::to_string(L - c) +
+              " (n + hop (F - 1)" + (c ? " - n / 2" : "") + "): the inverse plan stores no more";
+        return MIFFT_ERR_BAD_DIM;
+    }
+    const int64_t bare = envelope_first_below(pl.window, n, hop, F, c, T, 1e-11);
+    if (bare >= 0) {
+        why = "the window's squared overlap-add is zero at sample " + std::to_string(bare - c) +
+              " (nonzero overlap-add condition: below 1e-11)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    std::string w;
+    if (!stft_rows_supported(p, n, w)) {
+        why = "STFT with frames of " + std::to_string(n) + " points: " + w;
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    read_radices(bases_flat, bases_len[0], bases_len[1], pl.radices);
+    p.istft_adj = F;
+    return MIFFT_OK;
+}
+
+template <typename T>
+static hipError_t upload_istft_adj_tables_t(int64_t n, int64_t hop, int64_t F, const std::vector<double>& window, double gain,
+                                            void** d_win, void** d_env) {
+    std::vector<T> wa((size_t)n);  // 2 gain w[j] / n: the store halves bins 0 and n / 2, both factors exact
+    for (int64_t j = 0; j < n; ++j) wa[(size_t)j] = (T)(2.0 * gain * window[(size_t)j] / (double)n);
+    hipError_t e = upload_t<T>(wa, d_win);
+    if (e == hipSuccess) e = upload_t<T>(envelope_table_t<T>(n, hop, F, window), d_env);
+    return e;
+}
+
+// the one pass: dim 1 (n points) over the payload's F frames of every batch entry
+int build_istft_adj(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
+                    std::string& why) {
+    const int64_t n = p.dims[1], F = p.istft_adj, hop = p.stft_hop();
+    DimPass ps;
+    ps.dim_index = 1;
+    ps.N = n;
+    ps.inner = 1;
+    ps.outer = F;
+    ps.radices = ordered;
+    ps.processed = processed;
+    ps.first = true;
+    ps.half_pitch = n / 2 + 1;
+    if (!select_jit_stft_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    if (e == hipSuccess) {
+        try {
+            e = p.out_dtype == MIFFT_F64 ? upload_istft_adj_tables_t<double>(n, hop, F, pl.window, pl.gain, &ps.d_aux2, &ps.d_aux3)
+                                         : upload_istft_adj_tables_t<float>(n, hop, F, pl.window, pl.gain, &ps.d_aux2, &ps.d_aux3);
+        } catch (const std::bad_alloc&) {  // (up to 2^26 entries on the host)
+            e = hipErrorOutOfMemory;
+        }
+    }
+    p.passes.push_back(ps);
+    if (e != hipSuccess) return hip_error(e, "inverse STFT adjoint table upload");
+    return MIFFT_OK;
 }
 
 // ---- IMDCT plans: the payload w[0 .. 2M-1] | MIFFT_MDCT_TAG | gain on a MIFFT_FLAG_ISTFT plan -------------------------------------

@@ -327,6 +327,8 @@ FramedKind framed_kind(const Plan& p, const uint32_t* bases_flat, const int32_t*
         if (conv_detect(p.ndim, bases_flat, bases_len)) return FramedKind::Conv;
         // a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points
         if (mdct_detect(p.ndim, p.dims, bases_flat, bases_len)) return FramedKind::Mdct;
+        // ... or with MIFFT_ISTFT_ADJ_TAG (no power bit: there that slot is the power's): the adjoint of the inverse STFT
+        if (!(p.flags & MIFFT_FLAG_STFT_POWER) && istft_adj_detect(p.ndim, p.dims, bases_flat, bases_len)) return FramedKind::IstftAdjoint;
         return FramedKind::Stft;
     }
     // the window of a MIFFT_FLAG_ISTFT plan tagged with MIFFT_STFT_ADJ_TAG: the adjoint of the STFT, the ISTFT pass without
@@ -349,6 +351,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
         case FramedKind::Mdct: rc = mdct_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Imdct: rc = imdct_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Adjoint: rc = stft_adj_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::IstftAdjoint: rc = istft_adj_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Stft: rc = stft_check(p, why); break;
         case FramedKind::Istft: rc = istft_check(p, bases_flat, bases_len, pl, why); break;
     }
@@ -375,6 +378,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
         case FramedKind::Mdct: rc = build_mdct(p, ordered[td], processed[td], pl, why); break;
         case FramedKind::Imdct: rc = build_imdct(p, ordered[td], processed[td], pl, why); break;
         case FramedKind::Stft: rc = build_stft(p, ordered[td], processed[td], pl, why); break;
+        case FramedKind::IstftAdjoint: rc = build_istft_adj(p, ordered[td], processed[td], pl, why); break;
         case FramedKind::Adjoint:  // (the inverse STFT's pass, without the envelope)
         case FramedKind::Istft: rc = build_istft(p, ordered[td], processed[td], pl, why); break;
     }

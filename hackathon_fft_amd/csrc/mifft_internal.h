@@ -220,6 +220,7 @@ struct Plan {
     int64_t stft_hop() const { return (int64_t)((flags & MIFFT_FLAG_STFT_HOP_MASK) >> 16); }
     int stft_center() const { return (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) ? 1 : (flags & MIFFT_FLAG_STFT_CENTER_ZEROS) ? 2 : 0; }
     int64_t stft_frames() const {
+        if (istft_adj) return istft_adj;  // (the payload's: those of X, which `length` may have cropped)
         if (conv.is_conv()) return conv.F;  // (no frames, no hop: one row per batch entry, or the blocks of an overlap-save row)
         if (mdct) return (dims[0] + mdct - 1) / mdct + 1;
         return 1 + (stft_center() ? dims[0] : dims[0] - dims[1]) / stft_hop();
@@ -239,6 +240,10 @@ struct Plan {
     // Set by stft_adj_check.
     int stft_adj = 0;
     bool stft_adj_edges() const { return stft_adj && (flags & MIFFT_FLAG_STFT_CENTER_REFLECT) != 0; }
+    // a MIFFT_FLAG_STFT plan whose window payload is tagged with MIFFT_ISTFT_ADJ_TAG: the adjoint of the inverse STFT plan of
+    // istft_adj = F frames and dims[0] = T stored samples, dims = {T, n}; x is the incoming gradient (batch, T, 1), out
+    // (batch, F, n / 2 + 1, 2).  MIFFT_FLAG_STFT_CENTER_ZEROS: the inverse plan is centred.  0: not one.  Set by istft_adj_check.
+    int64_t istft_adj = 0;
     // a MIFFT_FLAG_STFT plan whose payload starts with MIFFT_CONV_TAG or MIFFT_CONV_GRAD_TAG: the decoded request (conv.cpp)
     ConvRequest conv;
     // a MIFFT_FLAG_DCT plan whose `bases` start with MIFFT_DCT_TYPE4_TAG: DCT-IV instead of DCT-II / DCT-III
@@ -391,7 +396,7 @@ int build_dctn(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                const std::vector<std::vector<uint32_t>>& processed, std::string& why);
 // ---- the framed family: MIFFT_FLAG_STFT / MIFFT_FLAG_ISTFT plans and what their tagged payloads select -----------------------
 // Which member a plan is: decided once, by framed_kind (mifft_api.cpp), from the mode bit and the *_detect predicates below.
-enum class FramedKind { Stft, Istft, Adjoint, Mdct, Imdct, Conv, ConvGrad };
+enum class FramedKind { Stft, Istft, Adjoint, IstftAdjoint, Mdct, Imdct, Conv, ConvGrad };
 // What a member's check decodes from `bases` for its build: the window (empty: rectangular), the filterbank and the matrix
 // after the bands of a spectrogram plan, the gain of the inverse kinds, the user radices of the one transformed dim (empty:
 // the default estimate).
@@ -503,6 +508,15 @@ bool stft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, 
 int stft_adj_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int launch_stft_adj(const Plan& plan, const DimPass& pass, const void* in, const void* mult, void* out, void* edge,
                     int64_t count, hipStream_t stream);
+// Inverse STFT adjoint plans (the MIFFT_FLAG_STFT payload tagged with MIFFT_ISTFT_ADJ_TAG; istft.cpp, beside the envelope
+// they share with the inverse plan).  istft_adj_detect: is bases_len[0] the tagged length 2 n + 6 with the tag behind the
+// window?  (Pure.)  istft_adj_check: the limits of the inverse plan it is the adjoint of (hop, covered length, the 2^26
+// padded samples, the overlap-add condition), then the STFT tile's; sets plan.istft_adj, the payload's frame count.
+// build_istft_adj: the STFT pass with TileCfg::IADJ over that many frames per entry, the reciprocal envelope in d_aux3.
+bool istft_adj_detect(int ndim, const int64_t* dims, const uint32_t* bases_flat, const int32_t* bases_len);
+int istft_adj_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
+int build_istft_adj(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
+                    const FramedPayload& payload, std::string& why);
 // first pass over a REAL tensor whose last pass will be a Hermitian twin: rows read as N / 2 packed complex points, unpacked
 // into the half spectrum by the store loop (TileCfg::R2C); pass.want_half asks for it.  LAB BUILD ONLY.
 bool select_jit_r2c(const Plan& plan, DimPass& pass, std::string& why_not);

@@ -282,7 +282,8 @@ struct TileParams {
     union { int stft_center; int conv_D; };   // CONV: filter rows; row r takes filter row r % D
     // ISTFT configurations reuse the four integers (frames per entry F, hop, output samples per entry T, centred or not) and
     // stft_win (the synthesis table, below); tiles_per_outer is the tiles of ONE entry, ceil(F / TILE), and istft_env the
-    // reciprocal envelope 1 / sum w^2 at every padded sample 0 .. 2 N + hop (F - 1) - 1, type T
+    // reciprocal envelope 1 / sum w^2 at every padded sample 0 .. 2 N + hop (F - 1) - 1, type T.  STFT tiles with IADJ (the
+    // adjoint of the inverse STFT) read the same table in their load.
     const void* istft_env;
     // SPEC configurations with a filterbank (TileCfg::FB): band m < spec_bands is sum_j spec_wt[spec_off[m] + j] *
     // P[spec_lo[m] + j], j < spec_len[m] (spec_lo[m] + spec_len[m] <= N + 1; weights of type T).  Without one the four
@@ -434,7 +435,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
           bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false, bool PART_ = false,
-          int ADJ_ = 0>
+          int ADJ_ = 0, bool IADJ_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -732,6 +733,18 @@ struct TileCfg {
     // where |X[k]| is (3), so that the product never exists in memory.
     static constexpr int ADJ = ADJ_;
     static_assert(ADJ_ >= 0 && ADJ_ <= 3 && (ADJ_ == 0 || ISTFT_), "ADJ: the adjoint twin of an ISTFT tile");
+    // IADJ (with STFT): the adjoint of the inverse STFT -- the gradient of istft with respect to its frames -- which is the
+    // one-sided STFT of gy / envelope.  `in` is the incoming gradient gy, (entries, stft_len) reals; stft_frames is the frame
+    // count of X (the plan's payload: `length` may have cropped the signal), stft_center 0 or 2.  The load multiplies the
+    // sample at padded position u = frame * hop + j by istft_env[u], the table the inverse plan divides by, when
+    // t = u - (centred ? N : 0) lies in [0, stft_len), and SELECTS an exact zero otherwise: neither gy nor the table is read
+    // there (the envelope may vanish outside the stored range, gy may hold anything), so a frame that sees no stored sample
+    // is an exact zero.  A frame wholly inside its entry loads gy and the table with one paired access each.  stft_win is
+    // 2 gain w[j] / 2N; the store halves bins 0 and N (c_0 = c_N = 1, every other c_k = 2) and writes an exact zero into their
+    // imaginary parts, which the forward ignores.  No LDS, scratch or atomics beyond the STFT tile's; a frame's result does not
+    // depend on batch, slab or grid.
+    static constexpr bool IADJ = IADJ_;
+    static_assert(!IADJ_ || (STFT_ && SPEC_ == 0 && !CONV_ && !MDCT_), "IADJ: the adjoint load and store of a plain STFT tile");
     // An even N lets one thread move FOUR adjacent reals x[4e .. 4e+3] at once: they are the packed elements
     // z_e = (x[4e], x[4e+2]) and z_(N-1-e) = (x[4e+3], x[4e+1]) -- one 16-byte HBM access and two whole LDS elements instead
     // of two 8-byte accesses and four 4-byte LDS slots (forward 15-25 % faster).  An odd N (n = 30) moves pairs,
@@ -2549,9 +2562,25 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     fr -= db * F;
                 }
                 const T* xe = x0 + (long long)db * len;
-                const int s0 = fr * hop - (mode ? C::N : 0);  // (fr * hop <= len: 32 bits hold it)
+                const int s0 = fr * hop - (mode ? C::N : 0);  // (fr * hop <= len, or with IADJ < the 2^26 padded samples of istft_adj_check: 32 bits hold it)
                 V x;
-                if (s0 >= 0 && s0 <= last_start) {
+                if constexpr (C::IADJ) {  // gy / envelope inside [0, len), a selected zero outside: neither is loaded there
+                    const T* env = (const T*)p.istft_env + (long long)fr * hop + 2 * m;  // (padded position u = fr hop + j)
+                    if (s0 >= 0 && s0 <= last_start) {
+                        const V e = gload_pair(env);
+                        x = gload_pair(xe + s0 + 2 * m);
+                        x = {x.x * e.x, x.y * e.y};
+                    } else {
+                        T v[2];
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const long long i = (long long)s0 + 2 * m + q;
+                            v[q] = (T)0;
+                            if (i >= 0 && i < len) v[q] = xe[i] * env[q];
+                        }
+                        x = {v[0], v[1]};
+                    }
+                } else if (s0 >= 0 && s0 <= last_start) {
                     x = gload_pair(xe + s0 + 2 * m);
                 } else {
                     T v[2];
@@ -2907,6 +2936,12 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
                     a.y *= -(T)p.scale;
                     b.x *= (T)p.scale;
                     b.y *= -(T)p.scale;
+                }
+                if constexpr (C::IADJ) {
+                    if (k == 0) {  // bins 0 and N: c_k = 1 (the table carries the 2 of the others), imaginary parts exactly 0
+                        a = {(T)0.5 * a.x, (T)0};
+                        b = {(T)0.5 * b.x, (T)0};
+                    }
                 }
                 V* row = gout + (row0 + c) * p.half_pitch;
                 gstore<(C::NT & 2) != 0>(row + k, a);

@@ -526,6 +526,35 @@ typedef struct mifft_stft_adj_args {
     const void* mult; /* (batch, F, n / 2 + 1) reals of the plan's type, or NULL in mode 1 */
     void* edge;       /* (batch, 2, n / 2) reals of the plan's type, or NULL without MIFFT_FLAG_STFT_CENTER_REFLECT */
 } mifft_stft_adj_args;
+/* THE ADJOINT OF THE INVERSE STFT (no reference counterpart): the gradient of a MIFFT_FLAG_ISTFT plan's result with respect to
+ * its frames, as a MIFFT_FLAG_STFT plan whose window payload carries the tag MIFFT_ISTFT_ADJ_TAG.
+ *   flags = MIFFT_FLAG_STFT | MIFFT_FLAG_STFT_HOP(hop) [| MIFFT_FLAG_STFT_CENTER_ZEROS: the inverse plan is centred], ndim = 2,
+ *   dims = {T, n} with T the inverse plan's stored samples, inverse = 0, in_components = 1, in_dtype == out_dtype in {F32, F64};
+ *       x (batch, T, 1)  ->  out (batch, F, n / 2 + 1, 2),   F from the payload (NOT derived from T: `length` may have cropped).
+ * With c = n / 2 for a centred plan (0 otherwise), E[u] = sum_f w[u - f hop]^2 the inverse plan's envelope at padded sample u,
+ * gy~ the incoming gradient with zeros outside [0, T), c_0 = c_(n/2) = 1 and every other c_k = 2:
+ *       out[b, f, k] = (c_k gain / n) sum_{j < n} w[j] gy~[b, f hop + j - c] / E[f hop + j] exp(-2 pi i j k / n)
+ * in the convention dL/dRe X + i dL/dIm X; the imaginary parts of bins 0 and n / 2 are written as exact zeros.
+ *   - bases_len[0] is exactly 2 n + 6 words: w[0 .. n-1] | TAG | gain | frames, 0 -- binary64 values, low word first, the window
+ *     always written out; TAG is the NaN MIFFT_ISTFT_ADJ_TAG_HI : MIFFT_ISTFT_ADJ_TAG_LO; gain, finite and not zero, is the
+ *     inverse plan's; frames is one 32-bit word, F >= 1, the last one reserved, 0.  Host data, taken by value.  Every other
+ *     MIFFT_FLAG_STFT payload (0, 2 n, the MDCT's 2 n + 4, those of MIFFT_FLAG_STFT_POWER, the convolutions') means what it meant;
+ *   - bases_len[1] is 0 (the default estimate) or the radices of n.
+ * Runs through plain mifft_exec_batch(plan, x, out, first, count, stream); no argument block.
+ * ONE launch, no scratch, no memset, no atomics: the STFT's tile (kernel rows<n>[_f64]_r2c_<radices>_stft_iadj_jit, compiled at
+ * run time only).  Its load multiplies sample t = f hop + j - c by 1 / E[f hop + j] -- the very table the inverse plan divides
+ * by, built in binary64 and rounded once -- when 0 <= t < T and SELECTS an exact zero otherwise: neither x nor the table is read
+ * there, so x may be followed by anything (NaN included) and a frame that sees no stored sample is an exact zero.  The window
+ * table is 2 gain w / n; the store halves bins 0 and n / 2.  A frame's result is bit-identical for any batch, first / count
+ * and grid.  mifft_plan_num_launches() is 1, mifft_plan_scratch_bytes() 0.
+ * Refused before any device work, each with its own reason: every limit of the inverse plan -- hop > n: MIFFT_ERR_UNSUPPORTED;
+ * T < 1 or T > n + hop (F - 1) - c, F < 1: MIFFT_ERR_BAD_DIM (the inverse plan's bound; the Python layer asks 2 <= T of both); F or n + hop (F - 1) beyond 2^26: MIFFT_ERR_TOO_LARGE; an
+ * envelope below 1e-11 somewhere in [c, c + T) (the nonzero overlap-add condition): MIFFT_ERR_UNSUPPORTED -- then the STFT
+ * tile's (an odd n, n < 8, a frame length it does not plan); MIFFT_FLAG_STFT_CENTER_REFLECT, inverse = 1 and every flag an
+ * STFT plan refuses: MIFFT_ERR_UNSUPPORTED; a gain that is zero or not finite, a non-zero reserved word, a window value that
+ * is not finite: MIFFT_ERR_BAD_BASES. */
+#define MIFFT_ISTFT_ADJ_TAG_LO 0x4A444901u
+#define MIFFT_ISTFT_ADJ_TAG_HI 0x7FF84D4Au
 /* Fused FFT convolution of real rows (numpy: irfft(rfft(x, n) * G, n)[..., o : o + Lo]; no reference counterpart): a
  * MIFFT_FLAG_STFT plan -- that bit ALONE, no hop, no centre bit -- whose payload starts with the tag MIFFT_CONV_TAG.
  *   flags = MIFFT_FLAG_STFT, ndim = 2, dims = {L, n}, inverse = 0, in_components = 1, in_dtype == out_dtype in {F32, F64};
