@@ -59,7 +59,8 @@ def _facts(plan, n, t, ols):
     return tile, grid
 
 
-# the (n, L, K, D, B, dtype) list of test_gpu_fftconv.py: every length class of the packed rows
+# the (n, L, K, D, B, dtype) list of test_gpu_fftconv.py: even half lengths, most of them powers of two.  Every length class
+# of the packed rows (odd half lengths, tiles of 62, 42, 3 and 1 rows, one to four passes) runs in test_gpu_packed_families.py
 LENGTHS = [(16, 8, 5, 1, 3, "f32"), (64, 37, 28, 3, 5, "f32"), (96, 50, 40, 2, 4, "f32"), (1000, 600, 300, 4, 2, "f32"),
            (2048, 1024, 1024, 3, 2, "f32"), (16384, 8192, 8192, 2, 2, "f32"), (12288, 6000, 6000, 2, 1, "f64"),
            (64, 37, 28, 3, 5, "f64"), (2048, 1024, 1024, 3, 2, "f64")]

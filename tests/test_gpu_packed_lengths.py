@@ -7,6 +7,8 @@ and store loops of tile_kernel.h branch on N itself as well (odd N: a middle wor
 reals per access in the DCT-II rows; a single radix: one wave per workgroup).  The feature tests all run the same few lengths.
 Here every class the function can produce gets one length, and every kernel runs at it against the fp64 numpy reference of its
 own module, with that module's error measure, bounded by conftest's REL_L2_TOL_F32 / REL_L2_TOL_F64 and nothing else.
+The families that came to ride on the same configuration function later -- the fused convolution and its filter gradient, the
+gradients of stft and istft, the sine transforms -- go through the same table in tests/test_gpu_packed_families.py.
 
 Every case asserts its class from the plan (radices from kernel_name, tile and threads from pass_geometry), writes into a
 NaN-prefilled output with a NaN guard behind it, and finds its input unchanged.  The shapes hold two full tiles and a ragged
@@ -87,10 +89,10 @@ def _ids(v):
 
 
 def _radices(name):
-    """the radices in a kernel name: the field after r2c / c2r / dct2 / dct3 / dct4"""
+    """the radices in a kernel name: the field after r2c / c2r / dct2 / dct3 / dct4 / dst2 / dst3 / dst4"""
     parts = name.split("_")
     for i, p in enumerate(parts):
-        if p in ("r2c", "c2r", "dct2", "dct3", "dct4"):
+        if p in ("r2c", "c2r", "dct2", "dct3", "dct4", "dst2", "dst3", "dst4"):
             return tuple(int(v) for v in parts[i + 1].split("x"))
     raise AssertionError(name)
 
