@@ -14,6 +14,7 @@ an FFT on the host or through torch.fft.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import enum
 import functools
@@ -2014,7 +2015,10 @@ class ConvRequest(NamedTuple):
     result on, ``F`` blocks per row and the first block's start ``s0`` (a single block: 0, 1, 0); ``Q`` > 0 taps per partition
     and ``P`` partitions on a partitioned one; the ``mode`` word, the device ``address`` of the filter spectra, the ``gates`` bits.  ``grad``: the
     filter gradient of that convolution instead, in ``partials`` sums per channel (0: the library's choice), ``gates`` fused
-    into its loads of x and gy."""
+    into its loads of x and gy.  ``stage`` (with ``grad``): 0 that fused gradient; 1 / 2 the spectra of its u-blocks / g-blocks
+    stored instead of summed, 3 the lag-group correlation over such spectra (``o`` = the stored u-frames per row, ``S`` = the lag
+    groups, ``F`` = ``Lo`` = the g-blocks per row, ``s0`` = the index of the first stored u-frame) -- the three plans of a
+    ``FusedPartConvGradPlan`` (word 10 of the payload; include/mifft.h)."""
     n: int
     D: int
     o: int
@@ -2029,6 +2033,7 @@ class ConvRequest(NamedTuple):
     gates: int = 0
     grad: bool = False
     partials: int = 0
+    stage: int = 0
 
 
 def _conv_payload(r: ConvRequest) -> list:
@@ -2048,9 +2053,11 @@ def _conv_payload(r: ConvRequest) -> list:
     for what in ("Q", "P", "partials"):
         if not 0 <= getattr(r, what) < 1 << 32:
             raise MifftError(-5, f"{what} = {getattr(r, what)} of a convolution plan does not fit an unsigned 32-bit word")
+    if r.stage not in (0, 1, 2, 3) or (r.stage and not r.grad):
+        raise MifftError(-5, f"stage = {r.stage} of a convolution plan: 0, or 1 / 2 / 3 on a filter-gradient request")
     if r.grad:  # (always the block geometry: a single block stores its Lo samples)
         return [CONV_GRAD_TAG_LO, CONV_GRAD_TAG_HI, r.D, r.o, r.S or r.Lo, r.mode, r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.partials,
-                0, r.gates, 0, 0, 0, 0]
+                r.stage, r.gates, 0, 0, 0, 0]
     words = [CONV_TAG_LO, CONV_TAG_HI, r.D, r.o, r.S if blocks else r.Lo, r.mode, r.address & 0xFFFFFFFF, (r.address >> 32) & 0xFFFFFFFF]
     if blocks:
         words += [r.F, r.s0 & 0xFFFFFFFF, r.Lo, r.gates]
@@ -2497,7 +2504,9 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     power-of-two block, 16384 / float64 8192), 1 <= Q <= block - 1, for any K; "auto" takes the paths above whenever they
     exist (the same bits) and fftconv_partition(K) otherwise.  One launch, no intermediate; the work grows with K / Q
     (DESIGN.md 3.4q).  It excludes ``n``; None refuses such filters as ever.  Gates, skip and autograd as on the other paths
-    (the filter gradient: one launch of the overlap-save filter-gradient plan per partition).
+    (the filter gradient: the fused partitioned plan, ``FusedPartConvGradPlan``, where it was measured not slower --
+    ``_FFTCONV_FUSED_GRAD``, or ``fftconv_fused_filter_grad`` around the call -- and otherwise one launch of the overlap-save
+    filter-gradient plan per partition).
     ``pregate`` / ``postgate`` / ``skip`` make it the gated filter stage of Hyena / H3 / S4 models in the same launch:
     ``postgate * (conv(pregate * x, k) + skip * (pregate * x))``.  ``pregate`` has exactly ``x``'s shape, ``postgate`` exactly
     the result's (ValueError otherwise: nothing is broadcast, a gate broadcast and then copied would cost what the fusion
@@ -2559,8 +2568,9 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, k, pregate, postgate, skip)):
         # (the forward of the Function runs with grad mode off: it comes back here and takes the lines below)
         skip_t = skip if isinstance(skip, torch.Tensor) else None
+        # (the selector's answer is taken here, on the caller's thread: the backward runs on autograd's)
         return _FFTConvFunction.apply(x, k, pregate, postgate, skip_t, None if skip_t is not None else skip,
-                                      (n, taps, mode, bool(correlate), Q, io_dtype))
+                                      (n, taps, mode, bool(correlate), Q, io_dtype, _fftconv_grad_fused(None, sdt, n, K, Q)))
     xr = x.to(sdt).contiguous().reshape(rows, L, 1)
     out = torch.empty((rows, out_length, 1), dtype=sdt, device=xr.device)
     gates = (1 if pregate is not None else 0) | (2 if postgate is not None else 0)
@@ -2762,16 +2772,311 @@ def _fftconv_part_grad_slice(L: int, Q: int, o: int, Lo: int, correlate: bool, p
     return (0, min(L, g1 - g0), g0, g1, 0)
 
 
+class FusedGradGeometry(NamedTuple):
+    """The geometry of the fused partitioned filter gradient (``_fftconv_fused_grad_geometry``; mirrored by the payload
+    decode of the library, include/mifft.h): ``H`` = n // 2 samples per step and lags per group, ``Pg`` lag groups, ``Fg``
+    g-blocks, ``c`` the index of a g-block's first sample (H, correlating 0), the u-frames ``m_lo`` .. ``m_hi`` the sums name,
+    the live ones among them ``u_first`` .. ``u_first + Fu - 1`` (``Fu`` = 0: none) and ``u_start``, the first sample of frame
+    ``u_first``.  ``frame_start(m)`` is the first sample of u-frame m, ``lag_frame(f, p)`` the frame (g-block f, lag group p)
+    meets, ``reachable`` the taps (j0, j1) -- j0 <= j < j1 -- that any pair of samples can reach."""
+    n: int
+    H: int
+    Pg: int
+    Fg: int
+    c: int
+    m_lo: int
+    m_hi: int
+    u_first: int
+    Fu: int
+    u_start: int
+    correlate: bool
+    offset: int
+    reachable: tuple
+
+    def frame_start(self, m: int) -> int:
+        return self.offset + m * self.H - (0 if self.correlate else self.H)
+
+    def lag_frame(self, f: int, p: int) -> int:
+        return f + p if self.correlate else f - p
+
+    def live(self, m: int) -> bool:
+        return self.u_first <= m < self.u_first + self.Fu
+
+
+def _fftconv_fused_grad_geometry(n: int, L: int, Lo: int, K: int, o: int, correlate: bool) -> FusedGradGeometry:
+    """The one host function of the fused partitioned filter gradient's geometry: with H = n // 2, g-block f holds
+    gv[f H + i], i < H, at index c + i; u-frame m is the n samples of u from o + m H - H on (correlating: o + m H), zeros
+    outside [0, L); lag group p of g-block f meets frame f - p (correlating: f + p).  A frame that holds no sample of [0, L)
+    is dead: neither transformed nor stored.  Pure: no device, no library call."""
+    n, L, Lo, K, o, correlate = int(n), int(L), int(Lo), int(K), int(o), bool(correlate)
+    H = n // 2
+    Pg, Fg = -(-K // H), -(-Lo // H)
+    m_lo, m_hi = (0, Fg + Pg - 2) if correlate else (-(Pg - 1), Fg - 1)
+    base = o if correlate else o - H  # (the first sample of frame 0)
+    # live: base + m H > -n and base + m H < L
+    first = max(m_lo, (-n - base) // H + 1)
+    last = min(m_hi, -(-(L - base) // H) - 1)
+    Fu = max(0, last - first + 1)
+    # tap j meets a pair of samples for some t in [0, Lo): 0 <= o + t - j < L (correlating: o + t + j < L)
+    reach = (0, max(0, min(K, L - o))) if correlate else (max(0, o - L + 1), max(0, min(K, o + Lo)))
+    return FusedGradGeometry(n, H, Pg, Fg, 0 if correlate else H, m_lo, m_hi, first, Fu, base + first * H, correlate, o, reach)
+
+
+# stage 2 reads what stage 1 just wrote from the memory-side cache while both spectra tensors of a slab, and the rows stage 1
+# streams past them, stay inside it: half the Infinity Cache (kInfinityCacheBytes, csrc/mifft_config.h) for the spectra
+_INFINITY_CACHE_BYTES = 256 << 20
+_FUSED_GRAD_SCRATCH_DEFAULT = _INFINITY_CACHE_BYTES // 2
+_FUSED_GRAD_MAX_LAG_GROUPS = 32
+
+
+def _fftconv_fused_grad_entry_bytes(g: FusedGradGeometry, channels: int, dtype) -> int:
+    """the bytes of the two spectra tensors of ONE batch entry: channels (Fu + Fg) (n // 2 + 1) complex values of ``dtype``"""
+    return int(channels) * (g.Fu + g.Fg) * (g.n // 2 + 1) * 2 * (8 if dtype == torch.float64 else 4)
+
+
+def _fftconv_fused_grad_slabs(batch: int, entry_bytes: int, limit: Optional[int]) -> list:
+    """The slabs [(b0, b1), ..] of the fused partitioned filter gradient: whole batch entries, ascending, covering the batch
+    once, each of at most ``limit`` bytes of spectra, the fewest such slabs, their sizes differing by one entry at most (the
+    larger first).  ``limit`` None is the default, ``_FUSED_GRAD_SCRATCH_DEFAULT`` -- or one entry where that alone is larger,
+    so the default never refuses.  MifftError(ERR_UNSUPPORTED) when a given limit does not hold one entry."""
+    batch, entry_bytes = int(batch), int(entry_bytes)
+    if limit is None:
+        limit = max(_FUSED_GRAD_SCRATCH_DEFAULT, entry_bytes)
+    limit = int(limit)
+    if entry_bytes > limit:
+        raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad(fused=True): the spectra of one batch entry take {entry_bytes} bytes, "
+                                          f"above scratch_bytes = {limit}; the composed per-partition plan (fused=False) needs "
+                                          "no scratch")
+    per = max(1, limit // max(entry_bytes, 1))
+    count = -(-batch // per)
+    small, extra = divmod(batch, count)
+    out, b = [], 0
+    for i in range(count):
+        size = small + (1 if i < extra else 0)
+        out.append((b, b + size))
+        b += size
+    return out
+
+
+class _ConvGradStagePlan(Plan):
+    """one stage of a ``FusedPartConvGradPlan``: a filter-gradient plan whose payload names a stage (ConvRequest.stage)"""
+
+    def __init__(self, dtype, in_shape, out_shape, ctx, req: ConvRequest, io_dtype=None):
+        self.ctx, self.io_dtype = ctx, io_dtype
+        super().__init__(dtype, dtype, in_shape, out_shape, device=ctx.device, conv=req)
+
+    def launch(self, out: "torch.Tensor", x, gy, pregate=None, postgate=None) -> None:
+        """``x`` / ``gy`` / the gates: device addresses (None where the stage reads none)"""
+        if self.conv_gates:
+            args = ConvGradGatedArgs(CONV_GRAD_GATED_ARGS_MAGIC, x, gy, pregate, postgate)
+        else:
+            args = ConvGradArgs(CONV_GRAD_ARGS_MAGIC, x, gy)
+        check(_lib.lib().mifft_exec_batch(self._h, ctypes.addressof(args), out.data_ptr(), 0, self.in_shape[0],
+                                          self.ctx.stream.cuda_stream))
+
+
+class FusedPartConvGradPlan:
+    """The plan of ``plan_fftconv_grad(partition=Q, fused=True)``: the filter gradient of the partitioned ``plan_fftconv`` plan
+    of the same arguments with every block of ``u`` and of ``gy`` transformed ONCE -- a frequency-domain delay line -- where
+    ``PartConvGradPlan`` transforms them again for every partition.  The gradient of a linear convolution is the
+    cross-correlation ``gk[j] = sum_t gy[t] u[o + t - j]`` whatever Q the forward chose, so the plan takes its own step
+    ``hop`` = n // 2 and ``lag_groups`` = ceil(taps / hop) groups of ``hop`` lags (``_fftconv_fused_grad_geometry``):
+    stage 1 stores the half spectra of the live u-frames and of the g-blocks (the filter-gradient tile's two loads, gates and
+    16-bit widening included: TileCfg::WSPEC), stage 2 (lag_corr.hip) sums ``conj(U[f - p]) G[f]`` over the batch and the
+    blocks for every lag group p, and one ``irfftn`` of ``channels * lag_groups`` rows gives the taps.
+    The spectra live in plan-owned scratch, ``scratch_bytes`` in all (what was allocated): the batch is cut into ``slabs`` of
+    whole entries whose spectra stay under the limit (``scratch_bytes=``; default half the Infinity Cache, so that stage 2
+    reads from the cache what stage 1 wrote), three launches and one partial per slab; the partials are summed in ascending
+    order.  Every sum runs in an order the plan fixes: two runs, or two plans of the same arguments, give the same bits.
+    ``partition`` / ``partitions`` / ``step`` describe the forward plan, as on ``PartConvGradPlan``.  Limits: ``lag_groups`` <=
+    32 (ERR_UNSUPPORTED beyond, as for one batch entry above a given ``scratch_bytes``: the composed plan takes those), first
+    order only, no fused gradient of the gates themselves."""
+
+    def __init__(self, dtype, batch, channels, length, n, offset, out_length, correlate, ctx, taps, partition, io_dtype=None,
+                 pregate=False, postgate=False, scratch_bytes=None):
+        self.ctx, self.dtype, self.io_dtype = ctx, dtype, io_dtype
+        self.pregate, self.postgate = bool(pregate), bool(postgate)
+        self.channels, self.length, self.n = channels, length, n
+        self.offset, self.out_length, self.correlate = offset, out_length, bool(correlate)
+        self.taps, self.partition, self.partitions = taps, partition, -(-taps // partition)
+        self.step = n - partition + 1
+        self.batch = batch
+        rows = batch * channels
+        self.in_shape, self.grad_shape = (rows, length, 1), (rows, out_length, 1)
+        self.device = int(ctx.device)
+        g = self.geometry = _fftconv_fused_grad_geometry(n, length, out_length, taps, offset, correlate)
+        self.hop, self.lag_groups = g.H, g.Pg
+        if g.Pg > _FUSED_GRAD_MAX_LAG_GROUPS:
+            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad(fused=True): taps = {taps} at n = {n} are {g.Pg} lag groups of "
+                                              f"{g.H}, above {_FUSED_GRAD_MAX_LAG_GROUPS}; the composed per-partition plan "
+                                              "(fused=False) has no such limit")
+        self.entry_bytes = _fftconv_fused_grad_entry_bytes(g, channels, dtype)
+        self.slabs = _fftconv_fused_grad_slabs(batch, self.entry_bytes, scratch_bytes)
+        self._stages, self._U, self._G, self.partials = {}, None, None, 0
+        if g.Fu == 0:  # (no sample of gy meets a sample of u: every tap is an exact zero)
+            self.slabs = []
+            return
+        bins, mode = n // 2 + 1, 1 if correlate else 0
+        gates = (1 if self.pregate else 0) | (2 if self.postgate else 0)
+        for b0, b1 in self.slabs:
+            r = (b1 - b0) * channels
+            if r in self._stages:
+                continue
+            up = _ConvGradStagePlan(dtype, (r, length, 1), (r, g.Fu * g.H, 1), ctx, ConvRequest(
+                n, channels, 0, g.Fu * g.H, S=g.H, F=g.Fu, s0=g.u_start, mode=mode | _io_mode_bits(io_dtype), grad=True,
+                gates=gates & 1, stage=1), io_dtype)
+            gp = _ConvGradStagePlan(dtype, (r, max(out_length, 2), 1), (r, out_length, 1), ctx, ConvRequest(
+                n, channels, g.c, out_length, S=g.H, F=g.Fg, s0=0, mode=mode | _io_mode_bits(io_dtype), grad=True,
+                gates=gates & 2, stage=2), io_dtype)
+            lp = _ConvGradStagePlan(dtype, (r, max(g.Fu, 2), 1), (r, g.Fg, 1), ctx, ConvRequest(
+                n, channels, g.Fu, g.Fg, S=g.Pg, F=g.Fg, s0=g.u_first, mode=mode, grad=True, stage=3))
+            lp.partials = lp.out_bytes // (channels * g.Pg * bins * 2 * (8 if dtype == torch.float64 else 4))
+            self._stages[r] = (up, gp, lp)
+        self.partials = sum(self._stages[(b1 - b0) * channels][2].partials for b0, b1 in self.slabs)
+        most = max(b1 - b0 for b0, b1 in self.slabs) * channels
+        with torch.cuda.stream(ctx.stream):
+            self._U = torch.empty((most, g.Fu, bins, 2), dtype=dtype, device=f"cuda:{ctx.device}")
+            self._G = torch.empty((most, g.Fg, bins, 2), dtype=dtype, device=f"cuda:{ctx.device}")
+
+    @property
+    def plans(self) -> list:
+        """the (u-spectra, g-spectra, lag-group) plans of every slab, in slab order"""
+        return [self._stages[(b1 - b0) * self.channels] for b0, b1 in self.slabs]
+
+    @property
+    def num_launches(self) -> int:
+        return sum(sum(pl.num_launches for pl in trio) for trio in self.plans)
+
+    @property
+    def scratch_bytes(self) -> int:
+        return 0 if self._U is None else (self._U.numel() * self._U.element_size() + self._G.numel() * self._G.element_size())
+
+    def close(self) -> None:
+        for trio in self._stages.values():
+            for pl in trio:
+                pl.close()
+        self._stages, self._U, self._G, self.slabs = {}, None, None, []
+
+    def spectra(self, x: "torch.Tensor", gy: "torch.Tensor", slab: int = 0, *, pregate=None, postgate=None) -> tuple:
+        """stage 1 alone on slab ``slab``: (U, G), views of the plan's scratch -- complex (rows of the slab, Fu, n // 2 + 1) and
+        (.., Fg, n // 2 + 1), stored frame j of U being u-frame ``geometry.u_first`` + j -- valid until the next call"""
+        self._check(x, gy, pregate, postgate)
+        b0, b1 = self.slabs[slab]
+        with torch.cuda.stream(self.ctx.stream):
+            U, G = self._stage1(x, gy, pregate, postgate, b0, b1)
+        return torch.view_as_complex(U), torch.view_as_complex(G)
+
+    def _check(self, x, gy, pregate, postgate) -> None:
+        for t, want, what in ((pregate, self.pregate, "pregate"), (postgate, self.postgate, "postgate")):
+            if want and t is None:
+                raise MifftError(-12, f"the plan has a {what}: filter_grad(..., {what}=) is missing")
+            if not want and t is not None:
+                raise MifftError(ERR_UNSUPPORTED, f"the plan has no {what}: plan_fftconv_grad(..., {what}=True) makes one that has")
+        sdt = self.io_dtype or self.dtype
+        _check_tensor(x, self.in_shape, sdt, self.device, "x")
+        _check_tensor(gy, self.grad_shape, sdt, self.device, "gy")
+        if pregate is not None:
+            _check_tensor(pregate, self.in_shape, sdt, self.device, "pregate")
+        if postgate is not None:
+            _check_tensor(postgate, self.grad_shape, sdt, self.device, "postgate")
+
+    def _stage1(self, x, gy, pregate, postgate, b0: int, b1: int) -> tuple:
+        r0, r = b0 * self.channels, (b1 - b0) * self.channels
+        up, gp, _ = self._stages[r]
+        U, G = self._U[:r], self._G[:r]
+        xb, gb = x.element_size() * self.length, gy.element_size() * self.out_length  # (bytes per row)
+        up.launch(U, x.data_ptr() + r0 * xb, None, None if pregate is None else pregate.data_ptr() + r0 * xb, None)
+        gp.launch(G, None, gy.data_ptr() + r0 * gb, None, None if postgate is None else postgate.data_ptr() + r0 * gb)
+        return U, G
+
+    def filter_grad(self, x: "torch.Tensor", gy: "torch.Tensor", K: int, *, pregate: Optional["torch.Tensor"] = None,
+                    postgate: Optional["torch.Tensor"] = None) -> "torch.Tensor":
+        """the real (channels, K) gradient of the filter, K <= taps, from ``x`` of ``in_shape`` and ``gy`` of ``grad_shape``
+        (on a gated plan with ``pregate`` of ``in_shape`` and ``postgate`` of ``grad_shape``, fused into stage 1's loads):
+        per slab the two spectra launches and the lag-group launch, then the sum of the partials in ascending order, one
+        ``irfftn`` and the first ``hop`` lags of every group.  Taps that no pair of samples can reach are exact zeros."""
+        K = int(K)
+        if K < 1 or K > self.taps:
+            raise MifftError(-2, f"filter_grad: K = {K} taps on a partitioned plan of taps = {self.taps}: 1 <= K <= {self.taps}")
+        self._check(x, gy, pregate, postgate)
+        g, D = self.geometry, self.channels
+        with torch.cuda.stream(self.ctx.stream):
+            if g.Fu == 0:
+                return torch.zeros((D, K), dtype=self.dtype, device=x.device)
+            out = torch.empty((self.partials, D, g.Pg, self.n // 2 + 1, 2), dtype=self.dtype, device=x.device)
+            at = 0
+            for b0, b1 in self.slabs:
+                U, G = self._stage1(x, gy, pregate, postgate, b0, b1)
+                lp = self._stages[(b1 - b0) * D][2]
+                lp.launch(out[at:at + lp.partials], U.data_ptr(), G.data_ptr())
+                at += lp.partials
+            A = out[0] if self.partials == 1 else out.sum(0)
+            gk = irfftn(A.reshape(D * g.Pg, self.n // 2 + 1, 2), self.n).reshape(D, g.Pg, self.n)[:, :, :g.H]
+            gk = gk.reshape(D, g.Pg * g.H)[:, :K].contiguous()
+            j0, j1 = g.reachable
+            if j0 > 0:
+                gk[:, :min(j0, K)] = 0
+            if j1 < K:
+                gk[:, j1:] = 0
+            return gk
+
+
+# Where the fused partitioned filter gradient is taken by default (``fused=None``): {storage dtype: {n: least lag groups}},
+# the keys at which profiles/r26_fftconv_part_grad.txt (tools/fftconv_part_grad_probe.py; DESIGN.md 3.4v) shows its median
+# not above the composed plan's beyond the spread of the composed plan's own windows, at every shape measured for the key.
+# Every (dtype, n) that was not measured keeps the composed plan.
+_FFTCONV_FUSED_GRAD = {
+    torch.float32: {16384: 4},   # 4 x 256 x 32768, 4 x 256 x 65536, 4 x 64 x 131072: 0.59, 0.34 and 0.17 of the composed plan
+    torch.float64: {8192: 8},    # 4 x 64 x 32768: 0.38
+    torch.bfloat16: {16384: 8},  # 4 x 256 x 65536 with both gates: 0.34
+}
+
+_fused_grad_override = threading.local()
+
+
+@contextlib.contextmanager
+def fftconv_fused_filter_grad(fused: Optional[bool]):
+    """Within the block, ``fftconv_filter_grad(fused=None)`` and every ``fftconv`` call on a partitioned path -- for its backward,
+    whenever that runs -- take the fused partitioned filter gradient (True), the composed one (False) or the measured default
+    (None), on this thread."""
+    before = getattr(_fused_grad_override, "value", None)
+    _fused_grad_override.value = fused
+    try:
+        yield
+    finally:
+        _fused_grad_override.value = before
+
+
+def _fftconv_grad_fused(fused: Optional[bool], sdt, n: int, K: int, Q) -> bool:
+    """The one selector of the partitioned filter gradient: does (storage dtype, block length, taps) take the fused plan?
+    ``fused`` True / False is the caller's word (True off the partitioned path is an error), None the override of
+    ``fftconv_fused_filter_grad`` and then the table ``_FFTCONV_FUSED_GRAD``."""
+    if fused and Q is None:
+        raise MifftError(-2, "fused=True is the fused gradient of the PARTITIONED path: it goes with partition=")
+    if Q is None:
+        return False
+    if fused is None:
+        fused = getattr(_fused_grad_override, "value", None)
+    if fused is None:
+        least = _FFTCONV_FUSED_GRAD.get(sdt, {}).get(int(n))
+        lags = -(-int(K) // (int(n) // 2))
+        return least is not None and least <= lags <= _FUSED_GRAD_MAX_LAG_GROUPS
+    return bool(fused)
+
+
 def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, taps: Optional[int] = None, offset: int = 0,
                       out_length: Optional[int] = None, correlate: bool = False, partials: Optional[int] = None,
                       ctx: Optional[DeviceContext] = None, partition: Optional[int] = None, io_dtype=None,
-                      pregate: bool = False, postgate: bool = False):
+                      pregate: bool = False, postgate: bool = False, fused: bool = False, scratch_bytes: Optional[int] = None):
     """Plan of the fused filter gradient (no reference counterpart) of the ``plan_fftconv`` plan of the same arguments:
     ``gk[d, j] = sum over b and t of gy[b, d, t] * u[b, d, o + t - j]`` (``correlate``: ``o + t + j``), computed as
     ``irfft(sum_b conj(rfft(u[b, d], n)) * rfft(gy[b, d] put at o, n), n)[:K]`` in ONE launch that reads ``u`` and ``gy`` once
     each and writes ``channels * partials`` rows of n // 2 + 1 bins -- the exact adjoint of what the forward plan computes,
     circular where that is, block by block on an overlap-save plan (``taps=K``).  ``partition=Q`` (with ``taps=K``, any K >= 1)
-    gives the gradient of the partitioned plan as a ``PartConvGradPlan``: one such launch per partition.  ``partials`` workgroups share a channel's
+    gives the gradient of the partitioned plan as a ``PartConvGradPlan``: one such launch per partition -- or, with ``fused=True``,
+    as a ``FusedPartConvGradPlan`` that transforms every block once (spectra in scratch bounded by ``scratch_bytes=``, default
+    half the Infinity Cache; ERR_UNSUPPORTED above 32 lag groups of n // 2 taps or when a given ``scratch_bytes`` does not hold
+    one batch entry: the composed plan takes those).  ``partials`` workgroups share a channel's
     sum (default: enough that channels * partials fills the device; capped by the (row, block) pairs of a channel); the
     order of every sum is fixed by the plan, so two runs give the same bits.  ``pregate`` / ``postgate`` = True make it the
     filter gradient of the gated forward plan ``y = b * conv(a * x)``: ``u`` = a * x and the gradient b * gy are formed in the
@@ -2790,6 +3095,25 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
         partials = int(partials)
         if partials < 1 or partials > 65535:
             raise MifftError(-5, f"plan_fftconv_grad: partials = {partials}: 1 .. 65535")
+    if fused and partition is None:
+        raise MifftError(-2, "plan_fftconv_grad: fused=True is the fused gradient of a PARTITIONED plan: it goes with taps=K, partition=Q")
+    if scratch_bytes is not None and not fused:
+        raise MifftError(-2, "plan_fftconv_grad: scratch_bytes bounds the spectra of the fused partitioned gradient (fused=True)")
+    if fused:  # (the refusals first: lag groups and one entry's spectra, before any device work)
+        g = _fftconv_fused_grad_geometry(n, length, out_length, taps, offset, correlate)
+        if partials is not None:
+            raise MifftError(ERR_UNSUPPORTED, "plan_fftconv_grad(fused=True): the partial sums of the lag-group stage are the "
+                                              "library's choice (partials=None)")
+        if g.Pg > _FUSED_GRAD_MAX_LAG_GROUPS:
+            raise MifftError(ERR_UNSUPPORTED, f"plan_fftconv_grad(fused=True): taps = {taps} at n = {n} are {g.Pg} lag groups of "
+                                              f"{g.H}, above {_FUSED_GRAD_MAX_LAG_GROUPS}; the composed per-partition plan "
+                                              "(fused=False) has no such limit")
+        if scratch_bytes is not None and int(scratch_bytes) < 1:
+            raise MifftError(-5, f"plan_fftconv_grad: scratch_bytes = {scratch_bytes}: a positive number of bytes, or None")
+        _fftconv_fused_grad_slabs(batch, _fftconv_fused_grad_entry_bytes(g, channels, dtype), scratch_bytes)
+        return FusedPartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate,
+                                     DeviceContext() if ctx is None else ctx, taps, partition, io_dtype=io_dtype, pregate=pregate,
+                                     postgate=postgate, scratch_bytes=scratch_bytes)
     if partition is not None:  # (the composed gradient of a partitioned plan: PartConvGradPlan)
         return PartConvGradPlan(dtype, batch, channels, length, n, offset, out_length, correlate, DeviceContext() if ctx is None else ctx, taps,
                                 partition, partials=partials, io_dtype=io_dtype, pregate=pregate, postgate=postgate)
@@ -2800,24 +3124,29 @@ def plan_fftconv_grad(dtype, batch: int, channels: int, length: int, n: int, *, 
                         partials=partials, io_dtype=io_dtype, pregate=pregate, postgate=postgate)
 
 
-def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None, gates=0):
-    """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK)"""
+def _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q=None, io_dtype=None, gates=0,
+                       fused=False):
+    """the cached filter-gradient plan of ``fftconv``'s forward plan of the same key (the caller holds _PLAN_CACHE_LOCK);
+    ``fused``: the selector's answer (_fftconv_grad_fused), part of the key"""
     return _plan_cached(("fftconv_grad", dtype, rows, D, L, n, offset, out_length, bool(correlate)), device, lambda: plan_fftconv_grad(
         dtype, rows // D, D, L, n, taps=taps, offset=offset, out_length=out_length, partition=Q, correlate=correlate,
-        ctx=DeviceContext(device), io_dtype=io_dtype, pregate=bool(gates & 1), postgate=bool(gates & 2)),
-        key_tail=(taps, Q, io_dtype, gates))
+        ctx=DeviceContext(device), io_dtype=io_dtype, pregate=bool(gates & 1), postgate=bool(gates & 2), fused=bool(fused)),
+        key_tail=(taps, Q, io_dtype, gates) + (("fused",) if fused else ()))  # (the composed plan's key is what it was)
 
 
 def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Optional[int] = None, mode: str = "causal",
                         correlate: bool = False, block: Optional[int] = None, partition=None, io_dtype=None,
-                        pregate: Optional["torch.Tensor"] = None, postgate: Optional["torch.Tensor"] = None) -> "torch.Tensor":
+                        pregate: Optional["torch.Tensor"] = None, postgate: Optional["torch.Tensor"] = None,
+                        fused: Optional[bool] = None) -> "torch.Tensor":
     """The gradient of ``sum(gy * fftconv(x, k, n=n, mode=mode, correlate=correlate, block=block))`` with respect to a filter
     ``k`` of ``K`` taps, by the fused filter-gradient kernel in one launch (plus a sum of partials and one irfftn, both on
     ``channels`` rows): ``x`` (..., D, L) and ``gy`` of the result's shape (..., D, Lo) give (D, K); a 1-D ``x`` (L,) with
     ``gy`` (Lo,) gives (K,), the gradient of a 1-D filter.  (A 1-D filter shared by rows (..., L): reshape to (-1, 1, L) and take
     row 0.)  The choice of ``n`` / overlap-save mirrors ``fftconv``'s for the same arguments, so this is the gradient of THAT
     call, circular where it is.  With ``partition=`` (as ``fftconv``'s) it is the gradient of the partitioned call: one launch
-    per partition.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s.
+    per partition (``fused=False``), or the fused plan that transforms every block once (``fused=True``:
+    ``FusedPartConvGradPlan``); ``fused=None`` takes the fused plan where it was measured not slower (``_FFTCONV_FUSED_GRAD``)
+    and the composed one everywhere else.  float32 / float64; other input is converted to float64.  Plans are cached like ``fftconv``'s.
     ``io_dtype`` = torch.bfloat16 or torch.float16: ``x`` and ``gy`` are read as tensors of it (no copy when they already
     are), widened exactly in the kernel's loads, and the result is float32 -- the bits of the float32 call on the widened
     tensors.  The partitioned route stays composed, one half-storage launch per partition.
@@ -2844,6 +3173,7 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     dtype, sdt = _fftconv_dtypes(x, io_dtype)
     n, taps, Q = _fftconv_pick_part("fftconv_filter_grad", L, K, dtype, n, block, partition)
     offset, out_length = _fftconv_window(mode, L, K)
+    use_fused = _fftconv_grad_fused(fused, sdt, n, K, Q)
     if tuple(gy.shape) != logical[:-1] + (out_length,):
         raise ValueError(f"fftconv_filter_grad: gy is {tuple(gy.shape)}, the result of that fftconv call is "
                          f"{logical[:-1] + (out_length,)}")
@@ -2869,7 +3199,7 @@ def fftconv_filter_grad(x: "torch.Tensor", gy: "torch.Tensor", K: int, *, n: Opt
     b = None if postgate is None else postgate.detach().to(sdt).contiguous().reshape(rows, out_length, 1)
     gates = (1 if a is not None else 0) | (2 if b is not None else 0)
     with _PLAN_CACHE_LOCK:
-        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q, io_dtype, gates)
+        plan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, offset, out_length, correlate, device, Q, io_dtype, gates, use_fused)
         gk = plan.filter_grad(xr, gr, K, pregate=a, postgate=b)
     return gk if x.dim() >= 2 else gk.reshape(K)
 
@@ -2880,6 +3210,8 @@ class _FFTConvFunction(torch.autograd.Function):
     gx = a gu, ga = x gu, gb = gy v with v recomputed without the postgate, gk and gd from the fused filter gradient of
     (u, gv), both formed in its loads.  The filter spectra of the cached plans are rewritten from the saved k and skip by every launch here: a second
     layer of the same shape may have overwritten them since the forward.
+    The seventh value of ``cfg`` is the selector's answer for a partitioned path (_fftconv_grad_fused, asked in the forward):
+    the fused partitioned filter gradient, or the composed one.
     With ``io_dtype`` (the sixth value of ``cfg``) x, a, b, gy and every launch's result are tensors of it: gu comes from the
     half-storage plan (b fused into its load, a into its store when only x wants a gradient; modes with o > 0 pad gy and b
     separately instead of their product), the products of 16-bit tensors (a gu, x gu, gy v) are torch's, computed in float32
@@ -2891,7 +3223,7 @@ class _FFTConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, k, pregate, postgate, skip_t, skip_f, cfg):
-        n, taps, mode, correlate, Q, io = cfg
+        n, taps, mode, correlate, Q, io, _ = cfg
         ctx.cfg, ctx.skip_f = cfg, skip_f
         ctx.save_for_backward(x, k, pregate, postgate, skip_t)
         return fftconv(x, k, mode=mode, correlate=correlate, pregate=pregate, postgate=postgate, io_dtype=io,
@@ -2901,7 +3233,7 @@ class _FFTConvFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, k, a, b, skip_t = ctx.saved_tensors
-        n, taps, mode, correlate, Q, io = ctx.cfg
+        n, taps, mode, correlate, Q, io, fused = ctx.cfg
         skip = skip_t.detach() if skip_t is not None else ctx.skip_f
         need_x, need_k, need_a, need_b, need_d = ctx.needs_input_grad[:5]
         logical = tuple(x.shape)
@@ -2953,7 +3285,7 @@ class _FFTConvFunction(torch.autograd.Function):
         if need_k or need_d:  # (the gates go to the kernel's loads: the sums are those of the products a x and b gy, bit for bit)
             gates = (1 if ar is not None else 0) | (2 if br is not None else 0)
             with _PLAN_CACHE_LOCK:
-                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q, io, gates)
+                gplan = _fftconv_grad_plan(dtype, rows, D, L, n, taps, o, Lo, correlate, device, Q, io, gates, fused)
                 g = gplan.filter_grad(xr.reshape(rows, L, 1), gyr.reshape(rows, Lo, 1), K,
                                       pregate=None if ar is None else ar.reshape(rows, L, 1),
                                       postgate=None if br is None else br.reshape(rows, Lo, 1))

@@ -23,6 +23,10 @@
 // The filter-gradient payload (MIFFT_CONV_GRAD_TAG, below) carries the forward plan's gates in its word 11: the kernel multiplies
 // x by the pregate and gy by the postgate as it loads them, and the exec takes a mifft_conv_grad_gated_args.
 //
+// Word 10 of the filter-gradient payload is a stage of the fused partitioned filter gradient: 1 / 2 the same tile storing the
+// half spectra of its u-blocks / g-blocks instead of summing them (TileCfg::WSPEC), 3 the lag-group correlation over such
+// spectra (lag_corr.hip), which has no transform of its own.  0 is the fused gradient above.
+//
 // Bits 8..15 of the mode word of every form, the filter-gradient payload included, are the STORAGE type of the rows: 0 the
 // plan's float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan (ConvRequest::io, TileCfg::IT): x, the gates and out are then
 // 2-byte elements, widened in the tile's load and rounded once in its store; H and the arithmetic stay float.
@@ -300,13 +304,78 @@ bool conv_grad_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases
     return bases_len[0] == 16 && bases_flat[0] == MIFFT_CONV_GRAD_TAG_LO && bases_flat[1] == MIFFT_CONV_GRAD_TAG_HI;
 }
 
-// MIFFT_CONV_GRAD_TAG: 16 words, D | c | S | mode | F | s0 | Lo | P behind the tag, a zero, the gates of the forward plan (0: none,
-// what every payload had there before there were any), then four zeros
+// Stage 3 of the fused partitioned filter gradient (word 10 = MIFFT_CONV_GRAD_STAGE_LAGS): the lag-group correlation over stored
+// spectra, D | Fu | Pg | mode | F | m0 | F | P behind the tag, a zero, the 3, then zeros (no gates: they went into stage 1's
+// loads).  dims = {max(Fu, 2), n}: Fu stored u-frames per row, the first of them frame m0 (signed); F g-blocks per row; Pg lag groups.
+static int conv_lag_check(Plan& p, const uint32_t* w, std::string& why) {
+    ConvRequest r;
+    r.grad = true;
+    r.stage = 3;
+    r.D = w[2];
+    r.u_frames = w[3];
+    r.lag_groups = w[4];
+    r.mode = w[5];
+    r.F = w[6];
+    r.u_first = (int32_t)w[7];
+    r.Lo = w[8];
+    r.P = w[9];
+    if (r.mode & ~1u) {
+        why = "the mode word of a lag-group payload (stage 3 of MIFFT_CONV_GRAD_TAG) has bit 0 (the forward correlated) alone: the "
+              "spectra are of the plan's float type, not " + std::to_string(r.mode);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.D < 1 || r.D > (1ll << 30) || p.batch % r.D != 0) {
+        why = "D = " + std::to_string(r.D) + " channels in a lag-group payload against batch = " + std::to_string(p.batch) +
+              " rows: 1 <= D <= 2^30, and the batch a multiple of it";
+        return r.D < 1 ? MIFFT_ERR_BAD_BASES : r.D > (1ll << 30) ? MIFFT_ERR_TOO_LARGE : MIFFT_ERR_BAD_BATCH;
+    }
+    if (r.lag_groups < 1) {
+        why = "Pg = 0 lag groups in a lag-group payload: 1 <= Pg <= 32";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.lag_groups > 32) {
+        why = "Pg = " + std::to_string(r.lag_groups) + " lag groups: the lag-group kernel keeps at most 32 accumulators per bin "
+              "(a longer filter: the composed per-partition gradient)";
+        return MIFFT_ERR_UNSUPPORTED;
+    }
+    if (r.F < 1 || r.F > (1ll << 30) || r.Lo != r.F) {
+        why = "F = " + std::to_string(r.F) + " g-blocks per row in a lag-group payload (word 6, and again word 8 = " +
+              std::to_string(r.Lo) + "): 1 <= F <= 2^30";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (std::max<int64_t>(r.u_frames, 2) != p.dims[0] || r.u_frames < 1 || r.u_frames > (1ll << 30)) {
+        why = "Fu = " + std::to_string(r.u_frames) + " stored u-frames per row in a lag-group payload against dims[0] = " +
+              std::to_string(p.dims[0]) + ": dims[0] = max(Fu, 2) (no plan has a dimension of 1), 1 <= Fu <= 2^30";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.P > 65535 || r.P > p.batch / r.D) {
+        why = "P = " + std::to_string(r.P) + " partial sums per channel in a lag-group payload: at most 65535 and at most the " +
+              std::to_string(p.batch / r.D) + " batch entries of a channel (0: the library's choice)";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (const int rc = conv_reserved_check(w, 10, 16, 1u << 10, "a lag-group", why)) return rc;
+    p.conv = r;
+    return MIFFT_OK;
+}
+
+// MIFFT_CONV_GRAD_TAG: 16 words, D | c | S | mode | F | s0 | Lo | P behind the tag, the stage (0: the fused gradient, what every
+// payload had there before there were stages), the gates of the forward plan (0: none, likewise), then four zeros
 int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
     if (const int rc = conv_header_check(p, "MIFFT_CONV_GRAD_TAG", why)) return rc;
     const uint32_t* w = bases_flat;
+    if (w[10] > MIFFT_CONV_GRAD_STAGE_LAGS) {
+        why = "the reserved word 10 of a filter-gradient payload must be 0, not " + std::to_string(w[10]) +
+              " (or a stage of the fused partitioned gradient: 1 / 2 the spectra of the u-blocks / g-blocks stored, 3 the "
+              "lag-group correlation)";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (w[10] == MIFFT_CONV_GRAD_STAGE_LAGS) {
+        if (const int rc = conv_lag_check(p, w, why)) return rc;
+        return conv_radices(bases_flat, bases_len, pl.radices, why);
+    }
     ConvRequest r;
     r.grad = true;
+    r.stage = (int)w[10];
     r.D = w[2];
     r.o = w[3];
     r.S = w[4];
@@ -328,7 +397,13 @@ int conv_grad_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
               std::to_string(r.gates);
         return MIFFT_ERR_BAD_BASES;
     }
-    if (const int rc = conv_reserved_check(w, 10, 16, 1u << 11, "a filter-gradient", why)) return rc;
+    if (r.stage && (r.gates & ~(uint32_t)r.stage)) {  // (stage 1 loads x alone, stage 2 gy alone)
+        why = "the gates word 11 of a filter-gradient payload of stage " + std::to_string(r.stage) + " has bit " +
+              std::to_string(r.stage - 1) + " alone (the " + (r.stage == 1 ? "pregate: only x is loaded" : "postgate: only gy is loaded") +
+              "), not " + std::to_string(r.gates);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (const int rc = conv_reserved_check(w, 10, 16, 3u << 10, "a filter-gradient", why)) return rc;
     if (const int rc = conv_radices(bases_flat, bases_len, pl.radices, why)) return rc;
     p.conv = r;
     return MIFFT_OK;
@@ -342,8 +417,20 @@ static int64_t conv_grad_partials(const Plan& p, const DimPass& ps) {
     return std::max<int64_t>(1, std::min<int64_t>({P, pairs / ps.tile, (int64_t)65535}));
 }
 
-// the one pass, as build_conv's; then P
+// the one pass, as build_conv's; then P.  Stage 3 has no transform: its pass is the precompiled lag-group kernel (lag_corr.hip)
 int build_conv_grad(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
+    if (p.conv.stage == 3) {
+        DimPass ps;
+        ps.dim_index = 1;
+        ps.N = p.dims[1];
+        ps.first = true;
+        ps.half_pitch = p.dims[1] / 2 + 1;
+        ps.kernel_name = lag_corr_kernel_name(p.out_dtype, (int)p.conv.lag_groups);
+        ps.threads = kLagCorrThreads;
+        p.passes.push_back(ps);
+        if (p.conv.P == 0) p.conv.P = lag_corr_partials(p);
+        return MIFFT_OK;
+    }
     const int rc = build_conv(p, ordered, processed, why);
     if (rc) return rc;
     if (p.conv.P == 0) p.conv.P = conv_grad_partials(p, p.passes[0]);

@@ -157,8 +157,8 @@ static int unpack_conv_grad_args(const Plan& p, const void*& x, const void*& gy,
     if (!gated) {
         const mifft_conv_grad_args* g = (const mifft_conv_grad_args*)x;
         if (g->magic != MIFFT_CONV_GRAD_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + how);
-        if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.x is NULL");
-        if (!g->gy) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.gy is NULL");
+        if (!g->x && p.conv.stage != 2) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.x is NULL");
+        if (!g->gy && p.conv.stage != 1) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_args.gy is NULL");
         gy = g->gy;
         x = g->x;
         return MIFFT_OK;
@@ -167,8 +167,8 @@ static int unpack_conv_grad_args(const Plan& p, const void*& x, const void*& gy,
     if (g->magic == MIFFT_CONV_GRAD_ARGS_MAGIC)
         return set_error(MIFFT_ERR_UNSUPPORTED, std::string("a mifft_conv_grad_args names no gates: ") + how);
     if (g->magic != MIFFT_CONV_GRAD_GATED_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + how);
-    if (!g->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_gated_args.x is NULL");
-    if (!g->gy) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_gated_args.gy is NULL");
+    if (!g->x && p.conv.stage != 2) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_gated_args.x is NULL");
+    if (!g->gy && p.conv.stage != 1) return set_error(MIFFT_ERR_NULL, "mifft_conv_grad_gated_args.gy is NULL");
     const bool want_a = p.conv.gates & 1u, want_b = p.conv.gates & 2u;
     if (want_a && !g->pregate)
         return set_error(MIFFT_ERR_NULL, "the plan has a pregate (gates bit 0): mifft_conv_grad_gated_args.pregate is NULL");
@@ -185,9 +185,25 @@ static int unpack_conv_grad_args(const Plan& p, const void*& x, const void*& gy,
     return MIFFT_OK;
 }
 
-// the bytes of a filter-gradient plan's result: (P D, n / 2 + 1) complex values
+// the bytes of a filter-gradient plan's result: (P D, n / 2 + 1) complex values; the spectra of stage 1 or 2: (batch, F, n / 2 + 1);
+// the lag-group sums of stage 3: (P D Pg, n / 2 + 1)
 static size_t conv_grad_out_bytes(const Plan& p) {
-    return (size_t)(p.conv.P * p.conv.D) * (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
+    const size_t line = (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
+    if (p.conv.stage == 1 || p.conv.stage == 2) return (size_t)p.batch * (size_t)p.conv.F * line;
+    if (p.conv.stage == 3) return (size_t)(p.conv.P * p.conv.D * p.conv.lag_groups) * line;
+    return (size_t)(p.conv.P * p.conv.D) * line;
+}
+
+// the bytes of the two inputs of such an exec (0: the stage does not read that one)
+static size_t conv_grad_x_bytes(const Plan& p) {
+    if (p.conv.stage == 2) return 0;
+    if (p.conv.stage == 3) return (size_t)p.batch * (size_t)p.conv.u_frames * (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
+    return (size_t)p.batch * p.in_row_bytes();
+}
+static size_t conv_grad_gy_bytes(const Plan& p) {
+    if (p.conv.stage == 1) return 0;
+    if (p.conv.stage == 3) return (size_t)p.batch * (size_t)p.conv.F * (size_t)(p.dims[1] / 2 + 1) * 2 * dtype_size(p.out_dtype);
+    return (size_t)p.batch * (size_t)p.conv.Lo * p.conv.elem_bytes(p.out_dtype);
 }
 
 static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first, int64_t count, void* stream) {
@@ -197,16 +213,16 @@ static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first
     const void *gy = nullptr, *pregate = nullptr, *postgate = nullptr;
     if (const int rc = unpack_conv_grad_args(p, x, gy, pregate, postgate)) return rc;
     const char *xb = (const char*)x, *gb = (const char*)gy, *ob = (const char*)out;
-    const size_t xn = (size_t)p.batch * p.in_row_bytes(), gn = (size_t)p.batch * (size_t)p.conv.Lo * p.conv.elem_bytes(p.out_dtype),
-                 on = conv_grad_out_bytes(p);
-    if (xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
-    if (gb < ob + on && ob < gb + gn) return set_error(MIFFT_ERR_ALIAS, "gy and out must not overlap");
+    const size_t xn = conv_grad_x_bytes(p), gn = conv_grad_gy_bytes(p), on = conv_grad_out_bytes(p);
+    if (xn && xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
+    if (gn && gb < ob + on && ob < gb + gn) return set_error(MIFFT_ERR_ALIAS, "gy and out must not overlap");
     // (the pregate has x's size, the postgate gy's; either may alias x, gy or the other: none is written)
     const char *ab = (const char*)pregate, *bb = (const char*)postgate;
     if (ab && ab < ob + on && ob < ab + xn) return set_error(MIFFT_ERR_ALIAS, "the pregate and out must not overlap");
     if (bb && bb < ob + on && ob < bb + gn) return set_error(MIFFT_ERR_ALIAS, "the postgate and out must not overlap");
     DeviceGuard guard(p.device);
     MIFFT_HIP_TRY(guard.err);
+    if (p.conv.stage == 3) return launch_lag_corr(p, x, gy, out, (hipStream_t)stream);  // (x: the spectra U, gy: the spectra G)
     return launch_jit_conv_grad(p, p.passes[0], x, gy, pregate, postgate, out, (hipStream_t)stream);
 }
 

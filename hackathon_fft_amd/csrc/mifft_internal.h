@@ -145,6 +145,15 @@ struct ConvRequest {
     // (mifft_conv_grad_args; with gates mifft_conv_grad_gated_args) -> (P D, n / 2 + 1) complex values, unscaled
     int64_t P = 0;
     bool grad = false;
+    // word 10 of a filter-gradient payload: the stage of the fused partitioned filter gradient the plan is (0: none, the fused
+    // gradient above).  1 / 2: the half spectra of the u-blocks / g-blocks of that geometry STORED, (batch, F, n / 2 + 1)
+    // complex values, instead of summed (TileCfg::WSPEC); P slices the walk.  3: the lag-group correlation over such spectra
+    // (lag_corr.hip): dims = {max(u_frames, 2), n}; U is (batch, u_frames, n / 2 + 1), stored frame j being frame u_first + j, G is
+    // (batch, F, n / 2 + 1); out row (s, d, p), p < lag_groups, is the sum over slice s of the batch entries b of channel d,
+    // ascending, and over f < F, ascending, of conj(U[b, d, f - p]) G[b, d, f] (mode bit 0: U[b, d, f + p], and the conjugate of
+    // the sum is stored), frames outside the stored ones counting as zeros that are never read; P such slices.
+    int stage = 0;
+    int64_t lag_groups = 0, u_frames = 0, u_first = 0;
     uint32_t mode = 0;
     // bits 8..15 of the mode word: the STORAGE type of x, the gates and out (a filter-gradient plan: of x, gy and the gates), 0 the plan's
     // float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan: 2-byte elements widened in the load and rounded once in the
@@ -486,6 +495,15 @@ int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, c
                          const void* postgate, void* out, hipStream_t stream);
 // workgroups per CU of a built tile-kernel pass's persistent grid (kernels_jit.cpp): the launches' rule, and build_conv_grad's
 long long pass_wg_per_cu(const DimPass& pass);
+// Stage 3 of the fused partitioned filter gradient (ConvRequest::stage; lag_corr.hip): the precompiled lag-group kernel.  A
+// workgroup of kLagCorrThreads work items owns a channel, that many consecutive bins and a slice of the batch; the name is
+// `lag_corr_<f32|f64>_p<bound>`, bound the compile-time count of accumulators (2, 4, 8, 16 or 32) that holds Pg.
+// lag_corr_partials: P of a plan whose payload left it to the library -- 1 unless D times the bin groups alone leave the
+// device short of workgroups, then enough slices of the batch to fill it, at most one per batch entry.
+constexpr int kLagCorrThreads = 256;
+const char* lag_corr_kernel_name(int dtype, int lag_groups);
+int64_t lag_corr_partials(const Plan& plan);
+int launch_lag_corr(const Plan& plan, const void* U, const void* G, void* out, hipStream_t stream);
 // the band tables of such a plan, one device allocation (DimPass::d_aux3): lo[M], len[M], off[M] as int32, padded to an even
 // count of ints, then the weights in the plan's float type, then the M Q weights of `post` in the same type
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }

@@ -322,6 +322,8 @@ struct TileParams {
     // w / P and stores row (w % P) D + w / P of `out`, (P D) rows of N + 1 complex values.  With GATE the gates of the forward
     // plan multiply the two inputs as they are loaded: wgrad_pregate (in the place of conv_h; x's shape) every sample of x,
     // gate_out (gy's shape: the forward's `out`) every sample of gy; null where there is no such gate.
+    // WSPEC configurations (WGRAD's store variant) read the same fields; `out` is (rows, ols_blocks, N + 1) complex values
+    // and wgrad_partials only slices the walk.  WSPEC = 1 never reads gate_in / gate_out, WSPEC = 2 never `in` / wgrad_pregate.
     // PART configurations (partitioned overlap-save) are OLS's with conv_Q and conv_parts set.
     // GATE configurations (CONV / OLS / PART with elementwise gates; the arguments of one exec, not plan state): gate_in has
     // the shape of `in` and multiplies every sample as it is loaded, gate_out the shape of `out` and multiplies every sample as
@@ -435,7 +437,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
           bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false, bool PART_ = false,
-          int ADJ_ = 0, bool IADJ_ = false>
+          int ADJ_ = 0, bool IADJ_ = false, int WSPEC_ = 0>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -706,6 +708,15 @@ struct TileCfg {
     // a load zero-extends reads no gate.  The bins equal the ungated kernel's on the products a . x and b . gy bit for bit.
     static constexpr bool WGRAD = WGRAD_;
     static_assert(!WGRAD_ || CONV_, "WGRAD: the filter-gradient twin of a CONV / OLS tile");
+    // WSPEC (with WGRAD, any GATE): the store variant of the filter-gradient tile, stage 1 of the fused partitioned filter
+    // gradient (conv.cpp, lag_corr.hip).  1: the walk runs WGRAD's u-block load alone (zero extension, pregate, widening),
+    // 2: its g-block load alone (the band [c, c + S), postgate); then the passes and the unpack of bin pairs as ever, and
+    // instead of accumulating every work item STORES the bins it unpacked: block f of signal row r goes to row (r F + f) of
+    // `out`, (rows, F, N + 1) complex values of type T, unscaled and unconjugated -- frames-major, whole lines, each value
+    // written once.  The slices of a channel's (signal, block) pairs and the grid of D P workgroups are WGRAD's; nothing is
+    // summed, so P only spreads the work.  No accumulators, no reduction through LDS.
+    static constexpr int WSPEC = WSPEC_;
+    static_assert(WSPEC_ >= 0 && WSPEC_ <= 2 && (WSPEC_ == 0 || WGRAD_), "WSPEC: the spectrum-store twin of a WGRAD tile");
     // PART (with CONV and OLS, any GATE): uniformly partitioned overlap-save, for filters longer than half a block.  The filter
     // is P partitions of Q taps with one spectrum each, H[d][p]; output block f of a signal is the sum over p of the spectrum of
     // the n samples from s0 + f S - p Q on (correlation: + p Q) times H[d][p] (its conjugate), folded and inverted ONCE.  A step
@@ -1747,6 +1758,30 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
             xb = {ex - tx, ty - ey};
         }
     };
+    // TileCfg::WSPEC: the bins of the step's nv live pairs, as unpacked, to row (signal row) F + block of `out`; consecutive
+    // work items hold consecutive bins k of one row, so the stores of X[k] run up whole lines and those of X[N-k] down them
+    auto store_bins = [&](int nv, long long b0, int fr0) {
+        V* const so = (V*)p.out;
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            const int f = tid + i * C::THREADS;
+            V xa, xb;
+            unpack(i, xa, xb);
+            if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
+                const int c = f / PAIRS, k = f - c * PAIRS;
+                if (c < nv) {
+                    int fr = fr0 + c, db = 0;
+                    if (fr >= F) {
+                        db = fr / F;
+                        fr -= db * F;
+                    }
+                    V* const row = so + (((b0 + db) * D + d) * F + fr) * (long long)(C::N + 1);
+                    row[k] = xa;
+                    if (2 * k != C::N) row[C::N - k] = xb;  // (k = 0: bin N)
+                }
+            }
+        }
+    };
     for (; q < q_end; q += C::TILE) {
         const int nv = q_end - q < C::TILE ? (int)(q_end - q) : C::TILE;
         tid = tid_entry;  // (opaque once per step, as in tile_kernel: the offsets derived from it are not kept live across steps)
@@ -1757,7 +1792,8 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
         const long long b0 = q / F;
         const int fr0 = (int)(q - b0 * F);
         // u-blocks: packed element m of pair c holds the samples s0 + fr S + 2 m and + 1 of its row, zeros outside [0, L)
-        for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
+        // (WSPEC = 2 stores the spectra of the g-blocks: no u-block is loaded)
+        for (int f = tid; C::WSPEC != 2 && f < C::TILE * C::N; f += C::THREADS) {
             const int c = f / C::N, m = f - c * C::N;
             V v = {(T)0, (T)0};
             if (c < nv) {
@@ -1789,12 +1825,21 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
             }
             lds[lds_index<C, -1>(c, m)] = v;
         }
-        __syncthreads();
-        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        if constexpr (C::WSPEC != 2) {
+            __syncthreads();
+            run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        }
+        if constexpr (C::WSPEC == 1) {
+            store_bins(nv, b0, fr0);
+            __syncthreads();
+            continue;
+        }
         V ua[IT], ub[IT];
+        if constexpr (C::WSPEC == 0) {
 #pragma unroll
-        for (int i = 0; i < IT; ++i) unpack(i, ua[i], ub[i]);
-        __syncthreads();
+            for (int i = 0; i < IT; ++i) unpack(i, ua[i], ub[i]);
+            __syncthreads();
+        }
         // g-blocks: sample i of the block is gy[row][fr S + i - c] for c <= i < c + S and fr S + i - c < Lo, zero elsewhere
         for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
             const int c = f / C::N, m = f - c * C::N;
@@ -1831,6 +1876,11 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
         }
         __syncthreads();
         run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        if constexpr (C::WSPEC == 2) {
+            store_bins(nv, b0, fr0);
+            __syncthreads();
+            continue;
+        }
 #pragma unroll
         for (int i = 0; i < IT; ++i) {
             V ga, gb;
@@ -1843,8 +1893,9 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
         }
         __syncthreads();
     }
+    if constexpr (C::WSPEC != 0) return;  // (every bin is in memory: nothing was summed)
     // the TILE rows in ascending order, through the tile's LDS: first the bins k, then the bins N - k
-    V* out = (V*)p.out + ((long long)sl * D + d) * (C::N + 1);
+    V* out =(V*)p.out + ((long long)sl * D + d) * (C::N + 1);
     const T cj = (p.conv_mode & 1) ? (T)-1 : (T)1;
     static_assert(C::TILE * PAIRS <= C::DATA_ELEMS, "WGRAD: one accumulator per (row, bin pair) fits the tile");
 #pragma unroll

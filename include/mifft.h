@@ -742,7 +742,8 @@ typedef struct mifft_gated_args {
  *     word  8      Lo >= 1: samples per row of gv
  *     word  9      P: partial sums per channel, 1 <= P <= min(65535, batch / D * F); 0: the library picks it, so that D P
  *                  workgroups fill the device when D alone does not
- *     word 10      reserved, 0
+ *     word 10      stage: 0 the fused gradient described here (every payload written before there were stages); 1, 2 or 3 a
+ *                  stage of the FUSED PARTITIONED FILTER GRADIENT below; above 3 reserved, MIFFT_ERR_BAD_BASES
  *     word 11      gates: 0 none (every payload written before there were any), bit 0 the forward plan's pregate, bit 1 its
  *                  postgate (1, 2 or 3); above 3 MIFFT_ERR_BAD_BASES.  See GATES below
  *     word 12 .. 15 reserved, 0
@@ -762,7 +763,7 @@ typedef struct mifft_gated_args {
  * the size of the (P D, n / 2 + 1, 2) result.
  * Refused before any device work, with the forward plan's statuses: the flag, direction, dtype and component checks, the
  * limits of n (even, 8 .. 16384, float64 to 12288, n / 2 without a prime factor above 32), D and batch % D; MIFFT_ERR_BAD_BASES for the geometry rules above, a mode word beyond bit 0, P beyond its range, a gates
- * word above 3 or a non-zero reserved word.  The 8-, 12- and 16-word MIFFT_CONV_TAG payloads are what they were.
+ * word above 3, a stage word above 3 or a non-zero reserved word.  The 8-, 12- and 16-word MIFFT_CONV_TAG payloads are what they were.
  * Half-precision storage: bits 8..15 of the mode word, as in the MIFFT_CONV_TAG forms above (0, MIFFT_F16 or MIFFT_BF16; an
  * F32 plan only: MIFFT_ERR_BAD_DTYPE otherwise; any other value or bit MIFFT_ERR_BAD_BASES).  x and gv are then arrays of
  * 2-byte elements, widened exactly in both block loads; the sums and the result stay float: mifft_plan_in_bytes() counts 2
@@ -783,7 +784,38 @@ typedef struct mifft_gated_args {
  * block lacks, a null x or gy; MIFFT_ERR_UNSUPPORTED: a gate the plan did not ask for; MIFFT_ERR_ALIAS: x, gy or a gate
  * overlapping out (storage sizes).  Nothing is launched in any of these cases.  The gates may alias x, gy or each other: none
  * is written.  A plan without gates takes the mifft_conv_grad_args block as ever.
+ *
+ * THE FUSED PARTITIONED FILTER GRADIENT (word 10): the filter gradient of a partitioned convolution (filters longer than half
+ * a block, K up to 32 n / 2 taps) as three plans of this tag that transform every block of u and of gv ONCE -- a
+ * frequency-domain delay line.  With H = n / 2, Pg = ceil(K / H) lag groups and Fg = ceil(Lo / H) g-blocks:
+ *     g-block f holds gv[f H + i], i < H, f H + i < Lo, at index H + i (forward correlated: at index i); zeros elsewhere
+ *     u-frame m is the n samples of u from o + m H - H on (forward correlated: from o + m H on), zeros outside [0, L)
+ *     A[d][p][k] = sum_b sum_f conj(U[b, d, f - p][k]) G[b, d, f][k]     (forward correlated: U[b, d, f + p], conjugate stored)
+ *     gk[d][p H + l] = irfft(A[d][p], n)[l],  l < H
+ * It does not depend on how the forward plan chose its Q.  A u-frame that holds no sample of [0, L) is neither transformed nor
+ * stored; the live frames are a contiguous range m0 .. m0 + Fu - 1.
+ *   stage 1 (MIFFT_CONV_GRAD_STAGE_U): the payload above with c = 0, S = H, F = Fu, s0 = the first sample of u-frame m0, Lo =
+ *     Fu H, gates 0 or 1.  The exec reads x (and the pregate) alone -- gy may be NULL -- and STORES rfft of every u-block:
+ *     out is (batch, Fu, n / 2 + 1, 2), unscaled, mifft_plan_out_bytes() its size.  P only slices the walk.
+ *   stage 2 (MIFFT_CONV_GRAD_STAGE_G): the payload above with c = H (forward correlated: 0), S = H, F = Fg, s0 = 0, Lo,
+ *     dims[0] = max(Lo, 2), gates 0 or 2.  The exec reads gy (and the postgate) alone -- x may be NULL -- and stores rfft of
+ *     every g-block: out is (batch, Fg, n / 2 + 1, 2).
+ *     Both are TileCfg::WSPEC on the WGRAD tile, its two block loads unchanged (zero extension, gates, 16-bit widening):
+ *     rows<n>[_f64]_r2c_<radices>_wspecu[_ols][_g1][_h16|_b16]_jit and .._wspecg[_ols][_g2][_h16|_b16]_jit, run time only.
+ *     A gates bit the stage does not load is MIFFT_ERR_BAD_BASES.
+ *   stage 3 (MIFFT_CONV_GRAD_STAGE_LAGS): the lag-group correlation, a precompiled kernel lag_corr_<f32|f64>_p<2|4|8|16|32>.
+ *     dims = {max(Fu, 2), n};  word 3 Fu, word 4 Pg (1 .. 32; above: MIFFT_ERR_UNSUPPORTED), word 5 mode (bit 0 alone),
+ *     word 6 Fg, word 7 m0 (signed), word 8 Fg again, word 9 P partial sums per channel (slices of the batch / D entries of a
+ *     channel, at most that many and 65535; 0: the library picks 1 unless D ceil((n / 2 + 1) / 256) workgroups leave the
+ *     device short), word 11 0.  The exec's block is a mifft_conv_grad_args whose x is U, (batch, Fu, n / 2 + 1, 2), and gy is
+ *     G, (batch, Fg, n / 2 + 1, 2), both of the plan's float type; out is (P, D, Pg, n / 2 + 1, 2).  Every sum runs over b
+ *     ascending, then f ascending; no atomics: two execs give the same bits.
+ * The caller owns U and G (scratch of about four times the bytes of x and gy) and may cut the batch into slabs of whole
+ * batch entries, one trio of execs and one partial per slab.
  */
+#define MIFFT_CONV_GRAD_STAGE_U 1u
+#define MIFFT_CONV_GRAD_STAGE_G 2u
+#define MIFFT_CONV_GRAD_STAGE_LAGS 3u
 #define MIFFT_CONV_GRAD_TAG_LO 0x44524701u
 #define MIFFT_CONV_GRAD_TAG_HI 0x7FF84D47u
 /* the argument block of a filter-gradient exec (above); the magic word is "MIFFTWG1" */
