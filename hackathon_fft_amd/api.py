@@ -1684,7 +1684,10 @@ def dctn(x: "torch.Tensor", type: int = 2, norm=None, *, dim=None, out_dtype=Non
     negative dims allowed), resolved through reduce_dims: the other dims are carried through in place.  One kernel launch per
     transformed dim and no transposition (MIFFT_FLAG_DCT_ND): the innermost transformed dim, when it is the last dim of size
     above 1, runs the row kernel of ``dct`` (an even length from 8 on); every other one is transformed in place as pairs of
-    adjacent real columns (any length from 2 to 4096 with prime factors up to 32, at an even stride of at least 4 elements).
+    adjacent real columns, at an even stride of at least 4 elements.  A float32 result takes any column length from 2 to 4096
+    with prime factors up to 32; a float64 result every such length up to 2056 and, from 2058 up, only those the library has a
+    three-pass column configuration for (4092 is the longest; 2058, 2080, 2100, 2401, 4000, 4095, 4096 and 150 more are
+    refused with MifftError -15 "no fused column configuration").
     The result has the shape of ``x`` and dtype ``out_dtype`` (default: that of a float32 / float64 ``x``, else float64); a
     non-contiguous ``x`` is copied first; an empty ``dim`` or one of size-1 dims only returns a converted copy.  Only
     ``type=2`` (MifftError -15 otherwise); ``norm`` as in ``dct``."""

@@ -251,8 +251,11 @@ typedef enum {
  *     v[n-1-j] = u[2j+1]), Z = FFT_n(v), and with W = e^(-i pi k / 2n) the store separates V_a = (Z[k] + conj Z[n-k]) / 2 and
  *     V_b = (Z[k] - conj Z[n-k]) / 2i and writes row k = (2 Re(W V_a), 2 Re(W V_b)), row n-k = (-2 Im(W V_a), -2 Im(W V_b)).
  *     Inverse: the load forms Z[k] = conj(W) (X[k] - i X[n-k]) / 2 from rows k and n-k (X[n] := 0), the n-point inverse
- *     follows and element j of its result is row 2j (j < ceil(n / 2)), element n-1-j row 2j+1.  Every n from 2 to 4096 whose
- *     prime factors are at most 32, odd lengths included; mifft_plan_stages() reports n-point stages, `bases` factor n.
+ *     follows and element j of its result is row 2j (j < ceil(n / 2)), element n-1-j row 2j+1.  F32: every n from 2 to 4096 whose
+ *     prime factors are at most 32, odd lengths included.  F64: every such n up to 2056; from 2058 up only the lengths with a
+ *     three-pass column configuration (4092 is the longest; 2058, 2080, 2100, 2401, 4000, 4095, 4096 and 150 more are refused:
+ *     the radix chooser prefers four passes, whose F64 tile holds at most 4096 elements, and does not retry with three).
+ *     mifft_plan_stages() reports n-point stages, `bases` factor n.
  *     The kernel is cols<n>[_f64]_dct2_<radices>_jit / ..._dct3_<radices>_jit: compiled at run time only.
  * mifft_plan_pass_geometry() works for both kinds of pass (a column pass counts tiles of pairs of columns).  Slab execs and
  * whole_batch behave as for every other plan.  x and out need the alignment of one element only.
@@ -263,8 +266,8 @@ typedef enum {
  *     instance (1024 points);
  *   - a transformed other dim whose stride S is odd;
  *   - a transformed other dim whose stride S is 2 (a trailing extent of 2: a single pair of columns is a row-shaped problem);
- *   - a transformed other dim above 4096 points, one with a prime factor above 32, or one whose narrowest column tile does
- *     not fit LDS (F64: 4096 points);
+ *   - a transformed other dim above 4096 points, one with a prime factor above 32, or one without a fused column configuration
+ *     (F64 only: 157 lengths from 2058 up, listed above; "no fused column configuration");
  *   - a forward plan with in_dtype != out_dtype whose last dim is kept (its first pass is a column pass, which reads the
  *     plan's own float type);
  *   - MIFFT_JIT=0 with any transformed dim but the last. */

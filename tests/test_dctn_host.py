@@ -100,7 +100,9 @@ def test_a_valid_request_gets_as_far_as_the_device(inverse):
     assert rc == -10, why
     rc, why = _create([2048, 8, 8192], inverse=inverse, in_dtype=1, out_dtype=1, batch=1)  # ... and long fp64 ones
     assert rc == -10, why
-    rc, why = _create([4096, 64], inverse=inverse, in_dtype=1, out_dtype=1)  # (no fp64 column tile of 4096 points fits LDS)
+    rc, why = _create([4096, 64], inverse=inverse, in_dtype=1, out_dtype=1)
+    # (8 x 8 x 8 x 8: a four-pass fp64 tile holds at most 4096 elements, two columns of 4096 points are 8192, and the chooser
+    #  does not retry with three passes -- as at 2058, 2080, .. where the tile would be 66 KB; test_column_classes_host.py)
     assert rc == UNSUPPORTED and "column configuration" in why, why
 
 
