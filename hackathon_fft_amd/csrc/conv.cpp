@@ -79,7 +79,7 @@ static int conv_header_check(const Plan& p, const char* tag, std::string& why) {
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
-    if (!conv_rows_supported(p, n, w)) {
+    if (!tile_family_supported(TileFamily::ConvRows, p, n, 1, w)) {
         why = "convolution at an FFT length of " + std::to_string(n) + ": " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -281,21 +281,11 @@ int conv_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, Fr
 // the one pass: dim 1 (n points) over the rows of the batch; the tables are the half-spectrum row pass's
 int build_conv(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
     const int64_t n = p.dims[1];
-    DimPass ps;
-    ps.dim_index = 1;
-    ps.N = n;
-    ps.inner = 1;
-    ps.outer = p.conv.F;  // (overlap-save: the block rows of one signal row; else 1)
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    ps.half_pitch = n / 2 + 1;
-    if (!select_jit_conv_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
-    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
-    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "convolution table upload");
-    return MIFFT_OK;
+    // (outer: overlap-save, the block rows of one signal row; else 1)
+    DimPass ps = fused_row_pass(1, n, p.conv.F, ordered, processed, /*half_pitch=*/true);
+    if (!select_tile_family(TileFamily::ConvRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    const hipError_t e = upload_packed_tables(p.out_dtype, false, ps);
+    return append_pass(p, ps, e, "convolution table upload");
 }
 
 // ---- the filter gradient: TAG_LO | TAG_HI | D | c | S | mode | F | s0 | Lo | P | 0 | gates | 0 x 4 (MIFFT_CONV_GRAD_TAG, include/mifft.h) ----

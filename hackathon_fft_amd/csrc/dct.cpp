@@ -58,13 +58,13 @@ int dct_check(const Plan& p, std::string& why) {
     }
     std::string w;
     if (p.dct4) {
-        if (!dct4_rows_supported(p, n, w)) {
+        if (!tile_family_supported(TileFamily::Dct4Rows, p, n, 1, w)) {
             why = "DCT-IV of " + std::to_string(n) + " points: " + w;
             return MIFFT_ERR_UNSUPPORTED;
         }
         return MIFFT_OK;
     }
-    if (!dct_rows_supported(p, n, w)) {
+    if (!tile_family_supported(TileFamily::DctRows, p, n, 1, w)) {
         why = "DCT of " + std::to_string(n) + " points: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -119,22 +119,13 @@ static double dct4_scale(int64_t n, bool inverse, bool ortho) {
 // the DCT-IV pass of n points over `outer` rows per batch entry: kernel, scale and tables; appended to plan.passes
 static int build_dct4_rows(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {
     const int64_t n = p.dims[0];
-    DimPass ps;
-    ps.dim_index = 0;
-    ps.N = n;
-    ps.inner = 1;
-    ps.outer = 1;
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    if (!select_jit_dct4_rows(p, ps, /*mdct=*/false, why)) return MIFFT_ERR_UNSUPPORTED;
+    DimPass ps = fused_row_pass(0, n, 1, ordered, processed, /*half_pitch=*/false);
+    if (!select_tile_family(TileFamily::Dct4Rows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
     ps.dct_s0 = ps.dct_s1 = dct4_scale(n, p.inverse != 0, (p.flags & MIFFT_FLAG_DCT_ORTHO) != 0);
     // the passes run n / 2 points, forward in both directions
     hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, n, &ps.d_aux2);
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "DCT-IV table upload");
-    return MIFFT_OK;
+    return append_pass(p, ps, e, "DCT-IV table upload");
 }
 
 // the scales of bin 0 and of the other bins.  Forward: X[k] = 2 Re(..), "ortho" times sqrt(1 / 4n) and sqrt(1 / 2n).
@@ -156,24 +147,13 @@ void dct_scales(int64_t n, bool inverse, bool ortho, double& s0, double& s1) {
 int build_dct_rows(Plan& p, int dim_index, int64_t outer, const std::vector<uint32_t>& ordered,
                    const std::vector<uint32_t>& processed, std::string& why) {
     const int64_t n = p.dims[dim_index];
-    DimPass ps;
-    ps.dim_index = dim_index;
-    ps.N = n;
-    ps.inner = 1;
-    ps.outer = outer;
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    ps.half_pitch = n / 2 + 1;  // (unused by the DCT loads and stores: both sides are rows of n reals)
-    if (!select_jit_dct_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    // (half_pitch: unused by the DCT loads and stores, both sides are rows of n reals)
+    DimPass ps = fused_row_pass(dim_index, n, outer, ordered, processed, /*half_pitch=*/true);
+    if (!select_tile_family(TileFamily::DctRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
     dct_scales(n, p.inverse != 0, (p.flags & MIFFT_FLAG_DCT_ORTHO) != 0, ps.dct_s0, ps.dct_s1);
-    // the passes run n / 2 points; the fold / unpacking needs W_n^k, forward; the DCT twiddle W_4n^k
-    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, p.inverse != 0, &ps.d_twiddle);
-    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
-    if (e == hipSuccess) e = upload_quarter_table(p.out_dtype, n, &ps.d_aux2);
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "DCT table upload");
-    return MIFFT_OK;
+    hipError_t e = upload_packed_tables(p.out_dtype, p.inverse != 0, ps);
+    if (e == hipSuccess) e = upload_quarter_table(p.out_dtype, n, &ps.d_aux2);  // the DCT twiddle W_4n^k
+    return append_pass(p, ps, e, "DCT table upload");
 }
 
 int build_dct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why) {

@@ -66,7 +66,7 @@ int dctn_check(const Plan& p, std::string& why) {
                 return MIFFT_ERR_UNSUPPORTED;
             }
             std::string w;
-            if (!dct_rows_supported(p, n, w)) {
+            if (!tile_family_supported(TileFamily::DctRows, p, n, 1, w)) {
                 why = "DCT of the last " + dim + ": " + w;
                 return MIFFT_ERR_UNSUPPORTED;
             }
@@ -92,7 +92,7 @@ int dctn_check(const Plan& p, std::string& why) {
                 return MIFFT_ERR_UNSUPPORTED;
             }
             std::string w;
-            if (!dct_cols_supported(p, n, s / 2, w)) {
+            if (!tile_family_supported(TileFamily::DctCols, p, n, s / 2, w)) {
                 why = "DCT column pass over " + dim + ": " + w;
                 return MIFFT_ERR_UNSUPPORTED;
             }
@@ -126,7 +126,7 @@ int build_dctn(Plan& p, const std::vector<std::vector<uint32_t>>& ordered,
         ps.processed = processed[i];
         ps.first = first;
         std::string w;
-        if (!select_jit_dct_cols(p, ps, w)) {
+        if (!select_tile_family(TileFamily::DctCols, p, ps, w)) {
             why = "DCT column pass over dimension " + std::to_string(i) + " (" + std::to_string(n) + " points): " + w;
             return MIFFT_ERR_UNSUPPORTED;
         }
@@ -134,8 +134,7 @@ int build_dctn(Plan& p, const std::vector<std::vector<uint32_t>>& ordered,
         // the n-point passes, and the quarter-sample twiddle W_4n^k of the separating store / combining load
         hipError_t e = upload_twiddle_table(p.out_dtype, n, p.inverse != 0, &ps.d_twiddle);
         if (e == hipSuccess) e = upload_quarter_table(p.out_dtype, n, &ps.d_aux2);
-        p.passes.push_back(ps);
-        if (e != hipSuccess) return hip_error(e, "DCT table upload");
+        if (const int rc = append_pass(p, ps, e, "DCT table upload")) return rc;
         first = false;
     }
     if (config().nd_mode & 2) {  // in-place passes alternate their walking direction (bit-identical results)

@@ -70,7 +70,7 @@ int half_spectrum_check(const Plan& p, std::string& why) {
             return MIFFT_ERR_UNSUPPORTED;
         }
     std::string w;
-    if (!half_rows_supported(p, n, w)) {
+    if (!tile_family_supported(TileFamily::HalfRows, p, n, 1, w)) {
         why = "half spectrum of a last dimension of " + std::to_string(n) + " points: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -93,16 +93,9 @@ int build_half_spectrum(Plan& p, const std::vector<std::vector<uint32_t>>& order
             const int rc = ps.prepare();
             if (rc) return rc;
         }
-        hipError_t e;
-        if (ps.r2c || ps.c2r) {  // the passes run N / 2 points; the fold / unpacking needs W_N^k, forward
-            e = upload_twiddle_table(p.out_dtype, ps.N / 2, p.inverse != 0, &ps.d_twiddle);
-            if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, ps.N, false, &ps.d_aux);
-        } else {
-            e = upload_twiddle_table(p.out_dtype, ps.N, p.inverse != 0, &ps.d_twiddle);
-        }
-        p.passes.push_back(ps);
-        if (e != hipSuccess) return hip_error(e, "twiddle table upload");
-        return MIFFT_OK;
+        const hipError_t e = ps.r2c || ps.c2r ? upload_packed_tables(p.out_dtype, p.inverse != 0, ps)
+                                              : upload_twiddle_table(p.out_dtype, ps.N, p.inverse != 0, &ps.d_twiddle);
+        return append_pass(p, ps, e, "twiddle table upload");
     };
     auto rows = [&](DimPass& ps) -> int {
         ps.dim_index = nd - 1;
@@ -112,7 +105,7 @@ int build_half_spectrum(Plan& p, const std::vector<std::vector<uint32_t>>& order
         ps.radices = ordered[nd - 1];
         ps.processed = processed[nd - 1];
         ps.half_pitch = h;
-        if (!select_jit_half_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+        if (!select_tile_family(TileFamily::HalfRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
         return add(ps);
     };
     auto column = [&](int j, DimPass& ps) -> int {

@@ -106,7 +106,7 @@ static int istft_check_impl(const Plan& p, const uint32_t* bases_flat, const int
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
-    if (!istft_rows_supported(p, n, w)) {
+    if (!tile_family_supported(TileFamily::IstftRows, p, n, 1, w)) {
         why = "STFT with frames of " + std::to_string(n) + " points: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -365,7 +365,7 @@ int istft_adj_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_le
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
-    if (!stft_rows_supported(p, n, w)) {
+    if (!tile_family_supported(TileFamily::StftRows, p, n, 1, w)) {
         why = "STFT with frames of " + std::to_string(n) + " points: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -388,18 +388,9 @@ static hipError_t upload_istft_adj_tables_t(int64_t n, int64_t hop, int64_t F, c
 int build_istft_adj(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
                     std::string& why) {
     const int64_t n = p.dims[1], F = p.istft_adj, hop = p.stft_hop();
-    DimPass ps;
-    ps.dim_index = 1;
-    ps.N = n;
-    ps.inner = 1;
-    ps.outer = F;
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    ps.half_pitch = n / 2 + 1;
-    if (!select_jit_stft_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
-    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
-    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    DimPass ps = fused_row_pass(1, n, F, ordered, processed, /*half_pitch=*/true);
+    if (!select_tile_family(TileFamily::StftRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    hipError_t e = upload_packed_tables(p.out_dtype, false, ps);
     if (e == hipSuccess) {
         try {
             e = p.out_dtype == MIFFT_F64 ? upload_istft_adj_tables_t<double>(n, hop, F, pl.window, pl.gain, &ps.d_aux2, &ps.d_aux3)
@@ -408,9 +399,7 @@ int build_istft_adj(Plan& p, const std::vector<uint32_t>& ordered, const std::ve
             e = hipErrorOutOfMemory;
         }
     }
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "inverse STFT adjoint table upload");
-    return MIFFT_OK;
+    return append_pass(p, ps, e, "inverse STFT adjoint table upload");
 }
 
 // ---- IMDCT plans: the payload w[0 .. 2M-1] | MIFFT_MDCT_TAG | gain on a MIFFT_FLAG_ISTFT plan -------------------------------------
@@ -466,7 +455,7 @@ int imdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, F
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
-    if (!imdct_rows_supported(p, M, w)) {
+    if (!tile_family_supported(TileFamily::ImdctRows, p, M, 1, w)) {
         why = "IMDCT with M = " + std::to_string(M) + " coefficients per frame: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -514,15 +503,8 @@ int build_imdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector
     const int64_t M = p.imdct;
     const std::vector<double>& window = pl.window;
     const double gain = pl.gain;
-    DimPass ps;
-    ps.dim_index = 2;
-    ps.N = M;
-    ps.inner = 1;
-    ps.outer = p.dims[1];
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    if (!select_jit_imdct_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    DimPass ps = fused_row_pass(2, M, p.dims[1], ordered, processed, /*half_pitch=*/false);
+    if (!select_tile_family(TileFamily::ImdctRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
     // (the sweep leaves the plain cosine sums: the whole scale is in the table below, and dct_s1 is not applied)
     hipError_t e = upload_twiddle_table(p.out_dtype, M / 2, false, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, M, &ps.d_aux2);
@@ -537,9 +519,7 @@ int build_imdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector
             e = upload_t<float>(ws, &ps.d_aux3);
         }
     }
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "IMDCT table upload");
-    return MIFFT_OK;
+    return append_pass(p, ps, e, "IMDCT table upload");
 }
 
 // the one pass: dim 2 (n points) over the F frames of every batch entry
@@ -548,19 +528,9 @@ int build_istft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector
     const int64_t F = p.dims[1], n = p.dims[2], hop = p.stft_hop();
     const std::vector<double>& window = pl.window;
     const double gain = pl.gain;
-    DimPass ps;
-    ps.dim_index = 2;
-    ps.N = n;
-    ps.inner = 1;
-    ps.outer = F;
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    ps.half_pitch = n / 2 + 1;
-    if (!select_jit_istft_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
-    // the passes run n / 2 points; the fold needs W_n^k, forward (as a half-spectrum row pass)
-    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, true, &ps.d_twiddle);
-    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    DimPass ps = fused_row_pass(2, n, F, ordered, processed, /*half_pitch=*/true);
+    if (!select_tile_family(TileFamily::IstftRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    hipError_t e = upload_packed_tables(p.out_dtype, true, ps);  // (as an inverse half-spectrum row pass)
     if (e == hipSuccess && p.stft_adj) {  // ws[j] = gain * w[j] / 2 (mode 2: gain * w[j]) with the sign of the conjugation; no envelope
         const double g = p.stft_adj == 2 ? gain : 0.5 * gain;
         std::vector<double> ws((size_t)n);
@@ -578,9 +548,7 @@ int build_istft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector
             e = hipErrorOutOfMemory;
         }
     }
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "inverse STFT table upload");
-    return MIFFT_OK;
+    return append_pass(p, ps, e, "inverse STFT table upload");
 }
 
 }  // namespace mifft

@@ -362,10 +362,33 @@ bool select_jit_ilv(const Plan& plan, DimPass& pass, std::string& why_not);
 int axes_check(const Plan& plan, std::string& why);
 int build_axes(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                const std::vector<std::vector<uint32_t>>& processed, std::string& why);
-// packed real rows of a half-spectrum plan (kernels_jit.cpp): R2C (forward) or C2R (inverse) for the last dimension, length
-// pass.N; half_rows_supported is the same check without a device (false + the reason: MIFFT_ERR_UNSUPPORTED)
-bool half_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_half_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+// ---- the families of fused tile passes (kernels_jit.cpp) ------------------------------------------------------------------------
+// Every fused feature is a variant of the packed-row (one: of the paired-column) tile kernel with a load or store of its own:
+//   HalfRows   packed real rows of a half-spectrum plan: R2C (forward) or C2R (inverse) over the last dimension
+//   DctRows    the same rows with TileCfg::DCT (DCT-II / its inverse; TileCfg::DST from the plan)
+//   StftRows   R2C rows with TileCfg::STFT: the rows are the pass.outer frames of every batch entry (spectrogram stages and
+//              TileCfg::IADJ from the plan)
+//   ConvRows   R2C rows with TileCfg::CONV (overlap-save, partitions, gates, storage type, filter gradient: from plan.conv)
+//   IstftRows  C2R rows with TileCfg::ISTFT: pass.outer frames per entry, overlap-added by the store (TileCfg::ADJ from the plan)
+//   DctCols    the column tile with TileCfg::DCT: pass.N points at a stride of pass.inner PAIRS of real columns
+//   Dct4Rows   complex rows of N / 2 points with TileCfg::DCT = 4 over rows of N reals
+//   MdctRows   ... whose rows are the pass.outer lapped frames of every batch entry (TileCfg::MDCT)
+//   ImdctRows  ... whose pass.outer frames per entry are unfolded and overlap-added by the store (TileCfg::IMDCT)
+// Only HalfRows and DctRows have precompiled instances (below); the others are compiled at run time only.
+// tile_family_supported: the family's check without a device, for the plan checks -- false + the reason
+// (MIFFT_ERR_UNSUPPORTED) when the length (`inner`: the stride, DctCols only) has no configuration, or under MIFFT_JIT=0 no
+// precompiled instance.  Pure.
+// select_tile_family: the same check, then the kernel -- a precompiled instance or the runtime specialisation -- on the plan's
+// device.  The pass must be FRESH: a newly constructed DimPass with dim_index, N, inner, outer, radices, processed, first and
+// the buffer routing filled in (fused_row_pass below makes the usual one), as every caller's is.  On success launch, kernel_name,
+// jit_fn, tile, threads and lds_bytes are the kernel's; every role field (r2c, c2r, dct, dst, mdct, imdct, stft, istft, conv,
+// wgrad, hs, prefix_ok, ilv, herm_d0 .. 2) is cleared and then set from the configuration that was compiled, so the pass is
+// what the kernel is; ld is the points the kernel runs (N / 2 of the row families, N of DctCols); IstftRows and ImdctRows
+// carry Config::istft_min_run into istft_min_run, which enters the grid (tile_launch_geometry).  Scales and tables are the
+// caller's.  On failure: false + the reason, the pass as it was.
+enum class TileFamily { HalfRows, DctRows, StftRows, ConvRows, IstftRows, DctCols, Dct4Rows, MdctRows, ImdctRows };
+bool tile_family_supported(TileFamily family, const Plan& plan, int64_t n, int64_t inner, std::string& why_not);
+bool select_tile_family(TileFamily family, const Plan& plan, DimPass& pass, std::string& why_not);
 // the precompiled packed-row kernels (kernels_half_rows.hip): the configuration's TileCfg type text, the kernel, its LDS bytes
 struct HalfRowsKernel {
     const char* cfg;
@@ -379,14 +402,8 @@ const HalfRowsKernel* dct_rows_kernels(int* count);  // (kernels_dct_rows.hip: t
 int half_spectrum_check(const Plan& plan, std::string& why);
 int build_half_spectrum(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                         const std::vector<std::vector<uint32_t>>& processed, std::string& why);
-// plans with MIFFT_FLAG_DCT (dct.cpp): the checks that need no device, then the single pass.  select_jit_dct_rows is the
-// packed-row kernel with TileCfg::DCT (kernels_jit.cpp), dct_rows_supported the same check without a device
-bool dct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_dct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+// plans with MIFFT_FLAG_DCT (dct.cpp): the checks that need no device, then the single pass (DctRows, or Dct4Rows for a DCT-IV)
 int dct_check(const Plan& plan, std::string& why);
-// DCT-IV rows (TileCfg::DCT = 4; compiled at run time only) and, with `mdct`, the lapped frames of an MDCT plan
-bool dct4_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_dct4_rows(const Plan& plan, DimPass& pass, bool mdct, std::string& why_not);
 hipError_t upload_dct4_table(int out_dtype, int64_t n, void** d_table);
 int build_dct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 // ... its pieces, shared with the N-D plans: the packed-row pass over dimension dim_index (`outer` rows per batch entry), the
@@ -395,11 +412,8 @@ int build_dct_rows(Plan& plan, int dim_index, int64_t outer, const std::vector<u
                    const std::vector<uint32_t>& processed, std::string& why);
 void dct_scales(int64_t n, bool inverse, bool ortho, double& s0, double& s1);
 hipError_t upload_quarter_table(int out_dtype, int64_t n, void** d_table);
-// plans with MIFFT_FLAG_DCT_ND (dctn.cpp): the checks that need no device, then one pass per transformed dimension.
-// select_jit_dct_cols is the column tile with TileCfg::DCT over pass.inner PAIRS of real columns (kernels_jit.cpp; compiled
-// at run time only), dct_cols_supported the same check without a device
-bool dct_cols_supported(const Plan& plan, int64_t n, int64_t inner, std::string& why_not);
-bool select_jit_dct_cols(const Plan& plan, DimPass& pass, std::string& why_not);
+// plans with MIFFT_FLAG_DCT_ND (dctn.cpp): the checks that need no device, then one pass per transformed dimension (DctRows
+// over the last one, DctCols over the others)
 int dctn_check(const Plan& plan, std::string& why);
 int build_dctn(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                const std::vector<std::vector<uint32_t>>& processed, std::string& why);
@@ -441,10 +455,7 @@ int refuse_flags(uint32_t flags, const FlagRefusal (&table)[N], const std::strin
     return MIFFT_OK;
 }
 // plans with MIFFT_FLAG_STFT (stft.cpp): the checks that need no device (flags, shape, the window carried in `bases`), then
-// the single pass.  select_jit_stft_rows is the packed-row kernel with TileCfg::STFT (kernels_jit.cpp; compiled at run time
-// only), stft_rows_supported the same check without a device.  stft_flag_check: the STFT bits of a plan WITHOUT the flag.
-bool stft_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_stft_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+// the single pass (StftRows).  stft_flag_check: the STFT bits of a plan WITHOUT the flag.
 int stft_flag_check(uint32_t flags, std::string& why);
 int stft_check(const Plan& plan, std::string& why);
 // the window of such a plan from bases_flat / bases_len (2 n words: the binary64 bits of w[0 .. n-1], low word first; none:
@@ -464,26 +475,21 @@ int mdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len,
 int build_mdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                const FramedPayload& payload, std::string& why);
 // IMDCT plans (the MIFFT_FLAG_ISTFT payload tagged with MIFFT_MDCT_TAG; istft.cpp), in the same manner.  imdct_detect: does
-// the window payload end in TAG | gain?  (Pure; the length itself is imdct_check's business.)  select_jit_imdct_rows is the
-// DCT-IV kernel with TileCfg::IMDCT (run time only), imdct_rows_supported the same check without a device.
+// the window payload end in TAG | gain?  (Pure; the length itself is imdct_check's business.)  build_imdct: the one pass
+// (ImdctRows).
 bool imdct_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
 int imdct_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_imdct(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                 const FramedPayload& payload, std::string& why);
-bool imdct_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_imdct_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 // Fused FFT convolution plans (the MIFFT_FLAG_STFT payload that starts with MIFFT_CONV_TAG; conv.cpp).  conv_detect: is
 // bases_len[0] a tagged length (8, 12: overlap-save, 16: gated, or 20: partitioned) with the tag in front?  (Pure; it looks at nothing else.)  conv_check: everything that can
 // be refused without a device, leaving the request in plan.conv and the user radices of n in `radices`.  build_conv: the
-// one pass.  select_jit_conv_rows is the packed-row kernel with TileCfg::CONV (kernels_jit.cpp; run time only),
-// conv_rows_supported the same check without a device; launch_jit_conv is its launch, which -- unlike a DimPass::launch --
+// one pass (ConvRows).  launch_jit_conv is its launch (kernels_jit.cpp), which -- unlike a DimPass::launch --
 // knows the first row of the exec, for the filter row of every launch row, and takes the exec's two gates (null where the plan
 // has none), offset to the exec's first signal row as `in` and `out` are.
 bool conv_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
 int conv_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_conv(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
-bool conv_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_conv_rows(const Plan& plan, DimPass& pass, std::string& why_not);
 int launch_jit_conv(const Plan& plan, const DimPass& pass, const void* in, void* out, const void* pregate,
                     const void* postgate, int64_t first, int64_t count, hipStream_t stream);
 // The filter-gradient plans (MIFFT_CONV_GRAD_TAG): the same trio and the launch of the whole batch; build_conv_grad picks P where the payload says 0
@@ -509,11 +515,7 @@ int launch_lag_corr(const Plan& plan, const void* U, const void* G, void* out, h
 inline int64_t spec_table_ints(int64_t M) { return (3 * M + 1) / 2 * 2; }
 // plans with MIFFT_FLAG_ISTFT (istft.cpp), in the same manner: istft_check needs no device and leaves the window (empty:
 // rectangular), the gain and the user radices in its outputs; it refuses a window whose squared overlap-add is zero
-// somewhere in the samples the plan stores.  select_jit_istft_rows is the C2R kernel with TileCfg::ISTFT (run time only),
-// istft_rows_supported the same check without a device; Config::istft_min_run, copied to DimPass::istft_min_run when the pass is
-// built, enters the grid (tile_launch_geometry).
-bool istft_rows_supported(const Plan& plan, int64_t n, std::string& why_not);
-bool select_jit_istft_rows(const Plan& plan, DimPass& pass, std::string& why_not);
+// somewhere in the samples the plan stores.  build_istft: the one pass (IstftRows).
 int istft_check(const Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
 int build_istft(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed,
                 const FramedPayload& payload, std::string& why);
@@ -566,6 +568,34 @@ bool build_fourstep(Plan& plan, int dim_index, std::string& why_not);
 bool build_transposed_dim(Plan& plan, int dim_index, const std::vector<uint32_t>& radices,
                           const std::vector<uint32_t>& processed, std::string& why_not);
 hipError_t upload_twiddle_table(int out_dtype, int64_t N, bool inverse, void** d_table);
+// ---- what the builders of the fused passes share --------------------------------------------------------------------------------
+// The fresh DimPass of a single fused row pass over dimension dim_index: n points, `outer` rows (frames, blocks) per batch
+// entry, reading x.  half_pitch: the complex side has rows of n / 2 + 1 bins.
+inline DimPass fused_row_pass(int dim_index, int64_t n, int64_t outer, const std::vector<uint32_t>& radices,
+                              const std::vector<uint32_t>& processed, bool half_pitch) {
+    DimPass ps;
+    ps.dim_index = dim_index;
+    ps.N = n;
+    ps.outer = outer;
+    ps.radices = radices;
+    ps.processed = processed;
+    ps.first = true;
+    if (half_pitch) ps.half_pitch = n / 2 + 1;
+    return ps;
+}
+// the table pair of a packed-row pass (r2c / c2r): the passes run N / 2 points, d_twiddle is that table in the given direction;
+// the fold / unpacking needs W_N^k, forward, in d_aux
+inline hipError_t upload_packed_tables(int out_dtype, bool inverse, DimPass& ps) {
+    hipError_t e = upload_twiddle_table(out_dtype, ps.N / 2, inverse, &ps.d_twiddle);
+    if (e == hipSuccess) e = upload_twiddle_table(out_dtype, ps.N, false, &ps.d_aux);
+    return e;
+}
+// the end of every builder: the pass joins the plan BEFORE the status of its uploads is looked at (the plan's owner frees what
+// has been uploaded), then that status, under the name `what`
+inline int append_pass(Plan& plan, const DimPass& ps, hipError_t e, const char* what) {
+    plan.passes.push_back(ps);
+    return e == hipSuccess ? MIFFT_OK : hip_error(e, what);
+}
 // every other plan (schedule.cpp): the general route, one kernel per pass over every dimension chosen by its scheduler
 int build_general(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                   const std::vector<std::vector<uint32_t>>& processed, std::string& why);

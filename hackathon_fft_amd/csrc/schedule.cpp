@@ -134,11 +134,7 @@ struct Scheduler {
 
     hipError_t upload_twiddles(DimPass& ps) const {
         const bool inv = p.inverse != 0;
-        if (ps.r2c) {  // packed real rows: the passes run N / 2 points; the unpacking needs W_N^k, forward
-            hipError_t e2 = upload_twiddle_table(p.out_dtype, ps.N / 2, inv, &ps.d_twiddle);
-            if (e2 == hipSuccess) e2 = upload_twiddle_table(p.out_dtype, ps.N, false, &ps.d_aux);
-            return e2;
-        }
+        if (ps.r2c) return upload_packed_tables(p.out_dtype, inv, ps);  // (the lab's packed real rows)
         // (four-step rows inside LDS: the table of the row side, M / N1 points; the column side's goes to d_aux when it
         //  differs, the M-entry table to d_aux3)
         hipError_t e = upload_twiddle_table(p.out_dtype, ps.row2d_m > 0 ? ps.row2d_m / ps.N1 : ps.N, inv, &ps.d_twiddle);

@@ -89,7 +89,7 @@ int stft_check(const Plan& p, std::string& why) {
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
-    if (!stft_rows_supported(p, n, w)) {
+    if (!tile_family_supported(TileFamily::StftRows, p, n, 1, w)) {
         why = "STFT with frames of " + std::to_string(n) + " points: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -365,7 +365,7 @@ int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, Fr
         return MIFFT_ERR_UNSUPPORTED;
     }
     std::string w;
-    if (!dct4_rows_supported(p, M, w)) {
+    if (!tile_family_supported(TileFamily::MdctRows, p, M, 1, w)) {
         why = "MDCT with M = " + std::to_string(M) + " coefficients per frame: " + w;
         return MIFFT_ERR_UNSUPPORTED;
     }
@@ -389,23 +389,14 @@ int mdct_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, Fr
 int build_mdct(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
                std::string& why) {
     const int64_t M = p.mdct;
-    DimPass ps;
-    ps.dim_index = 1;
-    ps.N = M;
-    ps.inner = 1;
-    ps.outer = p.stft_frames();
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    if (!select_jit_dct4_rows(p, ps, /*mdct=*/true, why)) return MIFFT_ERR_UNSUPPORTED;
+    DimPass ps = fused_row_pass(1, M, p.stft_frames(), ordered, processed, /*half_pitch=*/false);
+    if (!select_tile_family(TileFamily::MdctRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
     ps.dct_s0 = ps.dct_s1 = p.mdct_scale;  // (X = DCT-IV(u) / 2: the factor 2 of the DCT-IV store is simply not applied)
     hipError_t e = upload_twiddle_table(p.out_dtype, M / 2, false, &ps.d_twiddle);
     if (e == hipSuccess) e = upload_dct4_table(p.out_dtype, M, &ps.d_aux2);
     if (e == hipSuccess)
         e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(2 * M, pl.window, &ps.d_aux3) : upload_window_t<float>(2 * M, pl.window, &ps.d_aux3);
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "MDCT table upload");
-    return MIFFT_OK;
+    return append_pass(p, ps, e, "MDCT table upload");
 }
 
 // the (K, M) filterbank as bands: per column lo = its first non-zero row and len = its last non-zero row - lo + 1 (zeros in
@@ -442,27 +433,15 @@ static hipError_t upload_bands_t(int64_t K, int64_t M, const std::vector<double>
 int build_stft(Plan& p, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, const FramedPayload& pl,
                std::string& why) {
     const int64_t n = p.dims[1];
-    DimPass ps;
-    ps.dim_index = 1;
-    ps.N = n;
-    ps.inner = 1;
-    ps.outer = p.stft_frames();
-    ps.radices = ordered;
-    ps.processed = processed;
-    ps.first = true;
-    ps.half_pitch = n / 2 + 1;
-    if (!select_jit_stft_rows(p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
-    // the passes run n / 2 points; the unpacking needs W_n^k, forward (as a half-spectrum row pass); the window
-    hipError_t e = upload_twiddle_table(p.out_dtype, n / 2, false, &ps.d_twiddle);
-    if (e == hipSuccess) e = upload_twiddle_table(p.out_dtype, n, false, &ps.d_aux);
+    DimPass ps = fused_row_pass(1, n, p.stft_frames(), ordered, processed, /*half_pitch=*/true);
+    if (!select_tile_family(TileFamily::StftRows, p, ps, why)) return MIFFT_ERR_UNSUPPORTED;
+    hipError_t e = upload_packed_tables(p.out_dtype, false, ps);  // (as a half-spectrum row pass); then the window
     if (e == hipSuccess)
         e = p.out_dtype == MIFFT_F64 ? upload_window_t<double>(n, pl.window, &ps.d_aux2) : upload_window_t<float>(n, pl.window, &ps.d_aux2);
     if (e == hipSuccess && p.spec_bands > 0)
         e = p.out_dtype == MIFFT_F64 ? upload_bands_t<double>(n / 2 + 1, p.spec_bands, pl.fb, pl.post, p.spec_post_off, &ps.d_aux3)
                                      : upload_bands_t<float>(n / 2 + 1, p.spec_bands, pl.fb, pl.post, p.spec_post_off, &ps.d_aux3);
-    p.passes.push_back(ps);
-    if (e != hipSuccess) return hip_error(e, "STFT table upload");
-    return MIFFT_OK;
+    return append_pass(p, ps, e, "STFT table upload");
 }
 
 }  // namespace mifft
