@@ -64,6 +64,9 @@ CONV_GRAD_TAG_LO = 0x44524701  # MIFFT_CONV_GRAD_TAG_LO / _HI: the NaN in front 
 CONV_GRAD_TAG_HI = 0x7FF84D47  # filter gradient of a fused convolution (TAG | D | c | S | mode | F | s0 | Lo | P | 0 | gates | 0 x 4)
 CONV_GRAD_ARGS_MAGIC = 0x314757544646494D  # MIFFT_CONV_GRAD_ARGS_MAGIC ("MIFFTWG1")
 CONV_GRAD_GATED_ARGS_MAGIC = 0x324757544646494D  # MIFFT_CONV_GRAD_GATED_ARGS_MAGIC ("MIFFTWG2")
+CONV_PAIR_TAG_LO = 0x49415001  # MIFFT_CONV_PAIR_TAG_LO / _HI: the NaN in front of the 16-word payload of a FLAG_STFT plan that is the
+CONV_PAIR_TAG_HI = 0x7FF84D50  # convolution of two signal batches (TAG | K | ea | eb | o | Lo | mode | 0 x 8)
+CONV_PAIR_ARGS_MAGIC = 0x314150544646494D  # MIFFT_CONV_PAIR_ARGS_MAGIC ("MIFFTPA1")
 STFT_ADJ_TAG_LO = 0x4A444101   # MIFFT_STFT_ADJ_TAG_LO / _HI: the NaN behind the window of a FLAG_ISTFT plan that is the adjoint of
 STFT_ADJ_TAG_HI = 0x7FF84D41   # the STFT (w | TAG | gain | mode, 0)
 ISTFT_ADJ_TAG_LO = 0x4A444901  # MIFFT_ISTFT_ADJ_TAG_LO / _HI: the NaN behind the window of a FLAG_STFT plan that is the adjoint of
@@ -87,6 +90,11 @@ class ConvGradGatedArgs(ctypes.Structure):
     """mifft_conv_grad_gated_args: what the exec of a filter-gradient plan with gates takes, by host address, in the place of x"""
     _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("gy", ctypes.c_void_p), ("pregate", ctypes.c_void_p),
                 ("postgate", ctypes.c_void_p)]
+
+
+class ConvPairArgs(ctypes.Structure):
+    """mifft_conv_pair_args (include/mifft.h): the argument block of a two-signal convolution exec"""
+    _fields_ = [("magic", ctypes.c_uint64), ("x", ctypes.c_void_p), ("v", ctypes.c_void_p)]
 
 
 class StftAdjArgs(ctypes.Structure):
@@ -563,6 +571,8 @@ def _frame_payload(r) -> tuple:
     another length than the frames."""
     if isinstance(r, ConvRequest):
         return FLAG_STFT, _conv_payload(r), 1
+    if isinstance(r, ConvPairRequest):
+        return FLAG_STFT, _conv_pair_payload(r), 1
     if r.kind not in ("stft", "spec", "istft", "adjoint", "istft_adjoint", "mdct", "imdct"):
         raise MifftError(ERR_UNSUPPORTED, f"unknown kind of framed plan {r.kind!r}")
     bits = FLAG_STFT_HOP(r.hop)
@@ -684,7 +694,8 @@ class Plan:
     ``mode`` are the storage type of the rows (0, or the code of float16 / bfloat16 under float32: ``ConvPlan.io_dtype``).
     ``grad`` makes it the request of that convolution's filter gradient (``partials``; MIFFT_CONV_GRAD_TAG, ConvGradPlan),
     whose ``out_shape`` is the incoming gradient's.  ``_conv_payload`` is the words of either; ``_frame_payload`` encodes every
-    framed request."""
+    framed request.  ``conv`` = a ``ConvPairRequest`` instead: the convolution of two signal batches (MIFFT_CONV_PAIR_TAG,
+    plan_fftconv_pair), x (batch, L, 1) -> out (batch, Lo, 1) with v (batch, K, 1) given beside x at every exec."""
 
     io_dtype = None  # (a convolution plan with 16-bit rows in memory: ConvPlan / ConvGradPlan; None on every other plan)
 
@@ -693,7 +704,7 @@ class Plan:
                  dct: bool = False, norm=None, dctn: bool = False, stft_hop: int = 0, stft_center=None, stft_window=None,
                  istft_hop: int = 0, istft_gain: float = 1.0, stft_power=None, stft_fb=None, stft_log=None,
                  stft_post=None, dct_type: int = 2, mdct: int = 0, mdct_scale: float = 1.0, imdct: int = 0,
-                 imdct_gain: float = 1.0, dst: bool = False, conv: Optional[ConvRequest] = None, stft_adjoint: int = 0,
+                 imdct_gain: float = 1.0, dst: bool = False, conv=None, stft_adjoint: int = 0,
                  istft_adjoint: int = 0):
         in_shape, out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         mdct, imdct, flags = int(mdct), int(imdct), int(flags)
@@ -821,7 +832,7 @@ class Plan:
         self.stft_adjoint = int(stft_adjoint) if kind == "adjoint" else 0
         self.istft_adjoint = int(istft_adjoint) if kind == "istft_adjoint" else 0
         self.conv = conv
-        self.conv_gates = conv.gates if conv is not None else 0
+        self.conv_gates = getattr(conv, "gates", 0) if conv is not None else 0
         self._ndim = len(dims)
         c_dims = (ctypes.c_int64 * len(dims))(*dims)
         # 4. the payload and the radices as the lists of ``bases``, and the one call
@@ -2073,6 +2084,47 @@ def _conv_payload(r: ConvRequest) -> list:
     return words
 
 
+class ConvPairRequest(NamedTuple):
+    """What a two-signal convolution plan is asked for (``Plan(conv=)``; MIFFT_CONV_PAIR_TAG in include/mifft.h): the FFT
+    length ``n``, ``K`` samples per row of v, the indices ``ea`` / ``eb`` at which a row of x / of v starts inside its n
+    zero-extended samples, the stored samples ``o`` .. of ``Lo`` per row, the ``mode`` word (bit 0: correlate)."""
+    n: int
+    K: int
+    ea: int
+    eb: int
+    o: int
+    Lo: int
+    mode: int = 0
+
+
+def _conv_pair_payload(r: ConvPairRequest) -> list:
+    """The 16 payload words of a two-signal request; status -5 for a value that does not fit its word.  Pure."""
+    r = ConvPairRequest(*(int(v) for v in r))
+    for what in ("K", "ea", "eb", "o", "Lo", "mode"):
+        if not 0 <= getattr(r, what) < 1 << 32:
+            raise MifftError(-5, f"{what} = {getattr(r, what)} of a two-signal convolution plan does not fit an unsigned 32-bit word")
+    return [CONV_PAIR_TAG_LO, CONV_PAIR_TAG_HI, r.K, r.ea, r.eb, r.o, r.Lo, r.mode] + [0] * 8
+
+
+def _fftconv_pair_window(mode: str, L: int, K: int, correlate: bool) -> tuple:
+    """(ea, eb, o, Lo) of a mode of ``fftconv_pair``: scipy.signal's crops of the full convolution / correlation of L and K
+    samples ("causal": the first L samples of the plain product, lags 0 .. L - 1 of a correlation)"""
+    if mode == "causal":
+        return 0, 0, 0, L
+    o, Lo = _fftconv_window(mode, L, K)
+    return (K - 1 if correlate else 0), 0, o, Lo
+
+
+def _fftconv_pair_adjoints(L: int, K: int, ea: int, eb: int, o: int, Lo: int, correlate: bool) -> tuple:
+    """The two gradient plans of the pair plan (L, K, ea, eb, o, Lo, correlate), each as (first operand, La, Lb, ea', eb', o',
+    Lo', correlate') with the first operand "gy" or "x" and the second the other saved tensor: gx = pair(gy, v), gv =
+    pair(gy, x) -- or, of a correlation, pair(x, gy).  Exact adjoints, circular case included: the embedding offset of gy is the
+    forward's o, so nothing is padded."""
+    if not correlate:
+        return ("gy", Lo, K, o, eb, ea, L, True), ("gy", Lo, L, o, ea, eb, K, True)
+    return ("gy", Lo, K, o, eb, ea, L, False), ("x", L, Lo, ea, o, eb, K, True)
+
+
 def fftconv_length(m: int, dtype=torch.float32) -> int:
     """The smallest FFT length n >= m that a fused convolution plan of ``dtype`` accepts (even, 8 .. 16384, n // 2 without a
     prime factor above 32; float64 plans stop at 12288 and skip a few lengths more).  MifftError beyond the last one: longer
@@ -2583,6 +2635,192 @@ def fftconv(x: "torch.Tensor", k: "torch.Tensor", *, n: Optional[int] = None, mo
         b = postgate.to(sdt).contiguous().reshape(rows, out_length, 1) if postgate is not None else None
         _fftconv_exec(plan, out, xr, k, skip, a, b)
     return out.reshape(logical[:-1] + (out_length,))
+
+
+class ConvPairPlan(Plan):
+    """The plan of ``plan_fftconv_pair``: one launch per exec, no scratch, no state between execs.  ``in_shape``
+    (batch, length, 1) is x's, ``v_shape`` (batch, taps, 1) the second operand's, ``out_shape`` (batch, out_length, 1);
+    ``x_offset`` / ``v_offset`` / ``offset`` / ``correlate`` as given.  Runs through ``run(out, x, v)``."""
+
+    def __init__(self, dtype, batch, length, taps, n, x_offset, v_offset, offset, out_length, correlate, ctx):
+        self.ctx = ctx
+        self.length, self.taps, self.n = length, taps, n
+        self.x_offset, self.v_offset, self.offset, self.out_length = x_offset, v_offset, offset, out_length
+        self.correlate = bool(correlate)
+        self.v_shape = (batch, taps, 1)
+        super().__init__(dtype, dtype, (batch, length, 1), (batch, out_length, 1), device=ctx.device,
+                         conv=ConvPairRequest(n, taps, x_offset, v_offset, offset, out_length, 1 if correlate else 0))
+
+    def run(self, out: "torch.Tensor", x: "torch.Tensor", v: "torch.Tensor", *, first: Optional[int] = None,
+            count: Optional[int] = None) -> None:
+        """``out[r] = irfft(rfft(xe[r]) * G[r], n)[offset : offset + out_length]`` for the rows ``first`` .. ``first + count - 1``
+        (default: all), enqueued on the plan's stream.  ``x`` of ``in_shape``, ``v`` of ``v_shape``, ``out`` of ``out_shape``, the
+        plan's dtype, contiguous, on its device; all three are the WHOLE batch's, the library offsets them by ``first`` rows.
+        ``x`` and ``v`` may be the same tensor; neither may overlap ``out``; neither is written.  No autograd."""
+        _check_tensor(x, self.in_shape, self.in_dtype, self.device, "x")
+        _check_tensor(v, self.v_shape, self.in_dtype, self.device, "v")
+        _check_tensor(out, self.out_shape, self.out_dtype, self.device, "out")
+        first = 0 if first is None else int(first)
+        count = self.out_shape[0] - first if count is None else int(count)
+        args = ConvPairArgs(CONV_PAIR_ARGS_MAGIC, x.data_ptr(), v.data_ptr())
+        check(_lib.lib().mifft_exec_batch(self._h, ctypes.addressof(args), out.data_ptr(), first, count,
+                                          self.ctx.stream.cuda_stream))
+
+
+def plan_fftconv_pair(dtype, batch: int, length: int, taps: int, n: int, *, x_offset: int = 0, v_offset: int = 0,
+                      offset: int = 0, out_length: Optional[int] = None, correlate: bool = False,
+                      ctx: Optional[DeviceContext] = None) -> ConvPairPlan:
+    """Plan of the FFT convolution / correlation of two signal batches (no reference counterpart; MIFFT_CONV_PAIR_TAG in
+    include/mifft.h): ``batch`` rows of ``length`` samples against ``batch`` rows of ``taps`` samples, row by row, at the FFT
+    length ``n`` (see fftconv_length), in ONE kernel launch with no spectrum in memory.  With xe = zeros(n),
+    xe[x_offset : x_offset + length] = x[r] and ve likewise from ``v_offset`` on:
+    ``out[r] = irfft(rfft(xe) * rfft(ve), n)[offset : offset + out_length]`` (``correlate``: times conj(rfft(ve)), that is
+    y[t] = sum_j ve[j] xe[(t + j) mod n]).  ``out_length`` defaults to ``length``.  float32 / float64.  Every argument error is
+    raised before any device work.  ``plan.run(out, x, v)``; no autograd at the plan level (``fftconv_pair`` has it)."""
+    batch, length, taps, n = int(batch), int(length), int(taps), int(n)
+    ea, eb, offset = int(x_offset), int(v_offset), int(offset)
+    out_length = length if out_length is None else int(out_length)
+    who = "plan_fftconv_pair"
+    if dtype not in _OUT_DTYPES:
+        raise MifftError(-4, f"a two-signal convolution plan reads and writes float32 or float64, got {dtype}")
+    if batch < 1:
+        raise MifftError(-8, f"{who}: batch = {batch} must be positive")
+    _fftconv_check_length(who, "n", n, dtype)
+    if length < 2 or taps < 1:
+        raise MifftError(-2, f"{who}: rows of {length} samples (at least 2) against rows of {taps} samples (at least 1)")
+    if ea < 0 or eb < 0 or ea + length > n or eb + taps > n:
+        raise MifftError(-5, f"{who}: x_offset = {ea} with length = {length}, v_offset = {eb} with taps = {taps}: both rows lie "
+                             f"inside the FFT length, 0 <= offset and offset + samples <= n = {n}")
+    if offset < 0 or out_length < 1 or offset + out_length > n:
+        raise MifftError(-5, f"{who}: offset = {offset}, out_length = {out_length}: 0 <= offset, 1 <= out_length, "
+                             f"offset + out_length <= n = {n}")
+    return ConvPairPlan(dtype, batch, length, taps, n, ea, eb, offset, out_length, correlate, DeviceContext() if ctx is None else ctx)
+
+
+def _fftconv_pair_plan(dtype, rows, L, K, n, ea, eb, o, Lo, correlate, device) -> ConvPairPlan:
+    """the cached plan of ``fftconv_pair`` and of its backward (the caller holds _PLAN_CACHE_LOCK)"""
+    return _plan_cached(("fftconv_pair", dtype, rows, L, K, n, ea, eb, o, Lo, bool(correlate)), device, lambda: plan_fftconv_pair(
+        dtype, rows, L, K, n, x_offset=ea, v_offset=eb, offset=o, out_length=Lo, correlate=correlate, ctx=DeviceContext(device)))
+
+
+def _fftconv_pair_exec(dtype, a, b, n, ea, eb, o, Lo, correlate, device) -> "torch.Tensor":
+    """one launch of the cached pair plan on the contiguous (rows, La) and (rows, Lb) tensors a and b: (rows, Lo)"""
+    rows, La, Lb = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
+    out = torch.empty((rows, Lo, 1), dtype=dtype, device=a.device)
+    with _PLAN_CACHE_LOCK:
+        plan = _fftconv_pair_plan(dtype, rows, La, Lb, n, ea, eb, o, Lo, correlate, device)
+        plan.run(out, a.reshape(rows, La, 1), b.reshape(rows, Lb, 1))
+    return out.reshape(rows, Lo)
+
+
+def _fftconv_pair_call(x, v, n, mode, correlate) -> tuple:
+    """the checks of ``fftconv_pair``, all before any device work: (dtype, logical shape of x, L, K, n, ea, eb, o, Lo)"""
+    who = "fftconv_pair"
+    if x.is_complex() or v.is_complex():
+        raise MifftError(-3, f"{who} expects real tensors (complex rows are out of scope)")
+    if mode not in _FFTCONV_MODES:
+        raise ValueError(f"{who}: mode must be one of {_FFTCONV_MODES}, got {mode!r}")
+    if x.dim() < 1 or v.dim() < 1 or tuple(x.shape[:-1]) != tuple(v.shape[:-1]):
+        raise MifftError(-2, f"{who}: x is {tuple(x.shape)} and v is {tuple(v.shape)}: both operands are signals with exactly the "
+                             "same leading shape, one row of v per row of x (nothing is broadcast: a filter shared by the rows is "
+                             "fftconv's job)")
+    logical = tuple(x.shape)
+    L, K = int(logical[-1]), int(v.shape[-1])
+    if L < 2 or K < 1:
+        raise MifftError(-2, f"{who}: rows of {L} samples (at least 2) against rows of {K} samples (at least 1)")
+    if math.prod(logical[:-1]) < 1:
+        raise MifftError(-8, f"{who}: no rows in {logical}")
+    dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.float64
+    if n is None:
+        try:
+            n = fftconv_length(L + K - 1, dtype)
+        except MifftError as e:
+            if e.status != ERR_UNSUPPORTED:
+                raise
+            raise MifftError(ERR_UNSUPPORTED, f"{who}: rows of {L} and {K} samples need an FFT of {L + K - 1} points, beyond the "
+                                              f"last packed length ({_FFTCONV_MAX}; float64 12288): one FFT per row is all this "
+                                              "op has -- long rows against a shared filter live in fftconv(block=)") from None
+    else:
+        n = int(n)
+        _fftconv_check_length(who, "n", n, dtype)
+        if n < L + K - 1 and mode != "causal":
+            raise MifftError(-2, f"{who}: n = {n} is shorter than the full result of {L + K - 1} samples: the circular result "
+                                 f"goes with mode='causal' only, got {mode!r}")
+        if n < max(L, K):
+            raise MifftError(-2, f"{who}: n = {n} does not hold rows of {L} and {K} samples (n >= max(L, K))")
+    ea, eb, o, Lo = _fftconv_pair_window(mode, L, K, bool(correlate))
+    return dtype, logical, L, K, n, ea, eb, o, Lo
+
+
+def fftconv_pair(x: "torch.Tensor", v: "torch.Tensor", *, n: Optional[int] = None, mode: str = "full",
+                 correlate: bool = False) -> "torch.Tensor":
+    """Convolution (``correlate=True``: cross-correlation) by FFT of two real signal batches along the last dim, row by row:
+    ``x`` of shape (..., L) and ``v`` of shape (..., K) with exactly the same leading shape -- one row of ``v`` per row of
+    ``x``; nothing is broadcast (a filter shared by the rows is ``fftconv``'s job).  ONE kernel launch: both rows are
+    transformed in the kernel, multiplied, transformed back and cropped; no padded copy and no spectrum reaches memory.
+    ``x is v`` is the autocorrelation.  The result is (..., Lo).
+    Modes "full" / "same" / "valid" are scipy.signal.fftconvolve(x, v, mode) or, with ``correlate=True``,
+    scipy.signal.correlate(x, v, mode); "causal" is the first L samples of the product with both rows at index 0 -- of a
+    correlation the lags 0 .. L - 1, y[t] = sum_j v[j] x[t + j].
+    ``n`` is the FFT length, default fftconv_length(L + K - 1); a smaller one (n >= max(L, K)) is accepted with
+    ``mode="causal"`` only and gives the circular result.  Rows with L + K - 1 beyond the last packed length (16384; float64
+    12288) are refused.  float32 / float64; other input is converted to float64.
+    Differentiable, first order: when grad mode is on and ``x`` or ``v`` requires grad the call goes through a
+    torch.autograd.Function whose forward is this same launch (the same bits) and whose backward computes only the gradients
+    asked for, each by ONE launch of a cached plan of this same kind on the incoming gradient (made contiguous if it is not),
+    without padding it.  No double backward.  Otherwise the result carries no grad_fn."""
+    dtype, logical, L, K, n, ea, eb, o, Lo = _fftconv_pair_call(x, v, n, mode, correlate)
+    device = _signal_device(x, "x")
+    if v.device != x.device:
+        raise MifftError(-10, f"fftconv_pair: v lives on {v.device}, x on {x.device}")
+    if torch.is_grad_enabled() and (x.requires_grad or v.requires_grad):
+        return _FFTConvPairFunction.apply(x, v, (n, mode, bool(correlate)))
+    rows = math.prod(logical[:-1])
+    xr = x.to(dtype).contiguous().reshape(rows, L)
+    vr = xr if v is x else v.to(dtype).contiguous().reshape(rows, K)
+    return _fftconv_pair_exec(dtype, xr, vr, n, ea, eb, o, Lo, correlate, device).reshape(logical[:-1] + (Lo,))
+
+
+class _FFTConvPairFunction(torch.autograd.Function):
+    """``fftconv_pair`` with a backward (first order).  forward: the plain call, grad mode off.  backward: the gradients asked
+    for, one launch each of the pair plans of ``_fftconv_pair_adjoints`` on gy as it arrives."""
+
+    @staticmethod
+    def forward(ctx, x, v, cfg):
+        n, mode, correlate = cfg
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, v)
+        return fftconv_pair(x, v, n=n, mode=mode, correlate=correlate)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, v = ctx.saved_tensors
+        n, mode, correlate = ctx.cfg
+        dtype, logical, L, K, n, ea, eb, o, Lo = _fftconv_pair_call(x, v, n, mode, correlate)
+        rows = math.prod(logical[:-1])
+        device = x.device.index
+        gyr = gy.to(dtype).contiguous().reshape(rows, Lo)  # (sum().backward() hands in an expanded tensor)
+        xr = x.detach().to(dtype).contiguous().reshape(rows, L)
+        vr = v.detach().to(dtype).contiguous().reshape(rows, K)
+        # (no plan has a first dimension of 1: a one-sample gy that is the first operand gets one of the zeros the embedding
+        #  would add anyway, behind it, or in front of it at the last index of the FFT length)
+        front = Lo < 2 and o + 2 > n
+        gy2 = gyr if Lo >= 2 else torch.nn.functional.pad(gyr, (1, 0) if front else (0, 1))
+        grads = []
+        for need, other, (first, La, Lb, a_e, b_e, a_o, a_Lo, a_corr) in zip(
+                ctx.needs_input_grad[:2], (vr, xr), _fftconv_pair_adjoints(L, K, ea, eb, o, Lo, correlate)):
+            if not need:
+                grads.append(None)
+                continue
+            a, b = (gy2, other) if first == "gy" else (other, gyr)
+            if first == "gy" and front:
+                a_e -= 1
+            g = _fftconv_pair_exec(dtype, a, b, n, a_e, b_e, a_o, a_Lo, a_corr, device)
+            grads.append(g)
+        gx, gv = grads
+        back = lambda g, t: None if g is None else g.reshape(t.shape).to(t.dtype)
+        return back(gx, x), back(gv, v), None
 
 
 class ConvGradPlan(Plan):

@@ -27,6 +27,9 @@
 // half spectra of its u-blocks / g-blocks instead of summing them (TileCfg::WSPEC), 3 the lag-group correlation over such
 // spectra (lag_corr.hip), which has no transform of its own.  0 is the fused gradient above.
 //
+// The two-signal payload (MIFFT_CONV_PAIR_TAG, at the end) has no filter spectrum at all: the second operand is a tensor of rows
+// like x, both are arguments of every exec (mifft_conv_pair_args), and the tile transforms both (TileCfg::PAIR).
+//
 // Bits 8..15 of the mode word of every form, the filter-gradient payload included, are the STORAGE type of the rows: 0 the
 // plan's float type, or MIFFT_F16 / MIFFT_BF16 under an F32 plan (ConvRequest::io, TileCfg::IT): x, the gates and out are then
 // 2-byte elements, widened in the tile's load and rounded once in its store; H and the arithmetic stay float.
@@ -424,6 +427,56 @@ int build_conv_grad(Plan& p, const std::vector<uint32_t>& ordered, const std::ve
     const int rc = build_conv(p, ordered, processed, why);
     if (rc) return rc;
     if (p.conv.P == 0) p.conv.P = conv_grad_partials(p, p.passes[0]);
+    return MIFFT_OK;
+}
+
+// ---- two signals: TAG_LO | TAG_HI | K | ea | eb | o | Lo | mode | 0 x 8 (MIFFT_CONV_PAIR_TAG, include/mifft.h) -------------------
+bool conv_pair_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len) {
+    if (ndim != 2 || !bases_flat || !bases_len) return false;
+    return bases_len[0] == 16 && bases_flat[0] == MIFFT_CONV_PAIR_TAG_LO && bases_flat[1] == MIFFT_CONV_PAIR_TAG_HI;
+}
+
+// dims = {L, n}: x (batch, L, 1), v (batch, K, 1) -> out (batch, Lo, 1).  The pass is build_conv's.
+int conv_pair_check(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& pl, std::string& why) {
+    if (const int rc = conv_header_check(p, "MIFFT_CONV_PAIR_TAG", why)) return rc;
+    const uint32_t* w = bases_flat;
+    const int64_t L = p.dims[0], n = p.dims[1];
+    ConvRequest r;
+    r.pair = true;
+    r.D = 1;
+    r.K = w[2];
+    r.ea = w[3];
+    r.eb = w[4];
+    r.o = w[5];
+    r.Lo = w[6];
+    r.mode = w[7];
+    if (r.K < 1 || r.Lo < 1) {
+        why = "K = " + std::to_string(r.K) + " samples per row of v and Lo = " + std::to_string(r.Lo) +
+              " output samples per row in a two-signal convolution payload: K >= 1 and Lo >= 1";
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.ea + L > n) {
+        why = "rows of L = " + std::to_string(L) + " samples embedded at ea = " + std::to_string(r.ea) +
+              " in a two-signal convolution payload: ea + L <= n = " + std::to_string(n);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.eb + r.K > n) {
+        why = "rows of K = " + std::to_string(r.K) + " samples of v embedded at eb = " + std::to_string(r.eb) +
+              " in a two-signal convolution payload: eb + K <= n = " + std::to_string(n);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.o + r.Lo > n) {
+        why = "the output window o = " + std::to_string(r.o) + ", Lo = " + std::to_string(r.Lo) +
+              " of a two-signal convolution payload: Lo >= 1 and o + Lo <= n = " + std::to_string(n);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (r.mode & ~1u) {  // (no storage type: the rows are the plan's own float type)
+        why = "the mode word of a two-signal convolution payload has bit 0 (correlate) alone, not " + std::to_string(r.mode);
+        return MIFFT_ERR_BAD_BASES;
+    }
+    if (const int rc = conv_reserved_check(w, 8, 16, 0, "a two-signal convolution", why)) return rc;
+    if (const int rc = conv_radices(bases_flat, bases_len, pl.radices, why)) return rc;
+    p.conv = r;
     return MIFFT_OK;
 }
 

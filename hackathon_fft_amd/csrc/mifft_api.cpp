@@ -226,6 +226,34 @@ static int exec_conv_grad(const Plan& p, const void* x, void* out, int64_t first
     return launch_jit_conv_grad(p, p.passes[0], x, gy, pregate, postgate, out, (hipStream_t)stream);
 }
 
+// The exec of a two-signal convolution plan (conv.cpp; ConvRequest::pair): `args` is the HOST address of a mifft_conv_pair_args,
+// refused without a launch as above.  first / count offset x, v and out by whole rows of L, K and Lo samples.  x and v may be
+// the same buffer; neither may overlap the exec's part of out.
+static int exec_conv_pair(const Plan& p, const void* args, void* out, int64_t first, int64_t count, void* stream) {
+    static const char* kHow =
+        "the exec of a two-signal convolution plan takes the host address of a mifft_conv_pair_args (magic, x, v) in the place "
+        "of x: include/mifft.h";
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, args) != hipSuccess)
+        (void)hipGetLastError();  // (memory the runtime has never seen: host memory)
+    else if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray)
+        return set_error(MIFFT_ERR_UNSUPPORTED, std::string("x is a device address: ") + kHow);
+    const mifft_conv_pair_args* a = (const mifft_conv_pair_args*)args;
+    if (a->magic != MIFFT_CONV_PAIR_ARGS_MAGIC) return set_error(MIFFT_ERR_UNSUPPORTED, std::string("no magic word: ") + kHow);
+    if (!a->x) return set_error(MIFFT_ERR_NULL, "mifft_conv_pair_args.x is NULL");
+    if (!a->v) return set_error(MIFFT_ERR_NULL, "mifft_conv_pair_args.v is NULL");
+    const size_t x_row = p.in_row_bytes(), v_row = (size_t)p.conv.K * p.conv.elem_bytes(p.out_dtype), o_row = p.out_row_bytes();
+    const char* xb = (const char*)a->x + (size_t)first * x_row;
+    const char* vb = (const char*)a->v + (size_t)first * v_row;
+    char* ob = (char*)out + (size_t)first * o_row;
+    const size_t xn = (size_t)count * x_row, vn = (size_t)count * v_row, on = (size_t)count * o_row;
+    if (xb < ob + on && ob < xb + xn) return set_error(MIFFT_ERR_ALIAS, "x and out must not overlap");
+    if (vb < ob + on && ob < vb + vn) return set_error(MIFFT_ERR_ALIAS, "v and out must not overlap");
+    DeviceGuard guard(p.device);
+    MIFFT_HIP_TRY(guard.err);
+    return launch_jit_conv_pair(p, p.passes[0], xb, vb, ob, count, (hipStream_t)stream);
+}
+
 // The exec of an STFT adjoint plan (istft.cpp; Plan::stft_adj): `x` is the HOST address of a mifft_stft_adj_args, refused
 // without a launch as above.  x is the gradient (mode 1) or X (modes 2, 3); mult is present exactly for modes 2 and 3, edge
 // exactly with the reflect bit.  first / count offset all four tensors by whole entries.
@@ -340,6 +368,8 @@ FramedKind framed_kind(const Plan& p, const uint32_t* bases_flat, const int32_t*
         // a payload that STARTS with MIFFT_CONV_GRAD_TAG: the filter gradient of a fused FFT convolution; with MIFFT_CONV_TAG:
         // that convolution, of rows of dims[0] samples at length dims[1]
         if (conv_grad_detect(p.ndim, bases_flat, bases_len)) return FramedKind::ConvGrad;
+        // ... with MIFFT_CONV_PAIR_TAG: the convolution of two signal batches, row by row
+        if (conv_pair_detect(p.ndim, bases_flat, bases_len)) return FramedKind::ConvPair;
         if (conv_detect(p.ndim, bases_flat, bases_len)) return FramedKind::Conv;
         // a window payload tagged with MIFFT_MDCT_TAG: the MDCT, M = n / 2 coefficients per frame from a DCT-IV of M points
         if (mdct_detect(p.ndim, p.dims, bases_flat, bases_len)) return FramedKind::Mdct;
@@ -364,6 +394,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     switch (kind) {
         case FramedKind::ConvGrad: rc = conv_grad_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Conv: rc = conv_check(p, bases_flat, bases_len, pl, why); break;
+        case FramedKind::ConvPair: rc = conv_pair_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Mdct: rc = mdct_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Imdct: rc = imdct_check(p, bases_flat, bases_len, pl, why); break;
         case FramedKind::Adjoint: rc = stft_adj_check(p, bases_flat, bases_len, pl, why); break;
@@ -390,6 +421,7 @@ int create_framed(Plan& p, const uint32_t* bases_flat, const int32_t* bases_len,
     if (rc) return rc;
     switch (kind) {
         case FramedKind::ConvGrad: rc = build_conv_grad(p, ordered[td], processed[td], why); break;
+        case FramedKind::ConvPair:  // (the convolution's pass, with TileCfg::PAIR)
         case FramedKind::Conv: rc = build_conv(p, ordered[td], processed[td], why); break;
         case FramedKind::Mdct: rc = build_mdct(p, ordered[td], processed[td], pl, why); break;
         case FramedKind::Imdct: rc = build_imdct(p, ordered[td], processed[td], pl, why); break;
@@ -630,6 +662,7 @@ int mifft_exec_batch(const mifft_plan* plan, const void* x, void* out, int64_t f
     if (count == 0) return MIFFT_OK;
     if (!x || !out) return set_error(MIFFT_ERR_NULL, "x or out is NULL");
     if (p.stft_adj) return exec_stft_adj(p, x, out, first, count, stream);  // (`x`: the HOST address of the exec's mifft_stft_adj_args)
+    if (p.conv.pair) return exec_conv_pair(p, x, out, first, count, stream);  // (`x`: the HOST address of the exec's mifft_conv_pair_args)
     const void *pregate = nullptr, *postgate = nullptr;
     if (p.conv.gated()) {  // (a gated convolution: `x` is the HOST address of the exec's mifft_gated_args)
         const int rc = unpack_gated_args(p, x, pregate, postgate);  // (x: now the signal itself)

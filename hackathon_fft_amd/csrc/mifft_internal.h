@@ -164,7 +164,13 @@ struct ConvRequest {
     // In a filter-gradient plan they are the forward plan's gates, fused into the loads of x and of gy
     uint32_t gates = 0;
     const void* h = nullptr;
-    bool is_conv() const { return D > 0; }  // (forward or gradient)
+    // the payload tagged MIFFT_CONV_PAIR_TAG (conv_pair_check): the second operand is a signal, v (batch, K, 1), one row per row
+    // of x, and there is no filter spectrum (D = 1, h null).  Row r of x lies from index ea on in its n zero-extended samples,
+    // row r of v from eb on; out[r] is the samples o .. o + Lo - 1 of irfft(rfft(xe) rfft(ve), n) (mode bit 0: the conjugate of
+    // rfft(ve)).  x and v are arguments of every exec (mifft_conv_pair_args).  TileCfg::PAIR.
+    bool pair = false;
+    int64_t K = 0, ea = 0, eb = 0;
+    bool is_conv() const { return D > 0; }  // (forward, gradient or pair)
     bool overlap_save() const { return S > 0; }
     bool partitioned() const { return Q > 0; }
     bool gated() const { return gates != 0; }
@@ -368,7 +374,7 @@ int build_axes(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
 //   DctRows    the same rows with TileCfg::DCT (DCT-II / its inverse; TileCfg::DST from the plan)
 //   StftRows   R2C rows with TileCfg::STFT: the rows are the pass.outer frames of every batch entry (spectrogram stages and
 //              TileCfg::IADJ from the plan)
-//   ConvRows   R2C rows with TileCfg::CONV (overlap-save, partitions, gates, storage type, filter gradient: from plan.conv)
+//   ConvRows   R2C rows with TileCfg::CONV (overlap-save, partitions, gates, storage type, filter gradient, two signals: from plan.conv)
 //   IstftRows  C2R rows with TileCfg::ISTFT: pass.outer frames per entry, overlap-added by the store (TileCfg::ADJ from the plan)
 //   DctCols    the column tile with TileCfg::DCT: pass.N points at a stride of pass.inner PAIRS of real columns
 //   Dct4Rows   complex rows of N / 2 points with TileCfg::DCT = 4 over rows of N reals
@@ -419,7 +425,7 @@ int build_dctn(Plan& plan, const std::vector<std::vector<uint32_t>>& ordered,
                const std::vector<std::vector<uint32_t>>& processed, std::string& why);
 // ---- the framed family: MIFFT_FLAG_STFT / MIFFT_FLAG_ISTFT plans and what their tagged payloads select -----------------------
 // Which member a plan is: decided once, by framed_kind (mifft_api.cpp), from the mode bit and the *_detect predicates below.
-enum class FramedKind { Stft, Istft, Adjoint, IstftAdjoint, Mdct, Imdct, Conv, ConvGrad };
+enum class FramedKind { Stft, Istft, Adjoint, IstftAdjoint, Mdct, Imdct, Conv, ConvGrad, ConvPair };
 // What a member's check decodes from `bases` for its build: the window (empty: rectangular), the filterbank and the matrix
 // after the bands of a spectrogram plan, the gain of the inverse kinds, the user radices of the one transformed dim (empty:
 // the default estimate).
@@ -499,6 +505,12 @@ int conv_grad_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases
 int build_conv_grad(Plan& plan, const std::vector<uint32_t>& ordered, const std::vector<uint32_t>& processed, std::string& why);
 int launch_jit_conv_grad(const Plan& plan, const DimPass& pass, const void* x, const void* gy, const void* pregate,
                          const void* postgate, void* out, hipStream_t stream);
+// The two-signal plans (MIFFT_CONV_PAIR_TAG): the same trio; the pass is build_conv's with TileCfg::PAIR.  launch_jit_conv_pair
+// is its launch, which takes the exec's two operands, offset to the exec's first row by the caller as `out` is.
+bool conv_pair_detect(int ndim, const uint32_t* bases_flat, const int32_t* bases_len);
+int conv_pair_check(Plan& plan, const uint32_t* bases_flat, const int32_t* bases_len, FramedPayload& payload, std::string& why);
+int launch_jit_conv_pair(const Plan& plan, const DimPass& pass, const void* x, const void* v, void* out, int64_t count,
+                         hipStream_t stream);
 // workgroups per CU of a built tile-kernel pass's persistent grid (kernels_jit.cpp): the launches' rule, and build_conv_grad's
 long long pass_wg_per_cu(const DimPass& pass);
 // Stage 3 of the fused partitioned filter gradient (ConvRequest::stage; lag_corr.hip): the precompiled lag-group kernel.  A

@@ -315,7 +315,12 @@ struct TileParams {
     // loads the 2N samples from ols_start + f * ols_step on (zeros outside [0, conv_len)) and stores the samples
     // conv_o .. conv_o + ols_step - 1 of its result to out[f * ols_step ..] of its signal's row, up to conv_Lo.  conv_row0
     // counts signals, not launch rows.
-    int ols_step, ols_blocks, ols_start;
+    // PAIR configurations (two signals: TileCfg::PAIR) read three other names on the same bytes: pair_K the samples per row of
+    // v, pair_ea / pair_eb the index at which a row of x / of v starts inside its 2N zero-extended samples.  v itself is
+    // gate_in (rows of pair_K reals, at the exec's first row as `in` is); conv_h, conv_D and conv_row0 are unused.
+    union { int ols_step; int pair_K; };
+    union { int ols_blocks; int pair_ea; };
+    union { int ols_start; int pair_eb; };
     // WGRAD configurations (the filter gradient of CONV / OLS) always carry the three ols_* fields (a single block:
     // ols_blocks = 1, ols_start = 0, ols_step = Lo) and wgrad_partials = P in the place of conv_row0; there is no filter.  `in`
     // is x, gate_in is gy (rows of conv_Lo reals), n_rows the pairs of ONE channel, B F: workgroup w is slice w % P of channel
@@ -339,7 +344,10 @@ static_assert(sizeof(TileParams) == 352 && __builtin_offsetof(TileParams, conv_Q
                   __builtin_offsetof(TileParams, adj_mult) == __builtin_offsetof(TileParams, spec_wt) &&
                   __builtin_offsetof(TileParams, adj_edge) == __builtin_offsetof(TileParams, spec_post) &&
                   __builtin_offsetof(TileParams, wgrad_partials) == __builtin_offsetof(TileParams, spec_bands) &&
-                  __builtin_offsetof(TileParams, conv_mode) == __builtin_offsetof(TileParams, spec_q),
+                  __builtin_offsetof(TileParams, conv_mode) == __builtin_offsetof(TileParams, spec_q) &&
+                  __builtin_offsetof(TileParams, pair_K) == __builtin_offsetof(TileParams, ols_step) &&
+                  __builtin_offsetof(TileParams, pair_ea) == __builtin_offsetof(TileParams, ols_blocks) &&
+                  __builtin_offsetof(TileParams, pair_eb) == __builtin_offsetof(TileParams, ols_start),
               "TileParams: a CONV name left the field it shares");
 
 // the log stage of a TileCfg::LOG store: fma(a, log2(max(v + add, amin)), c)
@@ -437,7 +445,7 @@ template <typename T_, int N_, int NP_, int R0_, int R1_, int R2_, int R3_, int 
           int ILV_ = 0, int DCT_ = 0, bool STFT_ = false, bool ISTFT_ = false, int SPEC_ = 0, bool FB_ = false,
           bool LOG_ = false, bool POST_ = false, bool MDCT_ = false, bool IMDCT_ = false, bool DST_ = false,
           bool CONV_ = false, bool OLS_ = false, int GATE_ = 0, bool WGRAD_ = false, bool PART_ = false,
-          int ADJ_ = 0, bool IADJ_ = false, int WSPEC_ = 0>
+          int ADJ_ = 0, bool IADJ_ = false, int WSPEC_ = 0, bool PAIR_ = false>
 struct TileCfg {
     using T = T_;
     static constexpr int N = N_, NP = NP_, TILE = TILE_, THREADS = THREADS_, TWMODE = TWMODE_, MINW = MINW_;
@@ -731,6 +739,21 @@ struct TileCfg {
     // spectra are recomputed, never stored, so the work grows with P.  part_walk below; the main tile loop is not run.
     static constexpr bool PART = PART_;
     static_assert(!PART_ || (CONV_ && OLS_ && !WGRAD_ && TILE_ <= 64), "PART: the partitioned twin of an OLS tile");
+    // PAIR (with CONV; never OLS, PART, WGRAD or GATE): the second operand is a SIGNAL, one row of its own per row of x, not a
+    // filter spectrum: out[r] = irfft(rfft(xe) G, 2N)[o .. o + Lo), xe the 2N samples that hold x[r] (conv_len reals) from
+    // index pair_ea on and zeros elsewhere, G = rfft(ve) or its conjugate (conv_mode bit 0), ve holding v[r] (pair_K reals)
+    // from pair_eb on.  A step of the persistent grid takes TILE rows as the CONV tile does: the x-rows are loaded with the
+    // zero-extending load (packed element m holds the samples 2m - ea and 2m + 1 - ea of its row: a pair load where both lie
+    // inside, real by real at the ends, nothing outside), the passes run, every work item unpacks the bin pairs (k, N - k) it
+    // owns into registers; the v-rows go through the same LDS, passes and unpack; the products are folded with the C2R algebra
+    // into the two slots the item just read, the passes run again and the store writes the samples o .. o + Lo - 1, scaled by
+    // 1 / 2N, each exactly once (a pair as one access where both samples are wanted and the address is aligned to two
+    // elements).  x and v are read once each -- they may be the same buffer -- and no spectrum reaches memory; no scratch, no
+    // atomics, no LDS beyond the R2C tile's, no accumulators.  A row's result depends on that row of x and of v alone.  Rows
+    // from the tile's nv live ones on load zeros and store nothing.  pair_walk below; the main tile loop is not run.
+    static constexpr bool PAIR = PAIR_;
+    static_assert(!PAIR_ || (CONV_ && !OLS_ && !PART_ && !WGRAD_ && GATE_ == 0 && same_t<IT_, T_>::value),
+                  "PAIR: the two-signal twin of a plain CONV tile of the plan's own float type");
     // ADJ (with ISTFT): the adjoint of the framed, windowed, one-sided transform instead of its inverse -- the gradient of stft
     // with respect to the signal.  1: `in` is the incoming gradient g = dL/dRe X + i dL/dIm X.  The C2R load doubles the real
     // parts of bins 0 and N (their imaginary parts drop out as they always have), so the passes leave
@@ -1717,6 +1740,73 @@ MIFFT_DEV void run_pass(const TileParams& p, cpx<typename C::T>* lds, const cpx<
     }
 }
 
+// ---- the stages the walks below share (wgrad_walk, part_walk, pair_walk) --------------------------------------------------------
+// (Hoisted out of wgrad_walk and part_walk with their instructions kept: the reference parameters of the load and the store,
+//  the scaled samples as the store's arguments and the operand order of unpack_bins' twiddle products are what made the
+//  compiler emit the same code for those two walks as before -- DESIGN.md 3.4w.)
+// One packed element of a zero-extended row: the samples i and i + 1 of the `len` reals at xe, zeros outside [0, len) and never
+// loaded there; a pair load where both lie inside (aligned to one element), real by real at the ends.  The ungated load: a
+// pregate's second stream of loads stays with the two walks that have one.
+template <class C, typename I>
+MIFFT_DEV cpx<typename C::T> load_embedded(const typename C::IT* const& xe, const I& i, const int& len) {
+    using T = typename C::T;
+    cpx<T> v = {(T)0, (T)0};
+    if (i >= 0 && i + 1 < len) {
+        v = sload_pair<T>(xe + i);
+    } else {  // (zeros beyond the ends: no load at all)
+        if (i >= 0 && i < len) v.x = sload<T>(xe + i);
+        if (i + 1 >= 0 && i + 1 < len) v.y = sload<T>(&xe[i + 1]);
+    }
+    return v;
+}
+
+// X[k] and X[N-k] of row c of the tile from the packed spectrum its last pass left in LDS, as the R2C store unpacks them
+// (w: W_2N^k, TileParams::r2c_tw)
+template <class C>
+MIFFT_DEV void unpack_bins(const cpx<typename C::T>* lds, const cpx<typename C::T>* w, const int c, const int k,
+                           cpx<typename C::T>& xa, cpx<typename C::T>& xb) {
+    using T = typename C::T;
+    using V = cpx<T>;
+    const int m = k ? C::N - k : 0;
+    const V zk = lds[lds_index<C, C::NP - 1>(c, k)], zm = lds[lds_index<C, C::NP - 1>(c, m)];
+    const T ex = (T)0.5 * (zk.x + zm.x), ey = (T)0.5 * (zk.y - zm.y);
+    const T ox = (T)0.5 * (zk.y + zm.y), oy = (T)-0.5 * (zk.x - zm.x);
+    const V wk = w[k];
+    const T tx = ox * wk.x - oy * wk.y, ty = oy * wk.x + ox * wk.y;
+    xa = {ex + tx, ey + ty};
+    xb = {ex - tx, ty - ey};
+}
+
+// The C2R fold of the bins a = Y[k], b = Y[N-k] of row c, as the CONV product stage folds one product: conj Z of the packed row
+// goes to the slots k and N - k of the layout pass 0 gathers from (the imaginary parts of bins 0 and N dropped)
+template <class C>
+MIFFT_DEV void fold_bins(cpx<typename C::T>* lds, const cpx<typename C::T>* w, const int c, const int k, cpx<typename C::T> a,
+                         cpx<typename C::T> b) {
+    using T = typename C::T;
+    const int m = k ? C::N - k : 0;
+    if (k == 0) a.y = b.y = (T)0;
+    const cpx<T> wk = w[k];
+    const T fx = a.x + b.x, fy = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
+    const T px = dx * wk.x + dy * wk.y, py = dy * wk.x - dx * wk.y;
+    lds[lds_index<C, C::NP - 1>(c, k)] = {fx - py, -(fy + px)};
+    if (k != 0 && 2 * k != C::N) lds[lds_index<C, C::NP - 1>(c, m)] = {fx + py, fy - px};
+}
+
+// The store of the two finished samples of one packed element: y0 (wanted: w0) and y1 (w1) go to q[0] and q[1], as one access
+// where both are wanted and q is aligned to two elements, else real by real.  The ungated store: a postgate's loads stay with
+// the walk that has one.
+template <class C>
+MIFFT_DEV void store_window(typename C::IT* const& q, const bool& w0, const bool& w1, const typename C::T& y0,
+                            const typename C::T& y1) {
+    using ST = typename C::IT;
+    if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(ST) - 1)) == 0) {
+        sstore_pair(q, y0, y1);
+    } else {
+        if (w0) sstore(q, y0);
+        if (w1) sstore(q + 1, y1);
+    }
+}
+
 // The walk of a TileCfg::WGRAD workgroup (see there): the whole kernel body behind the table set-up.
 template <class C>
 MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx<typename C::T>* twr, const int tid_entry) {
@@ -1748,14 +1838,8 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
         const int f = tid + i * C::THREADS;
         xa = xb = {(T)0, (T)0};
         if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
-            const int c = f / PAIRS, k = f - c * PAIRS, m = k ? C::N - k : 0;
-            const V zk = lds[lds_index<C, C::NP - 1>(c, k)], zm = lds[lds_index<C, C::NP - 1>(c, m)];
-            const T ex = (T)0.5 * (zk.x + zm.x), ey = (T)0.5 * (zk.y - zm.y);
-            const T ox = (T)0.5 * (zk.y + zm.y), oy = (T)-0.5 * (zk.x - zm.x);
-            const V wk = w[k];
-            const T tx = wk.x * ox - wk.y * oy, ty = wk.x * oy + wk.y * ox;
-            xa = {ex + tx, ey + ty};
-            xb = {ex - tx, ty - ey};
+            const int c = f / PAIRS, k = f - c * PAIRS;
+            unpack_bins<C>(lds, w, c, k, xa, xb);
         }
     };
     // TileCfg::WSPEC: the bins of the step's nv live pairs, as unpacked, to row (signal row) F + block of `out`; consecutive
@@ -1806,21 +1890,23 @@ MIFFT_DEV void wgrad_walk(const TileParams& p, cpx<typename C::T>* lds, const cp
                 const ST* xe = x + row;
                 const ST* ae = ga0 + row;
                 const int i = s0 + fr * S + 2 * m;
-                if (i >= 0 && i + 1 < L) {
-                    v = sload_pair<T>(xe + i);
-                    if constexpr (C::GATE & 1) {
+                if constexpr (C::GATE & 1) {
+                    if (i >= 0 && i + 1 < L) {
+                        v = sload_pair<T>(xe + i);
                         const V g = sload_pair<T>(ae + i);
                         v = {g.x * v.x, g.y * v.y};
+                    } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
+                        if (i >= 0 && i < L) {
+                            v.x = sload<T>(xe + i);
+                            v.x = sload<T>(ae + i) * v.x;
+                        }
+                        if (i + 1 >= 0 && i + 1 < L) {
+                            v.y = sload<T>(&xe[i + 1]);
+                            v.y = sload<T>(&ae[i + 1]) * v.y;
+                        }
                     }
-                } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
-                    if (i >= 0 && i < L) {
-                        v.x = sload<T>(xe + i);
-                        if constexpr (C::GATE & 1) v.x = sload<T>(ae + i) * v.x;
-                    }
-                    if (i + 1 >= 0 && i + 1 < L) {
-                        v.y = sload<T>(&xe[i + 1]);
-                        if constexpr (C::GATE & 1) v.y = sload<T>(&ae[i + 1]) * v.y;
-                    }
+                } else {
+                    v = load_embedded<C>(xe, i, L);
                 }
             }
             lds[lds_index<C, -1>(c, m)] = v;
@@ -1988,21 +2074,23 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
                     const ST* xe = x0 + (long long)db * len;
                     const ST* ge = g0 + (long long)db * len;
                     const long long i = start(c, pp) + 2 * m;
-                    if (i >= 0 && i + 1 < len) {
-                        x = sload_pair<T>(xe + i);
-                        if constexpr (C::GATE & 1) {
+                    if constexpr (C::GATE & 1) {
+                        if (i >= 0 && i + 1 < len) {
+                            x = sload_pair<T>(xe + i);
                             const V g = sload_pair<T>(ge + i);
                             x = {g.x * x.x, g.y * x.y};
+                        } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
+                            if (i >= 0 && i < len) {
+                                x.x = sload<T>(xe + i);
+                                x.x = sload<T>(ge + i) * x.x;
+                            }
+                            if (i + 1 >= 0 && i + 1 < len) {
+                                x.y = sload<T>(&xe[i + 1]);
+                                x.y = sload<T>(&ge[i + 1]) * x.y;
+                            }
                         }
-                    } else {  // (zeros beyond the ends: no load at all, of x or of its gate)
-                        if (i >= 0 && i < len) {
-                            x.x = sload<T>(xe + i);
-                            if constexpr (C::GATE & 1) x.x = sload<T>(ge + i) * x.x;
-                        }
-                        if (i + 1 >= 0 && i + 1 < len) {
-                            x.y = sload<T>(&xe[i + 1]);
-                            if constexpr (C::GATE & 1) x.y = sload<T>(&ge[i + 1]) * x.y;
-                        }
+                    } else {
+                        x = load_embedded<C>(xe, i, len);
                     }
                 }
                 lds[lds_index<C, -1>(c, m)] = x;
@@ -2045,14 +2133,8 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
         for (int i = 0; i < IT; ++i) {
             const int f = tid + i * C::THREADS;
             if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
-                const int c = C::TILE == 1 ? 0 : f / PAIRS, k = f - c * PAIRS, m = k ? C::N - k : 0;
-                V a = acc_a[i], b = acc_b[i];
-                if (k == 0) a.y = b.y = (T)0;
-                const V wk = w[k];
-                const T fx = a.x + b.x, fy = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
-                const T px = dx * wk.x + dy * wk.y, py = dy * wk.x - dx * wk.y;
-                lds[lds_index<C, C::NP - 1>(c, k)] = {fx - py, -(fy + px)};
-                if (k != 0 && 2 * k != C::N) lds[lds_index<C, C::NP - 1>(c, m)] = {fx + py, fy - px};
+                const int c = C::TILE == 1 ? 0 : f / PAIRS, k = f - c * PAIRS;
+                fold_bins<C>(lds, w, c, k, acc_a[i], acc_b[i]);
             }
         }
         __syncthreads();
@@ -2074,23 +2156,113 @@ MIFFT_DEV void part_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx
             const V v = lds[lds_index<C, C::NP - 1>(c, j)];
             T y0 = v.x * s, y1 = -(v.y * s);
             ST* q = out0 + (long long)db * Lo + tt;
-            const ST* bq = q0 + (long long)db * Lo + tt;
-            if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(ST) - 1)) == 0) {
-                if constexpr (C::GATE & 2) {
+            if constexpr (C::GATE & 2) {
+                const ST* bq = q0 + (long long)db * Lo + tt;
+                if (w0 && w1 && ((unsigned long long)q & (2 * sizeof(ST) - 1)) == 0) {
                     const V g = sload_pair<T>(bq);
                     y0 = g.x * y0, y1 = g.y * y1;
+                    sstore_pair(q, y0, y1);
+                } else {
+                    if (w0) {
+                        y0 = sload<T>(bq) * y0;
+                        sstore(q, y0);
+                    }
+                    if (w1) {
+                        y1 = sload<T>(bq + 1) * y1;
+                        sstore(q + 1, y1);
+                    }
                 }
-                sstore_pair(q, y0, y1);
             } else {
-                if (w0) {
-                    if constexpr (C::GATE & 2) y0 = sload<T>(bq) * y0;
-                    sstore(q, y0);
-                }
-                if (w1) {
-                    if constexpr (C::GATE & 2) y1 = sload<T>(bq + 1) * y1;
-                    sstore(q + 1, y1);
-                }
+                store_window<C>(q, w0, w1, y0, y1);
             }
+        }
+        __syncthreads();
+    }
+}
+
+// The walk of a TileCfg::PAIR workgroup (see there): the whole kernel body behind the table set-up.
+template <class C>
+MIFFT_DEV void pair_walk(const TileParams& p, cpx<typename C::T>* lds, const cpx<typename C::T>* twr, const int tid_entry) {
+    using T = typename C::T;
+    using ST = typename C::IT;
+    using V = cpx<T>;
+    constexpr int PAIRS = C::N / 2 + 1;
+    constexpr int IT = (C::TILE * PAIRS + C::THREADS - 1) / C::THREADS;
+    const int L = p.conv_len, K = p.pair_K, ea = p.pair_ea, eb = p.pair_eb, o = p.conv_o, Lo = p.conv_Lo;
+    const T cj = (p.conv_mode & 1) ? (T)-1 : (T)1;
+    const T s = (T)p.scale;
+    const V* w = (const V*)p.r2c_tw;
+    V cur[1][C::R(0)];
+    for (long long t = blockIdx.x; t < p.n_tiles; t += gridDim.x) {
+        const long long r0 = t * C::TILE;
+        const int nv = p.n_rows - r0 < C::TILE ? (int)(p.n_rows - r0) : C::TILE;
+        const ST* x0 = (const ST*)p.in + r0 * L;
+        const ST* v0 = (const ST*)p.gate_in + r0 * K;
+        // (the thread index is made opaque once per stage, as part_walk does around its accumulators: what is derived from it --
+        //  LDS offsets, the twiddles w[k] -- is recomputed per stage instead of staying live beside the held bins of x)
+        int tid = tid_entry;
+#ifndef MIFFT_NO_OPAQUE_TID
+        asm volatile("" : "+v"(tid));
+#endif
+        // the x-rows: packed element m of row c holds the samples 2 m - ea and 2 m + 1 - ea of its row
+        for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
+            const int c = f / C::N, m = f - c * C::N;
+            V e = {(T)0, (T)0};
+            if (c < nv) e = load_embedded<C>(x0 + c * L, 2 * m - ea, L);
+            lds[lds_index<C, -1>(c, m)] = e;
+        }
+        __syncthreads();
+        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        V xa[IT], xb[IT];
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            const int f = tid + i * C::THREADS;
+            xa[i] = xb[i] = {(T)0, (T)0};
+            if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
+                const int c = C::TILE == 1 ? 0 : f / PAIRS, k = f - c * PAIRS;
+                unpack_bins<C>(lds, w, c, k, xa[i], xb[i]);
+            }
+        }
+        __syncthreads();
+        tid = tid_entry;
+#ifndef MIFFT_NO_OPAQUE_TID
+        asm volatile("" : "+v"(tid));
+#endif
+        // the v-rows, the same way, into the same LDS
+        for (int f = tid; f < C::TILE * C::N; f += C::THREADS) {
+            const int c = f / C::N, m = f - c * C::N;
+            V e = {(T)0, (T)0};
+            if (c < nv) e = load_embedded<C>(v0 + c * K, 2 * m - eb, K);
+            lds[lds_index<C, -1>(c, m)] = e;
+        }
+        __syncthreads();
+        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        tid = tid_entry;
+#ifndef MIFFT_NO_OPAQUE_TID
+        asm volatile("" : "+v"(tid));
+#endif
+        // X G (correlation: X conj G) of both bins of the pair, folded into the two slots the item just read: it is their only reader
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            const int f = tid + i * C::THREADS;
+            if (IT * C::THREADS == C::TILE * PAIRS || f < C::TILE * PAIRS) {
+                const int c = C::TILE == 1 ? 0 : f / PAIRS, k = f - c * PAIRS;
+                V ga, gb;
+                unpack_bins<C>(lds, w, c, k, ga, gb);
+                fold_bins<C>(lds, w, c, k, cmul(xa[i], V{ga.x, cj * ga.y}), cmul(xb[i], V{gb.x, cj * gb.y}));
+            }
+        }
+        __syncthreads();
+        run_pass<C, 0>(p, lds, twr, cur, 0, C::TILE, tid);
+        // the windowed store: sample u = 2 j - o (and u + 1) of row c goes to out[(r0 + c) Lo + u] for 0 <= u < Lo only
+        ST* out0 = (ST*)p.out + r0 * Lo;
+        for (int f = tid; f < nv * C::N; f += C::THREADS) {
+            const int c = f / C::N, j = f - c * C::N, u = 2 * j - o;
+            const bool w0 = u >= 0 && u < Lo, w1 = u + 1 >= 0 && u + 1 < Lo;
+            if (!w0 && !w1) continue;
+            const V e = lds[lds_index<C, C::NP - 1>(c, j)];
+            ST* q = out0 + (long long)c * Lo + u;
+            store_window<C>(q, w0, w1, e.x * s, -(e.y * s));
         }
         __syncthreads();
     }
@@ -2155,6 +2327,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void tile_kernel(const TilePar
     }
     if constexpr (C::PART) {  // (the partitioned convolution transforms several blocks per stored one: its own loop)
         part_walk<C>(p, lds, twr, tid0);
+        return;
+    }
+    if constexpr (C::PAIR) {  // (two signals per row: two loads and transforms per stored row: its own loop)
+        pair_walk<C>(p, lds, twr, tid0);
         return;
     }
     V pre[C::PREFETCH ? C::IPT(0) : 1][C::R(0)];

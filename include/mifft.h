@@ -838,6 +838,44 @@ typedef struct mifft_conv_grad_gated_args {
     const void* postgate; /* gy's shape and dtype, or NULL where the plan has no postgate */
 } mifft_conv_grad_gated_args;
 
+/*
+ * TWO-SIGNAL FFT CONVOLUTION / CORRELATION (MIFFT_CONV_PAIR_TAG; no reference counterpart): a MIFFT_FLAG_STFT plan whose 16-word
+ * payload starts with MIFFT_CONV_PAIR_TAG.  dims = {L, n}, batch rows, in_components = 1, in_dtype == out_dtype (F32 or F64),
+ * inverse = 0.  Both operands are signals: x is (batch, L, 1) real, v (batch, K, 1) real, one row of v per row of x, and out is
+ * (batch, Lo, 1) real.  For row r, everything modulo the FFT length n:
+ *     xe = zeros(n); xe[ea .. ea + L) = x[r]          ve = zeros(n); ve[eb .. eb + K) = v[r]
+ *     y  = irfft(rfft(xe) * G, n),  G = rfft(ve), or conj(rfft(ve)) with mode bit 0 (correlate: y[t] = sum_j ve[j] xe[(t + j) mod n])
+ *     out[r, t] = y[o + t],  0 <= t < Lo
+ * The imaginary parts of the product at bins 0 and n / 2 are dropped.  n < L + K - 1 gives the circular result.
+ *     word  0, 1   MIFFT_CONV_PAIR_TAG_LO, MIFFT_CONV_PAIR_TAG_HI
+ *     word  2      K   samples per row of v, K >= 1
+ *     word  3      ea  where a row of x starts in its n samples, ea + L <= n
+ *     word  4      eb  where a row of v starts in its n samples, eb + K <= n
+ *     word  5, 6   o, Lo  the stored samples, Lo >= 1, o + Lo <= n
+ *     word  7      mode: bit 0 correlate; every other bit, bits 8..15 included (no 16-bit storage), is refused
+ *     word  8..15  0
+ * then the radices of n (or none).  scipy.signal.correlate(x, v, "full") is ea = K - 1, eb = 0, o = 0, Lo = L + K - 1 with
+ * correlate; fftconvolve(x, v, "full") ea = eb = o = 0, Lo = L + K - 1.  The gradients of a plan are plans of this kind again
+ * (INTEGRATION.md).  MIFFT_ERR_BAD_BASES for a value outside these rules or a non-zero reserved word; the flags, dtypes and
+ * lengths n the other convolution plans refuse are refused alike (n even, 8 .. 16384, n / 2 without a prime factor above 32;
+ * compiled at run time only: MIFFT_JIT=0 is MIFFT_ERR_UNSUPPORTED).  One launch, no scratch; mifft_plan_in_bytes is x's size,
+ * mifft_plan_out_bytes out's.  A row's result depends on that row of x and v alone: bit-identical for any batch, slab and grid.
+ * THE EXEC takes the HOST address of a mifft_conv_pair_args in the place of x:
+ *     mifft_conv_pair_args a = { MIFFT_CONV_PAIR_ARGS_MAGIC, x, v };   mifft_exec(plan, &a, out, stream);
+ * mifft_exec_batch(first, count) offsets x by first * L, v by first * K and out by first * Lo samples.  MIFFT_ERR_NULL: x or v
+ * NULL; MIFFT_ERR_ALIAS: x or v overlapping the exec's part of out (x == v is allowed: autocorrelation);
+ * MIFFT_ERR_UNSUPPORTED: a device address or a block without the magic word.  Nothing is launched in any of these cases.
+ */
+#define MIFFT_CONV_PAIR_TAG_LO 0x49415001u
+#define MIFFT_CONV_PAIR_TAG_HI 0x7FF84D50u
+/* the argument block of a two-signal convolution exec (above); the magic word is "MIFFTPA1" */
+#define MIFFT_CONV_PAIR_ARGS_MAGIC 0x314150544646494Dull
+typedef struct mifft_conv_pair_args {
+    uint64_t magic;  /* MIFFT_CONV_PAIR_ARGS_MAGIC */
+    const void* x;   /* (batch, L, 1) reals on the plan's device */
+    const void* v;   /* (batch, K, 1) reals on the plan's device; may be x itself */
+} mifft_conv_pair_args;
+
 typedef struct mifft_plan mifft_plan;
 
 /*

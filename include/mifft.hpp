@@ -217,6 +217,19 @@ static_assert(MIFFT_CONV_GRAD_ARGS_MAGIC == 0x314757544646494Dull && sizeof(miff
               "mifft_conv_grad_args is the magic word \"MIFFTWG1\" and two pointers");
 static_assert(MIFFT_CONV_GRAD_GATED_ARGS_MAGIC == 0x324757544646494Dull && sizeof(mifft_conv_grad_gated_args) == 8 + 4 * sizeof(void*),
               "mifft_conv_grad_gated_args is the magic word \"MIFFTWG2\" and four pointers");
+// MIFFT_CONV_PAIR_TAG in front of 16 words -- TAG | K | ea | eb | o | Lo | mode | 0 x 8 -- on the same kind of plan: the
+// convolution (mode bit 0: correlation) of two signal batches row by row, x (batch, L, 1) and v (batch, K, 1) -> out
+// (batch, Lo, 1), with no filter spectrum.  The exec takes the host address of a mifft_conv_pair_args
+// {MIFFT_CONV_PAIR_ARGS_MAGIC, x, v} as its x (include/mifft.h).
+static_assert(MIFFT_CONV_PAIR_TAG_LO == 0x49415001u && MIFFT_CONV_PAIR_TAG_HI == 0x7FF84D50u &&
+                  (MIFFT_CONV_PAIR_TAG_HI & 0x7FF80000u) == 0x7FF80000u && MIFFT_CONV_PAIR_TAG_HI != MIFFT_CONV_TAG_HI &&
+                  MIFFT_CONV_PAIR_TAG_HI != MIFFT_CONV_GRAD_TAG_HI && MIFFT_CONV_PAIR_TAG_HI != MIFFT_MDCT_TAG_HI &&
+                  MIFFT_CONV_PAIR_TAG_HI != MIFFT_STFT_EXT_TAG_HI && MIFFT_CONV_PAIR_TAG_HI != MIFFT_STFT_ADJ_TAG_HI &&
+                  MIFFT_CONV_PAIR_TAG_HI != MIFFT_ISTFT_ADJ_TAG_HI,
+              "MIFFT_CONV_PAIR_TAG is the quiet NaN 0x7FF84D5049415001, distinct from the other payload tags");
+constexpr uint64_t kConvPairTag = ((uint64_t)MIFFT_CONV_PAIR_TAG_HI << 32) | MIFFT_CONV_PAIR_TAG_LO;
+static_assert(MIFFT_CONV_PAIR_ARGS_MAGIC == 0x314150544646494Dull && sizeof(mifft_conv_pair_args) == 8 + 2 * sizeof(void*),
+              "mifft_conv_pair_args is the magic word \"MIFFTPA1\" and two pointers");
 inline Plan plan_fft(mifft_dtype in_dtype, mifft_dtype out_dtype, const std::vector<int64_t>& in_layout,
                      const std::vector<int64_t>& out_layout, const DeviceContext& ctx,
                      const std::vector<std::vector<uint32_t>>* bases = nullptr, bool inverse = false,
